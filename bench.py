@@ -6,7 +6,12 @@ in-k-space noise -> inverse FFT -> gather -> near-field M.F -> Lanczos M_real^{1
 synthetic random-sphere suspension of BASELINE.json's metric point (N = 1e6, phi = 0.1, 256^3 grid, fp64), inputs
 resident in HBM before the timed region.  value = particle-steps/s summed over all ranks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n PARTICLES] [--grid G] [--no-cpu] [--traffic FILE] [--dry-run]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n PARTICLES] [--grid G] [--full] [--dump-outputs DIR] [--dry-run]
+A plain single-GPU run sets up, takes W warm-up steps, times EXACTLY K steps, times K steps of the queue-only form of the same step
+(ms_per_step: the faster valid form), writes what the last step of each form computed if --dump-outputs is given, and prints the
+line.  --full adds everything else the line can carry (M.F evaluations, percentiles, per-phase times, the roofline with its counter
+passes, the reference-rule grid, config 4, the CPU baseline); --no-cpu, --no-traffic, --no-ref-grid, --no-async and --no-cfg4
+leave single pieces out.
 With --gpus N > 1 and no torch.distributed environment the process launches the N ranks itself (one child
 `python bench.py ...` per GPU with RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set; the parent never touches the GPU) and relays
 rank 0's JSON line; started under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.  See DESIGN.md "Multi-GPU".
@@ -27,6 +32,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+METRIC = "BD particle-steps/s (full PSE Brownian step: M.F + k-space noise + Lanczos M^1/2.psi + Euler), N=1e6, phi=0.1"
+DTYPE_NOTE = ("all arithmetic fp64; inside the Lanczos mat-vec the pair coefficients are read from 16-byte records (26-bit fixed / 22-bit "
+              "block-floating point: single-precision accuracy) and, on one GPU, the neighbours' vector rows from 40-bit mantissas")
 
 
 def suspension(n, phi, seed=12345, fseed=54321):
@@ -35,6 +43,11 @@ def suspension(n, phi, seed=12345, fseed=54321):
     force = np.random.default_rng(fseed).normal(size=(n, 3))
     force -= force.mean(axis=0)
     return pos, force, L
+
+
+def workload_of(args, n, L, xi, info):
+    return (f"random-sphere suspension N={n}, phi={args.phi}, cubic L={L:.2f}, grid {args.grid}^3, xi={xi:.4f}, rcut={info['rcut']:.3f}, "
+            f"P={info['P']}, error={args.error}, kT={args.kT}, dt={args.dt}")
 
 
 def cpu_baseline(budget_s=12.0):
@@ -62,6 +75,27 @@ def cpu_baseline(budget_s=12.0):
     }
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, arrays, scalars):
+    """Write `arrays` (name -> float32 / float64 array, one row per particle) and `scalars` (name -> number, as one float64) as
+    d/<name>.npy.  Rows beyond DUMP_BYTES are left out: a fixed sample (seed 0, the same rows in every array and every run with these
+    arguments), whose particle indices go to d/rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // n for a in arrays.values())
+    if n * row_bytes > DUMP_BYTES - 4096:
+        k = (DUMP_BYTES - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = dict({name: a[rows] for name, a in arrays.items()}, rows=rows.astype(np.float64))
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+    for name, v in scalars.items():
+        np.save(os.path.join(d, name + ".npy"), np.array([v], dtype=np.float64))
+
+
 def measure_traffic(kernel_prefix, args):
     """HBM bytes per launch of one kernel, measured NOW: two child runs of this same script (a few steps, one stream, no
     extras) under `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` -- separate passes, as MI355X_MICROARCH.md prescribes; the
@@ -81,10 +115,11 @@ def measure_traffic(kernel_prefix, args):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="pse_pmc_", dir="/tmp")
         cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--", py, os.path.abspath(__file__),
-               "--steps", "3", "--warmup", "1", "--no-cpu", "--no-ref-grid", "--no-cfg4", "--no-async", "--no-traffic", "--n", str(args.n), "--phi", str(args.phi),
+               "--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-ref-grid", "--no-cfg4", "--no-async", "--no-traffic", "--n", str(args.n), "--phi", str(args.phi),
                "--grid", str(args.grid), "--error", str(args.error), "--kT", str(args.kT), "--dt", str(args.dt)]
         try:
-            r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300)
+            # (a pass takes seconds; the limit keeps a hung profiler from holding a --full run past ten minutes)
+            r = subprocess.run(cmd, cwd=d, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=120)
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
             if r.returncode != 0 or not files:
                 return None
@@ -659,6 +694,12 @@ def main():
     ap.add_argument("--error", type=float, default=1e-3)
     ap.add_argument("--kT", type=float, default=1.0)
     ap.add_argument("--dt", type=float, default=1e-3)
+    ap.add_argument("--full", action="store_true",
+                    help="single GPU: measure and check everything beside the headline as well (see the module docstring); a plain run "
+                         "takes the warm-up and times the K steps in the two forms of the step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single GPU: write what the last of the K host-checked timed steps computed (positions, velocities, images, "
+                         "the Lanczos count) as DIR/<name>.npy, and what the last of the K queue-only steps computed as DIR/queue_only_<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="HBM bytes per kernel from separate rocprofv3 --pmc passes of this command (tools/round_profile.sh)")
@@ -688,6 +729,10 @@ def main():
     ap.add_argument("--segment", choices=list(SEGMENTS), default=None, help=argparse.SUPPRESS)   # (set by supervise_segments for its children)
     args = ap.parse_args()
     argv = sys.argv[1:]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is for single-GPU runs")
     if args.gpus > 1 and args.segment is None:
         if not args.replicated:      # the owned-particle run: a sequence of segments, each a fresh set of rank processes
             raise SystemExit(supervise_segments(args, argv))
@@ -696,8 +741,8 @@ def main():
     if args.dry_run:
         print(json.dumps({"launch": None, "n_gpus": args.gpus}))
         return
-    if args.segment == "single":     # one process on GPU 0: what the team's speed-ups divide by
-        args.gpus, args.no_cpu, args.no_traffic, args.no_ref_grid = 1, True, True, True
+    if args.segment == "single":     # one process on GPU 0: what the team's speed-ups divide by (config 4 included)
+        args.gpus, args.full, args.no_cpu, args.no_traffic, args.no_ref_grid = 1, True, True, True, True
         args.steps, args.warmup = min(args.steps, 20), min(args.warmup, 5)
 
     import torch
@@ -757,33 +802,34 @@ def main():
     m = 2
     for it in range(args.warmup):
         m = sim.step(args.kT, args.dt, it, lanczos_m=m)
-    # M.F evals/s (deterministic part only), a few evaluations
-    barrier()
-    t0 = time.perf_counter()
-    n_mf = max(3, args.steps // 2)
-    for it in range(n_mf):
-        sim.mobility()
-    barrier()
-    t_mf = (time.perf_counter() - t0) / n_mf
-    # the same evaluation with MOVING particles: every call sees positions displaced by more than r_buff / 2 from the last one, so
-    # the kept neighbour list is never reused and every call sorts and walks the cells (single GPU; slab ranks keep no list)
-    t_mf_moving = None
-    if world == 1 and hasattr(sim, "engine") and hasattr(sim, "pos"):
-        rng = np.random.default_rng(99)
-        moved = []
-        for k in range(4):
-            p = sim.pos.clone()
-            p[:, :3] += torch.tensor(rng.uniform(-0.5, 0.5, (n, 3)), dtype=torch.float64, device="cuda")
-            moved.append(p)
-        for k in range(2):
-            sim.engine.mobility(moved[k], sim.force, vel=sim.vel)
-        torch.cuda.synchronize()
+    t_mf = t_mf_moving = None
+    if args.full:
+        # M.F evals/s (deterministic part only), a few evaluations
+        barrier()
         t0 = time.perf_counter()
+        n_mf = max(3, args.steps // 2)
         for it in range(n_mf):
-            sim.engine.mobility(moved[it % 4], sim.force, vel=sim.vel)
-        torch.cuda.synchronize()
-        t_mf_moving = (time.perf_counter() - t0) / n_mf
-        del moved
+            sim.mobility()
+        barrier()
+        t_mf = (time.perf_counter() - t0) / n_mf
+        # the same evaluation with MOVING particles: every call sees positions displaced by more than r_buff / 2 from the last one, so
+        # the kept neighbour list is never reused and every call sorts and walks the cells (single GPU; slab ranks keep no list)
+        if world == 1 and hasattr(sim, "engine") and hasattr(sim, "pos"):
+            rng = np.random.default_rng(99)
+            moved = []
+            for k in range(4):
+                p = sim.pos.clone()
+                p[:, :3] += torch.tensor(rng.uniform(-0.5, 0.5, (n, 3)), dtype=torch.float64, device="cuda")
+                moved.append(p)
+            for k in range(2):
+                sim.engine.mobility(moved[k], sim.force, vel=sim.vel)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for it in range(n_mf):
+                sim.engine.mobility(moved[it % 4], sim.force, vel=sim.vel)
+            torch.cuda.synchronize()
+            t_mf_moving = (time.perf_counter() - t0) / n_mf
+            del moved
 
     # headline: EXACTLY --steps steps, nothing else inside the timed region (no phase timing, no host synchronisation beyond
     # what the step itself needs: the Lanczos convergence check)
@@ -795,6 +841,14 @@ def main():
         ms.append(m)
     barrier()
     elapsed = time.perf_counter() - t0
+    outputs, scalars = None, {"lanczos_m": ms[-1]}
+    st = getattr(sim, "s", sim)      # the arrays a caller of the step holds (a team of one keeps them in .s)
+
+    def state(prefix):
+        return {prefix + "positions": st.pos[:, :3].cpu().numpy(), prefix + "velocities": st.vel[:, :3].cpu().numpy(),
+                prefix + "images": st.image.cpu().numpy().astype(np.float32)}
+    if args.dump_outputs:     # after the W + K host-checked steps from the seeded suspension (the queue-only form's end state is added below)
+        outputs = state("")
     # The same K steps through the queue-only form of the SAME entry point (pse_set_async(1): pse_step only queues work, the Lanczos
     # convergence decision is taken on the device, gated extra iterations leave at once, nothing is read back -- what a host that
     # does not want to stall its stream every step calls; captured-graph and parity tests: tests/test_gpu_async.py).  The steps are
@@ -829,10 +883,35 @@ def main():
         iq = eng.info()
         eng.set_lanczos_extra(-1)
         eng.set_async(False)
+        if outputs is not None:     # ... and after the K queue-only steps that followed them and their settling steps
+            outputs.update(state("queue_only_"))
+            scalars["queue_only_lanczos_m"] = iq["lanczos_m"]
         modes["queue_only"] = {"ms_per_step": el_q / args.steps * 1e3, "lanczos_m": iq["lanczos_m"], "lanczos_status": iq["lanczos_status"],
                                "starting_count": m_q, "gated_extras_off": lc.extras_off, "steps_that_ran_out": int(iq["lanczos_open_calls"] - open0)}
         if iq["lanczos_status"] == 0 and iq["lanczos_m"] == m_q and iq["lanczos_open_calls"] == open0 and el_q < elapsed:
             mode, elapsed = "queue_only", el_q
+    parallelism = sim.describe() + ("; steps through the queue-only form of pse_step (pse_set_async: device-side Lanczos decision, nothing "
+                                    "read back)" if mode == "queue_only" else "")
+    if not args.full:
+        if world > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if host_transport else "cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t[0])
+        info = sim.info()
+        if rank == 0:
+            t_step = elapsed / args.steps
+            out = {"metric": METRIC, "value": n / t_step, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                   "ms_per_step": t_step * 1e3, "step_modes": modes, "step_mode": mode, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+                   "dtype": "f64", "dtype_note": DTYPE_NOTE, "data": "synthetic",
+                   "config": {"workload": workload_of(args, n, L, xi, info), "parallelism": parallelism},
+                   "steps_per_s": 1.0 / t_step, "lanczos_m": float(np.mean(ms)), "lanczos_matvecs_per_step": info["lanczos_matvecs"],
+                   "roofline": None, "cpu_baseline": None, "extras": "not measured: bench.py --full"}
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs, scalars)
+            print(json.dumps(out))
+        if use_dist:
+            dist.destroy_process_group()
+        return
     # distribution of single steps (median, p10, p90), each bracketed by device events
     n_pct = max(10, min(50, args.steps))
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_pct)]
@@ -962,16 +1041,12 @@ def main():
         nl_note = {"r_buff": rb, "calls_that_built": nb_, "calls_that_reused": nr_,
                    "note": "mf_evals_per_s is measured at fixed positions and runs on the kept list; the steps of the headline do not"}
     out = {
-        "metric": "BD particle-steps/s (full PSE Brownian step: M.F + k-space noise + Lanczos M^1/2.psi + Euler), "
-                  "N=1e6, phi=0.1",
+        "metric": METRIC,
         "value": n / t_step, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": t_step * 1e3, "ms_per_step_percentiles": pct, "step_modes": modes, "step_mode": mode,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f64", "dtype_note": "all arithmetic fp64; inside the Lanczos mat-vec the pair coefficients are read from 16-byte records (26-bit fixed / 22-bit block-floating point: single-precision accuracy) and, on one GPU, the neighbours' vector rows from 40-bit mantissas", "data": "synthetic",
-        "config": {"workload": f"random-sphere suspension N={n}, phi={args.phi}, cubic L={L:.2f}, grid {grid}^3, "
-                               f"xi={xi:.4f}, rcut={info['rcut']:.3f}, P={info['P']}, error={args.error}, kT={args.kT}, "
-                               f"dt={args.dt}", "parallelism": sim.describe() + ("; steps through the queue-only form of pse_step (pse_set_async: device-side "
-                                                                                  "Lanczos decision, nothing read back)" if mode == "queue_only" else "")},
+        "dtype": "f64", "dtype_note": DTYPE_NOTE, "data": "synthetic",
+        "config": {"workload": workload_of(args, n, L, xi, info), "parallelism": parallelism},
         "steps_per_s": 1.0 / t_step, "mf_evals_per_s": 1.0 / t_mf, "mf_particle_evals_per_s": n / t_mf,
         "mf_evals_per_s_moving": (1.0 / t_mf_moving) if t_mf_moving else None,
         # the whole step against the roofline: SURVEY.md 8(d) A_step = A_MF + 32 N + (m + 1) 256 N + 32 N m + 160 N over all ranks
@@ -1056,6 +1131,8 @@ def main():
                          "speedup_8gpu": [6, None], "note": "[target, measured]; the 8-GPU clause is measured by `bench.py --gpus 8` (speedup_vs_single there)"}
     if not args.no_cpu and world == 1:     # the CPU baseline is reported with the single-GPU line only
         out["cpu_baseline"] = cpu_baseline()
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, scalars)
     print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()

@@ -248,3 +248,32 @@ def test_fallback_decision_reaches_every_supervisor_under_torch_distributed_run(
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["mode"] == "host_fallback" and d["n_gpus"] == 3 and "error" in d["modes"]["lanes"] and "error" in d["modes"]["one_stream"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per array, float32 / float64 only; above the byte budget the same seeded rows of every array (and
+    their indices), identical from call to call."""
+    import numpy as np
+    bench = _bench_module()
+    n = 1000
+    pos, vel = np.random.default_rng(1).normal(size=(n, 3)), np.random.default_rng(2).normal(size=(n, 3))
+    img = np.arange(3 * n, dtype=np.float32).reshape(n, 3)
+    bench.dump_outputs(str(tmp_path / "all"), {"positions": pos, "velocities": vel, "images": img}, {"lanczos_m": 7})
+    got = {p.name: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert sorted(got) == ["images.npy", "lanczos_m.npy", "positions.npy", "velocities.npy"]
+    assert np.array_equal(got["positions.npy"], pos) and np.array_equal(got["images.npy"], img) and got["lanczos_m.npy"].tolist() == [7.0]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 30_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"positions": pos, "velocities": vel, "images": img}, {"lanczos_m": 7})
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 30_000
+    rows = a["rows.npy"].astype(np.int64)
+    assert 0 < len(rows) < n and np.array_equal(np.unique(rows), rows)
+    assert np.array_equal(a["positions.npy"], pos[rows]) and np.array_equal(a["images.npy"], img[rows])
+    assert all(np.array_equal(a[k], b[k]) and a[k].dtype in (np.float32, np.float64) for k in a)
+
+
+def test_bench_refuses_zero_steps():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

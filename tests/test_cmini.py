@@ -120,3 +120,7 @@ def test_committed_fixtures_are_what_the_generators_produce(tmp_path, monkeypatc
     monkeypatch.setattr(mr, "OUT", str(tmp_path / "a.json"))
     mr.main()
     assert json.load(open(tmp_path / "a.json")) == json.load(open(os.path.join(golden, "reference_arithmetic.json")))
+    mx = importlib.import_module("make_example_names_fixture")
+    monkeypatch.setattr(mx, "OUT", str(tmp_path / "x.json"))
+    mx.main()
+    assert json.load(open(tmp_path / "x.json")) == json.load(open(os.path.join(golden, "reference_example_names.json")))

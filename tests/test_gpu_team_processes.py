@@ -19,29 +19,53 @@ def _free_port():
 
 
 # The cases of this module are independent of one another (each has its own processes, port and handles) and most of a case's time is
-# interpreter and library start-up in its ranks: the first test that asks starts them ALL, four at a time, and every test reads its
-# own outcome (tests/test_gpu_switches.py does the same with its child runs).
+# interpreter and library start-up in its ranks: the first test that asks starts them ALL, as many at a time as fit into GPU_PROCS, and
+# every test reads its own outcome (tests/test_gpu_switches.py does the same with its child runs).
+# A GPU node admits at most 16 processes with the device open at once, and this pytest process (which earlier modules' tests have
+# already made one of them) counts too: the jobs running at any moment together hold at most GPU_PROCS rank processes, each job
+# declaring how many it holds at most.
+GPU_PROCS = 12
 _JOBS, _OUTCOMES = {}, {}
 
 
-def _job(key, fn):
-    _JOBS[key] = fn
+def _job(key, fn, procs):
+    assert 0 < procs <= GPU_PROCS, (key, procs)
+    _JOBS[key] = (fn, procs)
 
 
 def _outcome(key):
     if not _OUTCOMES:
-        from concurrent.futures import ThreadPoolExecutor
-        keys = list(_JOBS)
+        import threading
+
+        free = [GPU_PROCS]
+        cv = threading.Condition()
 
         def run(k):
+            fn, procs = _JOBS[k]
             try:
-                return _JOBS[k]()
+                _OUTCOMES[k] = fn()
             except Exception as e:   # noqa: BLE001
                 import traceback
-                return ("exception", "".join(traceback.format_exception(type(e), e, e.__traceback__))[-3000:])
-        with ThreadPoolExecutor(max_workers=4) as pool:
-            for k, out in zip(keys, pool.map(run, keys)):
-                _OUTCOMES[k] = out
+                _OUTCOMES[k] = ("exception", "".join(traceback.format_exception(type(e), e, e.__traceback__))[-3000:])
+            finally:
+                with cv:
+                    free[0] += procs
+                    cv.notify_all()
+
+        threads = []
+        pending = sorted(_JOBS, key=lambda k: -_JOBS[k][1])      # the widest first: the narrow ones fill the gaps beside them
+        with cv:
+            while pending:
+                k = next((k for k in pending if _JOBS[k][1] <= free[0]), None)
+                if k is None:
+                    cv.wait()
+                    continue
+                pending.remove(k)
+                free[0] -= _JOBS[k][1]
+                threads.append(threading.Thread(target=run, args=(k,), daemon=True))
+                threads[-1].start()
+        for t in threads:
+            t.join()
     return _OUTCOMES[key]
 
 
@@ -145,11 +169,12 @@ def _run_ranks(procs, out, deadline_s=600):
                 p.join(timeout=10)
             if p.is_alive():
                 p.kill()
+                p.join(timeout=10)      # (gone before its job's share of GPU_PROCS is handed on)
 
 
 _TEAM_CASES = [(2, "", 0.0), (2, "slab", 0.2), (4, "", 0.25), (8, "", 0.0)]
 for _c in _TEAM_CASES:
-    _job(("team",) + _c, lambda c=_c: _spawn_ranks(_worker, c[0], lambda r, port, out: (r, c[0], port, c[1], c[2], out)))
+    _job(("team",) + _c, lambda c=_c: _spawn_ranks(_worker, c[0], lambda r, port, out: (r, c[0], port, c[1], c[2], out)), _c[0])
 
 
 @pytest.mark.parametrize("world,mode,xy", _TEAM_CASES)
@@ -166,7 +191,7 @@ def _bench_own_ranks():
                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=1200)
 
 
-_job("bench_own_ranks", _bench_own_ranks)
+_job("bench_own_ranks", _bench_own_ranks, 2)      # (one segment of two ranks at a time)
 
 
 def test_bench_launches_its_own_ranks():
@@ -221,7 +246,7 @@ def _bench_rccl_refused():
                            "--grid", "128", "--no-cfg4"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=1200)
 
 
-_job("bench_rccl_refused", _bench_rccl_refused)
+_job("bench_rccl_refused", _bench_rccl_refused, 3)      # (+ the supervisor, which asks torch how many GPUs there are)
 
 
 def test_bench_without_a_working_rccl_mode_reports_the_host_transport_and_says_so():
@@ -255,7 +280,7 @@ def _bench_under_launcher():
                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
 
 
-_job("bench_under_launcher", _bench_under_launcher)
+_job("bench_under_launcher", _bench_under_launcher, 2)
 
 
 def test_bench_as_ranks_of_torch_distributed_run():
@@ -322,15 +347,19 @@ def _random_worker(rank, seed, port, out):
 _RANDOM_SEEDS = [5, 7, 16, 18, 20, 22]
 
 
-def _random_case(seed):
+def _random_world(seed):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_gpu_random_teams import config
-    world = config(seed)["world"]
+    return config(seed)["world"]
+
+
+def _random_case(seed):
+    world = _random_world(seed)
     return world, _spawn_ranks(_random_worker, world, lambda r, port, out: (r, seed, port, out))
 
 
 for _s in _RANDOM_SEEDS:
-    _job(("random", _s), lambda s_=_s: _random_case(s_))
+    _job(("random", _s), lambda s_=_s: _random_case(s_), _random_world(_s))
 
 
 @pytest.mark.parametrize("seed", _RANDOM_SEEDS)
@@ -422,7 +451,7 @@ def _local_worker(rank, world, port, xy0, n, grid, out):
 
 _LOCAL_CASES = [(2, 0.1, 40_000, 96), (4, -0.15, 40_000, 96), (8, 0.0, 80_000, 128), (3, 0.47, 30_000, 96)]   # (the last: through a tilt flip)
 for _c in _LOCAL_CASES:
-    _job(("local",) + _c, lambda c=_c: _spawn_ranks(_local_worker, c[0], lambda r, port, out: (r, c[0], port, c[1], c[2], c[3], out)))
+    _job(("local",) + _c, lambda c=_c: _spawn_ranks(_local_worker, c[0], lambda r, port, out: (r, c[0], port, c[1], c[2], c[3], out)), _c[0])
 
 
 @pytest.mark.parametrize("world,xy0,n,grid", _LOCAL_CASES)
@@ -483,7 +512,7 @@ def _split_worker(rank, port, xy0, n, grid, out):
             pass
 
 
-_job("split", lambda: _spawn_ranks(_split_worker, 2, lambda r, port, out: (r, port, 0.1, 40_000, 96, out)))
+_job("split", lambda: _spawn_ranks(_split_worker, 2, lambda r, port, out: (r, port, 0.1, 40_000, 96, out)), 2)
 
 
 def test_functional_split_of_two_processes_follows_single_gpu():

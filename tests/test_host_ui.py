@@ -87,30 +87,21 @@ def test_seed_hash_matches_reference_arithmetic(mod, oracle):
 
 def test_hoomd_shim_covers_the_reference_example():
     """Every `hoomd....` name the reference's examples/run.py touches resolves on the stand-in package (the script itself
-    needs a GPU; it is not copied into this repo).  Skipped where the reference tree is not mounted."""
-    import ast
+    needs a GPU; it is not copied into this repo).  The names are tests/golden/reference_example_names.json, which
+    tests/golden/make_example_names_fixture.py reads off the script; where the reference tree is mounted the script is also run
+    top to bottom on the stand-in (and tests/test_cmini.py checks the stored names against it)."""
     import importlib
+    import json
     import os
     import sys
-    ref = "/root/reference/examples/run.py"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests", "golden"))
+    import make_example_names_fixture as mx
+    sys.path.pop(0)
+    used = json.load(open(mx.OUT))
+    imports, chains = used["imports"], {tuple(c) for c in used["chains"]}
     sys.path.insert(0, os.path.join(root, "compat"))
     try:
-        tree = ast.parse(open(ref).read())
-        chains, imports = set(), set()
-        for node in ast.walk(tree):
-            if isinstance(node, ast.Import):
-                imports.update(a.name for a in node.names if a.name.startswith("hoomd"))
-            elif isinstance(node, ast.ImportFrom) and node.module and node.module.startswith("hoomd"):
-                imports.update(node.module + "." + a.name for a in node.names)
-            elif isinstance(node, ast.Attribute):
-                parts, cur = [], node
-                while isinstance(cur, ast.Attribute):
-                    parts.append(cur.attr); cur = cur.value
-                if isinstance(cur, ast.Name) and cur.id == "hoomd":
-                    chains.add(tuple(reversed(parts)))
         assert chains and imports
         for name in sorted(imports):
             try:
@@ -133,45 +124,48 @@ def test_hoomd_shim_covers_the_reference_example():
         sig = inspect.signature(hoomd.PSEv1.shear_function.sine.__init__).parameters
         for kw in ("dt", "shear_rate", "shear_freq"):
             assert kw in sig, kw
-        # dry run: execute the script top to bottom with the two GPU-touching entry points replaced by recorders
-        import runpy
-        import tempfile
-        from pse_amd import context as pctx, integrate as pint, system as psys
-        calls = {}
+        # dry run, where the reference tree is mounted: execute the script top to bottom with the two GPU-touching entry points
+        # replaced by recorders
+        script = os.path.join(mx.REF, "examples", "run.py")
+        if os.path.exists(script):
+            import runpy
+            import tempfile
+            from pse_amd import context as pctx, integrate as pint, system as psys
+            calls = {}
 
-        class FakeSystem:
-            def __init__(self, a, n):
-                self.n, self.dt, self.timestep, self.integrators = n ** 3, None, 0, []
-                self.box = (n * a, n * a, n * a, 0.0)
-                calls["lattice"] = (a, n)
-                pctx.current = self
+            class FakeSystem:
+                def __init__(self, a, n):
+                    self.n, self.dt, self.timestep, self.integrators = n ** 3, None, 0, []
+                    self.box = (n * a, n * a, n * a, 0.0)
+                    calls["lattice"] = (a, n)
+                    pctx.current = self
 
-            def all(self):
-                return ("group", self)
+                def all(self):
+                    return ("group", self)
 
-            def run(self, nsteps):
-                calls["run"] = nsteps
+                def run(self, nsteps):
+                    calls["run"] = nsteps
 
-        def fake_pse(**kw):
-            calls["pse"] = kw
-            return object()
+            def fake_pse(**kw):
+                calls["pse"] = kw
+                return object()
 
-        real_create, real_pse = psys.System.create_lattice_sc, pint.PSEv1
-        psys.System.create_lattice_sc = classmethod(lambda cls, a, n, dt=1e-3: FakeSystem(a, n))
-        pint.PSEv1 = fake_pse
-        cwd = os.getcwd()
-        try:
-            with tempfile.TemporaryDirectory() as tmp:
-                os.chdir(tmp)
-                os.environ.pop("PSE_EXAMPLE_STEPS", None)
-                runpy.run_path(ref, run_name="__main__")
-        finally:
-            os.chdir(cwd)
-            psys.System.create_lattice_sc, pint.PSEv1 = real_create, real_pse
-            pctx.current = None
-        assert calls["lattice"] == (6.4, 10) and calls["run"] == 1000
-        assert pctx.current is None and calls["pse"]["xi"] == 0.5 and calls["pse"]["error"] == 1e-3 and calls["pse"]["seed"] == 1
-        assert type(calls["pse"]["function_form"]).__name__ == "sine"
+            real_create, real_pse = psys.System.create_lattice_sc, pint.PSEv1
+            psys.System.create_lattice_sc = classmethod(lambda cls, a, n, dt=1e-3: FakeSystem(a, n))
+            pint.PSEv1 = fake_pse
+            cwd = os.getcwd()
+            try:
+                with tempfile.TemporaryDirectory() as tmp:
+                    os.chdir(tmp)
+                    os.environ.pop("PSE_EXAMPLE_STEPS", None)
+                    runpy.run_path(script, run_name="__main__")
+            finally:
+                os.chdir(cwd)
+                psys.System.create_lattice_sc, pint.PSEv1 = real_create, real_pse
+                pctx.current = None
+            assert calls["lattice"] == (6.4, 10) and calls["run"] == 1000
+            assert pctx.current is None and calls["pse"]["xi"] == 0.5 and calls["pse"]["error"] == 1e-3 and calls["pse"]["seed"] == 1
+            assert type(calls["pse"]["function_form"]).__name__ == "sine"
     finally:
         sys.path.pop(0)
 

@@ -3,43 +3,36 @@
 they lie, into oracle/_ref/libpse_ref_shear.so (git-ignored; built in the build container, travels to the GPU box as a built file).
 Here the COMPILED reference is the judge of three things: (1) the fixture that round 2 produced by evaluating the text of those
 getters (tests/golden/reference_arithmetic.json, "as_written") -- so the text-evaluation route is itself checked against a real
-build; (2) the oracle's restatement; (3) the product's C++ host classes.  ("what's missing" 3.)"""
-import ctypes
+build; (2) the oracle's restatement; (3) the product's C++ host classes.  ("what's missing" 3.)
+The library's numbers are kept in tests/golden/reference_shear_built.json (tests/golden/make_built_shear_fixture.py), so that the
+checks run where the reference tree is not mounted; where the library has been built it must reproduce them exactly."""
 import json
 import os
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "oracle", "_ref", "libpse_ref_shear.so")
 FIX = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_arithmetic.json")))
 KIND = {"sine": 0, "sine_offset": 0, "steady": 1, "chirp": 2, "tukey": 3}
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_built_shear_fixture as built  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def ref():
-    if not os.path.exists(LIB):
-        if not os.path.isdir("/root/reference"):
-            pytest.skip("oracle/_ref/libpse_ref_shear.so has not been built (needs /root/reference: `make -C oracle ref`)")
-        import subprocess
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.DEVNULL)
-    L = ctypes.CDLL(LIB)
-    L.pse_ref_shear.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
-    L.pse_ref_shear_windowed.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                         ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
-
-    def args(a):
-        return (ctypes.c_double * len(a))(*[float(x) for x in a])
+    """value(name, t, what) of the reference as built (what = 0 shear rate, 1 strain, 2 offset): the numbers of
+    tests/golden/reference_shear_built.json -- and wherever build() has compiled oracle/_ref/libpse_ref_shear.so, the library
+    gives exactly those numbers."""
+    stored = json.load(open(built.OUT))
+    if os.path.exists(built.LIB):
+        assert built.values(built.library()) == stored, "tests/golden/reference_shear_built.json differs from the built reference"
+    at = {name: {t: k for k, t in enumerate(rows["timesteps"])} for name, rows in FIX["shear"]["functions"].items()}
 
     def value(name, t, what):
-        f = FIX["shear"]["functions"]
-        out = ctypes.c_double()
-        if name == "windowed_chirp_tukey":
-            rc = L.pse_ref_shear_windowed(2, args(f["chirp"]["args"]), 3, args(f["tukey"]["args"]), t, what, ctypes.byref(out))
-        else:
-            rc = L.pse_ref_shear(KIND[name], args(f[name]["args"]), t, what, ctypes.byref(out))
-        assert rc == 0
-        return out.value
+        if what == 2:
+            return stored[name]["offset"]
+        return stored[name]["shear_rate" if what == 0 else "strain"][at[name][t]]
     return value
 
 

@@ -3,7 +3,7 @@
 # step time, far-field phases, the candidates' probe times, and what the planner costs at create.
 #   bash tools/debug/place_ab.sh [repeats] [extra bench arguments, e.g. "--n 4194304 --phi 0.3 --grid 512 --steps 8 --warmup 3"]
 mkdir -p gpurun_out/place
-R=${1:-4}; X=${2:-}
+R=${1:-4}; X="--full ${2:-}"      # (the line read below needs the M.F rates and phases of --full)
 for rep in $(seq $R); do
 for k in 0 6; do
   echo "== PSE_PLACE_TRIALS=$k"
