@@ -416,10 +416,11 @@ def lanczos_sqrt(matvec, psi, m_in=2, tol=1e-3, m_max=100):
     return (norm * u).reshape(shape), m
 
 
-def brownian_velocity(pos, force, box, p, kT, dt, seed, timestep, m_in=2, pair_rounded=True):
+def brownian_velocity(pos, force, box, p, kT, dt, seed, timestep, m_in=2, pair_rounded=False):
     """Brownian.cu:772-923: u = M.F + sqrt(2kT/dt) M^{1/2} psi, wave noise drawn in k-space.
     pair_rounded: the near-field operator inside the Lanczos iteration with the rounded pair coefficients of the build's pair list
-    (False: the all-double algorithm the golden fixture was pinned with; the two differ by ~1e-8 relative)."""
+    (the bit-level restatement of the device); False, the default: the all-double algorithm, the truth the golden fixture was pinned
+    with (the two differ by ~1e-8 relative)."""
     nk = noise_k(box, p, kT, dt, seed, timestep) if kT > 0 else None
     u = mobility_wave(pos, force, box, p, extra_k=nk) + mobility_real(pos, force, box, p["xi"], p["rcut"])
     m = m_in

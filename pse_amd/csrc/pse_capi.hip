@@ -2004,6 +2004,10 @@ static int velocity(pse_team &T, const std::vector<Args> &a, const unsigned *gro
                     unsigned timestep, int *m_io, unsigned *mask, const StepTail *tail = nullptr) {
     for (pse_handle *h : T.m)
         if (h->loc.on) return fail(PSE_ERR_INVALID, "this handle is an owned-particle rank (pse_params.local_rows): drive it through pse_team_step_local");
+    // tail_done says that THIS call's Lanczos combination wrote the summed rows.  A call with noise but without the real-space half
+    // (parts = 2, kT > 0: no Lanczos iteration) must not read what an earlier Brownian call on the same handle left there -- it would
+    // skip its own sum and never write vel.  The reset here and the lz guards below each prevent that alone; both are kept.
+    for (pse_handle *h : T.m) h->tail_done = false;
     diag_begin(T);
     for (size_t r = 0; r < T.m.size(); ++r)
         if (T.solo < 0 || T.m[r]->slab_rank == T.solo)   // psi rides with the gather into cell order: the near-field pass that
@@ -2082,12 +2086,12 @@ static int velocity(pse_team &T, const std::vector<Args> &a, const unsigned *gro
         // every rank has all three contributions for the rows it owns: add them, exchange the row blocks once
         for (pse_handle *h : act(T))
             if ((parts & 2) && h->side_on) {   // join: the gathered far-field velocity is needed now
-                if (h == act(T)[0] && !(noise && h->tail_done)) diag_mark(T, 3, h->side);
+                if (h == act(T)[0] && !(lz && h->tail_done)) diag_mark(T, 3, h->side);
                 HIPCHK(hipEventRecord(h->ev_join, h->side));
                 HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
             }
         for (pse_handle *h : act(T)) {
-            if (noise && h->tail_done) continue;   // the Lanczos combination has written the summed rows already
+            if (lz && h->tail_done) continue;   // the Lanczos combination has written the summed rows already
             int lo, hi;
             row_range(h, N, lo, hi);
             launch_sum_rows((parts & 2) ? h->uw_s : nullptr, (parts & 1) ? h->ur_s : nullptr, lz ? h->ub_s : nullptr,
@@ -2105,7 +2109,7 @@ static int velocity(pse_team &T, const std::vector<Args> &a, const unsigned *gro
         const double4 *ua = T.G > 1 ? h->utot_s : ((parts & 2) ? h->uw_s : nullptr);
         const double4 *ub = T.G > 1 ? nullptr : ((parts & 1) ? h->ur_s : nullptr), *uc = T.G > 1 ? nullptr : (lz ? h->ub_s : nullptr);
         const unsigned *tags = T.G > 1 ? nullptr : h->tag_s;     // a team: the tag travels in the fourth component of its row
-        if (!(T.G == 1 && noise && h->tail_done)) launch_scatter_sum(ua, ub, uc, tags, N, a[r].vel, h->stream);   // (single GPU: the Lanczos combination has un-sorted the sum)
+        if (!(T.G == 1 && lz && h->tail_done)) launch_scatter_sum(ua, ub, uc, tags, N, a[r].vel, h->stream);   // (single GPU: the Lanczos combination has un-sorted the sum)
         if (tail) {
             // The Euler update stays its own pass in the CALLER's order (replicated state: every rank updates every particle,
             // bit-identically).  Fused into the un-sort it ran over the sorted rows and made five arrays scattered instead of

@@ -14,7 +14,7 @@ from oracle import pse_port as pp  # noqa: E402
 pos, force, box = make_suspension(64, L=16.0, xy=0.2, seed=2024, fseed=2025)
 xi, error, kT, dt, seed, ts = 0.5, 1e-3, 1.0, 1e-3, 31337, 42
 p = pp.select_params(box, xi, error, 0.5)
-ub, m = pp.brownian_velocity(pos, force, box, p, kT, dt, seed, ts)
+ub, m = pp.brownian_velocity(pos, force, box, p, kT, dt, seed, ts, pair_rounded=False)
 out = {
     "pos": pos.tolist(), "force": force.tolist(), "box": list(box), "xi": xi, "error": error, "kT": kT, "dt": dt,
     "seed": seed, "timestep": ts, "u_direct": pp.mobility_direct(pos, force, box, xi).tolist(),

@@ -246,6 +246,11 @@ def test_local_team_step_captured_into_a_graph(lanes, monkeypatch):
     st.synchronize()
     for s in S:
         s.refresh_force(cap.force_dev)
+    # step 0 from identical positions, both eager: the two teams agree to round-off
+    pe, ue, ie, oe = eager.gather()
+    pc, uc, ic, oc = cap.gather()
+    print(f"step 0: captured team against eager team {np.abs(pc - pe).max():.2e}", flush=True)
+    assert np.abs(pc - pe).max() < 1e-12 and np.array_equal(ic, ie) and np.array_equal(oc, oe), np.abs(pc - pe).max()
     g = torch.cuda.CUDAGraph()
     torch.cuda.synchronize()
     with torch.cuda.graph(g, stream=st, capture_error_mode="thread_local"):
@@ -262,6 +267,10 @@ def test_local_team_step_captured_into_a_graph(lanes, monkeypatch):
         pe, ue, ie, oe = eager.gather()
         pc, uc, ic, oc = cap.gather()
         assert [e.info()["lanczos_m"] for e in cap.engines] == [e.info()["lanczos_m"] for e in eager.engines], k
+        if k == 0:
+            # the first replay starts from positions that agree to round-off: one evaluation, 1e-9 of a step
+            print(f"replay 0: captured team against eager team {np.abs(pc - pe).max():.2e} (dt {dt})", flush=True)
+            assert np.abs(pc - pe).max() < 1e-9 * dt, np.abs(pc - pe).max()
         # (two teams, six Brownian steps: the far-field bins fill in the order their atomics arrive, sums differ by 1e-16, and a
         # rounded pair coefficient that rounds the other way moves one particle by ~1e-9 dt: conftest.py TRAJ_TOL_BROWNIAN)
         assert np.abs(pc - pe).max() < TRAJ_TOL_BROWNIAN * dt / 0.25 and np.array_equal(ic, ie) and np.array_equal(oc, oe), (k, np.abs(pc - pe).max())

@@ -57,8 +57,13 @@ def test_reused_list_matches_fresh_build(torch_cuda, oracle, xy):
     assert m == mref
     assert rel(vb.cpu().numpy()[:, :3], refb) < 1e-11, rel(vb.cpu().numpy()[:, :3], refb)
     p = oracle.select_params(box, 0.5, 1e-3, 0.5)
-    port, mp = oracle.brownian_velocity(moved, force, box, p, kT, dt, seed, 5)
+    port, mp = oracle.brownian_velocity(moved, force, box, p, kT, dt, seed, 5, pair_rounded=True)
     assert m == mp and rel(vb.cpu().numpy()[:, :3], port) < 1e-9
+    # the truth: the un-rounded algorithm (N = 2000: a fixed 1e-6 relative, m within one)
+    tru, mt = oracle.brownian_velocity(moved, force, box, p, kT, dt, seed, 5, pair_rounded=False)
+    # (MI355X: 6.9e-8 at xy = 0, 7.0e-8 at xy = 0.3, m 7 / 7)
+    print(f"truth reused list xy = {xy}: rel {rel(vb.cpu().numpy()[:, :3], tru):.2e}, m {m} / {mt}", flush=True)
+    assert abs(m - mt) <= 1 and rel(vb.cpu().numpy()[:, :3], tru) < 1e-6, (m, mt, rel(vb.cpu().numpy()[:, :3], tru))
 
 
 def test_distance_check_forces_a_rebuild(torch_cuda, oracle):
@@ -151,6 +156,11 @@ def test_overflow_rows_on_the_kept_list(torch_cuda, oracle):
     up, mp = oracle.lanczos_sqrt(matvec, psi, 2, 1e-3)
     assert m == mp, (m, mp)
     assert rel(out.cpu().numpy()[:, :3], up) < 1e-9
+    # the truth: the un-rounded operator (N = 2000: a fixed 1e-6 relative, m within one)
+    ut, mt = oracle.lanczos_sqrt(lambda v: oracle.mobility_real(moved, np.ascontiguousarray(v), box, 0.5, rcut, rounded=False), psi, 2, 1e-3)
+    # (MI355X: 8.2e-8, m 9 / 9)
+    print(f"truth overflow on the kept list: rel {rel(out.cpu().numpy()[:, :3], ut):.2e}, m {m} / {mt}", flush=True)
+    assert abs(m - mt) <= 1 and rel(out.cpu().numpy()[:, :3], ut) < 1e-6, (m, mt, rel(out.cpu().numpy()[:, :3], ut))
     d = moved[:nb, None] - moved[None]
     d -= L * np.round(d / L)
     counts = (np.linalg.norm(d, axis=2) < rcut).sum(1) - 1
@@ -165,6 +175,10 @@ def test_overflow_rows_on_the_kept_list(torch_cuda, oracle):
     mv2 = lambda v: oracle.mobility_real(pos2, np.ascontiguousarray(v), box, 0.5, rcut, rounded=True)
     up2, mp2 = oracle.lanczos_sqrt(mv2, psi, 2, 1e-3)
     assert m2 == mp2 and rel(out2.cpu().numpy()[:, :3], up2) < 1e-9
+    ut2, mt2 = oracle.lanczos_sqrt(lambda v: oracle.mobility_real(pos2, np.ascontiguousarray(v), box, 0.5, rcut, rounded=False), psi, 2, 1e-3)
+    # (MI355X: 2.2e-7, m 15 / 15)
+    print(f"truth too dense for the kept list: rel {rel(out2.cpu().numpy()[:, :3], ut2):.2e}, m {m2} / {mt2}", flush=True)
+    assert abs(m2 - mt2) <= 1 and rel(out2.cpu().numpy()[:, :3], ut2) < 1e-6, (m2, mt2, rel(out2.cpu().numpy()[:, :3], ut2))
 
 
 @pytest.mark.parametrize("edges,err", [(None, 1e-3), ((1.0, 1.35, 0.8), 1e-4)])

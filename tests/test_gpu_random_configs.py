@@ -86,7 +86,7 @@ def test_random_configuration(oracle, seed):
     assert (i["Nx"], i["Ny"], i["Nz"]) == p["grid"] and i["P"] == p["P"] and abs(i["eta"] - p["eta"]) < 1e-13
     pos, force = c["pos"], c["force"]
     ur = eng.mobility(to4(pos), to4(force), parts=1).cpu().numpy()[:, :3]
-    ref_r = oracle.mobility_real(pos, force, c["box"], c["xi"], i["rcut"])
+    ref_r = oracle.mobility_real(pos, force, c["box"], c["xi"], i["rcut"], rounded=False)
     assert rel(ur, ref_r) < 1e-12, ("near field", seed, rel(ur, ref_r))
     uw = eng.mobility(to4(pos), to4(force), parts=2).cpu().numpy()[:, :3]
     ref_w = oracle.mobility_wave(pos, force, c["box"], p)
@@ -94,9 +94,14 @@ def test_random_configuration(oracle, seed):
     u = eng.mobility(to4(pos), to4(force)).cpu().numpy()[:, :3]
     assert rel(u, ref_r + ref_w) < 1e-10
     vel, m = eng.brownian_velocity(to4(pos), to4(force), 0.7, 2e-3, 5 + seed)
-    ref, mref = oracle.brownian_velocity(pos, force, c["box"], p, 0.7, 2e-3, c["seed"], 5 + seed)
+    ref, mref = oracle.brownian_velocity(pos, force, c["box"], p, 0.7, 2e-3, c["seed"], 5 + seed, pair_rounded=True)
     assert m == mref, (seed, m, mref)
     assert rel(vel.cpu().numpy()[:, :3], ref) < 1e-9, ("Brownian", seed, rel(vel.cpu().numpy()[:, :3], ref))
+    # the truth: the un-rounded algorithm (beyond the dense matrix: a fixed 1e-6 relative, m within one)
+    tru, mt = oracle.brownian_velocity(pos, force, c["box"], p, 0.7, 2e-3, c["seed"], 5 + seed, pair_rounded=False)
+    # (MI355X, all 42 configurations: at most 4.7e-7, m equal in every one)
+    print(f"truth random {seed} Brownian: rel {rel(vel.cpu().numpy()[:, :3], tru):.2e}, m {m} / {mt}", flush=True)
+    assert abs(m - mt) <= 1 and rel(vel.cpu().numpy()[:, :3], tru) < 1e-6, ("Brownian truth", seed, m, mt, rel(vel.cpu().numpy()[:, :3], tru))
     if seed % 3 == 0 and c["n"] >= 64:
         # a particle GROUP (d_group_members / group_size of the reference): the listed particles interact among themselves only, the
         # others keep what they had; and the stand-alone near-field square root on the same group
@@ -106,7 +111,7 @@ def test_random_configuration(oracle, seed):
         vel = to4(np.full((n, 3), -3.0), w=1.25)
         eng.mobility(to4(pos), to4(force), vel=vel, group=g)
         v = vel.cpu().numpy()
-        sub_ref = oracle.mobility_real(pos[members], force[members], c["box"], c["xi"], i["rcut"]) + oracle.mobility_wave(pos[members], force[members], c["box"], p)
+        sub_ref = oracle.mobility_real(pos[members], force[members], c["box"], c["xi"], i["rcut"], rounded=False) + oracle.mobility_wave(pos[members], force[members], c["box"], p)
         assert rel(v[members, :3], sub_ref) < 1e-10, ("group", seed)
         others = np.setdiff1d(np.arange(n), members)
         assert np.all(v[others, :3] == -3.0) and np.all(v[:, 3] == 1.25)
@@ -115,6 +120,11 @@ def test_random_configuration(oracle, seed):
         mv = lambda x: oracle.mobility_real(pos[members], np.ascontiguousarray(x), c["box"], c["xi"], i["rcut"], rounded=True)   # noqa: E731
         up, mp = oracle.lanczos_sqrt(mv, psi[members], 2, 1e-4)
         assert ms == mp and rel(out.cpu().numpy()[members, :3], up) < 1e-9, ("sqrt on a group", seed, ms, mp)
+        mvt = lambda x: oracle.mobility_real(pos[members], np.ascontiguousarray(x), c["box"], c["xi"], i["rcut"], rounded=False)   # noqa: E731
+        ut, mt = oracle.lanczos_sqrt(mvt, psi[members], 2, 1e-4)
+        # (MI355X, 13 configurations: at most 4.9e-7, m equal)
+        print(f"truth random {seed} sqrt on a group: rel {rel(out.cpu().numpy()[members, :3], ut):.2e}, m {ms} / {mt}", flush=True)
+        assert abs(ms - mt) <= 1 and rel(out.cpu().numpy()[members, :3], ut) < 1e-6, ("sqrt on a group, truth", seed, ms, mt)
     if seed % 2 == 0 and c["n"] >= 8:
         # the force provider on the same cell grid (soft repulsion, O(N^2) port) and one full sheared step: Euler update and the
         # triclinic wrap in a box with three different edges (PSEv1/Stokes.cu:156-190)
@@ -127,11 +137,16 @@ def test_random_configuration(oracle, seed):
         accel = torch.zeros((n, 3), dtype=torch.float64, device="cuda")
         image = torch.zeros((n, 3), dtype=torch.int32, device="cuda")
         eng.step(dpos, dvel, accel, image, to4(force, w=0.5), 0.7, dt, ts, shear_rate=rate)
-        u, _ = oracle.brownian_velocity(pos, force, c["box"], p, 0.7, dt, c["seed"], ts)
+        u, _ = oracle.brownian_velocity(pos, force, c["box"], p, 0.7, dt, c["seed"], ts, pair_rounded=True)
         newpos, newimg = oracle.integrate(pos, np.zeros((n, 3), dtype=np.int64), u, c["box"], dt, rate)
         got = dpos.cpu().numpy()
         same = np.all(image.cpu().numpy() == newimg, axis=1)          # a particle that lands within rounding of a face may wrap either way
         assert same.sum() >= n - 1, ("images", seed, n - same.sum())
         assert np.abs(got[same, :3] - newpos[same]).max() < 1e-8, ("step", seed, np.abs(got[same, :3] - newpos[same]).max())
         assert np.all(got[:, 3] == 3.0) and np.abs(accel.cpu().numpy() - force / 2.0).max() < 1e-15
+        # the truth: the velocity the device's step wrote against the un-rounded algorithm (a fixed 1e-6 relative)
+        ut, _ = oracle.brownian_velocity(pos, force, c["box"], p, 0.7, dt, c["seed"], ts, pair_rounded=False)
+        # (MI355X, 20 configurations: at most 2.4e-7)
+        print(f"truth random {seed} step velocity: rel {rel(dvel.cpu().numpy()[:, :3], ut):.2e}", flush=True)
+        assert rel(dvel.cpu().numpy()[:, :3], ut) < 1e-6, ("step truth", seed, rel(dvel.cpu().numpy()[:, :3], ut))
     eng.close()

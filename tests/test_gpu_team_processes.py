@@ -397,6 +397,29 @@ def _local_worker(rank, world, port, xy0, n, grid, out):
             dpos, dF, vel = to4(pos), to4(force), to4(np.zeros((n, 3)), 1.0)
             accel = torch.zeros((n, 3), dtype=torch.float64, device="cuda"); image = torch.zeros((n, 3), dtype=torch.int32, device="cuda")
             _, m0 = ref.brownian_velocity(dpos, dF, kT, dt, 99, vel=to4(np.zeros((n, 3)), 1.0), lanczos_m=2)
+        # one Brownian evaluation from the loaded positions (no integration): deterministic, so the team agrees with the single GPU
+        # at 1e-9 with the same Lanczos count on every rank -- the trajectory bound below is for divergence over steps only.  The
+        # team's step only queues work: it starts at the count the single GPU converged at (tests/test_gpu_local.py does the same)
+        if rank == 0:
+            _, mb = ref.brownian_velocity(dpos, dF, kT, dt, 98, vel=to4(np.zeros((n, 3)), 1.0), lanczos_m=2)
+        box_m = [mb if rank == 0 else None]
+        dist.broadcast_object_list(box_m, src=0)
+        sim.step(kT, dt, 98, lanczos_m=box_m[0], integrate=False)
+        tg, p, u, im = sim.gather_local()
+        info = sim.engine.info()
+        got = [None] * world if rank == 0 else None
+        dist.gather_object((tg, p, u, info["lanczos_m"], info["lanczos_status"]), got, dst=0)
+        if rank == 0:
+            vb = to4(np.zeros((n, 3)), 1.0)
+            _, mb = ref.brownian_velocity(dpos, dF, kT, dt, 98, vel=vb, lanczos_m=mb)
+            U, P = np.full((n, 3), np.nan), np.full((n, 3), np.nan)
+            for r, (t_, p_, u_, m_, st_) in enumerate(got):
+                assert st_ == 0 and m_ == mb, ("single evaluation", r, m_, mb, st_)
+                U[t_] = u_; P[t_] = p_
+            vb = vb.cpu().numpy()[:, :3]
+            e1 = np.linalg.norm(U - vb) / np.linalg.norm(vb)
+            print(f"team of {world} processes, one Brownian evaluation: rel {e1:.2e}, m {mb}", flush=True)
+            assert e1 < 1e-9 and np.abs(P - pos).max() == 0.0, ("single evaluation", e1)
         box_m = [m0 if rank == 0 else None]
         dist.broadcast_object_list(box_m, src=0)
         m, xy = box_m[0], xy0

@@ -110,9 +110,9 @@ def test_lanczos_port_matches_dense_sqrt(oracle):
     pos, _, box = make_suspension(n, L=14.0)
     rcut = 5.2565
     eye = np.eye(3 * n)
-    M = np.stack([oracle.mobility_real(pos, eye[c].reshape(n, 3), box, 0.5, rcut).ravel() for c in range(3 * n)], 1)
+    M = np.stack([oracle.mobility_real(pos, eye[c].reshape(n, 3), box, 0.5, rcut, rounded=False).ravel() for c in range(3 * n)], 1)
     psi = oracle.psi_particles(n, 11, 4)
-    u, m = oracle.lanczos_sqrt(lambda v: oracle.mobility_real(pos, np.ascontiguousarray(v), box, 0.5, rcut), psi, 2, 1e-9)
+    u, m = oracle.lanczos_sqrt(lambda v: oracle.mobility_real(pos, np.ascontiguousarray(v), box, 0.5, rcut, rounded=False), psi, 2, 1e-9)
     ref = sl.sqrtm(M).real @ psi.ravel()
     assert np.linalg.norm(u.ravel() - ref) / np.linalg.norm(ref) < 1e-8
     assert abs(np.dot(u.ravel(), u.ravel()) - psi.ravel() @ M @ psi.ravel()) < 1e-7 * (psi.ravel() @ M @ psi.ravel())
@@ -127,7 +127,7 @@ def test_rounded_pair_coefficients_keep_one_symmetric_operator(oracle):
     pos, _, box = make_suspension(n, L=15.0, xy=0.25)
     rcut = 5.2565
     eye = np.eye(3 * n)
-    M = np.stack([oracle.mobility_real(pos, eye[c].reshape(n, 3), box, 0.5, rcut).ravel() for c in range(3 * n)], 1)
+    M = np.stack([oracle.mobility_real(pos, eye[c].reshape(n, 3), box, 0.5, rcut, rounded=False).ravel() for c in range(3 * n)], 1)
     Mf = np.stack([oracle.mobility_real(pos, eye[c].reshape(n, 3), box, 0.5, rcut, rounded=True).ravel() for c in range(3 * n)], 1)
     assert np.array_equal(Mf, Mf.T)
     assert 1e-9 < np.abs(Mf - M).max() < 3e-7 * np.abs(M).max()
@@ -198,7 +198,7 @@ def test_golden_fixture(oracle):
     assert m == g["lanczos_m"]
     assert np.abs(ub - np.array(g["u_brownian_port"])).max() < 1e-9 * np.abs(ub).max()
     # the same step with the rounded pair coefficients of the build's Lanczos mat-vecs: same m, within 1e-7
-    uf, mf = oracle.brownian_velocity(pos, force, box, p, g["kT"], g["dt"], g["seed"], g["timestep"])
+    uf, mf = oracle.brownian_velocity(pos, force, box, p, g["kT"], g["dt"], g["seed"], g["timestep"], pair_rounded=True)
     assert mf == m and 0.0 < np.abs(uf - ub).max() < 1e-7 * np.abs(ub).max()
     assert [int(x) for x in oracle.philox4x32(1, 2, 3, 4, 5, 6)] == g["philox_1_2_3_4_5_6"]
     assert oracle.hash_seed(1) == g["hash_seed_1"]
