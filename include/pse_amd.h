@@ -18,7 +18,10 @@
  * the 16-byte records of the per-step pair list, rounded to single-precision accuracy (f to 2^-25 absolute, the vector to 2^-22 of its
  * largest component), and (single GPU) its neighbours' vector rows to 2^-39 of their largest component; sums accumulate in fp64, the
  * operator stays exactly symmetric, the deterministic U = M.F never sees those numbers (oracle/pse_oracle.c pair_term restates the
- * rounding of the coefficients operation by operation; DESIGN.md sections 2 and 4).
+ * rounding of the coefficients operation by operation; DESIGN.md sections 2 and 4).  That rounding bounds what the tolerance can buy:
+ * below about 1e-6 the 16-byte records do NOT honour it (their own error is 1e-6 - 1e-5 of M_real^{1/2} psi in dense suspensions, at
+ * large xi or with close pairs).  pse_set_lanczos_operator(h, PSE_LANCZOS_FP64) keeps the operator of the iteration in fp64 throughout
+ * -- coefficients, the neighbours' rows and the root -- and then the tolerance holds down to the fp64 round-off.
  */
 #ifndef PSE_AMD_H
 #define PSE_AMD_H
@@ -50,7 +53,8 @@ typedef struct pse_params {
     unsigned int n_max;      /* capacity in particles (N_total of the reference) */
     double Lx, Ly, Lz, xy;   /* box; |xy| <= 0.5 (HOOMD flips the box there; beyond it the minimum image is not exact): else PSE_ERR_INVALID */
     double xi;               /* Ewald splitting parameter (PSEv1/Stokes.cc:91) */
-    double error;            /* tolerance for all approximations (m_error) */
+    double error;            /* tolerance for all approximations (m_error); the Lanczos noise honours it below ~1e-6 only with
+                                PSE_LANCZOS_FP64 (pse_set_lanczos_operator): the default 16-byte pair records are single-precision accurate */
     double max_strain;       /* largest |xy| the box will take; sizes P (PSEv1/Stokes.cc:217-229) */
     unsigned int seed;       /* RNG seed as used on the device (the host class hashes the user seed, Stokes.cc:102) */
     int Nx, Ny, Nz;          /* FFT grid override (0 = PSEv1/Stokes.cc:138-199).  The reference's rule makes the three spacings equal up
@@ -337,6 +341,20 @@ int pse_team_set_lanczos_extra(pse_team *team, int extra);
  * all (ten launches that would leave at once: ~ 25 us of a 3 ms step at the metric point); pse_info.lanczos_status = 1 /
  * lanczos_open_calls say when it did not.  The reference iterates until the step norm passes (PSEv1/Brownian.cu:606-724). */
 int pse_set_lanczos_extra(pse_handle *h, int extra);
+/* The near-field operator inside the Lanczos iteration of M_real^{1/2} psi (pse_brownian_velocity, pse_brownian_velocity_part, pse_step,
+ * pse_sqrt_mreal, the team calls).  PSE_LANCZOS_RECORDS16 (default): the pair coefficients from the 16-byte records of the per-step pair
+ * list, rounded to single-precision accuracy, and (single GPU) the neighbours' rows from their 16-byte mirror -- see the precision note
+ * at the top; tolerances below about 1e-6 are not honoured.  PSE_LANCZOS_FP64: the exact fp64 operator everywhere the iteration applies
+ * it -- a 32-byte plane of fp64 coefficients beside the records (allocated by the first call that selects it, here on the host, and
+ * counted in pse_info.device_bytes: 32 bytes per pair-list slot), the rows gathered as doubles, the square root in double; each
+ * mat-vec streams about three times the bytes.  The environment variable PSE_LANCZOS_OP=fp64, read in pse_create, sets the starting
+ * mode.  Calls already queued keep the mode they were queued with; a graph captured before a switch keeps its mode and must be
+ * captured again.  In-process team calls refuse members whose modes differ (PSE_ERR_INVALID); the ranks of a process team must all
+ * set the same mode.  The deterministic U = M.F and the far field are fp64 in either mode.  Other values, a null handle or pointer:
+ * PSE_ERR_INVALID. */
+enum pse_lanczos_operator { PSE_LANCZOS_RECORDS16 = 0, PSE_LANCZOS_FP64 = 1 };
+int pse_set_lanczos_operator(pse_handle *h, int op);
+int pse_get_lanczos_operator(pse_handle *h, int *op);
 /* row capacities of an owned-particle handle: own rows (= capacity the caller's arrays need), ghost rows per side, records per
  * neighbour message of the first exchange; cell layers along x in all and per rank (any pointer may be null) */
 int pse_local_layout(pse_handle *h, int *rows_own, int *rows_ghost, int *records, int *layers, int *layers_per_rank);

@@ -143,6 +143,8 @@ SYMBOLS = {
     "pse_team_local_status": (_i, [_vp, _ip]),
     "pse_team_set_lanczos_extra": (_i, [_vp, _i]),
     "pse_set_lanczos_extra": (_i, [_vp, _i]),
+    "pse_set_lanczos_operator": (_i, [_vp, _i]),
+    "pse_get_lanczos_operator": (_i, [_vp, _ip]),
     "pse_team_redistribute_local": (_i, [_vp] + [ctypes.POINTER(_vp)] * 7),
     "pse_team_set_diag": (_i, [_vp, _i]),
     "pse_team_get_diag": (_i, [_vp, ctypes.POINTER(pse_team_diag)]),

@@ -18,6 +18,7 @@ struct pse_handle {
     std::vector<double> coef;
     int n_intervals = 0;
     unsigned long long steps = 0;
+    int lz_op = PSE_LANCZOS_RECORDS16;
 };
 struct pse_team { int unused; };
 
@@ -91,6 +92,18 @@ int pse_debug_grid_placement(pse_handle *, int *, float *, float *) { return no_
 int pse_debug_vq_roundtrip(int, const double *, double *) { return no_device("pse_debug_vq_roundtrip"); }
 int pse_debug_matvec_ms(pse_handle *, int, float *) { return no_device("pse_debug_matvec_ms"); }
 int pse_set_lanczos_extra(pse_handle *, int) { return no_device("pse_set_lanczos_extra"); }
+// the operator choice is host state (the fp64 plane would be allocated on the device: the stub only records the choice)
+int pse_set_lanczos_operator(pse_handle *h, int op) {
+    if (!h) return fail(PSE_ERR_INVALID, "pse_set_lanczos_operator: null handle");
+    if (op != PSE_LANCZOS_RECORDS16 && op != PSE_LANCZOS_FP64) return fail(PSE_ERR_INVALID, "pse_set_lanczos_operator: %d is not an operator", op);
+    h->lz_op = op;
+    return 0;
+}
+int pse_get_lanczos_operator(pse_handle *h, int *op) {
+    if (!h || !op) return fail(PSE_ERR_INVALID, "pse_get_lanczos_operator: null argument");
+    *op = h->lz_op;
+    return 0;
+}
 int pse_brownian_velocity_part(pse_handle *, const pse_double4 *, const pse_double4 *, pse_double4 *, const unsigned int *, unsigned int, double,
                                double, unsigned int, int, int *) { return no_device("pse_brownian_velocity_part"); }
 int pse_integrate(pse_handle *, pse_double4 *, const pse_double4 *, pse_double3 *, pse_int3 *, const pse_double4 *, const unsigned int *, unsigned int,

@@ -31,6 +31,13 @@ void Stokes::setParams() {
     p.Nx = m_Nx; p.Ny = m_Ny; p.Nz = m_Nz; p.P = m_P; p.rcut = m_rcut;
     p.device = -1; p.n_slabs = 1; p.slab_rank = 0;
     check(pse_create(&p, &m_h), "Error initializing Stokes");
+    if (m_lanczos_op >= 0) check(pse_set_lanczos_operator(m_h, m_lanczos_op), "Stokes::setLanczosOperator");
+}
+
+void Stokes::setLanczosOperator(int op) {
+    if (op != PSE_LANCZOS_RECORDS16 && op != PSE_LANCZOS_FP64) throw std::invalid_argument("Stokes::setLanczosOperator: unknown operator");
+    m_lanczos_op = op;
+    if (m_h) check(pse_set_lanczos_operator(m_h, op), "Stokes::setLanczosOperator");
 }
 
 void Stokes::setBox(BoxDim box) {

@@ -33,6 +33,9 @@ public:
     // explicit overrides of the parameter rule (0 = reference rule); must precede setParams
     void setOverrides(int Nx, int Ny, int Nz, int P, double rcut) { m_Nx = Nx; m_Ny = Ny; m_Nz = Nz; m_P = P; m_rcut = rcut; }
     void setParams();                                                                      // Stokes.cc:129-424
+    // the near-field operator of the Lanczos noise (enum pse_lanczos_operator; -1: the engine's default): applied now if the engine
+    // exists, and again by every setParams.  No reference counterpart (the reference's Lanczos is single precision throughout)
+    void setLanczosOperator(int op);
     void setBox(BoxDim box);                                                               // per-step box under shear
     void integrateStepOne(unsigned int timestep, const ParticleArrays &p);                 // Stokes.cc:429-523
     void integrateStepTwo(unsigned int) {}                                                 // Stokes.cc:528-530
@@ -54,6 +57,7 @@ private:
     int m_Nx = 0, m_Ny = 0, m_Nz = 0, m_P = 0;
     double m_rcut = 0.0;
     int m_m_Lanczos = 2;                                                                   // Stokes.cc:132
+    int m_lanczos_op = -1;
     pse_handle *m_h = nullptr;
 };
 

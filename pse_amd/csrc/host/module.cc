@@ -56,6 +56,7 @@ PYBIND11_MODULE(_PSEv1, m) {
         .def("setShear", &Stokes::setShear)
         .def("setDeltaT", &Stokes::setDeltaT)
         .def("setOverrides", &Stokes::setOverrides)
+        .def("setLanczosOperator", &Stokes::setLanczosOperator)
         .def("setBox", [](Stokes &s, double Lx, double Ly, double Lz, double xy) { s.setBox(BoxDim{Lx, Ly, Lz, xy}); })
         .def("integrateStepOne", [](Stokes &s, unsigned int timestep, std::uintptr_t pos, std::uintptr_t vel, std::uintptr_t accel,
                                     std::uintptr_t image, std::uintptr_t force, std::uintptr_t group, unsigned int n) {

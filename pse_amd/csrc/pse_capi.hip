@@ -95,6 +95,7 @@ struct pse_handle {
         int vq = 1;                  // PSE_VQ=0: the pair-list mat-vec gathers the neighbours' rows as doubles (two gathers per pair) (A/B)
         int place_trials = 10;       // PSE_PLACE_TRIALS=K: the two grids are allocated up to K times and the pair the x + inverse y + z passes run fastest on is kept (0, 1: off)
         int lz_extra = 2;            // PSE_LANCZOS_EXTRA: iterations a queue-only Brownian call queues beyond the starting count (gated on the device-side decision)
+        int lz_op = PSE_LANCZOS_RECORDS16;   // PSE_LANCZOS_OP=fp64: the handle starts with the fp64 Lanczos operator (pse_set_lanczos_operator)
     } tun;
     DCells bidx_nc = {0, 0, 0};      // cell grid the boundary-cell indices on the device belong to
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -111,7 +112,9 @@ struct pse_handle {
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
-    NbList nb = {};
+    NbList nb = {};              // nb.c64 = nb64 while the fp64 Lanczos operator is selected, else null
+    double4 *nb64 = nullptr;     // the fp64 plane of the pair list (allocated when the mode is first selected)
+    int lz_op = PSE_LANCZOS_RECORDS16;
     bool nb_valid = false;   // the pair list matches the current sorted positions
     bool lz_last_queued = false;   // the most recent Brownian call took its Lanczos decision on the device (pse_get_info then reads the host mirror)
     // neighbour list kept across steps (HOOMD's NeighborList with r_buff and a distance check every step, PSEv1/integrate.py:60,79)
@@ -226,6 +229,21 @@ static int dmalloc(pse_handle *h, T **p, size_t n) {
     h->bytes += n * sizeof(T);
     return 0;
 }
+// The Lanczos operator of the handle (pse_set_lanczos_operator): it travels with the pair list -- nb.c64 non-null selects the F64
+// instantiations of every kernel that writes or reads the list (pse_kernels.hip), so each launch keeps the mode it was queued with.
+static int set_lanczos_op(pse_handle *h, int op) {
+    if (op == PSE_LANCZOS_FP64 && h->nb.cap > 0 && !h->nb64) {   // (no pair list: every mat-vec walks the cells with the exact f, g already)
+        HIPCHK(hipSetDevice(h->device));
+        TRY(dmalloc(h, &h->nb64, nb_list64_bytes((size_t)h->n_pad + 1024, h->nb.cap) / sizeof(double4)));   // the geometry of nb.data
+        h->info.device_bytes = h->bytes;
+    }
+    if (op != h->lz_op) h->nb_valid = false;   // the list in place was written for the other operator
+    h->lz_op = op;
+    h->nb.c64 = op == PSE_LANCZOS_FP64 ? h->nb64 : nullptr;
+    return 0;
+}
+// the 16-byte mirror of the Lanczos vector, where the mat-vec reads it (records mode; the fp64 operator gathers the rows as doubles)
+static void *vq_of(const pse_handle *h) { return h->nb.c64 ? nullptr : h->vq; }
 // The passes that READ the spectra (inverse z, both y passes, the x pass) run 5 - 20 % faster or slower depending on where the driver
 // placed the two grids -- a property of the allocation that holds for the life of the buffers (round 5: the two speeds of the 512^3 x
 // pass; round 6: at 256^3 the inverse y + z passes take 0.293 - 0.329 ms on six pairs allocated one after another in one process, the
@@ -390,7 +408,7 @@ extern "C" int pse_destroy(pse_handle *h) {
     if (h->info_inv) rocfft_execution_info_destroy(h->info_inv);
     void *ptrs[] = {h->keys, h->keys_s, h->vals, h->perm, h->tag_s, h->sort_tmp, h->cell_off, h->cnt_block, h->sw.rec_t, h->sw.fb.off, h->sw.fb.rank_s, h->sw.fb.tmp, h->nb.data, h->nb.cnt, h->vl.idx, h->vl.cnt, h->pos_build, h->pos_s, h->posf_s, h->pv,
                     h->f_s, h->uw_s, h->ur_s, h->ub_s, h->psi_s, h->w_s, h->coef, h->rgrid, h->cgrid, h->sendbuf, h->recvbuf, h->d_bidx, h->d_bounds, h->utot_s, h->w2_s, h->u_s, h->sums_all, h->twiddle, h->twiddle_y_owned, h->twiddle_z_owned, h->fft_work, h->V,
-                    h->scal, h->partials, h->lz_state, h->vq};
+                    h->scal, h->partials, h->lz_state, h->vq, h->nb64};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &p : h->ph) { if (p.a) (void)hipEventDestroy(p.a); if (p.b) (void)hipEventDestroy(p.b); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -564,6 +582,7 @@ static int create_impl(const pse_params *p, pse_handle *h) {
         t.lz_extra = std::max(0, std::min(32, ienv("PSE_LANCZOS_EXTRA", 2)));
         t.place_trials = std::max(0, std::min(12, ienv("PSE_PLACE_TRIALS", 10)));
         t.vq = ienv("PSE_VQ", 1);
+        if (const char *v = getenv("PSE_LANCZOS_OP")) t.lz_op = !strcmp(v, "fp64") ? PSE_LANCZOS_FP64 : PSE_LANCZOS_RECORDS16;
         if (const char *v = getenv("PSE_TEAM_SCHED")) {
             int a = 1, b = 2, c = 3;
             if (sscanf(v, "%d,%d,%d", &a, &b, &c) == 3) { t.team_sched[0] = a; t.team_sched[1] = b; t.team_sched[2] = c; }
@@ -782,6 +801,7 @@ static int create_impl(const pse_params *p, pse_handle *h) {
         TRY(dmalloc(h, &h->partials, (size_t)LZ_NGRAM * h->npart_cap));
     }
     for (auto &ph : h->ph) { HIPCHK(hipEventCreate(&ph.a)); HIPCHK(hipEventCreate(&ph.b)); }
+    TRY(set_lanczos_op(h, h->tun.lz_op));
     h->info.device_bytes = h->bytes;
     if (h->tun.verbose) {
         // the parameter summary the reference prints at notice level 2 (PSEv1/Stokes.cc:241-252), one block on stderr
@@ -1676,7 +1696,7 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
     // the vector part of iteration j: x_{j+1} from the sums that are still in place
     auto vector_part = [&](int j, const int *gate) {
         launch_lz_update(vec(j), h->w_s, j > 0 ? vec(j - 1) : nullptr, h->V + (size_t)(j + 1) * stride, j, h->scal, rg, nrg_all, h->stream,
-                         nullptr, 0, h->sc_host_dev, gate, h->vq);   // (+ the mirror of x_{j+1}: the next mat-vec's gathers)
+                         nullptr, 0, h->sc_host_dev, gate, vq_of(h));   // (+ the mirror of x_{j+1}: the next mat-vec's gathers)
     };
     auto iteration = [&](int j, bool scalars_only, const int *gate) -> int {
         const bool have_y = j == 0 && h->w_is_mpsi;
@@ -1689,7 +1709,7 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
         if (fused)
             launch_mreal_lanczos(h->pos_s, vec(j), h->w_s, row_map(0, N), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
                                  LzFuse{vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr}, h->scal, nullptr, nullptr, h->stream,
-                                 h->vl_use ? h->vl : VerletList{}, 1, gate, DevRowArgs{}, j > 0 ? h->vq : nullptr);
+                                 h->vl_use ? h->vl : VerletList{}, 1, gate, DevRowArgs{}, j > 0 ? vq_of(h) : nullptr);
         else if (!(j == 0 && h->sums0_done))
             launch_lz_dots(vec(j), h->w_s, vjm1, 0, N, h->partials, h->npart_cap, h->scal, h->stream);
         h->w_is_mpsi = false; h->sums0_done = false;
@@ -1761,7 +1781,7 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
                     launch_mreal_lanczos(h->pos_s, xj, h->w_s, row_map(lo, hi), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef,
                                          h->nb, LzFuse{vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr}, h->scal,
                                          ev ? h->ph[PH_MATVEC].a : nullptr, ev ? h->ph[PH_MATVEC].b : nullptr, h->stream,
-                                         h->vl_use ? h->vl : VerletList{}, 1, nullptr, DevRowArgs{}, done > 0 && T.G <= 1 ? h->vq : nullptr);
+                                         h->vl_use ? h->vl : VerletList{}, 1, nullptr, DevRowArgs{}, done > 0 && T.G <= 1 ? vq_of(h) : nullptr);
                     if (timed) h->matvec_timed = true;
                 } else if (!(done == 0 && h->sums0_done)) {   // (iteration 0: the sums came with the pass that built the pair list)
                     launch_lz_dots(xj, h->w_s, vjm1, lo, hi, h->partials, h->npart_cap, h->scal, h->stream);
@@ -1783,7 +1803,7 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
                 const double4 *xj = done == 0 ? h->psi_s : h->V + (size_t)done * stride;
                 launch_lz_update(xj, h->w_s, done > 1 ? h->V + (size_t)(done - 1) * stride : (done == 1 ? h->psi_s : nullptr),
                                  h->V + (size_t)(done + 1) * stride, done, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0, h == h0 ? h->sc_host_dev : nullptr,
-                                 nullptr, T.G <= 1 ? h->vq : nullptr);
+                                 nullptr, T.G <= 1 ? vq_of(h) : nullptr);
             }
         }
         // (alpha, beta and the norm are already on their way: the update kernels write them to the mapped host buffer as well)
@@ -1835,7 +1855,7 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
             const double4 *xj = j == 0 ? h->psi_s : h->V + (size_t)j * stride;
             launch_lz_update(xj, h->w_s, j > 1 ? h->V + (size_t)(j - 1) * stride : (j == 1 ? h->psi_s : nullptr),
                              h->V + (size_t)(j + 1) * stride, j, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0, h == h0 ? h->sc_host_dev : nullptr,
-                             nullptr, T.G <= 1 ? h->vq : nullptr);
+                             nullptr, T.G <= 1 ? vq_of(h) : nullptr);
         }
         pending_beta = done;
         target = std::min(M_MAX, done + std::max(2, done / 4));
@@ -2575,7 +2595,7 @@ extern "C" int pse_debug_matvec_ms(pse_handle *h, int reps, float *ms_per_launch
         for (int r = 0; r < n; ++r)
             launch_mreal_lanczos(h->pos_s, h->V + stride, h->w_s, rm, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
                                  LzFuse{h->psi_s, h->partials, h->npart_cap, nullptr, nullptr, nullptr}, h->scal, nullptr, nullptr, h->stream,
-                                 VerletList{}, 1, nullptr, DevRowArgs{}, h->vq, true);
+                                 VerletList{}, 1, nullptr, DevRowArgs{}, vq_of(h), true);   // (the mat-vec of the handle's current operator)
     };
     run(2);
     HIPCHK(hipEventRecord(e0, h->stream));
@@ -2815,6 +2835,15 @@ extern "C" int pse_team_debug_solo(pse_team *T, int slab_rank) {
     return fail(PSE_ERR_INVALID, "no member with slab rank %d", slab_rank);
 }
 
+// the members of an in-process team run one Lanczos iteration together: they must apply the same operator
+static int team_same_operator(const pse_team *T) {
+    for (size_t r = 1; r < T->m.size(); ++r)
+        if (T->m[r]->lz_op != T->m[0]->lz_op)
+            return fail(PSE_ERR_INVALID, "team members use different Lanczos operators (member 0: %d, member %zu: %d): pse_set_lanczos_operator on every member",
+                        T->m[0]->lz_op, r, T->m[r]->lz_op);
+    return 0;
+}
+
 extern "C" int pse_team_mobility(pse_team *T, const pse_double4 *const *pos, const pse_double4 *const *force,
                                  pse_double4 *const *vel, const unsigned *group, unsigned N, int parts) {
     if (!T || !pos || !force || !vel) return fail(PSE_ERR_INVALID, "null argument");
@@ -2827,6 +2856,7 @@ extern "C" int pse_team_brownian_velocity(pse_team *T, const pse_double4 *const 
                                           pse_double4 *const *vel, const unsigned *group, unsigned N, double kT, double dt,
                                           unsigned timestep, int *lanczos_m) {
     if (!T || !pos || !force || !vel) return fail(PSE_ERR_INVALID, "null argument");
+    TRY(team_same_operator(T));
     std::vector<Args> a;
     for (size_t r = 0; r < T->m.size(); ++r) a.push_back(Args{(const double4 *)pos[r], (const double4 *)force[r], (double4 *)vel[r]});
     return do_brownian(*T, a, group, N, kT, dt, timestep, lanczos_m);
@@ -2836,6 +2866,7 @@ extern "C" int pse_team_step(pse_team *T, pse_double4 *const *pos, pse_double4 *
                              pse_int3 *const *image, const pse_double4 *const *net_force, const unsigned *group, unsigned N,
                              double kT, double dt, unsigned timestep, double shear_rate, int *lanczos_m) {
     if (!T || !pos || !vel || !accel || !image || !net_force) return fail(PSE_ERR_INVALID, "null argument");
+    TRY(team_same_operator(T));
     std::vector<StepArgs> a;
     for (size_t r = 0; r < T->m.size(); ++r)
         a.push_back(StepArgs{(double4 *)pos[r], (double4 *)vel[r], (double3 *)accel[r], (int3 *)image[r], (const double4 *)net_force[r]});
@@ -2846,6 +2877,7 @@ extern "C" int pse_team_step_local(pse_team *T, pse_double4 *const *pos, pse_dou
                                    const pse_double4 *const *net_force, unsigned int *const *tag, unsigned int *const *n_local, double kT,
                                    double dt, unsigned int timestep, double shear_rate, int integrate, int *lanczos_m) {
     if (!T || !pos || !vel || !accel || !image || !net_force || !tag || !n_local) return fail(PSE_ERR_INVALID, "null argument");
+    TRY(team_same_operator(T));
     std::vector<LocalCaller> ca;
     for (size_t r = 0; r < T->m.size(); ++r)
         ca.push_back(LocalCaller{(double4 *)pos[r], (double4 *)vel[r], (double3 *)accel[r], (int3 *)image[r], (const double4 *)net_force[r], tag[r], n_local[r]});
@@ -2961,6 +2993,18 @@ extern "C" int pse_local_layout(pse_handle *h, int *rows_own, int *rows_ghost, i
     if (records) *records = h->loc.g.c_x;
     if (layers) *layers = h->loc.g.nx;
     if (layers_per_rank) *layers_per_rank = h->loc.g.per;
+    return 0;
+}
+
+extern "C" int pse_set_lanczos_operator(pse_handle *h, int op) {
+    if (!h) return fail(PSE_ERR_INVALID, "pse_set_lanczos_operator: null handle");
+    if (op != PSE_LANCZOS_RECORDS16 && op != PSE_LANCZOS_FP64)
+        return fail(PSE_ERR_INVALID, "pse_set_lanczos_operator: %d is neither PSE_LANCZOS_RECORDS16 (0) nor PSE_LANCZOS_FP64 (1)", op);
+    return set_lanczos_op(h, op);
+}
+extern "C" int pse_get_lanczos_operator(pse_handle *h, int *op) {
+    if (!h || !op) return fail(PSE_ERR_INVALID, "pse_get_lanczos_operator: null argument");
+    *op = h->lz_op;
     return 0;
 }
 

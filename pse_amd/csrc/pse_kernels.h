@@ -131,11 +131,16 @@ void launch_permute_vec(const double4 *vec, const unsigned *tag_s, int N, double
 // three 22-bit mantissas under one exponent: nb_pack in pse_kernels.hip; pair term f v + sgn (s.v) s), groups of one wave back to back
 // -- a wave streams one contiguous region with 16-byte loads only.  Read by the Lanczos mat-vecs only.
 // Row r = i - lo (lo: first row of the rank, fixed within a step); record (r / 64) * cap + slot.
+// c64 (nullable): the fp64 Lanczos operator (pse_set_lanczos_operator) -- a parallel plane of 32-byte records (f, s = d sqrt|h|) in
+// the same geometry (record k of data <-> c64[k]); the 16-byte record then supplies the row and the sign of h only.  Kernels that
+// see c64 != null take their F64 instantiation: the list passes write the plane, the mat-vecs read it and gather the rows as doubles.
 struct NbList {
     char *data;
     int *cnt;             // neighbour count per particle; -1 if it exceeded cap (dense cluster): that row walks the cells
     int cap;
+    double4 *c64;
 };
+__host__ __device__ inline size_t nb_list64_bytes(size_t rows, int cap) { return ((rows + 63) / 64) * (size_t)cap * 64 * 32; }
 // Neighbour (Verlet) list kept ACROSS steps, as the reference keeps HOOMD's NeighborListGPUBinned(rcut, r_buff = 0.4) with a
 // distance check every step (PSEv1/integrate.py:60,79; Stokes.cc:433): every pair closer than rcut + skin when it was built.
 // The same wave-blocked layout, entries only: groups of four slots [64 lanes][4 x u32 neighbour slot] = 1024 bytes.

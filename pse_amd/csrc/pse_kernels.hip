@@ -351,6 +351,32 @@ __device__ __forceinline__ void nb_store(char *rec, int slot, int lane, unsigned
 }
 constexpr unsigned NB_NEG = 1u << 27;   // entry = neighbour row | NB_NEG if h < 0
 
+// The fp64 operator (F64 instantiations, NbList::c64): the same term f v + sgn (s.v) s with f and s = d sqrt|h| in double -- no rounding
+// beyond that of the arithmetic, the root in double.  Every place the Lanczos iteration applies the operator (ride-along vector of the
+// build, list mat-vecs, rows that did not fit) goes through pair_coef64 + pair_apply64, and the list carries exactly the four doubles
+// pair_coef64 returns: ONE operator, exactly symmetric (d_ji = -d_ij, f and h depend on r^2 alone).
+struct PairCoef64 { double f, sx, sy, sz; bool neg; };
+__device__ __forceinline__ PairCoef64 pair_coef64(double f, double h, double dx, double dy, double dz) {
+    const double hs = sqrt(fabs(h));
+    return PairCoef64{f, dx * hs, dy * hs, dz * hs, h < 0.0};
+}
+__device__ __forceinline__ void pair_apply64(const PairCoef64 &p, double vx, double vy, double vz, double &ux, double &uy, double &uz) {
+    double sd = p.sx * vx + p.sy * vy + p.sz * vz;
+    if (p.neg) sd = -sd;
+    ux += p.f * vx + sd * p.sx; uy += p.f * vy + sd * p.sy; uz += p.f * vz + sd * p.sz;
+}
+typedef double d4v __attribute__((ext_vector_type(4)));
+// record `slot` of a row: the 16-byte record (row | sign; the rounded fields stay zero) and its 32-byte fp64 twin at the same index
+template <bool STREAM = false>
+__device__ __forceinline__ void nb_store64(char *rec, double4 *rec64, int slot, int lane, unsigned j, const PairCoef64 &p) {
+    const size_t k = (size_t)(slot >> 2) * 256 + (slot & 3) * 64 + lane;
+    nb4 w;
+    w.x = j | (p.neg ? NB_NEG : 0u); w.y = 0u; w.z = 0u; w.w = 128u << 24;
+    const d4v c = {p.f, p.sx, p.sy, p.sz};
+    if (STREAM) { __builtin_nontemporal_store(w, (nb4 *)rec + k); __builtin_nontemporal_store(c, (d4v *)rec64 + k); }
+    else { ((nb4 *)rec)[k] = w; ((d4v *)rec64)[k] = c; }
+}
+
 __device__ __forceinline__ void vl_store(char *vrec, int slot, int lane, unsigned j) {
     ((unsigned *)(vrec + (size_t)(slot >> 2) * 1024))[lane * 4 + (slot & 3)] = j;
 }
@@ -366,7 +392,9 @@ __device__ __forceinline__ void vl_store(char *vrec, int slot, int lane, unsigne
 // pass keeps its 166 registers (with the few extra scalars it spilled)
 // PK: the drain reads a neighbour's position AND vector from the packed 48-byte record pv[j] (three 16-byte gathers from one or two
 // lines instead of four from two arrays): the pass is bound by the drain's round trips through the texture addresser, not by its scan.
-template <bool LIST, bool CL, bool TWO, bool VL, bool DEV = false, bool PK = false>
+// F64 (with LIST): the fp64 Lanczos operator -- the list gets the fp64 plane nb.c64 beside its records, the ride-along vector the
+// same un-rounded coefficients (pair_coef64)
+template <bool LIST, bool CL, bool TWO, bool VL, bool DEV = false, bool PK = false, bool F64 = false>
 __global__ void __launch_bounds__(TPB, ((LIST && CL && !VL) ? 3 : 1))   // the list-building pass of every step: <= 168 VGPRs (it takes 166)
 k_mreal_cells(const double4 *__restrict__ pos_s, const float4 *__restrict__ posf_s, const double4 *__restrict__ vec_s,
               double4 *__restrict__ out_s, RowMap rm_arg, const int *__restrict__ cell_off, DBox box, DCells nc, double rcut2,
@@ -413,6 +441,7 @@ k_mreal_cells(const double4 *__restrict__ pos_s, const float4 *__restrict__ posf
     int qn = 0, total = 0, vtotal = 0;
     const int lane = lr & 63;
     char *rec = LIST ? nb.data + (size_t)(lr >> 6) * nb.cap * NB_REC : nullptr;
+    double4 *rec64 = (LIST && F64) ? nb.c64 + (size_t)(lr >> 6) * nb.cap * 64 : nullptr;
     char *vrec = VL ? (char *)vl.idx + (size_t)(lr >> 6) * (vl.cap / 4) * 1024 : nullptr;
     const double rq2 = VL ? vl.rskin * vl.rskin : rcut2;   // what enters the queue
 
@@ -462,7 +491,15 @@ k_mreal_cells(const double4 *__restrict__ pos_s, const float4 *__restrict__ posf
                     const double rd = (dx * F[u].x + dy * F[u].y + dz * F[u].z) * h;
                     ux += f * F[u].x + rd * dx; uy += f * F[u].y + rd * dy; uz += f * F[u].z + rd * dz;
                 }
-                if (LIST) {
+                if (LIST && F64) {
+                    const PairCoef64 pc = pair_coef64(f, h, dx, dy, dz);
+                    if (TWO) pair_apply64(pc, G[u].x, G[u].y, G[u].z, wx, wy, wz);
+                    else pair_apply64(pc, F[u].x, F[u].y, F[u].z, ux, uy, uz);
+                    if (in) {   // row | sign in 16 B, (f, s) in 32 B of doubles
+                        if (total < nb.cap) nb_store64<true>(rec, rec64, total, lane, (unsigned)j[u], pc);
+                        ++total;
+                    }
+                } else if (LIST) {
                     const PairCoef pc = pair_coef(f, h, dx, dy, dz);
                     if (TWO) pair_apply(pc, G[u].x, G[u].y, G[u].z, wx, wy, wz);
                     else pair_apply(pc, F[u].x, F[u].y, F[u].z, ux, uy, uz);
@@ -602,8 +639,8 @@ k_mreal_cells(const double4 *__restrict__ pos_s, const float4 *__restrict__ posf
 // one 16-byte load), gathers the neighbours' (position, vec) records (+ vec2), takes the minimum image itself (particles may
 // have crossed the periodic boundary since the build) and evaluates f, g densely; pairs beyond rcut (about a quarter at
 // skin = 0.4) contribute zero.  LIST: writes the step's pair list for the Lanczos mat-vecs, exactly as the cell pass does.
-// PK: pv holds (position, vec_s) records (three 16-byte gathers per neighbour instead of four).
-template <bool LIST, bool TWO, bool PK>
+// PK: pv holds (position, vec_s) records (three 16-byte gathers per neighbour instead of four).  F64: as in k_mreal_cells.
+template <bool LIST, bool TWO, bool PK, bool F64 = false>
 __global__ void __launch_bounds__(TPB)
 k_mreal_verlet(const double4 *__restrict__ pos_s, const double2 *__restrict__ pv, const double4 *__restrict__ vec_s,
                double4 *__restrict__ out_s, int N, DBox box, double rcut2, double self, const double *__restrict__ coef_g, int ncoef,
@@ -623,6 +660,7 @@ k_mreal_verlet(const double4 *__restrict__ pos_s, const double2 *__restrict__ pv
     const int lane = i & 63, cnt = vl.cnt[i];
     const char *vrec = (const char *)vl.idx + (size_t)(i >> 6) * (vl.cap / 4) * 1024;
     char *rec = LIST ? nb.data + (size_t)(i >> 6) * nb.cap * NB_REC : nullptr;
+    double4 *rec64 = (LIST && F64) ? nb.c64 + (size_t)(i >> 6) * nb.cap * 64 : nullptr;
     int total = 0;
     constexpr int U = 4;
     for (int s0 = 0; s0 < cnt; s0 += U) {
@@ -659,7 +697,15 @@ k_mreal_verlet(const double4 *__restrict__ pos_s, const double2 *__restrict__ pv
                 const double rd = (dx * Fx + dy * Fy + dz * Fz) * h;
                 ux += f * Fx + rd * dx; uy += f * Fy + rd * dy; uz += f * Fz + rd * dz;
             }
-            if (LIST) {   // (as the cell pass: the vector of the Lanczos iteration sees the coefficients the list carries)
+            if (LIST && F64) {
+                const PairCoef64 pc = pair_coef64(f, h, dx, dy, dz);
+                if (TWO) pair_apply64(pc, G[u].x, G[u].y, G[u].z, wx, wy, wz);
+                else pair_apply64(pc, Fx, Fy, Fz, ux, uy, uz);
+                if (in) {
+                    if (total < nb.cap) nb_store64(rec, rec64, total, lane, e[u], pc);
+                    ++total;
+                }
+            } else if (LIST) {   // (as the cell pass: the vector of the Lanczos iteration sees the coefficients the list carries)
                 const PairCoef pc = pair_coef(f, h, dx, dy, dz);
                 if (TWO) pair_apply(pc, G[u].x, G[u].y, G[u].z, wx, wy, wz);
                 else pair_apply(pc, Fx, Fy, Fz, ux, uy, uz);
@@ -708,7 +754,9 @@ __device__ __forceinline__ void eval_fg_lean(double r2, const double *__restrict
 // FUSE: 0 none; 1 the three sums of the one-step iteration; 2 the Gram sums of a two-step block (this launch is its SECOND
 // mat-vec: vec = w1 = M q, result w2); 3 the sums of a single step in the two-step driver (vec = q, result w1).
 // VQ: the neighbours' rows come from the 16-byte mirror of the vector (vq_pack, pse_device.h): ONE gather per pair instead of two.
-template <int FUSE, int UNROLL, int NT, int WSP = 1, bool VQ = false>
+// F64: the fp64 operator -- the coefficients from the 32-byte plane nb.c64 (the 16-byte record gives the row and the sign of h), the
+// neighbours' rows as doubles (never VQ), the rows that did not fit the list through pair_coef64: 48 B of list per pair instead of 16.
+template <int FUSE, int UNROLL, int NT, int WSP = 1, bool VQ = false, bool F64 = false>
 __global__ void __launch_bounds__(NT, (WSP == 4 ? 5 : 1))   // the split kernel: <= 96 VGPRs, five workgroups per CU (it is bound by the round trips its waves have in flight)
 k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_s, double4 *__restrict__ out_s, RowMap rm_arg,
              DBox box, double self, NbList nb, LzFuse lz,
@@ -750,9 +798,11 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                 // streamed once: non-temporal, so the list does not evict the neighbour rows the gathers reuse from L1
                 unsigned e[UNROLL];
                 nb4 c[UNROLL];
+                d4v c64[F64 ? UNROLL : 1];
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
                     c[u] = __builtin_nontemporal_load((const nb4 *)grp + u * 64 + lane);
+                    if (F64) c64[u] = __builtin_nontemporal_load((const d4v *)nb.c64 + (size_t)(lr >> 6) * nb.cap * 64 + (size_t)(s0 >> 2) * 256 + u * 64 + lane);
                     e[u] = c[u].x;
                     if (u && s0 + u >= cnt) e[u] = e[0];          // slots past the row's count were never written
                 }
@@ -761,7 +811,7 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                 vq4 vq[UNROLL];
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
-                    if (VQ) { vq[u] = vec_q[e[u] & JMASK]; continue; }   // the row in 16 bytes: one gather
+                    if (VQ && !F64) { vq[u] = vec_q[e[u] & JMASK]; continue; }   // the row in 16 bytes: one gather
                     const double4 *vj = vec_s + (e[u] & JMASK);   // 24 of the row's 32 bytes: a 16- and an 8-byte gather from one line
                     vxy[u] = *reinterpret_cast<const double2 *>(vj);
                     vz[u] = vj->z;
@@ -769,6 +819,11 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
                     const bool ok = s0 + u < cnt;
+                    if (F64) {   // (selects, not products: the slots past cnt hold whatever the memory held)
+                        const PairCoef64 pc{ok ? c64[u].x : 0.0, ok ? c64[u].y : 0.0, ok ? c64[u].z : 0.0, ok ? c64[u].w : 0.0, (c[u].x & NB_NEG) != 0u};
+                        pair_apply64(pc, vxy[u].x, vxy[u].y, vz[u], ux, uy, uz);
+                        continue;
+                    }
                     const PairCoef pc = nb_unpack(c[u], ok);
                     if (VQ) { vq_unpack(vq[u], vxy[u].x, vxy[u].y, vz[u]); }
                     pair_apply(pc, vxy[u].x, vxy[u].y, vz[u], ux, uy, uz);
@@ -792,7 +847,8 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                     double f, h;
                     eval_fg_lean(r2, coef, f, h);
                     const double4 Fj = vec_s[j];
-                    pair_apply(pair_coef(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);   // (the coefficients the list would have carried)
+                    if (F64) pair_apply64(pair_coef64(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
+                    else pair_apply(pair_coef(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);   // (the coefficients the list would have carried)
                 }
             }
         } else {
@@ -812,7 +868,8 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                         double f, h;
                         eval_fg_lean(r2, coef, f, h);
                         const double4 Fj = vec_s[j];
-                        pair_apply(pair_coef(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
+                        if (F64) pair_apply64(pair_coef64(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
+                        else pair_apply(pair_coef(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
                     }
                 }
             });
@@ -889,19 +946,22 @@ void launch_mreal(const double4 *pos_s, const float4 *posf_s, const double4 *vec
     const dim3 g(nblocks(rows, TPB)), b(TPB);
     const size_t cb = mreal_lds_bytes(ncoef);
     const bool cl = mreal_table_in_lds(ncoef);
+    const bool f64 = nb.c64 != nullptr;   // the fp64 Lanczos operator (the instantiations with F64)
     if (mode == MREAL_USE_LIST) {
-        hipLaunchKernelGGL((k_mreal_list<0, 4, TPB>), g, b, 0, s, pos_s, vec_s, out_s, rm, box, self, nb, LzFuse{}, cell_off, nc, rcut * rcut, coef,
-                           vl_mode == VL_USE ? vl : VerletList{}, nullptr, DevRowArgs{});
+        if (f64) hipLaunchKernelGGL((k_mreal_list<0, 4, TPB, 1, false, true>), g, b, 0, s, pos_s, vec_s, out_s, rm, box, self, nb, LzFuse{}, cell_off, nc, rcut * rcut, coef,
+                                    vl_mode == VL_USE ? vl : VerletList{}, nullptr, DevRowArgs{}, nullptr);
+        else hipLaunchKernelGGL((k_mreal_list<0, 4, TPB>), g, b, 0, s, pos_s, vec_s, out_s, rm, box, self, nb, LzFuse{}, cell_off, nc, rcut * rcut, coef,
+                                vl_mode == VL_USE ? vl : VerletList{}, nullptr, DevRowArgs{});
         return;
     }
     const bool list = mode == MREAL_BUILD_LIST, two = list && vec2_s != nullptr;
     if (vl_mode == VL_USE) {   // rows [0, N) of a single rank; the table is in LDS (the caller checked mreal_table_in_lds)
         const int hi = rm.hi[0];
-#define PSE_VERLET(L, T) do { if (pv) hipLaunchKernelGGL((k_mreal_verlet<L, T, true>), g, b, cb, s, pos_s, pv, vec_s, out_s, hi, box, rcut * rcut, self, coef, ncoef, nb, vl, two ? vec2_s : nullptr, out2_s, gate); \
-        else hipLaunchKernelGGL((k_mreal_verlet<L, T, false>), g, b, cb, s, pos_s, pv, vec_s, out_s, hi, box, rcut * rcut, self, coef, ncoef, nb, vl, two ? vec2_s : nullptr, out2_s, gate); } while (0)
-        if (list && two) PSE_VERLET(true, true);
-        else if (list) PSE_VERLET(true, false);
-        else PSE_VERLET(false, false);
+#define PSE_VERLET(L, T, F) do { if (pv) hipLaunchKernelGGL((k_mreal_verlet<L, T, true, F>), g, b, cb, s, pos_s, pv, vec_s, out_s, hi, box, rcut * rcut, self, coef, ncoef, nb, vl, two ? vec2_s : nullptr, out2_s, gate); \
+        else hipLaunchKernelGGL((k_mreal_verlet<L, T, false, F>), g, b, cb, s, pos_s, pv, vec_s, out_s, hi, box, rcut * rcut, self, coef, ncoef, nb, vl, two ? vec2_s : nullptr, out2_s, gate); } while (0)
+        if (list && two) { if (f64) PSE_VERLET(true, true, true); else PSE_VERLET(true, true, false); }
+        else if (list) { if (f64) PSE_VERLET(true, false, true); else PSE_VERLET(true, false, false); }
+        else PSE_VERLET(false, false, false);
 #undef PSE_VERLET
         return;
     }
@@ -911,8 +971,11 @@ void launch_mreal(const double4 *pos_s, const float4 *posf_s, const double4 *vec
     const double cmax = 1.5 * (box.Lx + std::fabs(box.xy) * box.Ly + box.Ly + box.Lz);
     const double rpre = (wr ? vl.rskin : rcut) + 16.0 * cmax * 5.97e-8;
     const float rcut2_pre = (float)(rpre * rpre * (1.0 + 1e-6));
-#define PSE_CELLS(L, C, T, V) hipLaunchKernelGGL((k_mreal_cells<L, C, T, V>), g, b, (C) ? cb : 0, s, pos_s, posf_s, vec_s, out_s, rm, cell_off, box, nc, rcut * rcut, rcut2_pre, self, coef, ncoef, nb, two ? vec2_s : nullptr, out2_s, vl, (two && (C)) ? sums0 : nullptr, sums0_cap, gate, dr, nullptr)
-#define PSE_CELLS_PK(L, T, D) hipLaunchKernelGGL((k_mreal_cells<L, true, T, false, D, true>), g, b, cb, s, pos_s, posf_s, vec_s, out_s, rm, cell_off, box, nc, rcut * rcut, rcut2_pre, self, coef, ncoef, nb, two ? vec2_s : nullptr, out2_s, vl, (two && !(D)) ? sums0 : nullptr, sums0_cap, gate, dr, pv)
+#define PSE_CELLS_F(L, C, T, V, F) hipLaunchKernelGGL((k_mreal_cells<L, C, T, V, false, false, F>), g, b, (C) ? cb : 0, s, pos_s, posf_s, vec_s, out_s, rm, cell_off, box, nc, rcut * rcut, rcut2_pre, self, coef, ncoef, nb, two ? vec2_s : nullptr, out2_s, vl, (two && (C)) ? sums0 : nullptr, sums0_cap, gate, dr, nullptr)
+#define PSE_CELLS_PK_F(L, T, D, F) hipLaunchKernelGGL((k_mreal_cells<L, true, T, false, D, true, F>), g, b, cb, s, pos_s, posf_s, vec_s, out_s, rm, cell_off, box, nc, rcut * rcut, rcut2_pre, self, coef, ncoef, nb, two ? vec2_s : nullptr, out2_s, vl, (two && !(D)) ? sums0 : nullptr, sums0_cap, gate, dr, pv)
+    // (only the passes that write the pair list have an F64 twin: the others apply the exact f, h to F alone)
+#define PSE_CELLS(L, C, T, V) do { if ((L) && f64) PSE_CELLS_F(L, C, T, V, (L)); else PSE_CELLS_F(L, C, T, V, false); } while (0)
+#define PSE_CELLS_PK(L, T, D) do { if ((L) && f64) PSE_CELLS_PK_F(L, T, D, (L)); else PSE_CELLS_PK_F(L, T, D, false); } while (0)
     if (dr.rm) {   // owned-particle ranks (table in LDS, no kept list, packed records): the two passes of pse_team_step_local
         if (list && two) PSE_CELLS_PK(true, true, true); else PSE_CELLS_PK(false, false, true);
         return;
@@ -927,6 +990,8 @@ void launch_mreal(const double4 *pos_s, const float4 *posf_s, const double4 *vec
     else PSE_CELLS(false, false, false, false);
 #undef PSE_CELLS_PK
 #undef PSE_CELLS
+#undef PSE_CELLS_PK_F
+#undef PSE_CELLS_F
     if (sums0 && list && two && cl)   // one partial per wavefront of the pass -> scal[LZ_TMP .. LZ_TMP + 2]
         hipLaunchKernelGGL(k_lz_reduce, dim3(3), dim3(1024), 0, s, sums0, (int)g.x * (TPB / 64), sums0_cap, 3, scal, nullptr);
 }
@@ -945,10 +1010,14 @@ void launch_mreal_lanczos(const double4 *pos_s, const double4 *vec_s, double4 *w
     // per workgroup (two waves: 0.182, eight: 0.196).
     const int nb64 = nblocks(rows, 64);
 #define PSE_LIST(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr)
-    if (sums == 1 && vec_q)
+#define PSE_LIST64(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4, false, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr, nullptr)
+    if (nb.c64) {   // the fp64 operator: the neighbours' rows as doubles, the mirror vec_q is not read
+        if (sums == 0) PSE_LIST64(0); else if (sums == 1) PSE_LIST64(1); else if (sums == 2) PSE_LIST64(2); else PSE_LIST64(3);
+    } else if (sums == 1 && vec_q)
         hipLaunchKernelGGL((k_mreal_list<1, 4, 256, 4, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr,
                            (const vq4 *)vec_q);
     else if (sums == 0) PSE_LIST(0); else if (sums == 1) PSE_LIST(1); else if (sums == 2) PSE_LIST(2); else PSE_LIST(3);
+#undef PSE_LIST64
 #undef PSE_LIST
     if (ev_end) (void)hipEventRecord(ev_end, s);
     if (no_reduce) return;   // (pse_debug_matvec_ms: the mat-vec kernel alone, back to back)

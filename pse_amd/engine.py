@@ -38,6 +38,16 @@ def _chk_arr(t, name, cols, dtype, n):
         raise ValueError(f"{name} must be a contiguous (N>={n},{cols}) {dtype} CUDA tensor")
 
 
+# the near-field operator of the Lanczos iteration (pse_set_lanczos_operator): name -> enum pse_lanczos_operator
+LANCZOS_OPERATORS = {"records16": 0, "fp64": 1}
+
+
+def _lanczos_operator_code(name):
+    if name not in LANCZOS_OPERATORS:
+        raise ValueError(f"lanczos_operator must be one of {sorted(LANCZOS_OPERATORS)}, not {name!r}")
+    return LANCZOS_OPERATORS[name]
+
+
 def host_select_params(box, xi=0.5, error=1e-3, max_strain=0.5, grid=(0, 0, 0), P=0, rcut=0.0):
     """Parameter rule of Stokes::setParams (PSEv1/Stokes.cc:129-236,319), host only."""
     lib = _lib.load()
@@ -65,7 +75,10 @@ class Engine:
     """One PSE engine instance == one `Stokes` object's device state (PSEv1/Stokes.h:128-150)."""
 
     def __init__(self, n_max, box, xi=0.5, error=1e-3, max_strain=0.5, seed=0, grid=(0, 0, 0), P=0, rcut=0.0,
-                 device=-1, n_slabs=1, slab_rank=0, local_rows=0):
+                 device=-1, n_slabs=1, slab_rank=0, local_rows=0, lanczos_operator=None):
+        """lanczos_operator: "records16" (the 16-byte pair records, single-precision accurate) or "fp64" (the exact operator: tight
+        tolerances of the Lanczos noise mean what they say); None keeps the handle's default (PSE_LANCZOS_OP in the environment)."""
+        op = None if lanczos_operator is None else _lanczos_operator_code(lanczos_operator)
         self._lib = _lib.load()
         self._h = ctypes.c_void_p()
         box = tuple(float(b) for b in box) + ((0.0,) if len(box) == 3 else ())
@@ -75,6 +88,20 @@ class Engine:
                                  local_rows=int(local_rows))
         _lib.check(self._lib.pse_create(ctypes.byref(self.params), ctypes.byref(self._h)))
         self.box = box
+        if op is not None:
+            _lib.check(self._lib.pse_set_lanczos_operator(self._h, op))
+
+    def set_lanczos_operator(self, name):
+        """The near-field operator of the Lanczos iteration from now on (pse_set_lanczos_operator): "records16" or "fp64".  A graph
+        captured before the switch keeps its mode."""
+        _lib.check(self._lib.pse_set_lanczos_operator(self._h, _lanczos_operator_code(name)))
+
+    @property
+    def lanczos_operator(self):
+        """"records16" or "fp64" (pse_get_lanczos_operator)."""
+        v = ctypes.c_int(-1)
+        _lib.check(self._lib.pse_get_lanczos_operator(self._h, ctypes.byref(v)))
+        return {c: n for n, c in LANCZOS_OPERATORS.items()}[v.value]
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -405,6 +432,21 @@ class Team:
             if any(t.shape[0] < self._rows_own[k] for t in ts):
                 raise ValueError(f"member {k}: pos / vel / force / accel / image / tag need {self._rows_own[k]} rows (rows_own of pse_local_layout), "
                                  f"not the current particle count")
+
+    def set_lanczos_operator(self, name):
+        """The Lanczos operator ("records16" or "fp64") on every member of this process (the team calls refuse members whose modes
+        differ; the ranks of a process team each set it)."""
+        code = _lanczos_operator_code(name)
+        for e in self.engines:
+            _lib.check(self._lib.pse_set_lanczos_operator(e._h, code))
+
+    @property
+    def lanczos_operator(self):
+        """The members' operator; raises if they differ."""
+        ops = {e.lanczos_operator for e in self.engines}
+        if len(ops) != 1:
+            raise _lib.PSEError(f"team members use different Lanczos operators: {sorted(ops)}")
+        return ops.pop()
 
     def set_lanczos_extra(self, extra):
         """Iterations an owned-particle step queues beyond its starting count (pse_team_set_lanczos_extra; -1: the default, gated

@@ -3,6 +3,7 @@ function_form, max_strain, nlist_type)`, `.set_params`, `.stop_shear`, backed by
 import math
 
 from . import _PSEv1, context, shear_function
+from .engine import _lanczos_operator_code
 
 
 class _const_or_variant:
@@ -13,7 +14,10 @@ class _const_or_variant:
 
 class PSEv1:
     def __init__(self, group, T, seed=0, xi=0.5, error=0.001, function_form=None, max_strain=0.5, nlist_type="cell",
-                 grid=None, P=0, rcut=0.0):
+                 grid=None, P=0, rcut=0.0, lanczos_operator=None):
+        # lanczos_operator (an extension, no reference counterpart): "records16" | "fp64" | None (the engine's default), see
+        # pse_amd.Engine
+        lz_op = None if lanczos_operator is None else _lanczos_operator_code(lanczos_operator)
         self.group = group
         self.system = group.system
         # real-space cutoff from the error estimate of the spectral sums (integrate.py:47, Stokes.cc:135)
@@ -34,6 +38,8 @@ class PSEv1:
         if grid is not None or P or rcut:
             g = grid or (0, 0, 0)
             self.cpp_method.setOverrides(g[0], g[1], g[2], int(P), float(rcut))
+        if lz_op is not None:
+            self.cpp_method.setLanczosOperator(lz_op)
         self.cpp_method.setParams()                                                     # integrate.py:96
         s.integrators.append(self)
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-phase timings of the engine on a synthetic suspension (developer tool; bench.py is the contract).
 
-  python3 tools/perf.py --n 1000000 --phi 0.1 --grid 256 [--error 1e-3] [--xy 0.0] [--steps 5] [--no-step]
+  python3 tools/perf.py --n 1000000 --phi 0.1 --grid 256 [--error 1e-3] [--xy 0.0] [--steps 5] [--no-step] [--lanczos-operator fp64]
 Prints the hipEvent phase times of pse_mobility and pse_brownian_velocity, then untimed-loop rates.
 """
 import argparse
@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--only-mf", action="store_true")
+    ap.add_argument("--lanczos-operator", choices=("records16", "fp64"), default=None,
+                    help="near-field operator of the Lanczos iteration (default: the engine's, PSE_LANCZOS_OP)")
     a = ap.parse_args()
 
     import torch
@@ -42,8 +44,9 @@ def main():
     grid = (a.grid,) * 3 if a.grid else (0, 0, 0)
     xi = a.xi if a.xi > 0 else math.pi * a.grid / (2 * L * math.sqrt(-math.log(a.error)))
     t0 = time.time()
-    eng = pse_amd.Engine(n, box, xi=xi, error=a.error, seed=1, grid=grid)
+    eng = pse_amd.Engine(n, box, xi=xi, error=a.error, seed=1, grid=grid, lanczos_operator=a.lanczos_operator)
     i = eng.info()
+    print("Lanczos operator:", eng.lanczos_operator)
     print("create %.2fs" % (time.time() - t0), {k: i[k] for k in ("Nx", "Ny", "Nz", "P", "rcut", "eta", "ncell_x", "device_bytes")})
     dpos, dF = to4(pos, 1.0), to4(force)
     vel = to4(np.zeros((n, 3)), 1.0)
@@ -58,6 +61,7 @@ def main():
             _, m = eng.brownian_velocity(dpos, dF, a.kT, 1e-3, it, vel=vel, lanczos_m=m)
         i = eng.info()
         print("Brownian phases ms:", {k: round(v, 4) for k, v in i.items() if k.startswith("t_") and v > 0}, "m", m, i["lanczos_matvecs"])
+        print("pair-list mat-vec %.4f ms (%s)" % (eng.matvec_ms(), eng.lanczos_operator))
     eng.set_timing(False)
     torch.cuda.synchronize(); t0 = time.time()
     for it in range(a.steps):
