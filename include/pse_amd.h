@@ -201,6 +201,17 @@ int pse_eval_realspace(pse_handle *h, const double *r_host, int n, double *f_hos
  * incremented (accumulate = 1); w is kept. */
 int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
                        double k, double sigma, int accumulate);
+/* The same pass with the pair observables a rheology run samples (no reference counterpart: the reference leaves forces, and with them
+ * their stress, to HOOMD): out8 (DEVICE, 8 doubles) = U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs of the pairs with r < sigma among the N
+ * group members, each unordered pair once.  U = sum k/2 (sigma - r)^2;  W_ab = sum_{i<j} d_a F_b with d = r_i - r_j (minimum image) and
+ * F = k (sigma - r) d / r the force ON i FROM j -- symmetric (central force), positive on the diagonal for a repulsion; the particle
+ * stress is sigma_ab = -W_ab / V with V = Lx Ly Lz, and dU/d(strain xy) = -Wxy.  npairs counts 1.0 per pair.  force as in
+ * pse_pair_repulsion, or NULL: observables only.  The sums use no atomics and the cell sort is stable: equal inputs give the same
+ * eight doubles bit for bit.  The call only queues work on the handle's stream wherever pse_pair_repulsion does and reads nothing
+ * back; out8 may point into a larger device array (row r of a log that is read once at the end of a run).  Single-GPU handles only:
+ * a slab rank (n_slabs >= 2) orders only its own cells, its sums would be partial -- PSE_ERR_INVALID. */
+int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* may be NULL */,
+                              const unsigned *group, unsigned N, double k, double sigma, int accumulate, double *out8);
 /* copy the three real-space grids (x-major, z fastest: idx = (x*Ny + y)*Nz + z, PSEv1/Mobility.cu:233) of the
  * most recent spread (stage 0) or inverse FFT (stage 1) to a host buffer of 3*nx_local*Ny*Nz doubles */
 int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out);

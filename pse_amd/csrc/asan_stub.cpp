@@ -1,8 +1,8 @@
 // Device entry points of include/pse_amd.h for the CPU SANITIZER build only (python -m pse_amd.build --asan; never part of
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
-// exercised under -fsanitize=address,undefined against this stand-in.  The six calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion) keep a small host object that runs the REAL parameter
+// exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <cmath>
 #include <vector>
@@ -70,6 +70,15 @@ int pse_pair_repulsion(pse_handle *h, const pse_double4 *, pse_double4 *, const 
     if (N == 0 || N > h->par.n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, h->par.n_max);
     if (!(sigma > 0.0) || sigma > h->d.rcut) return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]", sigma, h->d.rcut);
     return 0;
+}
+int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *, pse_double4 *, const unsigned *, unsigned N, double, double sigma, int,
+                              double *out8) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    if (N == 0 || N > h->par.n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, h->par.n_max);
+    if (!out8) return fail(PSE_ERR_INVALID, "null out8");
+    if (h->par.n_slabs > 1) return fail(PSE_ERR_INVALID, "pse_pair_repulsion_virial: this handle is a slab rank");
+    if (!(sigma > 0.0) || sigma > h->d.rcut) return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]", sigma, h->d.rcut);
+    return 0;   // out8 is a device pointer and there is no device: nothing is written
 }
 
 int pse_set_stream(pse_handle *, void *) { return no_device("pse_set_stream"); }

@@ -61,6 +61,13 @@ void Stokes::pairRepulsion(const pse_double4 *pos, pse_double4 *force, const uns
     check(pse_pair_repulsion(m_h, pos, force, group, n, k, sigma, accumulate ? 1 : 0), "Stokes::pairRepulsion");
 }
 
+void Stokes::pairRepulsionVirial(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k,
+                                 double sigma, bool accumulate, double *out8) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    // (an empty group is refused by the C-ABI: there is no device code here that could write zeros to out8)
+    check(pse_pair_repulsion_virial(m_h, pos, force, group, n, k, sigma, accumulate ? 1 : 0, out8), "Stokes::pairRepulsionVirial");
+}
+
 pse_info Stokes::info() const {
     pse_info i{};
     if (m_h) pse_get_info(m_h, &i);

@@ -42,6 +42,10 @@ public:
     // force provider on the integrator's own cell list (the reference takes net_force from HOOMD, Stokes.cc:447)
     void pairRepulsion(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k,
                        double sigma, bool accumulate);
+    // ... and the same pass with the pair observables a rheology run samples (pse_pair_repulsion_virial): out8 = U, Wxx, Wxy, Wxz, Wyy,
+    // Wyz, Wzz, npairs, eight DEVICE doubles written by the stream; force may be null (observables only)
+    void pairRepulsionVirial(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k,
+                             double sigma, bool accumulate, double *out8);
     pse_info info() const;
     int lanczosIterations() const { return m_m_Lanczos; }
     unsigned int hashedSeed() const { return m_seed; }

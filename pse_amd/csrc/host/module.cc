@@ -69,6 +69,11 @@ PYBIND11_MODULE(_PSEv1, m) {
                                  double sigma, bool accumulate) {
             s.pairRepulsion(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate);
         })
+        .def("pairRepulsionVirial", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, double k,
+                                       double sigma, bool accumulate, std::uintptr_t out8) {
+            s.pairRepulsionVirial(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate,
+                                  ptr<double>(out8));
+        })
         .def("lanczosIterations", &Stokes::lanczosIterations)
         .def("hashedSeed", &Stokes::hashedSeed)
         .def("info", [](const Stokes &s) {

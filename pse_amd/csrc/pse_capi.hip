@@ -109,6 +109,7 @@ struct pse_handle {
     int *cell_cnt = nullptr;
     size_t sort_tmp_bytes = 0;
     int *cell_off = nullptr;
+    double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
@@ -408,7 +409,7 @@ extern "C" int pse_destroy(pse_handle *h) {
     if (h->info_inv) rocfft_execution_info_destroy(h->info_inv);
     void *ptrs[] = {h->keys, h->keys_s, h->vals, h->perm, h->tag_s, h->sort_tmp, h->cell_off, h->cnt_block, h->sw.rec_t, h->sw.fb.off, h->sw.fb.rank_s, h->sw.fb.tmp, h->nb.data, h->nb.cnt, h->vl.idx, h->vl.cnt, h->pos_build, h->pos_s, h->posf_s, h->pv,
                     h->f_s, h->uw_s, h->ur_s, h->ub_s, h->psi_s, h->w_s, h->coef, h->rgrid, h->cgrid, h->sendbuf, h->recvbuf, h->d_bidx, h->d_bounds, h->utot_s, h->w2_s, h->u_s, h->sums_all, h->twiddle, h->twiddle_y_owned, h->twiddle_z_owned, h->fft_work, h->V,
-                    h->scal, h->partials, h->lz_state, h->vq, h->nb64};
+                    h->scal, h->partials, h->lz_state, h->vq, h->nb64, h->pv_rows};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &p : h->ph) { if (p.a) (void)hipEventDestroy(p.a); if (p.b) (void)hipEventDestroy(p.b); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -789,6 +790,7 @@ static int create_impl(const pse_params *p, pse_handle *h) {
     TRY(dmalloc(h, &h->V, (size_t)(M_MAX + 1) * n));
     // single GPU: the newest Lanczos vector also in 16 bytes per row (vq_pack): what the pair-list mat-vec gathers its neighbours from
     if (h->n_slabs == 1 && !h->loc.on && h->tun.vq > 0) TRY(dmalloc(h, (char **)&h->vq, (size_t)16 * n));
+    TRY(dmalloc(h, &h->pv_rows, pair_virial_rows((int)n)));
     TRY(dmalloc(h, &h->scal, (size_t)LZ_NSCAL));
     TRY(dmalloc(h, &h->lz_state, 1));
     HIPCHK(hipMemset(h->lz_state, 0, sizeof(LzState)));
@@ -2542,6 +2544,26 @@ extern "C" int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_dou
                     sigma, h->d.rcut);
     TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
     launch_pair_repulsion(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The same force pass with the pair observables of the repulsion (include/pse_amd.h): energy, virial and pair count in eight device
+// doubles.  Queue-only wherever pse_pair_repulsion is: nothing is read back, out8 is written by the stream.
+extern "C" int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                         double k, double sigma, int accumulate, double *out8) {
+    TRY(check_n(h, N));
+    if (!pos) return fail(PSE_ERR_INVALID, "null array");
+    if (!out8) return fail(PSE_ERR_INVALID, "null out8: the observables need eight device doubles");
+    if (h->n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "pse_pair_repulsion_virial: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums "
+                                     "would be partial", h->n_slabs);
+    if (!(sigma > 0.0) || sigma > h->d.rcut)
+        return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]: the cell list is built for the hydrodynamic cutoff",
+                    sigma, h->d.rcut);
+    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    launch_pair_repulsion_virial(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->pv_rows,
+                                 out8, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

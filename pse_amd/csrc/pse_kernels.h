@@ -349,5 +349,12 @@ void launch_eval_fg(const double *r, int n, const double *coef, double *f, doubl
 // soft pair repulsion from the cell list, scattered to the caller's order (force provider)
 void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
                            double k, double sigma, int accumulate, double4 *force, hipStream_t s);
+// the same pass + the pair observables U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs over the rows j > i: one row of PAIR_VIRIAL_NOBS doubles
+// per workgroup into `rows` (pair_virial_rows(N) doubles), added up in a fixed order into out8 (device) by a second, one-workgroup
+// kernel; force may be null (observables only)
+constexpr int PAIR_VIRIAL_NOBS = 8;
+size_t pair_virial_rows(int n);
+void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
+                                  double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
 
 }  // namespace pse

@@ -2718,6 +2718,92 @@ void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, c
                        accumulate, force);
 }
 
+// The same pass with the pair observables of a rheology run (no reference counterpart: the reference leaves forces and their
+// stress to HOOMD): besides the force on row i from ALL its neighbours, the rows j > i of the sorted order -- every unordered pair
+// once -- add U = k/2 (sigma - r)^2, the six components W_ab = c d_a d_b of the symmetric virial sum_{i<j} r_ij (x) F_ij
+// (d = r_i - r_j minimum image, c = k (sigma - r)/r: c d is the force on i from j) and a pair count.  The eight sums are reduced over
+// the wave with wave_sum, over the four waves through LDS with ONE barrier for the whole 8-vector, and each workgroup writes one
+// row of eight doubles; k_pair_virial_finish adds the rows up.  No floating-point atomics: every sum has a fixed order given the
+// sorted order, and the cell sort is a stable sort (k_cell_order), so the eight numbers are bit-reproducible from call to call on
+// equal inputs.  force == nullptr: observables only.
+constexpr int PV_NOBS = PAIR_VIRIAL_NOBS;
+__global__ void __launch_bounds__(TPB)
+k_pair_repulsion_virial(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off,
+                        DBox box, DCells nc, double k, double sigma, int accumulate, double4 *__restrict__ force,
+                        double *__restrict__ rows /* [gridDim.x][PV_NOBS] */) {
+    __shared__ double sh[TPB / 64][PV_NOBS];
+    const int blk = xcd_block(blockIdx.x, gridDim.x);
+    const int i = blk * TPB + threadIdx.x;
+    double o[PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = 0.0;
+    if (i < N) {   // (no early return: the lanes past the last row take part in the reduction with zeros)
+        const double4 pi = pos_s[i];
+        double fx, fy, fz;
+        frac_coords(box, pi.x, pi.y, pi.z, fx, fy, fz);
+        const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
+        const double s2 = sigma * sigma;
+        double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
+            for (int j = jb; j < je; ++j) {
+                const double4 pj = pos_s[j];
+                double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                min_image(box, dx, dy, dz);
+                const double r2 = dx * dx + dy * dy + dz * dz;
+                if (r2 < s2 && j != i && r2 > 0.0) {
+                    const double r = sqrt(r2), c = k * (sigma - r) / r;
+                    Fx += c * dx; Fy += c * dy; Fz += c * dz;
+                    if (j > i) {
+                        const double cdx = c * dx, cdy = c * dy;
+                        o[0] += 0.5 * k * (sigma - r) * (sigma - r);
+                        o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
+                        o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
+                        o[7] += 1.0;
+                    }
+                }
+            }
+        });
+        if (force) {
+            const unsigned idx = tag_s[i];
+            double4 f = force[idx];
+            if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
+            force[idx] = f;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+}
+// One workgroup adds the nrows workgroup rows in a fixed order (the reduce_partials pattern, for the 8-vector at once): thread t
+// owns component t % 8 of the rows t / 8, t / 8 + 32, ...; then the 32 partial sums of a component are added in index order.
+__global__ void __launch_bounds__(TPB)
+k_pair_virial_finish(const double *__restrict__ rows, int nrows, double *__restrict__ out8) {
+    __shared__ double sh[TPB];
+    const int q = threadIdx.x % PV_NOBS;
+    double v = 0.0;
+    for (int r = threadIdx.x / PV_NOBS; r < nrows; r += TPB / PV_NOBS) v += rows[(size_t)r * PV_NOBS + q];
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x < PV_NOBS) {
+        double s = 0.0;
+        for (int t = threadIdx.x; t < TPB; t += PV_NOBS) s += sh[t];
+        out8[threadIdx.x] = s;
+    }
+}
+void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
+                                  double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
+    const int nb = nblocks(N, TPB);
+    hipLaunchKernelGGL(k_pair_repulsion_virial, dim3(nb), dim3(TPB), 0, s, pos_s, tag_s, N, cell_off, box, nc, k, sigma, accumulate,
+                       force, rows);
+    hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
+}
+size_t pair_virial_rows(int n) { return (size_t)nblocks(n, TPB) * PV_NOBS; }
+
 // K10 gpu_stokes_LinearCombination_kernel (PSEv1/Helper.cu:113-133) as the final un-sort: vel.xyz = a + b + c, keep w
 __global__ void k_scatter_sum(const double4 *__restrict__ a, const double4 *__restrict__ b,
                               const double4 *__restrict__ c, const unsigned *__restrict__ tag_s, int N,

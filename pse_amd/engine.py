@@ -233,6 +233,25 @@ class Engine:
                                                 1 if accumulate else 0))
         return force
 
+    def pair_repulsion_virial(self, pos, force, k, sigma=2.0, group=None, accumulate=True, out=None):
+        """pair_repulsion plus the pair observables of the same pass (pse_pair_repulsion_virial): returns the 8-element float64 CUDA
+        tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs (W_ab = sum_{i<j} d_a F_b, stress = -W / V; see include/pse_amd.h).  `force`
+        may be None (observables only).  `out`: where to write them -- e.g. a row of a (samples, 8) log tensor; nothing is read
+        back, the tensor is filled when the stream gets there."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if force is not None:
+            _chk4(force, "force")
+        if out is None:
+            out = torch.empty(8, dtype=torch.float64, device=pos.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
+                and out.is_contiguous()):
+            raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+        _lib.check(self._lib.pse_pair_repulsion_virial(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                       1 if accumulate else 0, _ptr(out)))
+        return out
+
     def random_psi(self, n, timestep, group=None):
         import torch
         rows = n if group is None else int(group.max().item()) + 1
