@@ -212,6 +212,24 @@ int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force
  * a slab rank (n_slabs >= 2) orders only its own cells, its sums would be partial -- PSE_ERR_INVALID. */
 int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* may be NULL */,
                               const unsigned *group, unsigned N, double k, double sigma, int accumulate, double *out8);
+/* A tabulated central pair potential on the same cell list, the counterpart of HOOMD's pair.table for the one particle type of this
+ * engine (no reference counterpart: the reference leaves forces to HOOMD).  table (DEVICE, width x 2 doubles, 16-byte aligned) holds
+ * V_k, F_k interleaved at the nodes r_k = rmin + k dr, dr = (rmax - rmin)/(width - 1): V_k the pair energy, F_k the magnitude of the
+ * radial force, positive for a repulsion.  Between the nodes both are linear: t = (r - rmin)(width - 1)/(rmax - rmin),
+ * k = min(floor(t), width - 2), w = t - k, V(r) = V_k + w (V_k+1 - V_k), F(r) likewise.  The pass acts on the minimum-image pairs among
+ * the N group members with rmin <= r < rmax and r > 0; a pair outside that interval contributes nothing (no extrapolation, as in
+ * HOOMD's table).  The force ON i FROM j is F(r) d / r, d = r_i - r_j.  force is overwritten (accumulate = 0) or incremented
+ * (accumulate = 1) as in pse_pair_repulsion, w is kept; force = NULL: observables only.  out8 (DEVICE, 8 doubles, or NULL) = U, Wxx,
+ * Wxy, Wxz, Wyy, Wyz, Wzz, npairs with the meaning and signs of pse_pair_repulsion_virial: U = sum V(r), W_ab = sum_{i<j} d_a F_b,
+ * each unordered pair once, stress = -W / V, no atomics, bit-reproducible on equal inputs.  out8 = NULL: forces only, and the
+ * reduction is not run.  PSE_ERR_INVALID: pos or table null, force and out8 both null, width outside [2, 2048] (the table is staged
+ * in 32 KB of LDS per workgroup), rmin or rmax not finite, rmin < 0, rmax <= rmin, rmax > rcut (the cell list is built for the
+ * hydrodynamic cutoff), a table that is not 16-byte aligned, out8 on a slab rank (n_slabs >= 2: its sums would be partial).  The
+ * call only queues work on the handle's stream wherever pse_pair_repulsion does and reads nothing back: the table is read by the
+ * stream, the caller keeps it alive and unchanged until the stream has passed the call. */
+int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* may be NULL */, const unsigned *group, unsigned N,
+                   const double *table /* DEVICE, width x 2: V_k, F_k interleaved */, int width, double rmin, double rmax,
+                   int accumulate, double *out8 /* DEVICE, may be NULL */);
 /* copy the three real-space grids (x-major, z fastest: idx = (x*Ny + y)*Nz + z, PSEv1/Mobility.cu:233) of the
  * most recent spread (stage 0) or inverse FFT (stage 1) to a host buffer of 3*nx_local*Ny*Nz doubles */
 int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out);

@@ -122,6 +122,7 @@ SYMBOLS = {
     "pse_random_psi": (_i, [_vp, _vp, _vp, _u, _u]),
     "pse_pair_repulsion": (_i, [_vp, _vp, _vp, _vp, _u, _d, _d, _i]),
     "pse_pair_repulsion_virial": (_i, [_vp, _vp, _vp, _vp, _u, _d, _d, _i, _vp]),
+    "pse_pair_table": (_i, [_vp, _vp, _vp, _vp, _u, _vp, _i, _d, _d, _i, _vp]),
     "pse_eval_realspace": (_i, [_vp, _dp, _i, _dp, _dp]),
     "pse_debug_copy_grid": (_i, [_vp, _i, _dp]),
     "pse_debug_spread": (_i, [_vp, _vp, _vp, _vp, _u]),

@@ -2,9 +2,10 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <cmath>
+#include <cstdint>
 #include <vector>
 
 #include "pse_err.h"
@@ -79,6 +80,22 @@ int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *, pse_double4 *,
     if (h->par.n_slabs > 1) return fail(PSE_ERR_INVALID, "pse_pair_repulsion_virial: this handle is a slab rank");
     if (!(sigma > 0.0) || sigma > h->d.rcut) return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]", sigma, h->d.rcut);
     return 0;   // out8 is a device pointer and there is no device: nothing is written
+}
+int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, const double *table, int width,
+                   double rmin, double rmax, int, double *out8) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    if (N == 0 || N > h->par.n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, h->par.n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_pair_table: null pos");
+    if (!table) return fail(PSE_ERR_INVALID, "pse_pair_table: null table");
+    if (((uintptr_t)table & 15u) != 0) return fail(PSE_ERR_INVALID, "pse_pair_table: the table is not 16-byte aligned");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_pair_table: force and out8 are both null: nothing to compute");
+    if (width < 2 || width > 2048) return fail(PSE_ERR_INVALID, "pse_pair_table: table width %d outside [2, 2048]", width);
+    if (!std::isfinite(rmin) || !std::isfinite(rmax)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g, rmax = %g must be finite", rmin, rmax);
+    if (rmin < 0.0) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g is negative", rmin);
+    if (!(rmax > rmin)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmax = %g must exceed rmin = %g", rmax, rmin);
+    if (rmax > h->d.rcut) return fail(PSE_ERR_INVALID, "pse_pair_table: table range rmax = %.4f beyond rcut = %.4f", rmax, h->d.rcut);
+    if (out8 && h->par.n_slabs > 1) return fail(PSE_ERR_INVALID, "pse_pair_table: this handle is a slab rank");
+    return 0;   // table, force and out8 are device pointers and there is no device: nothing is read or written
 }
 
 int pse_set_stream(pse_handle *, void *) { return no_device("pse_set_stream"); }

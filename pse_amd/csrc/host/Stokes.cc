@@ -68,6 +68,12 @@ void Stokes::pairRepulsionVirial(const pse_double4 *pos, pse_double4 *force, con
     check(pse_pair_repulsion_virial(m_h, pos, force, group, n, k, sigma, accumulate ? 1 : 0, out8), "Stokes::pairRepulsionVirial");
 }
 
+void Stokes::pairTable(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, const double *table,
+                       int width, double rmin, double rmax, bool accumulate, double *out8) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    check(pse_pair_table(m_h, pos, force, group, n, table, width, rmin, rmax, accumulate ? 1 : 0, out8), "Stokes::pairTable");
+}
+
 pse_info Stokes::info() const {
     pse_info i{};
     if (m_h) pse_get_info(m_h, &i);

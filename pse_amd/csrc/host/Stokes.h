@@ -46,6 +46,10 @@ public:
     // Wyz, Wzz, npairs, eight DEVICE doubles written by the stream; force may be null (observables only)
     void pairRepulsionVirial(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k,
                              double sigma, bool accumulate, double *out8);
+    // a tabulated central pair potential on the same cell list (pse_pair_table): table = width x (V, F) DEVICE doubles at the nodes
+    // rmin + k (rmax - rmin)/(width - 1), linear in between; force or out8 may be null (observables only / forces only), not both
+    void pairTable(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, const double *table, int width,
+                   double rmin, double rmax, bool accumulate, double *out8);
     pse_info info() const;
     int lanczosIterations() const { return m_m_Lanczos; }
     unsigned int hashedSeed() const { return m_seed; }

@@ -74,6 +74,11 @@ PYBIND11_MODULE(_PSEv1, m) {
             s.pairRepulsionVirial(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate,
                                   ptr<double>(out8));
         })
+        .def("pairTable", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, std::uintptr_t table,
+                             int width, double rmin, double rmax, bool accumulate, std::uintptr_t out8) {
+            s.pairTable(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, ptr<const double>(table), width,
+                        rmin, rmax, accumulate, ptr<double>(out8));
+        })
         .def("lanczosIterations", &Stokes::lanczosIterations)
         .def("hashedSeed", &Stokes::hashedSeed)
         .def("info", [](const Stokes &s) {

@@ -2568,6 +2568,33 @@ extern "C" int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, 
     return 0;
 }
 
+// Tabulated pair potential on the same cell list (include/pse_amd.h), with or without the eight observables.  Queue-only wherever
+// pse_pair_repulsion is; the table is read by the stream.
+extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                              const double *table, int width, double rmin, double rmax, int accumulate, double *out8) {
+    TRY(check_n(h, N));
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_pair_table: null pos");
+    if (!table) return fail(PSE_ERR_INVALID, "pse_pair_table: null table");
+    if (((uintptr_t)table & 15u) != 0) return fail(PSE_ERR_INVALID, "pse_pair_table: the table is not 16-byte aligned (it is read as (V, F) entries)");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_pair_table: force and out8 are both null: nothing to compute");
+    if (width < 2 || width > PAIR_TABLE_MAX_WIDTH)
+        return fail(PSE_ERR_INVALID, "pse_pair_table: table width %d outside [2, %d] (the table is staged in 32 KB of LDS)", width, PAIR_TABLE_MAX_WIDTH);
+    if (!std::isfinite(rmin) || !std::isfinite(rmax)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g, rmax = %g must be finite", rmin, rmax);
+    if (rmin < 0.0) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g is negative", rmin);
+    if (!(rmax > rmin)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmax = %g must exceed rmin = %g", rmax, rmin);
+    if (rmax > h->d.rcut)
+        return fail(PSE_ERR_INVALID, "pse_pair_table: table range rmax = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic cutoff",
+                    rmax, h->d.rcut);
+    if (out8 && h->n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "pse_pair_table: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums would be "
+                                     "partial (out8 must be null here)", h->n_slabs);
+    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    launch_pair_table(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, table, width, rmin, rmax, accumulate, (double4 *)force,
+                      h->pv_rows, out8, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int pse_random_psi(pse_handle *h, pse_double4 *psi, const unsigned *group, unsigned N, unsigned timestep) {
     TRY(check_n(h, N));
     if (!psi) return fail(PSE_ERR_INVALID, "null array");

@@ -356,5 +356,11 @@ constexpr int PAIR_VIRIAL_NOBS = 8;
 size_t pair_virial_rows(int n);
 void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
                                   double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
+// tabulated central pair potential from the cell list (k_pair_table): table = width x (V, F) on the device, 16-byte aligned, nodes
+// r_e = rmin + e (rmax - rmin)/(width - 1), linear between them, staged in width * 16 bytes of LDS per workgroup.  out8 != null: the
+// eight observables through `rows` as above; out8 == null: forces only, no reduction (rows is not touched)
+constexpr int PAIR_TABLE_MAX_WIDTH = 2048;   // 32 KB of LDS
+void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
+                       int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
 
 }  // namespace pse

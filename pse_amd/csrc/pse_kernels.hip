@@ -2804,6 +2804,102 @@ void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, i
 }
 size_t pair_virial_rows(int n) { return (size_t)nblocks(n, TPB) * PV_NOBS; }
 
+// Tabulated central pair potential on the same cell list (the counterpart of HOOMD's pair.table for the engine's one particle type;
+// no reference counterpart: the reference leaves forces to HOOMD).  table[e] = (V, F) at r_e = rmin + e dr, F the magnitude of the
+// radial force, positive for a repulsion; between the nodes both are interpolated linearly: t = (r - rmin) scale with
+// scale = (width - 1)/(rmax - rmin), e = min(floor(t), width - 2), w = t - e.  A pair with rmin <= r, r^2 < rmax^2, r > 0 adds
+// F(r) d / r to row i; the rest contributes nothing.
+// LDS: every workgroup first copies the table, one 16-byte (V, F) entry per lane and trip (global_load_dwordx4 -> ds_write_b128,
+// coalesced), into `width` 16-byte entries -- 32 KB at the cap of PAIR_TABLE_MAX_WIDTH -- and a pair then makes two ds_read_b128, entries
+// e and e + 1: V and F of a node share one read, the LDS serves 16-byte reads at its full rate and an entry never straddles two
+// bank rows.  The lanes' e are unrelated, so these reads conflict; that is accepted, the pass is bound by the position gathers.
+// OBS: the eight sums of k_pair_repulsion_virial with U = V(r) and c = F(r)/r, over the rows j > i, reduced and written to `rows`
+// exactly as there (k_pair_virial_finish adds the rows up).  No lane leaves before the barrier behind the staging loop, nor, with
+// OBS, before the one of the reduction.
+// (the native vector type, not double2: hipcc splits a double2 read from LDS into its members and pairs them up again as ds_read2_b64,
+// which the LDS serves at a quarter of the rate of ds_read_b128)
+typedef double pt_entry __attribute__((ext_vector_type(2)));   // x = V, y = F
+template <bool OBS>
+__global__ void __launch_bounds__(TPB)
+k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off, DBox box,
+             DCells nc, const double2 *__restrict__ table, int width, double rmin, double rmax, double scale, int accumulate,
+             double4 *__restrict__ force, double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
+    extern __shared__ pt_entry pt_tab[];   // [width]
+    __shared__ double sh[OBS ? TPB / 64 : 1][PV_NOBS];
+    for (int e = threadIdx.x; e < width; e += TPB) pt_tab[e] = ((const pt_entry *)table)[e];
+    __syncthreads();
+    const int blk = xcd_block(blockIdx.x, gridDim.x);
+    const int i = blk * TPB + threadIdx.x;
+    double o[PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = 0.0;
+    if (i < N) {
+        const double4 pi = pos_s[i];
+        double fx, fy, fz;
+        frac_coords(box, pi.x, pi.y, pi.z, fx, fy, fz);
+        const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
+        const double rmax2 = rmax * rmax;
+        const int elast = width - 2;
+        double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
+            for (int j = jb; j < je; ++j) {
+                const double4 pj = pos_s[j];
+                double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                min_image(box, dx, dy, dz);
+                const double r2 = dx * dx + dy * dy + dz * dz;
+                if (r2 < rmax2 && j != i && r2 > 0.0) {
+                    const double r = sqrt(r2);
+                    if (r >= rmin) {
+                        const double t = (r - rmin) * scale;        // 0 <= t <= width - 1 (+ an ulp): e stays inside the table
+                        const int e = min((int)t, elast);
+                        const double w = t - (double)e;
+                        const pt_entry a = pt_tab[e], b = pt_tab[e + 1];
+                        const double c = (a.y + w * (b.y - a.y)) * (1.0 / r);
+                        Fx += c * dx; Fy += c * dy; Fz += c * dz;
+                        if (OBS && j > i) {
+                            const double cdx = c * dx, cdy = c * dy;
+                            o[0] += a.x + w * (b.x - a.x);
+                            o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
+                            o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
+                            o[7] += 1.0;
+                        }
+                    }
+                }
+            }
+        });
+        if (force) {
+            const unsigned idx = tag_s[i];
+            double4 f = force[idx];
+            if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
+            force[idx] = f;
+        }
+    }
+    if (OBS) {
+#pragma unroll
+        for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
+        }
+        __syncthreads();
+        if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    }
+}
+void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
+                       int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
+    const int nb = nblocks(N, TPB);
+    const size_t lds = (size_t)width * sizeof(double2);
+    const double scale = (double)(width - 1) / (rmax - rmin);
+    if (out8) {
+        hipLaunchKernelGGL(k_pair_table<true>, dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N, cell_off, box, nc, (const double2 *)table,
+                           width, rmin, rmax, scale, accumulate, force, rows);
+        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
+    } else {
+        hipLaunchKernelGGL(k_pair_table<false>, dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N, cell_off, box, nc, (const double2 *)table,
+                           width, rmin, rmax, scale, accumulate, force, nullptr);
+    }
+}
+
 // K10 gpu_stokes_LinearCombination_kernel (PSEv1/Helper.cu:113-133) as the final un-sort: vel.xyz = a + b + c, keep w
 __global__ void k_scatter_sum(const double4 *__restrict__ a, const double4 *__restrict__ b,
                               const double4 *__restrict__ c, const unsigned *__restrict__ tag_s, int N,

@@ -252,6 +252,32 @@ class Engine:
                                                        1 if accumulate else 0, _ptr(out)))
         return out
 
+    def pair_table(self, pos, force, table, rmin, rmax, group=None, accumulate=True, out=None, observables=True):
+        """A tabulated central pair potential on the engine's cell list (pse_pair_table; see include/pse_amd.h).  `table`: contiguous
+        (width, 2) float64 CUDA tensor, V and F (magnitude of the radial force, positive for a repulsion) at the nodes
+        rmin + k (rmax - rmin)/(width - 1), linear in between; pairs with rmin <= r < rmax act.  `force` is incremented (or stored,
+        accumulate=False), or None: observables only.  observables=True: returns the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz,
+        Wyy, Wyz, Wzz, npairs, written to `out` when one is given (e.g. a row of a log tensor).  observables=False: forces only, the
+        reduction is not run, `out` is left alone and None is returned.  Nothing is read back; the stream reads `table`, so keep it
+        alive and unchanged until the stream has passed the call."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if force is not None:
+            _chk4(force, "force")
+        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and table.dim() == 2
+                and table.shape[1] == 2 and table.is_contiguous()):
+            raise ValueError("table must be a contiguous (width, 2) float64 CUDA tensor: V and F at the nodes")
+        if observables:
+            if out is None:
+                out = torch.empty(8, dtype=torch.float64, device=pos.device)
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
+                    and out.is_contiguous()):
+                raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+        _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
+                                            float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out) if observables else None))
+        return out if observables else None
+
     def random_psi(self, n, timestep, group=None):
         import torch
         rows = n if group is None else int(group.max().item()) + 1

@@ -2,47 +2,45 @@
 PSEv1/Stokes.cc:447; its example script has none).  SURVEY.md 8 f4: the step either side of the hot path, kept minimal."""
 
 
-class HarmonicRepulsion:
-    """F_i = sum_j k (sigma - r)(r_i - r_j)/r for minimum-image pairs with r < sigma (sigma = 2a: contact of unit spheres).
-    Evaluated on the integrator's own cell list; sigma must not exceed the hydrodynamic real-space cutoff.
+class _PairProvider:
+    """What the pair providers share: the eight device doubles of the most recent fused call -- U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
+    npairs -- where that call writes them (a row of a StressLog on a sample step, a buffer of the provider's own otherwise), and the
+    host-side readers.  A subclass sets NAME (what its messages call it) and makes the call in compute()."""
 
-    virial=True: compute() makes the fused call (pse_pair_repulsion_virial) instead -- the same forces, plus the potential energy
-    and the virial of the same pass in eight device doubles.  `energy`, `virial` and `stress()` copy them to the host when they are
-    read (that waits for the stream); a StressLog samples them without any wait."""
+    NAME = "pair provider"
 
-    def __init__(self, integrator, k, sigma=2.0, virial=False):
-        self.integrator, self.k, self.sigma = integrator, float(k), float(sigma)
+    def __init__(self, integrator, virial):
+        self.integrator = integrator
         self._fused = bool(virial)
         self._own = None     # where a fused call writes when no log takes the sample
         self._obs = None     # the eight device doubles of the most recent fused call: U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs
         self.log = None      # a StressLog registers itself here
         integrator.system.forces.append(self)
 
-    def compute(self, timestep):
+    def _group_args(self):
+        """(system, address of the group's members or 0, number of members)"""
         s, g = self.integrator.system, self.integrator.group
         m = g.members
-        if not self._fused:
-            self.integrator.cpp_method.pairRepulsion(s.pos.data_ptr(), s.net_force.data_ptr(), 0 if m is None else m.data_ptr(),
-                                                     len(g), self.k, self.sigma, True)
-            return
+        return s, 0 if m is None else m.data_ptr(), len(g)
+
+    def _out(self, timestep):
+        """The eight doubles the fused call of this step writes."""
         out = self.log.row(timestep) if self.log is not None else None
         if out is None:
             if self._own is None:
                 import torch
-                self._own = torch.zeros(8, dtype=torch.float64, device=s.pos.device)
+                self._own = torch.zeros(8, dtype=torch.float64, device=self.integrator.system.pos.device)
             out = self._own
-        self.integrator.cpp_method.pairRepulsionVirial(s.pos.data_ptr(), s.net_force.data_ptr(), 0 if m is None else m.data_ptr(),
-                                                       len(g), self.k, self.sigma, True, out.data_ptr())
-        self._obs = out
+        return out
 
     def _observables(self):
         if self._obs is None:
-            raise RuntimeError("no observables yet: HarmonicRepulsion(..., virial=True) and one compute() first")
+            raise RuntimeError(f"no observables yet: {self.NAME}(..., virial=True) and one compute() first")
         return self._obs.cpu().numpy()
 
     @property
     def energy(self):
-        """U = sum over pairs of k/2 (sigma - r)^2 at the most recent compute()."""
+        """U = the sum of the pair energies (HarmonicRepulsion: k/2 (sigma - r)^2) at the most recent compute()."""
         return float(self._observables()[0])
 
     @property
@@ -60,6 +58,75 @@ class HarmonicRepulsion:
         return -self.virial / (Lx * Ly * Lz)
 
 
+class HarmonicRepulsion(_PairProvider):
+    """F_i = sum_j k (sigma - r)(r_i - r_j)/r for minimum-image pairs with r < sigma (sigma = 2a: contact of unit spheres).
+    Evaluated on the integrator's own cell list; sigma must not exceed the hydrodynamic real-space cutoff.
+
+    virial=True: compute() makes the fused call (pse_pair_repulsion_virial) instead -- the same forces, plus the potential energy
+    and the virial of the same pass in eight device doubles.  `energy`, `virial` and `stress()` copy them to the host when they are
+    read (that waits for the stream); a StressLog samples them without any wait."""
+
+    NAME = "HarmonicRepulsion"
+
+    def __init__(self, integrator, k, sigma=2.0, virial=False):
+        self.k, self.sigma = float(k), float(sigma)
+        super().__init__(integrator, virial)
+
+    def compute(self, timestep):
+        s, members, n = self._group_args()
+        if not self._fused:
+            self.integrator.cpp_method.pairRepulsion(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True)
+            return
+        out = self._out(timestep)
+        self.integrator.cpp_method.pairRepulsionVirial(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True,
+                                                       out.data_ptr())
+        self._obs = out
+
+
+class TablePair(_PairProvider):
+    """A tabulated central pair potential (pse_pair_table; HOOMD's pair.table for the one particle type here): `table` is a NumPy or
+    torch (width, 2) array, 2 <= width <= 2048, of V and F -- the pair energy and the magnitude of the radial force, positive for a
+    repulsion -- at the nodes r_k = rmin + k (rmax - rmin)/(width - 1); both are linear between the nodes.  Pairs with
+    rmin <= r < rmax act, the rest contribute nothing; rmax must not exceed the hydrodynamic real-space cutoff.  The table is copied
+    to the device once, here.
+
+    virial=True: the same call also writes the potential energy, the virial and the pair count: `energy`, `virial`, `stress()`,
+    `npairs` and StressLog as for HarmonicRepulsion."""
+
+    NAME = "TablePair"
+
+    def __init__(self, integrator, table, rmin, rmax, virial=False):
+        import torch
+        t = torch.as_tensor(table).detach().to(dtype=torch.float64)
+        if t.dim() != 2 or t.shape[1] != 2 or not 2 <= t.shape[0] <= 2048:
+            raise ValueError("table must have shape (width, 2) with 2 <= width <= 2048: V and F at the nodes")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("table has non-finite entries")
+        self.rmin, self.rmax = float(rmin), float(rmax)
+        if not 0.0 <= self.rmin < self.rmax < float("inf"):
+            raise ValueError("need 0 <= rmin < rmax, both finite")
+        self.table = t.to(integrator.system.pos.device).contiguous().clone()
+        super().__init__(integrator, virial)
+
+    @classmethod
+    def from_functions(cls, integrator, V, F, rmin, rmax, width, virial=False):
+        """Sample the callables V(r) and F(r) = -dV/dr (one float in, one float out) at the `width` nodes."""
+        import numpy as np
+        width, rmin, rmax = int(width), float(rmin), float(rmax)
+        if width < 2:
+            raise ValueError("width must be at least 2")
+        r = rmin + np.arange(width) * ((rmax - rmin) / (width - 1))
+        return cls(integrator, np.array([[float(V(x)), float(F(x))] for x in r]), rmin, rmax, virial=virial)
+
+    def compute(self, timestep):
+        s, members, n = self._group_args()
+        out = self._out(timestep) if self._fused else None
+        self.integrator.cpp_method.pairTable(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
+                                             int(self.table.shape[0]), self.rmin, self.rmax, True, 0 if out is None else out.data_ptr())
+        if out is not None:
+            self._obs = out
+
+
 def _sym3(w):
     import numpy as np
     xx, xy, xz, yy, yz, zz = (float(v) for v in w)
@@ -67,7 +134,7 @@ def _sym3(w):
 
 
 class StressLog:
-    """Energy and stress of a HarmonicRepulsion(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
+    """Energy and stress of a HarmonicRepulsion or TablePair(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
     sample step the provider's fused call writes its eight doubles straight into the next row, the step number, the box tilt and the
     volume are noted on the host, and nothing waits for the device until table() is read.  Once full, the oldest rows are replaced."""
 
@@ -76,7 +143,7 @@ class StressLog:
     def __init__(self, provider, period, capacity):
         import torch
         if not getattr(provider, "_fused", False):
-            raise ValueError("StressLog needs a HarmonicRepulsion(..., virial=True)")
+            raise ValueError(f"StressLog needs a {getattr(provider, 'NAME', HarmonicRepulsion.NAME)}(..., virial=True)")
         if int(period) < 1 or int(capacity) < 1:
             raise ValueError("period and capacity must be positive")
         self.provider, self.period, self.capacity = provider, int(period), int(capacity)
