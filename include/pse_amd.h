@@ -230,6 +230,47 @@ int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4
 int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* may be NULL */, const unsigned *group, unsigned N,
                    const double *table /* DEVICE, width x 2: V_k, F_k interleaved */, int width, double rmin, double rmax,
                    int accumulate, double *out8 /* DEVICE, may be NULL */);
+
+/* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
+ * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
+ * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,
+ * pse_set_box) and r = |d|, the force ON i FROM j is c d:
+ *   PSE_BOND_HARMONIC  V = k/2 (r - r0)^2,                    c = -k (r - r0)/r
+ *   PSE_BOND_FENE      V = -k/2 r0^2 ln(1 - (r/r0)^2), r < r0, c = -k / (1 - (r/r0)^2)
+ * A bond with r == 0 contributes nothing and is not counted (the rule of the pair passes).  A FENE bond with r >= r0 contributes
+ * nothing to the force, U or W, is not counted in nbonds and adds one to a counter in the object (HOOMD aborts there; a call that only
+ * queues work cannot, so it counts): read it with pse_bonds_overstretched.  Duplicate bonds are legal and act once each, as in HOOMD.
+ * The minimum image is the nearest one only for bonds shorter than half the smallest perpendicular box width: longer bonds are the
+ * caller's error and are not detected.
+ * The object is stored as one row of (partner, type) entries per particle, every bond in both endpoints' rows, each row sorted
+ * (pse_host_bond_rows): forces and sums are therefore bit-identical for any order of the bond list and either order of a bond's endpoints.
+ * The object belongs to its handle: pse_destroy frees the bond objects still alive, pse_bonds_destroy after that is a caller error.
+ * pse_bonds_create returns PSE_ERR_INVALID, with a message naming the value, for: a null h, pairs_host, out or parameter array,
+ * n == 0 or n > n_max, nbonds == 0 or nbonds > 2^30, an endpoint >= n, a bond with i == j, ntypes outside [1, 64], a type >= ntypes,
+ * an unknown kind, a non-finite k or r0, r0 < 0, FENE with r0 <= 0. */
+#define PSE_BOND_HARMONIC 0   /* V = k/2 (r - r0)^2 */
+#define PSE_BOND_FENE     1   /* V = -k/2 r0^2 ln(1 - (r/r0)^2), r < r0 */
+typedef struct pse_bonds pse_bonds;
+int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds,
+                     const unsigned *pairs_host /* nbonds x 2 particle indices */,
+                     const unsigned *types_host /* nbonds, or NULL: all type 0 */,
+                     int ntypes, const int *kind_host, const double *k_host, const double *r0_host /* ntypes each */,
+                     pse_bonds **out);
+int pse_bonds_destroy(pse_bonds *b);
+/* The bonded forces of the object on the n rows of pos, and their observables.  force (n rows, or NULL: observables only):
+ * accumulate = 1 adds to .xyz of the bonded particles, rows of unbonded particles are neither read nor written; accumulate = 0
+ * overwrites .xyz of all n rows, with zero for unbonded particles; w is kept in every case.  out8 (DEVICE, 8 doubles -- a row of a
+ * larger array will do -- or NULL: forces only, the reduction is not run) = U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nbonds with the signs of
+ * pse_pair_repulsion_virial: U = sum V, W_ab = sum d_a (c d_b) with each bond once, stress = -W / V, dU/d(xy) = -Wxy, nbonds = 1.0
+ * per bond that acted.  force and out8 both NULL: PSE_ERR_INVALID.  The pass walks the object's rows, not the cell list: it does not
+ * sort, leaves the kept neighbour list and its counters alone, and works on a slab rank's handle too (positions are replicated there,
+ * the sums over all bonds are complete); owned-particle steps are not supported.  The call only queues work on the handle's stream
+ * and reads nothing back; no floating-point atomics, bit-reproducible on equal inputs. */
+int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force /* may be NULL */,
+                    int accumulate, double *out8 /* DEVICE, may be NULL */);
+/* FENE bonds found at r >= r0 by all pse_bond_forces calls on this object since its creation.  Waits for the handle's stream: the
+ * only call of the bond interface that reads back. */
+int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count);
 /* copy the three real-space grids (x-major, z fastest: idx = (x*Ny + y)*Nz + z, PSEv1/Mobility.cu:233) of the
  * most recent spread (stage 0) or inverse FFT (stage 1) to a host buffer of 3*nx_local*Ny*Nz doubles */
 int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out);
@@ -423,6 +464,13 @@ int pse_team_debug_solo(pse_team *team, int slab_rank);
 int pse_host_lanczos_sqrt_e1(int m, const double *alpha, const double *beta, double *t);
 /* host-only: the parameter rule of Stokes::setParams (PSEv1/Stokes.cc:129-236,319) without creating a handle */
 int pse_host_select_params(const pse_params *params, pse_info *info);
+/* host-only: the per-particle rows a pse_bonds object stores (pse_bonds_create calls this after validating).  A CSR over the n
+ * particles: row i is entries[2 row_off[i]] .. entries[2 row_off[i + 1]), one (partner, type) pair of unsigned per bond end; every
+ * bond appears in both endpoints' rows (duplicates as often as they are listed), each row sorted by (partner, type), so the rows
+ * are a function of the bond SET, not of the list order or of the order of a bond's endpoints.  types == NULL: all type 0.
+ * PSE_ERR_INVALID: a null array, n == 0, nbonds == 0 or > 2^30, an endpoint >= n, a bond with i == j. */
+int pse_host_bond_rows(unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types /* or NULL */,
+                       int *row_off /* n + 1 */, unsigned *entries /* 2 nbonds x 2: partner, type */);
 
 #ifdef __cplusplus
 }

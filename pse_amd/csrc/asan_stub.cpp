@@ -2,8 +2,9 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, pse_bonds_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -20,6 +21,12 @@ struct pse_handle {
     int n_intervals = 0;
     unsigned long long steps = 0;
     int lz_op = PSE_LANCZOS_RECORDS16;
+    std::vector<pse_bonds *> bond_lists;
+};
+struct pse_bonds {   // the REAL rows (pse_host_bond_rows), kept on the host
+    pse_handle *h;
+    std::vector<int> row_off;
+    std::vector<unsigned> entries;
 };
 struct pse_team { int unused; };
 
@@ -42,7 +49,11 @@ int pse_create(const pse_params *p, pse_handle **out) {
     *out = h;
     return 0;
 }
-int pse_destroy(pse_handle *h) { delete h; return 0; }
+int pse_destroy(pse_handle *h) {
+    if (h) for (pse_bonds *b : h->bond_lists) delete b;
+    delete h;
+    return 0;
+}
 int pse_set_box(pse_handle *h, double Lx, double Ly, double Lz, double xy) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
     if (!(Lx > 0 && Ly > 0 && Lz > 0)) return fail(PSE_ERR_INVALID, "box lengths must be positive");
@@ -96,6 +107,36 @@ int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, co
     if (rmax > h->d.rcut) return fail(PSE_ERR_INVALID, "pse_pair_table: table range rmax = %.4f beyond rcut = %.4f", rmax, h->d.rcut);
     if (out8 && h->par.n_slabs > 1) return fail(PSE_ERR_INVALID, "pse_pair_table: this handle is a slab rank");
     return 0;   // table, force and out8 are device pointers and there is no device: nothing is read or written
+}
+int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
+                     const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_bonds_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_bonds_create: null handle");
+    if (int rc = bonds_validate(h->par.n_max, n, nbonds, pairs_host, types_host, ntypes, kind_host, k_host, r0_host)) return rc;
+    pse_bonds *b = new pse_bonds{h, std::vector<int>((size_t)n + 1), std::vector<unsigned>((size_t)nbonds * 4)};
+    if (int rc = pse_host_bond_rows(n, nbonds, pairs_host, types_host, b->row_off.data(), b->entries.data())) { delete b; return rc; }
+    h->bond_lists.push_back(b);
+    *out = b;
+    return 0;
+}
+int pse_bonds_destroy(pse_bonds *b) {
+    if (!b) return 0;
+    std::vector<pse_bonds *> &l = b->h->bond_lists;
+    l.erase(std::remove(l.begin(), l.end(), b), l.end());
+    delete b;
+    return 0;
+}
+int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force, int, double *out8) {
+    if (!b) return fail(PSE_ERR_INVALID, "pse_bond_forces: null bond object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_bond_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_bond_forces: force and out8 are both null: nothing to compute");
+    return 0;   // pos, force and out8 are device pointers and there is no device: nothing is read or written
+}
+int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) {
+    if (!b || !count) return fail(PSE_ERR_INVALID, "pse_bonds_overstretched: null argument");
+    *count = 0;
+    return 0;
 }
 
 int pse_set_stream(pse_handle *, void *) { return no_device("pse_set_stream"); }

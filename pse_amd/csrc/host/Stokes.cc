@@ -23,6 +23,7 @@ Stokes::~Stokes() {
 
 void Stokes::setParams() {
     if (m_h) { pse_destroy(m_h); m_h = nullptr; }
+    m_bonds.clear();   // pse_destroy freed them
     m_m_Lanczos = 2;   // "try two Lanczos iterations to start" (PSEv1/Stokes.cc:131-132)
     pse_params p{};
     p.n_max = m_n_total;
@@ -72,6 +73,36 @@ void Stokes::pairTable(const pse_double4 *pos, pse_double4 *force, const unsigne
                        int width, double rmin, double rmax, bool accumulate, double *out8) {
     if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
     check(pse_pair_table(m_h, pos, force, group, n, table, width, rmin, rmax, accumulate ? 1 : 0, out8), "Stokes::pairTable");
+}
+
+int Stokes::bondsCreate(unsigned int n, unsigned int nbonds, const unsigned int *pairs, const unsigned int *types, int ntypes, const int *kind,
+                        const double *k, const double *r0) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    pse_bonds *b = nullptr;
+    check(pse_bonds_create(m_h, n, nbonds, pairs, types, ntypes, kind, k, r0, &b), "Stokes::bondsCreate");
+    m_bonds.push_back(b);
+    return (int)m_bonds.size() - 1;
+}
+
+pse_bonds *Stokes::bondObject(int id) const {
+    if (id < 0 || id >= (int)m_bonds.size() || !m_bonds[id])
+        throw std::invalid_argument("Stokes: no bond object with id " + std::to_string(id) + " (setParams invalidates the ids)");
+    return m_bonds[id];
+}
+
+void Stokes::bondForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8) {
+    check(pse_bond_forces(bondObject(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::bondForces");
+}
+
+unsigned long long Stokes::bondsOverstretched(int id) {
+    unsigned long long c = 0;
+    check(pse_bonds_overstretched(bondObject(id), &c), "Stokes::bondsOverstretched");
+    return c;
+}
+
+void Stokes::bondsDestroy(int id) {
+    check(pse_bonds_destroy(bondObject(id)), "Stokes::bondsDestroy");
+    m_bonds[id] = nullptr;
 }
 
 pse_info Stokes::info() const {

@@ -4,6 +4,7 @@
 #pragma once
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../../include/pse_amd.h"
 #include "ShearFunction.h"
@@ -50,6 +51,15 @@ public:
     // rmin + k (rmax - rmin)/(width - 1), linear in between; force or out8 may be null (observables only / forces only), not both
     void pairTable(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, const double *table, int width,
                    double rmin, double rmax, bool accumulate, double *out8);
+    // bonded forces (pse_bonds_create / pse_bond_forces / pse_bonds_overstretched): bondsCreate copies the HOST arrays -- nbonds x 2
+    // particle indices, nbonds types or null, ntypes x (kind, k, r0) -- to the engine and returns the id the other calls take.  The
+    // bond objects belong to the engine: setParams, which makes a new one, invalidates every id
+    int bondsCreate(unsigned int n, unsigned int nbonds, const unsigned int *pairs, const unsigned int *types, int ntypes, const int *kind,
+                    const double *k, const double *r0);
+    // force or out8 (eight DEVICE doubles: U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nbonds) may be null, not both
+    void bondForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8);
+    unsigned long long bondsOverstretched(int id);   // waits for the stream
+    void bondsDestroy(int id);
     pse_info info() const;
     int lanczosIterations() const { return m_m_Lanczos; }
     unsigned int hashedSeed() const { return m_seed; }
@@ -67,6 +77,8 @@ private:
     int m_m_Lanczos = 2;                                                                   // Stokes.cc:132
     int m_lanczos_op = -1;
     pse_handle *m_h = nullptr;
+    std::vector<pse_bonds *> m_bonds;   // by id; null once destroyed
+    pse_bonds *bondObject(int id) const;
 };
 
 }  // namespace pse_host

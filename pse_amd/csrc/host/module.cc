@@ -79,6 +79,17 @@ PYBIND11_MODULE(_PSEv1, m) {
             s.pairTable(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, ptr<const double>(table), width,
                         rmin, rmax, accumulate, ptr<double>(out8));
         })
+        // host arrays by address too (numpy .ctypes.data): nbonds x 2 uint32, nbonds uint32 or 0, ntypes int32 / float64 / float64
+        .def("bondsCreate", [](Stokes &s, unsigned int n, unsigned int nbonds, std::uintptr_t pairs, std::uintptr_t types, int ntypes,
+                               std::uintptr_t kind, std::uintptr_t k, std::uintptr_t r0) {
+            return s.bondsCreate(n, nbonds, ptr<const unsigned int>(pairs), ptr<const unsigned int>(types), ntypes, ptr<const int>(kind),
+                                 ptr<const double>(k), ptr<const double>(r0));
+        })
+        .def("bondForces", [](Stokes &s, int id, std::uintptr_t pos, std::uintptr_t force, bool accumulate, std::uintptr_t out8) {
+            s.bondForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
+        })
+        .def("bondsOverstretched", &Stokes::bondsOverstretched)
+        .def("bondsDestroy", &Stokes::bondsDestroy)
         .def("lanczosIterations", &Stokes::lanczosIterations)
         .def("hashedSeed", &Stokes::hashedSeed)
         .def("info", [](const Stokes &s) {

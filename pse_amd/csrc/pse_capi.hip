@@ -110,6 +110,7 @@ struct pse_handle {
     size_t sort_tmp_bytes = 0;
     int *cell_off = nullptr;
     double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
+    std::vector<pse_bonds *> bond_lists;   // the bond objects created on this handle and still alive (pse_destroy frees them)
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
@@ -397,10 +398,29 @@ static int collect_times(pse_handle *h, unsigned mask) {
     return 0;
 }
 
+// A bond topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, the per-type parameters and the counter of
+// overstretched FENE bonds.  Owned by its handle.
+struct pse_bonds {
+    pse_handle *h = nullptr;
+    unsigned n = 0, nbonds = 0;
+    int ntypes = 0;
+    unsigned *row_off = nullptr;            // n + 1
+    uint2 *entries = nullptr;               // 2 nbonds: (partner, type)
+    BondParam *par = nullptr;               // ntypes
+    unsigned long long *over = nullptr;     // FENE bonds seen at r >= r0 since creation
+};
+static void bonds_free(pse_bonds *b) {
+    void *ptrs[] = {b->row_off, b->entries, b->par, b->over};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete b;
+}
+
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    for (pse_bonds *b : h->bond_lists) bonds_free(b);
+    h->bond_lists.clear();
     if (h->plan_fwd) rocfft_plan_destroy(h->plan_fwd);
     if (h->plan_inv) rocfft_plan_destroy(h->plan_inv);
     if (h->plan_x_fwd) rocfft_plan_destroy(h->plan_x_fwd);
@@ -2592,6 +2612,73 @@ extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4
     launch_pair_table(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, table, width, rmin, rmax, accumulate, (double4 *)force,
                       h->pv_rows, out8, h->stream);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- bonded forces (include/pse_amd.h) ----------------------------------------------------------------------------------------
+extern "C" int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
+                                const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_bonds_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_bonds_create: null handle");
+    TRY(bonds_validate((unsigned)h->n_max, n, nbonds, pairs_host, types_host, ntypes, kind_host, k_host, r0_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)nbonds * 4);
+    TRY(pse_host_bond_rows(n, nbonds, pairs_host, types_host, off.data(), ent.data()));
+    std::vector<BondParam> par((size_t)ntypes);
+    for (int t = 0; t < ntypes; ++t)
+        par[t] = BondParam{k_host[t], r0_host[t], r0_host[t] > 0.0 ? 1.0 / (r0_host[t] * r0_host[t]) : 0.0, (double)kind_host[t]};
+    pse_bonds *b = new pse_bonds();
+    b->h = h; b->n = n; b->nbonds = nbonds; b->ntypes = ntypes;
+    auto put = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, bytes);
+        if (e != hipSuccess) return e;
+        return src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
+    };
+    hipError_t e = put((void **)&b->row_off, off.data(), off.size() * sizeof(int));
+    if (e == hipSuccess) e = put((void **)&b->entries, ent.data(), ent.size() * sizeof(unsigned));
+    if (e == hipSuccess) e = put((void **)&b->par, par.data(), par.size() * sizeof(BondParam));
+    if (e == hipSuccess) e = put((void **)&b->over, nullptr, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memset is the one call above that may return early)
+    if (e != hipSuccess) {
+        bonds_free(b);
+        return fail(PSE_ERR_HIP, "pse_bonds_create: copying %u bonds to the device failed: %s", nbonds, hipGetErrorString(e));
+    }
+    h->bond_lists.push_back(b);
+    *out = b;
+    return 0;
+}
+
+extern "C" int pse_bonds_destroy(pse_bonds *b) {
+    if (!b) return 0;
+    pse_handle *h = b->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
+    h->bond_lists.erase(std::remove(h->bond_lists.begin(), h->bond_lists.end(), b), h->bond_lists.end());
+    bonds_free(b);
+    return 0;
+}
+
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
+    if (!b) return fail(PSE_ERR_INVALID, "pse_bond_forces: null bond object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_bond_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_bond_forces: force and out8 are both null: nothing to compute");
+    pse_handle *h = b->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_bond_forces((const double4 *)pos, (int)b->n, b->row_off, b->entries, b->par, b->ntypes, h->dbox, accumulate, (double4 *)force,
+                       h->pv_rows, out8, b->over, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) {
+    if (!b || !count) return fail(PSE_ERR_INVALID, "pse_bonds_overstretched: null argument");
+    pse_handle *h = b->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(count, b->over, sizeof *count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
 

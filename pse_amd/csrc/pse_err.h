@@ -17,5 +17,9 @@ void fill_info(const Derived &d, pse_info *o);
 // coarsest of the three grid spacings (an override the reference's rule cannot produce) -- shared by pse_create, pse_set_box,
 // pse_host_select_params and the sanitizer build's stand-in, so that all agree on which configurations are valid
 int gaussian_fits(const Derived &d, double hx, double hy, double hz);
+// 0, or PSE_ERR_INVALID with a message naming the offending value: the argument checks of pse_bonds_create that need no device
+// (include/pse_amd.h lists them) -- shared by the device library and the sanitizer build's stand-in
+int bonds_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types, int ntypes, const int *kind,
+                   const double *k, const double *r0);
 
 }  // namespace pse

@@ -10,6 +10,8 @@ constexpr int RS_DEG = 9;           // 10 coefficients per function
 constexpr int RS_NCOEF = RS_DEG + 1;
 constexpr int RS_PER_UNIT = 8;      // intervals of width 1/8 (in units of the particle radius)
 
+constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS
+
 struct Box {
     double Lx, Ly, Lz, xy;
 };

@@ -3,6 +3,7 @@
 // (LAPACKE_spteqr + the host loops at PSEv1/Brownian.cu:540-582).  Plain C++: linked into libpse_amd.so, and -- with
 // pse_params.cpp and a stub of the device entry points -- into the sanitizer build that the CPU tests run against.
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -47,6 +48,30 @@ int gaussian_fits(const Derived &d, double hx, double hy, double hz) {
     return 0;
 }
 
+int bonds_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types, int ntypes, const int *kind,
+                   const double *k, const double *r0) {
+    if (!pairs) return fail(PSE_ERR_INVALID, "pse_bonds_create: null pairs_host");
+    if (!kind || !k || !r0) return fail(PSE_ERR_INVALID, "pse_bonds_create: null parameter array (kind_host, k_host, r0_host)");
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "pse_bonds_create: n = %u outside (0, n_max = %u]", n, n_max);
+    if (nbonds == 0 || nbonds > (1u << 30)) return fail(PSE_ERR_INVALID, "pse_bonds_create: nbonds = %u outside (0, 2^30]", nbonds);
+    if (ntypes < 1 || ntypes > BOND_MAX_TYPES) return fail(PSE_ERR_INVALID, "pse_bonds_create: ntypes = %d outside [1, %d]", ntypes, BOND_MAX_TYPES);
+    for (int t = 0; t < ntypes; ++t) {
+        if (kind[t] != PSE_BOND_HARMONIC && kind[t] != PSE_BOND_FENE)
+            return fail(PSE_ERR_INVALID, "pse_bonds_create: type %d has kind %d, neither PSE_BOND_HARMONIC nor PSE_BOND_FENE", t, kind[t]);
+        if (!std::isfinite(k[t]) || !std::isfinite(r0[t]))
+            return fail(PSE_ERR_INVALID, "pse_bonds_create: type %d has k = %g, r0 = %g: both must be finite", t, k[t], r0[t]);
+        if (r0[t] < 0.0) return fail(PSE_ERR_INVALID, "pse_bonds_create: type %d has r0 = %g < 0", t, r0[t]);
+        if (kind[t] == PSE_BOND_FENE && !(r0[t] > 0.0)) return fail(PSE_ERR_INVALID, "pse_bonds_create: FENE type %d needs r0 > 0, not %g", t, r0[t]);
+    }
+    for (unsigned b = 0; b < nbonds; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1];
+        if (i >= n || j >= n) return fail(PSE_ERR_INVALID, "pse_bonds_create: bond %u = (%u, %u) has an endpoint >= n = %u", b, i, j, n);
+        if (i == j) return fail(PSE_ERR_INVALID, "pse_bonds_create: bond %u joins particle %u to itself", b, i);
+        if (types && types[b] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "pse_bonds_create: bond %u has type %u >= ntypes = %d", b, types[b], ntypes);
+    }
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -69,5 +94,33 @@ extern "C" int pse_host_lanczos_sqrt_e1(int m, const double *alpha, const double
     std::vector<double> tv;
     if (!lanczos_sqrt_e1(m, alpha, beta, tv)) return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve did not converge");
     std::copy(tv.begin(), tv.end(), t);
+    return 0;
+}
+
+// Counting sort of the 2 nbonds bond ends by particle, then each row sorted by (partner, type): O(nbonds) plus the row sorts.
+extern "C" int pse_host_bond_rows(unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types, int *row_off, unsigned *entries) {
+    if (!pairs || !row_off || !entries) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: null array");
+    if (n == 0) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: n = 0");
+    if (nbonds == 0 || nbonds > (1u << 30)) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: nbonds = %u outside (0, 2^30]", nbonds);
+    for (unsigned b = 0; b < nbonds; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1];
+        if (i >= n || j >= n) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: bond %u = (%u, %u) has an endpoint >= n = %u", b, i, j, n);
+        if (i == j) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: bond %u joins particle %u to itself", b, i);
+    }
+    // (offsets are counted as unsigned: at the cap of 2^30 bonds the last one is 2^31, which the device reads as unsigned too)
+    unsigned *off = reinterpret_cast<unsigned *>(row_off);
+    std::fill(off, off + (size_t)n + 1, 0u);
+    for (unsigned b = 0; b < nbonds; ++b) { ++off[pairs[2 * (size_t)b] + 1]; ++off[pairs[2 * (size_t)b + 1] + 1]; }
+    for (unsigned i = 0; i < n; ++i) off[i + 1] += off[i];
+    std::vector<unsigned> fill(off, off + n);
+    struct End { unsigned partner, type; };
+    End *e = reinterpret_cast<End *>(entries);
+    for (unsigned b = 0; b < nbonds; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1], t = types ? types[b] : 0u;
+        e[fill[i]++] = End{j, t};
+        e[fill[j]++] = End{i, t};
+    }
+    for (unsigned i = 0; i < n; ++i)
+        std::sort(e + off[i], e + off[i + 1], [](const End &a, const End &b) { return a.partner != b.partner ? a.partner < b.partner : a.type < b.type; });
     return 0;
 }

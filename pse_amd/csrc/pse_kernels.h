@@ -362,5 +362,16 @@ void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, i
 constexpr int PAIR_TABLE_MAX_WIDTH = 2048;   // 32 KB of LDS
 void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
                        int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
+// bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
+// entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
+// eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does
+// not act and adds one to *overstretched.
+struct BondParam {   // 32 bytes, staged in LDS as two 16-byte words (the device array is a hipMalloc of its own: aligned)
+    double k, r0;
+    double ir02;     // 1 / r0^2 (FENE; 0 where r0 = 0)
+    double kind;     // PSE_BOND_HARMONIC or PSE_BOND_FENE as a double
+};
+void launch_bond_forces(const double4 *pos, int n, const unsigned *row_off, const uint2 *entries, const BondParam *par, int ntypes, DBox box,
+                        int accumulate, double4 *force, double *rows, double *out8, unsigned long long *overstretched, hipStream_t s);
 
 }  // namespace pse

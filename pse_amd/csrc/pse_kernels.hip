@@ -2900,6 +2900,111 @@ void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const
     }
 }
 
+// Bonded forces (HOOMD's bond.harmonic and bond.fene; no reference counterpart: the reference leaves forces to HOOMD).  One thread
+// per particle of the CALLER-order arrays walks its row of the bond object -- entries (partner, type), one 8-byte load each, sorted by
+// (partner, type) on the host -- and gathers each partner's position with one double4 load.  With d = r_i - r_j (minimum image),
+// the force on i from j is c d, c = -k (r - r0)/r (harmonic) or -k / (1 - (r/r0)^2) (FENE, r < r0).  Every bond is in both
+// endpoints' rows, so each thread owns its force row: no atomics on forces, and the order of the sum is the order of the row, a function
+// of the bond SET -- forces and sums are bit-identical for any permutation of the bond list and either order of a bond's endpoints
+// (min_image is odd in d, so both ends see the same r).  A bond with r == 0 does nothing; a FENE bond with r >= r0 does nothing either
+// and is counted: its lower endpoint adds it to a per-thread count, and a thread that saw one makes ONE integer atomicAdd.
+// Per-type parameters: the type differs from lane to lane, so a wave-uniform (scalar) load cannot serve them; they are staged in
+// LDS instead, 32 bytes per type (k, r0, 1/r0^2, kind), at most 2 KB, copied by the first lanes of each workgroup before one barrier,
+// and read as two 16-byte words per bond.  In the common case of one type every lane reads the same entry, which the LDS broadcasts.
+// OBS: the endpoint with the LOWER index adds the bond to the eight sums U, W (six), count; reduction, row per workgroup and
+// k_pair_virial_finish as in k_pair_repulsion_virial.  No lane leaves before either barrier.
+// accumulate != 0: the rows of unbonded particles are neither read nor written; accumulate == 0: every row's xyz is overwritten, w kept.
+template <bool OBS>
+__global__ void __launch_bounds__(TPB)
+k_bond_forces(const double4 *__restrict__ pos, int n, const unsigned *__restrict__ row_off, const uint2 *__restrict__ entries,
+              const BondParam *__restrict__ par, int ntypes, DBox box, int accumulate, double4 *__restrict__ force,
+              double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */, unsigned long long *__restrict__ overstretched) {
+    __shared__ pt_entry bp[2 * BOND_MAX_TYPES];   // [type][0] = (k, r0), [type][1] = (1/r0^2, kind)
+    __shared__ double sh[OBS ? TPB / 64 : 1][PV_NOBS];
+    if ((int)threadIdx.x < 2 * ntypes) bp[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
+    __syncthreads();
+    const int blk = xcd_block(blockIdx.x, gridDim.x);
+    const int i = blk * TPB + threadIdx.x;
+    double o[PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = 0.0;
+    if (i < n) {
+        const unsigned eb = row_off[i], ee = row_off[i + 1];
+        if (ee > eb) {
+            const double4 pi = pos[i];
+            double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+            unsigned over = 0;
+            for (unsigned e = eb; e < ee; ++e) {
+                const uint2 en = entries[e];                  // x = partner, y = type
+                const double4 pj = pos[en.x];
+                const pt_entry a = bp[2 * en.y], b = bp[2 * en.y + 1];
+                double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                min_image(box, dx, dy, dz);
+                const double r2 = dx * dx + dy * dy + dz * dz;
+                if (r2 > 0.0) {
+                    const bool lower = (unsigned)i < en.x;
+                    double c, u;
+                    bool acts = true;
+                    if (b.y == 0.0) {                          // harmonic
+                        const double r = sqrt(r2), dr = r - a.y;
+                        c = -a.x * dr / r;
+                        u = 0.5 * a.x * dr * dr;
+                    } else {                                   // FENE
+                        const double x = r2 * b.x;             // (r / r0)^2
+                        acts = x < 1.0;
+                        c = -a.x / (1.0 - x);
+                        u = OBS ? -0.5 * a.x * a.y * a.y * log1p(-x) : 0.0;
+                        if (!acts && lower) ++over;
+                    }
+                    if (acts) {
+                        Fx += c * dx; Fy += c * dy; Fz += c * dz;
+                        if (OBS && lower) {
+                            const double cdx = c * dx, cdy = c * dy;
+                            o[0] += u;
+                            o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
+                            o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
+                            o[7] += 1.0;
+                        }
+                    }
+                }
+            }
+            if (force) {
+                double4 f = force[i];
+                if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
+                force[i] = f;
+            }
+            if (over) atomicAdd(overstretched, (unsigned long long)over);
+        } else if (force && !accumulate) {
+            double4 f = force[i];
+            f.x = 0.0; f.y = 0.0; f.z = 0.0;
+            force[i] = f;
+        }
+    }
+    if (OBS) {
+#pragma unroll
+        for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
+        }
+        __syncthreads();
+        if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    }
+}
+void launch_bond_forces(const double4 *pos, int n, const unsigned *row_off, const uint2 *entries, const BondParam *par, int ntypes, DBox box,
+                        int accumulate, double4 *force, double *rows, double *out8, unsigned long long *overstretched, hipStream_t s) {
+    static_assert(sizeof(BondParam) == 2 * sizeof(pt_entry) && 2 * BOND_MAX_TYPES <= TPB, "one lane stages one 16-byte word of the parameters");
+    const int nb = nblocks(n, TPB);
+    if (out8) {
+        hipLaunchKernelGGL(k_bond_forces<true>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, rows,
+                           overstretched);
+        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
+    } else {
+        hipLaunchKernelGGL(k_bond_forces<false>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, nullptr,
+                           overstretched);
+    }
+}
+
 // K10 gpu_stokes_LinearCombination_kernel (PSEv1/Helper.cu:113-133) as the final un-sort: vel.xyz = a + b + c, keep w
 __global__ void k_scatter_sum(const double4 *__restrict__ a, const double4 *__restrict__ b,
                               const double4 *__restrict__ c, const unsigned *__restrict__ tag_s, int N,

@@ -71,6 +71,88 @@ def host_lanczos_sqrt_e1(alpha, beta):
     return t
 
 
+# the bond potentials of pse_bonds_create: name -> PSE_BOND_*
+BOND_KINDS = {"harmonic": 0, "fene": 1}
+
+
+def _per_type(v, name):
+    """A scalar or a sequence as a list (strings are scalars)."""
+    import numpy as np
+    if isinstance(v, str) or np.ndim(v) == 0:
+        return [v]
+    return list(v)
+
+
+class BondList:
+    """Owner of a pse_bonds object: a fixed set of harmonic / FENE bonds among the rows of the caller-order arrays.  Holds a reference
+    to its engine, whose handle owns the device object."""
+
+    def __init__(self, engine, pairs, types, kinds, k, r0, n):
+        import numpy as np
+        pairs = np.asarray(pairs)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0 or not np.issubdtype(pairs.dtype, np.integer):
+            raise ValueError("pairs must be a non-empty integer (nbonds, 2) array of particle indices")
+        if pairs.min() < 0 or pairs.max() >= 2 ** 32:
+            raise ValueError("pairs holds an index outside [0, 2^32)")
+        nb = pairs.shape[0]
+        if types is not None:
+            types = np.asarray(types)
+            if types.shape != (nb,) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0 or types.max() >= 2 ** 32:
+                raise ValueError("types must be a non-negative integer array with one entry per bond")
+            types = np.ascontiguousarray(types, dtype=np.uint32)
+        kinds, k, r0 = _per_type(kinds, "kinds"), _per_type(k, "k"), _per_type(r0, "r0")
+        if not (len(kinds) == len(k) == len(r0)) or not kinds:
+            raise ValueError("kinds, k and r0 must have one entry per bond type each")
+        for v in kinds:
+            if isinstance(v, str) and v not in BOND_KINDS:
+                raise ValueError(f"bond kind must be one of {sorted(BOND_KINDS)}, not {v!r}")
+        kind_a = np.array([BOND_KINDS[v] if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32)
+        k_a, r0_a = np.array(k, dtype=np.float64), np.array(r0, dtype=np.float64)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+        self.n = int(engine.params.n_max if n is None else n)
+        if not 0 <= self.n < 2 ** 32:
+            raise ValueError("n outside [0, 2^32)")
+        self.nbonds, self.engine, self._lib = nb, engine, engine._lib
+        self._b = ctypes.c_void_p()
+        vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        _lib.check(self._lib.pse_bonds_create(engine._h, self.n, nb, vp(pairs), vp(types), len(kind_a), vp(kind_a), vp(k_a), vp(r0_a),
+                                              ctypes.byref(self._b)))
+
+    def forces(self, pos, force, accumulate=True, out=None, observables=True):
+        """The bonded forces on the first n rows of `pos` (pse_bond_forces), added to `force` (or stored: accumulate=False, which zeroes
+        the rows of unbonded particles), or force=None: observables only.  observables=True: returns the 8-element float64 CUDA tensor
+        U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nbonds, written to `out` when one is given (e.g. a row of a log tensor); observables=False:
+        forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
+        import torch
+        if self._b is None or not self._b.value:
+            raise ValueError("this BondList is closed")
+        _chk4(pos, "pos", self.n)
+        if force is not None:
+            _chk4(force, "force", self.n)
+        if observables:
+            if out is None:
+                out = torch.empty(8, dtype=torch.float64, device=pos.device)
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
+                    and out.is_contiguous()):
+                raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+        _lib.check(self._lib.pse_bond_forces(self._b, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out) if observables else None))
+        return out if observables else None
+
+    @property
+    def overstretched(self):
+        """FENE bonds found at r >= r0 by all calls since creation (pse_bonds_overstretched: waits for the stream)."""
+        v = ctypes.c_ulonglong(0)
+        _lib.check(self._lib.pse_bonds_overstretched(self._b, ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self):
+        b, self._b = getattr(self, "_b", None), None
+        if b is not None and b.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
+            self._lib.pse_bonds_destroy(b)
+
+    __del__ = close
+
+
 class Engine:
     """One PSE engine instance == one `Stokes` object's device state (PSEv1/Stokes.h:128-150)."""
 
@@ -277,6 +359,12 @@ class Engine:
         _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
                                             float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out) if observables else None))
         return out if observables else None
+
+    def bonds(self, pairs, types=None, kinds=(0,), k=(1.0,), r0=(1.0,), n=None):
+        """A bond topology on the device (pse_bonds_create; see include/pse_amd.h): `pairs` (nbonds, 2) particle indices into arrays of
+        `n` rows (default: n_max), `types` (nbonds,) indices into the per-type sequences `kinds` ("harmonic" | "fene" or
+        BOND_KINDS codes), `k`, `r0`, or None: all type 0.  Returns a BondList."""
+        return BondList(self, pairs, types, kinds, k, r0, n)
 
     def random_psi(self, n, timestep, group=None):
         import torch

@@ -127,6 +127,66 @@ class TablePair(_PairProvider):
             self._obs = out
 
 
+class Bonds(_PairProvider):
+    """Harmonic and FENE bonds (pse_bond_forces; HOOMD's bond.harmonic and bond.fene): `pairs` is an (nbonds, 2) integer array of
+    particle indices into the system's arrays.  kind = "harmonic": V = k/2 (r - r0)^2; "fene": V = -k/2 r0^2 ln(1 - (r/r0)^2), r < r0.
+    `kind`, `k` and `r0` are scalars (one bond type) or sequences with one entry per type, and `types` then gives each bond's type
+    (None: all type 0).  The topology is copied to the device once, here.  Duplicate bonds act once each.  A bond must stay shorter
+    than half the smallest perpendicular box width: the minimum image is the nearest one only there.  A FENE bond found at r >= r0
+    contributes nothing and is counted in `overstretched` (HOOMD aborts there).
+
+    virial=True: the same call also writes the bond energy, the virial and the number of bonds that acted: `energy`, `virial`,
+    `stress()`, `nbonds` and StressLog as for HarmonicRepulsion."""
+
+    NAME = "Bonds"
+    KINDS = {"harmonic": 0, "fene": 1}
+
+    def __init__(self, integrator, pairs, kind="harmonic", k=1.0, r0=1.0, types=None, virial=False):
+        import numpy as np
+        seq = lambda v: [v] if isinstance(v, str) or np.ndim(v) == 0 else list(v)
+        kind, k, r0 = seq(kind), seq(k), seq(r0)
+        nt = max(len(kind), len(k), len(r0))
+        kind, k, r0 = (v * nt if len(v) == 1 else v for v in (kind, k, r0))   # a scalar serves every type
+        if not len(kind) == len(k) == len(r0) == nt:
+            raise ValueError("kind, k and r0 must be scalars or sequences of one length (one entry per bond type)")
+        for v in kind:
+            if v not in self.KINDS:
+                raise ValueError(f"bond kind must be one of {sorted(self.KINDS)}, not {v!r}")
+        pairs = np.asarray(pairs)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0 or not np.issubdtype(pairs.dtype, np.integer) or pairs.min() < 0:
+            raise ValueError("pairs must be a non-empty (nbonds, 2) array of non-negative integer particle indices")
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+        if types is not None:
+            types = np.asarray(types)
+            if types.shape != (pairs.shape[0],) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
+                raise ValueError("types must be a non-negative integer array with one entry per bond")
+            types = np.ascontiguousarray(types, dtype=np.uint32)
+        self.kind, self.k, self.r0 = tuple(kind), tuple(float(v) for v in k), tuple(float(v) for v in r0)
+        kind_a = np.array([self.KINDS[v] for v in kind], dtype=np.int32)
+        k_a, r0_a = np.array(self.k, dtype=np.float64), np.array(self.r0, dtype=np.float64)
+        self._id = integrator.cpp_method.bondsCreate(integrator.system.n, pairs.shape[0], pairs.ctypes.data,
+                                                     0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, k_a.ctypes.data,
+                                                     r0_a.ctypes.data)
+        super().__init__(integrator, virial)
+
+    def compute(self, timestep):
+        s = self.integrator.system
+        out = self._out(timestep) if self._fused else None
+        self.integrator.cpp_method.bondForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, 0 if out is None else out.data_ptr())
+        if out is not None:
+            self._obs = out
+
+    @property
+    def nbonds(self):
+        """The number of bonds that acted at the most recent compute() (the count the pair providers call npairs)."""
+        return self.npairs
+
+    @property
+    def overstretched(self):
+        """FENE bonds found at r >= r0 by all compute() calls so far (waits for the stream)."""
+        return int(self.integrator.cpp_method.bondsOverstretched(self._id))
+
+
 def _sym3(w):
     import numpy as np
     xx, xy, xz, yy, yz, zz = (float(v) for v in w)
@@ -134,7 +194,7 @@ def _sym3(w):
 
 
 class StressLog:
-    """Energy and stress of a HarmonicRepulsion or TablePair(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
+    """Energy and stress of a HarmonicRepulsion, TablePair or Bonds(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
     sample step the provider's fused call writes its eight doubles straight into the next row, the step number, the box tilt and the
     volume are noted on the host, and nothing waits for the device until table() is read.  Once full, the oldest rows are replaced."""
 
