@@ -271,6 +271,48 @@ int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force /* 
 /* FENE bonds found at r >= r0 by all pse_bond_forces calls on this object since its creation.  Waits for the handle's stream: the
  * only call of the bond interface that reads back. */
 int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count);
+
+/* ---- angle forces: HOOMD's angle.harmonic and angle.cosinesq (no reference counterpart: the reference leaves forces to HOOMD) ----
+ * A pse_angles object is a fixed set of nangles triples (i, j, k) of particle indices into the caller-order arrays of n rows, j the
+ * VERTEX, each with one of ntypes <= 64 parameter sets (kind, k, theta0).  With d1 = r_i - r_j and d2 = r_k - r_j (each by minimum
+ * image in the handle's current box, pse_set_box, as for the bonds), r1 = |d1|, r2 = |d2| and c = d1.d2 / (r1 r2) clamped to [-1, 1]:
+ *   PSE_ANGLE_HARMONIC  V = k/2 (theta - theta0)^2, theta = acos(c),  g = -dV/dc = k (theta - theta0) / s, s = max(sqrt(1 - c^2), 1e-3)
+ *   PSE_ANGLE_COSINESQ  V = k/2 (c - cos theta0)^2,                   g = -dV/dc = -k (c - cos theta0)
+ *   F_i = g (d2 / (r1 r2) - c d1 / r1^2),  F_k = g (d1 / (r1 r2) - c d2 / r2^2),  F_j = -(F_i + F_k)
+ * The floor on s is HOOMD's rule for the straight (and the folded) angle, where 1/s diverges: for sin(theta) < 1e-3 the harmonic
+ * force is no longer exactly minus the gradient of the harmonic energy (it is smaller); at theta0 = pi the force still goes to zero
+ * with theta -> pi.  The cosine-squared kind has no singularity and takes no acos.
+ * An angle with r1 == 0 or r2 == 0 contributes nothing and is not counted (the rule of the pair and bond passes).  Duplicate angles are
+ * legal and act once each.  The minimum image is the nearest one only for arms shorter than half the smallest perpendicular box
+ * width: longer arms are the caller's error and are not detected.
+ * The object is stored as one row of (i, j, k, type) entries per particle, every angle in the rows of all three of its particles, ends
+ * canonicalised to i < k and each row sorted (pse_host_angle_rows): forces and sums are therefore bit-identical for any order of the
+ * list and either order of an angle's ends.
+ * The object belongs to its handle: pse_destroy frees the angle objects still alive, pse_angles_destroy after that is a caller error.
+ * pse_angles_create returns PSE_ERR_INVALID, with a message naming the value, for: a null h, triples_host, out or parameter array,
+ * n == 0 or n > n_max, nangles == 0 or nangles > 2^28, an index >= n, an angle with two equal members, ntypes outside [1, 64], a
+ * type >= ntypes, an unknown kind, a non-finite k, a theta0 that is not finite or outside [0, pi].  *out is null after a refusal. */
+#define PSE_ANGLE_HARMONIC 0   /* V = k/2 (theta - theta0)^2 */
+#define PSE_ANGLE_COSINESQ 1   /* V = k/2 (cos theta - cos theta0)^2 */
+typedef struct pse_angles pse_angles;
+int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles,
+                      const unsigned *triples_host /* nangles x 3 particle indices: end, vertex, end */,
+                      const unsigned *types_host /* nangles, or NULL: all type 0 */,
+                      int ntypes, const int *kind_host, const double *k_host, const double *theta0_host /* ntypes each */,
+                      pse_angles **out);
+int pse_angles_destroy(pse_angles *a);
+/* The angle forces of the object on the n rows of pos, and their observables.  force (n rows, or NULL: observables only):
+ * accumulate = 1 adds to .xyz of the particles that are in an angle, rows of the others are neither read nor written; accumulate = 0
+ * overwrites .xyz of all n rows, with zero for particles in no angle; w is kept in every case.  out8 (DEVICE, 8 doubles -- a row of a
+ * larger array will do -- or NULL: forces only, the reduction is not run) = U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nangles with the signs of
+ * pse_pair_repulsion_virial: U = sum V, W_ab = sum (d1_a F_i,b + d2_a F_k,b) with each angle once, stress = -W / V,
+ * dU/d(xy) = -Wxy, nangles = 1.0 per angle that acted.  W is symmetric and its trace is zero to rounding for both kinds (an angle
+ * does not change when everything is scaled).  force and out8 both NULL: PSE_ERR_INVALID.  The pass walks the object's rows, not
+ * the cell list: it does not sort, leaves the kept neighbour list and its counters alone, and works on a slab rank's handle too
+ * (positions are replicated there, the sums over all angles are complete); owned-particle steps are not supported.  The call only
+ * queues work on the handle's stream and reads nothing back; no floating-point atomics, bit-reproducible on equal inputs. */
+int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force /* may be NULL */,
+                     int accumulate, double *out8 /* DEVICE, may be NULL */);
 /* copy the three real-space grids (x-major, z fastest: idx = (x*Ny + y)*Nz + z, PSEv1/Mobility.cu:233) of the
  * most recent spread (stage 0) or inverse FFT (stage 1) to a host buffer of 3*nx_local*Ny*Nz doubles */
 int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out);
@@ -471,6 +513,15 @@ int pse_host_select_params(const pse_params *params, pse_info *info);
  * PSE_ERR_INVALID: a null array, n == 0, nbonds == 0 or > 2^30, an endpoint >= n, a bond with i == j. */
 int pse_host_bond_rows(unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types /* or NULL */,
                        int *row_off /* n + 1 */, unsigned *entries /* 2 nbonds x 2: partner, type */);
+/* host-only: the per-particle rows a pse_angles object stores (pse_angles_create calls this after validating).  A CSR over the n
+ * particles: row p is entries[4 row_off[p]] .. entries[4 row_off[p + 1]), one (i, j, k, type) quadruple of unsigned -- 16 bytes -- per
+ * angle p takes part in, j the vertex and the ends swapped where needed so that i < k; p is one of i, j, k, which is its role.  Every
+ * angle appears in the rows of all three of its particles (duplicates as often as they are listed), each row sorted by
+ * (i, j, k, type), so the rows are a function of the angle SET, not of the list order or of which end is written first.
+ * types == NULL: all type 0.  PSE_ERR_INVALID: a null array, n == 0, nangles == 0 or > 2^28 (3 nangles must fit the int
+ * offsets), an index >= n, an angle with two equal members. */
+int pse_host_angle_rows(unsigned n, unsigned nangles, const unsigned *triples, const unsigned *types /* or NULL */,
+                        int *row_off /* n + 1 */, unsigned *entries /* 3 nangles x 4: i, j, k, type */);
 
 #ifdef __cplusplus
 }

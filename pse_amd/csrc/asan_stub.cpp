@@ -2,7 +2,7 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, pse_bonds_*) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, pse_bonds_*, pse_angles_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -22,6 +22,12 @@ struct pse_handle {
     unsigned long long steps = 0;
     int lz_op = PSE_LANCZOS_RECORDS16;
     std::vector<pse_bonds *> bond_lists;
+    std::vector<pse_angles *> angle_lists;
+};
+struct pse_angles {   // the REAL rows (pse_host_angle_rows), kept on the host
+    pse_handle *h;
+    std::vector<int> row_off;
+    std::vector<unsigned> entries;
 };
 struct pse_bonds {   // the REAL rows (pse_host_bond_rows), kept on the host
     pse_handle *h;
@@ -51,6 +57,7 @@ int pse_create(const pse_params *p, pse_handle **out) {
 }
 int pse_destroy(pse_handle *h) {
     if (h) for (pse_bonds *b : h->bond_lists) delete b;
+    if (h) for (pse_angles *a : h->angle_lists) delete a;
     delete h;
     return 0;
 }
@@ -137,6 +144,31 @@ int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) {
     if (!b || !count) return fail(PSE_ERR_INVALID, "pse_bonds_overstretched: null argument");
     *count = 0;
     return 0;
+}
+int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, const unsigned *triples_host, const unsigned *types_host, int ntypes,
+                      const int *kind_host, const double *k_host, const double *theta0_host, pse_angles **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_angles_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_angles_create: null handle");
+    if (int rc = angles_validate(h->par.n_max, n, nangles, triples_host, types_host, ntypes, kind_host, k_host, theta0_host)) return rc;
+    pse_angles *a = new pse_angles{h, std::vector<int>((size_t)n + 1), std::vector<unsigned>((size_t)nangles * 12)};
+    if (int rc = pse_host_angle_rows(n, nangles, triples_host, types_host, a->row_off.data(), a->entries.data())) { delete a; return rc; }
+    h->angle_lists.push_back(a);
+    *out = a;
+    return 0;
+}
+int pse_angles_destroy(pse_angles *a) {
+    if (!a) return 0;
+    std::vector<pse_angles *> &l = a->h->angle_lists;
+    l.erase(std::remove(l.begin(), l.end(), a), l.end());
+    delete a;
+    return 0;
+}
+int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, int, double *out8) {
+    if (!a) return fail(PSE_ERR_INVALID, "pse_angle_forces: null angle object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_angle_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_angle_forces: force and out8 are both null: nothing to compute");
+    return 0;   // pos, force and out8 are device pointers and there is no device: nothing is read or written
 }
 
 int pse_set_stream(pse_handle *, void *) { return no_device("pse_set_stream"); }

@@ -24,6 +24,7 @@ Stokes::~Stokes() {
 void Stokes::setParams() {
     if (m_h) { pse_destroy(m_h); m_h = nullptr; }
     m_bonds.clear();   // pse_destroy freed them
+    m_angles.clear();
     m_m_Lanczos = 2;   // "try two Lanczos iterations to start" (PSEv1/Stokes.cc:131-132)
     pse_params p{};
     p.n_max = m_n_total;
@@ -103,6 +104,30 @@ unsigned long long Stokes::bondsOverstretched(int id) {
 void Stokes::bondsDestroy(int id) {
     check(pse_bonds_destroy(bondObject(id)), "Stokes::bondsDestroy");
     m_bonds[id] = nullptr;
+}
+
+int Stokes::anglesCreate(unsigned int n, unsigned int nangles, const unsigned int *triples, const unsigned int *types, int ntypes,
+                         const int *kind, const double *k, const double *theta0) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    pse_angles *a = nullptr;
+    check(pse_angles_create(m_h, n, nangles, triples, types, ntypes, kind, k, theta0, &a), "Stokes::anglesCreate");
+    m_angles.push_back(a);
+    return (int)m_angles.size() - 1;
+}
+
+pse_angles *Stokes::angleObject(int id) const {
+    if (id < 0 || id >= (int)m_angles.size() || !m_angles[id])
+        throw std::invalid_argument("Stokes: no angle object with id " + std::to_string(id) + " (setParams invalidates the ids)");
+    return m_angles[id];
+}
+
+void Stokes::angleForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8) {
+    check(pse_angle_forces(angleObject(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::angleForces");
+}
+
+void Stokes::anglesDestroy(int id) {
+    check(pse_angles_destroy(angleObject(id)), "Stokes::anglesDestroy");
+    m_angles[id] = nullptr;
 }
 
 pse_info Stokes::info() const {

@@ -60,6 +60,14 @@ public:
     void bondForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8);
     unsigned long long bondsOverstretched(int id);   // waits for the stream
     void bondsDestroy(int id);
+    // angle forces (pse_angles_create / pse_angle_forces): anglesCreate copies the HOST arrays -- nangles x 3 particle indices (end,
+    // vertex, end), nangles types or null, ntypes x (kind, k, theta0) -- to the engine and returns the id the other calls take; the
+    // ids live and die as those of the bond objects do
+    int anglesCreate(unsigned int n, unsigned int nangles, const unsigned int *triples, const unsigned int *types, int ntypes, const int *kind,
+                     const double *k, const double *theta0);
+    // force or out8 (eight DEVICE doubles: U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nangles) may be null, not both
+    void angleForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8);
+    void anglesDestroy(int id);
     pse_info info() const;
     int lanczosIterations() const { return m_m_Lanczos; }
     unsigned int hashedSeed() const { return m_seed; }
@@ -79,6 +87,8 @@ private:
     pse_handle *m_h = nullptr;
     std::vector<pse_bonds *> m_bonds;   // by id; null once destroyed
     pse_bonds *bondObject(int id) const;
+    std::vector<pse_angles *> m_angles; // by id; null once destroyed
+    pse_angles *angleObject(int id) const;
 };
 
 }  // namespace pse_host

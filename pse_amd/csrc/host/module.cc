@@ -90,6 +90,16 @@ PYBIND11_MODULE(_PSEv1, m) {
         })
         .def("bondsOverstretched", &Stokes::bondsOverstretched)
         .def("bondsDestroy", &Stokes::bondsDestroy)
+        // nangles x 3 uint32 (end, vertex, end), nangles uint32 or 0, ntypes int32 / float64 / float64
+        .def("anglesCreate", [](Stokes &s, unsigned int n, unsigned int nangles, std::uintptr_t triples, std::uintptr_t types, int ntypes,
+                                std::uintptr_t kind, std::uintptr_t k, std::uintptr_t theta0) {
+            return s.anglesCreate(n, nangles, ptr<const unsigned int>(triples), ptr<const unsigned int>(types), ntypes, ptr<const int>(kind),
+                                  ptr<const double>(k), ptr<const double>(theta0));
+        })
+        .def("angleForces", [](Stokes &s, int id, std::uintptr_t pos, std::uintptr_t force, bool accumulate, std::uintptr_t out8) {
+            s.angleForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
+        })
+        .def("anglesDestroy", &Stokes::anglesDestroy)
         .def("lanczosIterations", &Stokes::lanczosIterations)
         .def("hashedSeed", &Stokes::hashedSeed)
         .def("info", [](const Stokes &s) {

@@ -111,6 +111,7 @@ struct pse_handle {
     int *cell_off = nullptr;
     double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
     std::vector<pse_bonds *> bond_lists;   // the bond objects created on this handle and still alive (pse_destroy frees them)
+    std::vector<pse_angles *> angle_lists; // the same for the angle objects
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
@@ -415,12 +416,29 @@ static void bonds_free(pse_bonds *b) {
     delete b;
 }
 
+// An angle topology on the device (include/pse_amd.h): the rows of pse_host_angle_rows and the per-type parameters.  Owned by its handle.
+struct pse_angles {
+    pse_handle *h = nullptr;
+    unsigned n = 0, nangles = 0;
+    int ntypes = 0;
+    int *row_off = nullptr;                 // n + 1
+    uint4 *entries = nullptr;               // 3 nangles: (i, j, k, type), j the vertex, i < k
+    AngleParam *par = nullptr;              // ntypes
+};
+static void angles_free(pse_angles *a) {
+    void *ptrs[] = {a->row_off, a->entries, a->par};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete a;
+}
+
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     for (pse_bonds *b : h->bond_lists) bonds_free(b);
     h->bond_lists.clear();
+    for (pse_angles *a : h->angle_lists) angles_free(a);
+    h->angle_lists.clear();
     if (h->plan_fwd) rocfft_plan_destroy(h->plan_fwd);
     if (h->plan_inv) rocfft_plan_destroy(h->plan_inv);
     if (h->plan_x_fwd) rocfft_plan_destroy(h->plan_x_fwd);
@@ -2679,6 +2697,61 @@ extern "C" int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) 
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(count, b->over, sizeof *count, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- angle forces (include/pse_amd.h) ------------------------------------------------------------------------------------------
+extern "C" int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, const unsigned *triples_host, const unsigned *types_host,
+                                 int ntypes, const int *kind_host, const double *k_host, const double *theta0_host, pse_angles **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_angles_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_angles_create: null handle");
+    TRY(angles_validate((unsigned)h->n_max, n, nangles, triples_host, types_host, ntypes, kind_host, k_host, theta0_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)nangles * 12);
+    TRY(pse_host_angle_rows(n, nangles, triples_host, types_host, off.data(), ent.data()));
+    std::vector<AngleParam> par((size_t)ntypes);
+    for (int t = 0; t < ntypes; ++t) par[t] = AngleParam{k_host[t], theta0_host[t], std::cos(theta0_host[t]), (double)kind_host[t]};
+    pse_angles *a = new pse_angles();
+    a->h = h; a->n = n; a->nangles = nangles; a->ntypes = ntypes;
+    auto put = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, bytes);
+        if (e != hipSuccess) return e;
+        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    };
+    hipError_t e = put((void **)&a->row_off, off.data(), off.size() * sizeof(int));
+    if (e == hipSuccess) e = put((void **)&a->entries, ent.data(), ent.size() * sizeof(unsigned));
+    if (e == hipSuccess) e = put((void **)&a->par, par.data(), par.size() * sizeof(AngleParam));
+    if (e != hipSuccess) {
+        angles_free(a);
+        return fail(PSE_ERR_HIP, "pse_angles_create: copying %u angles to the device failed: %s", nangles, hipGetErrorString(e));
+    }
+    h->angle_lists.push_back(a);
+    *out = a;
+    return 0;
+}
+
+extern "C" int pse_angles_destroy(pse_angles *a) {
+    if (!a) return 0;
+    pse_handle *h = a->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
+    h->angle_lists.erase(std::remove(h->angle_lists.begin(), h->angle_lists.end(), a), h->angle_lists.end());
+    angles_free(a);
+    return 0;
+}
+
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
+    if (!a) return fail(PSE_ERR_INVALID, "pse_angle_forces: null angle object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_angle_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_angle_forces: force and out8 are both null: nothing to compute");
+    pse_handle *h = a->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_angle_forces((const double4 *)pos, (int)a->n, a->row_off, a->entries, a->par, a->ntypes, h->dbox, accumulate, (double4 *)force,
+                        h->pv_rows, out8, h->stream);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -21,5 +21,8 @@ int gaussian_fits(const Derived &d, double hx, double hy, double hz);
 // (include/pse_amd.h lists them) -- shared by the device library and the sanitizer build's stand-in
 int bonds_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types, int ntypes, const int *kind,
                    const double *k, const double *r0);
+// the same for pse_angles_create
+int angles_validate(unsigned n_max, unsigned n, unsigned nangles, const unsigned *triples, const unsigned *types, int ntypes,
+                    const int *kind, const double *k, const double *theta0);
 
 }  // namespace pse

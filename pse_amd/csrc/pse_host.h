@@ -11,6 +11,7 @@ constexpr int RS_NCOEF = RS_DEG + 1;
 constexpr int RS_PER_UNIT = 8;      // intervals of width 1/8 (in units of the particle radius)
 
 constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS
+constexpr int ANGLE_MAX_TYPES = 64;  // parameter sets of an angle object (pse_angles_create): staged in 2 KB of LDS
 
 struct Box {
     double Lx, Ly, Lz, xy;

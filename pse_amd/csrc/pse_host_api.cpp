@@ -72,6 +72,32 @@ int bonds_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *
     return 0;
 }
 
+int angles_validate(unsigned n_max, unsigned n, unsigned nangles, const unsigned *triples, const unsigned *types, int ntypes,
+                    const int *kind, const double *k, const double *theta0) {
+    if (!triples) return fail(PSE_ERR_INVALID, "pse_angles_create: null triples_host");
+    if (!kind || !k || !theta0) return fail(PSE_ERR_INVALID, "pse_angles_create: null parameter array (kind_host, k_host, theta0_host)");
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "pse_angles_create: n = %u outside (0, n_max = %u]", n, n_max);
+    if (nangles == 0 || nangles > (1u << 28)) return fail(PSE_ERR_INVALID, "pse_angles_create: nangles = %u outside (0, 2^28]", nangles);
+    if (ntypes < 1 || ntypes > ANGLE_MAX_TYPES) return fail(PSE_ERR_INVALID, "pse_angles_create: ntypes = %d outside [1, %d]", ntypes, ANGLE_MAX_TYPES);
+    const double pi = 3.14159265358979323846;
+    for (int t = 0; t < ntypes; ++t) {
+        if (kind[t] != PSE_ANGLE_HARMONIC && kind[t] != PSE_ANGLE_COSINESQ)
+            return fail(PSE_ERR_INVALID, "pse_angles_create: type %d has kind %d, neither PSE_ANGLE_HARMONIC nor PSE_ANGLE_COSINESQ", t, kind[t]);
+        if (!std::isfinite(k[t]) || !std::isfinite(theta0[t]))
+            return fail(PSE_ERR_INVALID, "pse_angles_create: type %d has k = %g, theta0 = %g: both must be finite", t, k[t], theta0[t]);
+        if (theta0[t] < 0.0 || theta0[t] > pi) return fail(PSE_ERR_INVALID, "pse_angles_create: type %d has theta0 = %g outside [0, pi]", t, theta0[t]);
+    }
+    for (unsigned a = 0; a < nangles; ++a) {
+        const unsigned i = triples[3 * (size_t)a], j = triples[3 * (size_t)a + 1], l = triples[3 * (size_t)a + 2];
+        if (i >= n || j >= n || l >= n)
+            return fail(PSE_ERR_INVALID, "pse_angles_create: angle %u = (%u, %u, %u) has an index >= n = %u", a, i, j, l, n);
+        if (i == j || j == l || i == l)
+            return fail(PSE_ERR_INVALID, "pse_angles_create: angle %u = (%u, %u, %u) has two equal members", a, i, j, l);
+        if (types && types[a] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "pse_angles_create: angle %u has type %u >= ntypes = %d", a, types[a], ntypes);
+    }
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -122,5 +148,40 @@ extern "C" int pse_host_bond_rows(unsigned n, unsigned nbonds, const unsigned *p
     }
     for (unsigned i = 0; i < n; ++i)
         std::sort(e + off[i], e + off[i + 1], [](const End &a, const End &b) { return a.partner != b.partner ? a.partner < b.partner : a.type < b.type; });
+    return 0;
+}
+
+// Counting sort of the 3 nangles memberships by particle, then each row sorted by the canonical (i, j, k, type), i < k.
+extern "C" int pse_host_angle_rows(unsigned n, unsigned nangles, const unsigned *triples, const unsigned *types, int *row_off, unsigned *entries) {
+    if (!triples || !row_off || !entries) return fail(PSE_ERR_INVALID, "pse_host_angle_rows: null array");
+    if (n == 0) return fail(PSE_ERR_INVALID, "pse_host_angle_rows: n = 0");
+    if (nangles == 0 || nangles > (1u << 28)) return fail(PSE_ERR_INVALID, "pse_host_angle_rows: nangles = %u outside (0, 2^28]", nangles);
+    for (unsigned a = 0; a < nangles; ++a) {
+        const unsigned i = triples[3 * (size_t)a], j = triples[3 * (size_t)a + 1], k = triples[3 * (size_t)a + 2];
+        if (i >= n || j >= n || k >= n)
+            return fail(PSE_ERR_INVALID, "pse_host_angle_rows: angle %u = (%u, %u, %u) has an index >= n = %u", a, i, j, k, n);
+        if (i == j || j == k || i == k)
+            return fail(PSE_ERR_INVALID, "pse_host_angle_rows: angle %u = (%u, %u, %u) has two equal members", a, i, j, k);
+    }
+    std::fill(row_off, row_off + (size_t)n + 1, 0);   // (3 nangles <= 3 * 2^28 < 2^31)
+    for (size_t m = 0; m < 3 * (size_t)nangles; ++m) ++row_off[triples[m] + 1];
+    for (unsigned p = 0; p < n; ++p) row_off[p + 1] += row_off[p];
+    std::vector<int> fill(row_off, row_off + n);
+    struct Entry { unsigned i, j, k, type; };
+    Entry *e = reinterpret_cast<Entry *>(entries);
+    for (unsigned a = 0; a < nangles; ++a) {
+        const unsigned x = triples[3 * (size_t)a], j = triples[3 * (size_t)a + 1], y = triples[3 * (size_t)a + 2];
+        const Entry en{std::min(x, y), j, std::max(x, y), types ? types[a] : 0u};
+        e[fill[en.i]++] = en;
+        e[fill[en.j]++] = en;
+        e[fill[en.k]++] = en;
+    }
+    for (unsigned p = 0; p < n; ++p)
+        std::sort(e + row_off[p], e + row_off[p + 1], [](const Entry &a, const Entry &b) {
+            if (a.i != b.i) return a.i < b.i;
+            if (a.j != b.j) return a.j < b.j;
+            if (a.k != b.k) return a.k < b.k;
+            return a.type < b.type;
+        });
     return 0;
 }

@@ -373,5 +373,15 @@ struct BondParam {   // 32 bytes, staged in LDS as two 16-byte words (the device
 };
 void launch_bond_forces(const double4 *pos, int n, const unsigned *row_off, const uint2 *entries, const BondParam *par, int ntypes, DBox box,
                         int accumulate, double4 *force, double *rows, double *out8, unsigned long long *overstretched, hipStream_t s);
+// angle forces (k_angle_forces): one row of (i, j, k, type) entries per particle of the caller-order arrays, row p =
+// entries[row_off[p] .. row_off[p + 1]), j the vertex, i < k, sorted (pse_host_angle_rows); par = ntypes <= ANGLE_MAX_TYPES parameter
+// sets.  out8 != null: the eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.
+struct AngleParam {   // 32 bytes, staged in LDS as two 16-byte words (the device array is a hipMalloc of its own: aligned)
+    double k, theta0;
+    double cos0;     // cos(theta0)
+    double kind;     // PSE_ANGLE_HARMONIC or PSE_ANGLE_COSINESQ as a double
+};
+void launch_angle_forces(const double4 *pos, int n, const int *row_off, const uint4 *entries, const AngleParam *par, int ntypes, DBox box,
+                         int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
 
 }  // namespace pse

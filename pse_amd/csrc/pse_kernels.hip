@@ -3005,6 +3005,115 @@ void launch_bond_forces(const double4 *pos, int n, const unsigned *row_off, cons
     }
 }
 
+// Angle forces (HOOMD's angle.harmonic and angle.cosinesq; no reference counterpart: the reference leaves forces to HOOMD).  One
+// thread per particle of the CALLER-order arrays walks its row of the angle object -- entries (i, j, k, type), j the vertex, i < k,
+// one 16-byte load each, sorted by (i, j, k, type) on the host.  The thread loads all three positions from memory, its own included,
+// and evaluates d1 = r_i - r_j, d2 = r_k - r_j (minimum image), c = d1.d2 / (r1 r2) in [-1, 1], g = -dV/dc and
+//   F_i = g (d2/(r1 r2) - c d1/r1^2),  F_k = g (d1/(r1 r2) - c d2/r2^2),  F_j = -(F_i + F_k)
+// in this CANONICAL order whatever its own role is, then takes the force of its role: the three threads of an angle run the same
+// arithmetic on the same numbers and hold bit-identical F_i and F_k.  Each thread owns its force row: no atomics on forces, and the
+// order of the sum is the order of the row, a function of the angle SET -- forces and sums are bit-identical for any permutation of
+// the list and either order of an angle's ends.  harmonic: g = k (theta - theta0)/s with s = max(sqrt(1 - c^2), 1e-3) (HOOMD's floor
+// for the straight angle), the only branch that takes an acos; cosine-squared: g = -k (c - cos theta0).  An angle with r1 == 0 or
+// r2 == 0 does nothing.
+// Per-type parameters as in k_bond_forces: the type differs from lane to lane, so they are staged in LDS, 32 bytes per type
+// (k, theta0, cos theta0, kind), at most 2 KB, copied by the first lanes of each workgroup before one barrier and read as two 16-byte
+// words per angle; with one type every lane reads the same entry, which the LDS broadcasts.
+// OBS: the VERTEX thread alone adds the angle to the eight sums U, W_ab = d1_a F_i,b + d2_a F_k,b (six), count; reduction, row per
+// workgroup and k_pair_virial_finish as in k_pair_repulsion_virial.  No lane leaves before either barrier.
+// accumulate != 0: the rows of particles in no angle are neither read nor written; accumulate == 0: every row's xyz is overwritten, w kept.
+template <bool OBS>
+__global__ void __launch_bounds__(TPB)
+k_angle_forces(const double4 *__restrict__ pos, int n, const int *__restrict__ row_off, const uint4 *__restrict__ entries,
+               const AngleParam *__restrict__ par, int ntypes, DBox box, int accumulate, double4 *__restrict__ force,
+               double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
+    __shared__ pt_entry ap[2 * ANGLE_MAX_TYPES];   // [type][0] = (k, theta0), [type][1] = (cos theta0, kind)
+    __shared__ double sh[OBS ? TPB / 64 : 1][PV_NOBS];
+    if ((int)threadIdx.x < 2 * ntypes) ap[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
+    __syncthreads();
+    const int blk = xcd_block(blockIdx.x, gridDim.x);
+    const int p = blk * TPB + threadIdx.x;
+    double o[PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = 0.0;
+    if (p < n) {
+        const int eb = row_off[p], ee = row_off[p + 1];
+        if (ee > eb) {
+            double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+            for (int e = eb; e < ee; ++e) {
+                const uint4 en = entries[e];                  // x = i, y = j (vertex), z = k, w = type
+                const double4 pi = pos[en.x], pj = pos[en.y], pk = pos[en.z];
+                const pt_entry a = ap[2 * en.w], b = ap[2 * en.w + 1];
+                double d1x = pi.x - pj.x, d1y = pi.y - pj.y, d1z = pi.z - pj.z;
+                double d2x = pk.x - pj.x, d2y = pk.y - pj.y, d2z = pk.z - pj.z;
+                min_image(box, d1x, d1y, d1z);
+                min_image(box, d2x, d2y, d2z);
+                const double r1sq = d1x * d1x + d1y * d1y + d1z * d1z, r2sq = d2x * d2x + d2y * d2y + d2z * d2z;
+                if (r1sq > 0.0 && r2sq > 0.0) {
+                    const double ir12 = 1.0 / (sqrt(r1sq) * sqrt(r2sq));
+                    double c = (d1x * d2x + d1y * d2y + d1z * d2z) * ir12;
+                    c = fmin(1.0, fmax(-1.0, c));
+                    double g, u;
+                    if (b.y == 0.0) {                          // harmonic
+                        const double dth = acos(c) - a.y;
+                        g = a.x * dth / fmax(sqrt(1.0 - c * c), 1e-3);
+                        u = 0.5 * a.x * dth * dth;
+                    } else {                                   // cosine-squared
+                        const double dc = c - b.x;
+                        g = -a.x * dc;
+                        u = 0.5 * a.x * dc * dc;
+                    }
+                    const double g12 = g * ir12, g11 = g * c / r1sq, g22 = g * c / r2sq;
+                    const double Fix = g12 * d2x - g11 * d1x, Fiy = g12 * d2y - g11 * d1y, Fiz = g12 * d2z - g11 * d1z;
+                    const double Fkx = g12 * d1x - g22 * d2x, Fky = g12 * d1y - g22 * d2y, Fkz = g12 * d1z - g22 * d2z;
+                    if ((unsigned)p == en.y) {                 // the vertex
+                        Fx -= Fix + Fkx; Fy -= Fiy + Fky; Fz -= Fiz + Fkz;
+                        if (OBS) {
+                            o[0] += u;
+                            o[1] += d1x * Fix + d2x * Fkx; o[2] += d1x * Fiy + d2x * Fky; o[3] += d1x * Fiz + d2x * Fkz;
+                            o[4] += d1y * Fiy + d2y * Fky; o[5] += d1y * Fiz + d2y * Fkz; o[6] += d1z * Fiz + d2z * Fkz;
+                            o[7] += 1.0;
+                        }
+                    } else {
+                        const bool first = (unsigned)p == en.x;
+                        Fx += first ? Fix : Fkx; Fy += first ? Fiy : Fky; Fz += first ? Fiz : Fkz;
+                    }
+                }
+            }
+            if (force) {
+                double4 f = force[p];
+                if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
+                force[p] = f;
+            }
+        } else if (force && !accumulate) {
+            double4 f = force[p];
+            f.x = 0.0; f.y = 0.0; f.z = 0.0;
+            force[p] = f;
+        }
+    }
+    if (OBS) {
+#pragma unroll
+        for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
+        }
+        __syncthreads();
+        if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    }
+}
+void launch_angle_forces(const double4 *pos, int n, const int *row_off, const uint4 *entries, const AngleParam *par, int ntypes, DBox box,
+                         int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
+    static_assert(sizeof(AngleParam) == 2 * sizeof(pt_entry) && 2 * ANGLE_MAX_TYPES <= TPB, "one lane stages one 16-byte word of the parameters");
+    const int nb = nblocks(n, TPB);
+    if (out8) {
+        hipLaunchKernelGGL(k_angle_forces<true>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, rows);
+        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
+    } else {
+        hipLaunchKernelGGL(k_angle_forces<false>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, nullptr);
+    }
+}
+
 // K10 gpu_stokes_LinearCombination_kernel (PSEv1/Helper.cu:113-133) as the final un-sort: vel.xyz = a + b + c, keep w
 __global__ void k_scatter_sum(const double4 *__restrict__ a, const double4 *__restrict__ b,
                               const double4 *__restrict__ c, const unsigned *__restrict__ tag_s, int N,

@@ -4,6 +4,7 @@ Arrays follow HOOMD's layout with Scalar = double: pos/vel/force are (N,4) float
 (x,y,z,type|mass|energy), accel (N,3) float64, image (N,3) int32, group_members (N,) int32/uint32.
 """
 import ctypes
+import math
 
 from . import _lib
 from ._lib import pse_info, pse_params
@@ -149,6 +150,73 @@ class BondList:
         b, self._b = getattr(self, "_b", None), None
         if b is not None and b.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
             self._lib.pse_bonds_destroy(b)
+
+    __del__ = close
+
+
+# the angle potentials of pse_angles_create: name -> PSE_ANGLE_*
+ANGLE_KINDS = {"harmonic": 0, "cosinesq": 1}
+
+
+class AngleList:
+    """Owner of a pse_angles object: a fixed set of harmonic / cosine-squared angles (end, vertex, end) among the rows of the
+    caller-order arrays.  Holds a reference to its engine, whose handle owns the device object."""
+
+    def __init__(self, engine, triples, types, kinds, k, theta0, n):
+        import numpy as np
+        triples = np.asarray(triples)
+        if triples.ndim != 2 or triples.shape[1] != 3 or triples.shape[0] == 0 or not np.issubdtype(triples.dtype, np.integer):
+            raise ValueError("triples must be a non-empty integer (nangles, 3) array of particle indices (end, vertex, end)")
+        if triples.min() < 0 or triples.max() >= 2 ** 32:
+            raise ValueError("triples holds an index outside [0, 2^32)")
+        na = triples.shape[0]
+        if types is not None:
+            types = np.asarray(types)
+            if types.shape != (na,) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0 or types.max() >= 2 ** 32:
+                raise ValueError("types must be a non-negative integer array with one entry per angle")
+            types = np.ascontiguousarray(types, dtype=np.uint32)
+        kinds, k, theta0 = _per_type(kinds, "kinds"), _per_type(k, "k"), _per_type(theta0, "theta0")
+        if not (len(kinds) == len(k) == len(theta0)) or not kinds:
+            raise ValueError("kinds, k and theta0 must have one entry per angle type each")
+        for v in kinds:
+            if isinstance(v, str) and v not in ANGLE_KINDS:
+                raise ValueError(f"angle kind must be one of {sorted(ANGLE_KINDS)}, not {v!r}")
+        kind_a = np.array([ANGLE_KINDS[v] if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32)
+        k_a, t0_a = np.array(k, dtype=np.float64), np.array(theta0, dtype=np.float64)
+        triples = np.ascontiguousarray(triples, dtype=np.uint32)
+        self.n = int(engine.params.n_max if n is None else n)
+        if not 0 <= self.n < 2 ** 32:
+            raise ValueError("n outside [0, 2^32)")
+        self.nangles, self.engine, self._lib = na, engine, engine._lib
+        self._a = ctypes.c_void_p()
+        vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        _lib.check(self._lib.pse_angles_create(engine._h, self.n, na, vp(triples), vp(types), len(kind_a), vp(kind_a), vp(k_a), vp(t0_a),
+                                               ctypes.byref(self._a)))
+
+    def forces(self, pos, force, accumulate=True, out=None, observables=True):
+        """The angle forces on the first n rows of `pos` (pse_angle_forces), added to `force` (or stored: accumulate=False, which zeroes
+        the rows of particles in no angle), or force=None: observables only.  observables=True: returns the 8-element float64 CUDA tensor
+        U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nangles, written to `out` when one is given (e.g. a row of a log tensor); observables=False:
+        forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
+        import torch
+        if self._a is None or not self._a.value:
+            raise ValueError("this AngleList is closed")
+        _chk4(pos, "pos", self.n)
+        if force is not None:
+            _chk4(force, "force", self.n)
+        if observables:
+            if out is None:
+                out = torch.empty(8, dtype=torch.float64, device=pos.device)
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
+                    and out.is_contiguous()):
+                raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+        _lib.check(self._lib.pse_angle_forces(self._a, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out) if observables else None))
+        return out if observables else None
+
+    def close(self):
+        a, self._a = getattr(self, "_a", None), None
+        if a is not None and a.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
+            self._lib.pse_angles_destroy(a)
 
     __del__ = close
 
@@ -365,6 +433,12 @@ class Engine:
         `n` rows (default: n_max), `types` (nbonds,) indices into the per-type sequences `kinds` ("harmonic" | "fene" or
         BOND_KINDS codes), `k`, `r0`, or None: all type 0.  Returns a BondList."""
         return BondList(self, pairs, types, kinds, k, r0, n)
+
+    def angles(self, triples, types=None, kinds=(0,), k=(1.0,), theta0=(math.pi,), n=None):
+        """An angle topology on the device (pse_angles_create; see include/pse_amd.h): `triples` (nangles, 3) particle indices (end,
+        vertex, end) into arrays of `n` rows (default: n_max), `types` (nangles,) indices into the per-type sequences `kinds`
+        ("harmonic" | "cosinesq" or ANGLE_KINDS codes), `k`, `theta0` (radians, in [0, pi]), or None: all type 0.  Returns an AngleList."""
+        return AngleList(self, triples, types, kinds, k, theta0, n)
 
     def random_psi(self, n, timestep, group=None):
         import torch

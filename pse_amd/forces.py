@@ -1,5 +1,6 @@
 """Force providers: what fills `net_force` before the integrator consumes it (HOOMD's force computes in the reference,
 PSEv1/Stokes.cc:447; its example script has none).  SURVEY.md 8 f4: the step either side of the hot path, kept minimal."""
+import math
 
 
 class _PairProvider:
@@ -187,6 +188,64 @@ class Bonds(_PairProvider):
         return int(self.integrator.cpp_method.bondsOverstretched(self._id))
 
 
+class Angles(_PairProvider):
+    """Harmonic and cosine-squared angles (pse_angle_forces; HOOMD's angle.harmonic and angle.cosinesq): `triples` is an (nangles, 3)
+    integer array of particle indices into the system's arrays, (end, vertex, end).  With theta the angle at the vertex between the
+    two arms, kind = "harmonic": V = k/2 (theta - theta0)^2; "cosinesq": V = k/2 (cos theta - cos theta0)^2.  `kind`, `k` and `theta0`
+    (radians, in [0, pi]) are scalars (one angle type) or sequences with one entry per type, and `types` then gives each angle's type
+    (None: all type 0).  The topology is copied to the device once, here.  Duplicate angles act once each.  An arm must stay shorter
+    than half the smallest perpendicular box width: the minimum image is the nearest one only there.  Within sin(theta) < 1e-3 of the
+    straight or the folded angle the harmonic force is capped (HOOMD's rule) and no longer exactly the gradient of the energy.
+
+    virial=True: the same call also writes the angle energy, the virial (traceless) and the number of angles that acted: `energy`,
+    `virial`, `stress()`, `nangles` and StressLog as for HarmonicRepulsion."""
+
+    NAME = "Angles"
+    KINDS = {"harmonic": 0, "cosinesq": 1}
+
+    def __init__(self, integrator, triples, kind="harmonic", k=1.0, theta0=math.pi, types=None, virial=False):
+        import numpy as np
+        seq = lambda v: [v] if isinstance(v, str) or np.ndim(v) == 0 else list(v)
+        kind, k, theta0 = seq(kind), seq(k), seq(theta0)
+        nt = max(len(kind), len(k), len(theta0))
+        kind, k, theta0 = (v * nt if len(v) == 1 else v for v in (kind, k, theta0))   # a scalar serves every type
+        if not len(kind) == len(k) == len(theta0) == nt:
+            raise ValueError("kind, k and theta0 must be scalars or sequences of one length (one entry per angle type)")
+        for v in kind:
+            if v not in self.KINDS:
+                raise ValueError(f"angle kind must be one of {sorted(self.KINDS)}, not {v!r}")
+        triples = np.asarray(triples)
+        if (triples.ndim != 2 or triples.shape[1] != 3 or triples.shape[0] == 0 or not np.issubdtype(triples.dtype, np.integer)
+                or triples.min() < 0 or triples.max() >= 2 ** 32):
+            raise ValueError("triples must be a non-empty (nangles, 3) array of integer particle indices in [0, 2^32) (end, vertex, end)")
+        triples = np.ascontiguousarray(triples, dtype=np.uint32)
+        if types is not None:
+            types = np.asarray(types)
+            if (types.shape != (triples.shape[0],) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0
+                    or types.max() >= 2 ** 32):
+                raise ValueError("types must be an integer array in [0, 2^32) with one entry per angle")
+            types = np.ascontiguousarray(types, dtype=np.uint32)
+        self.kind, self.k, self.theta0 = tuple(kind), tuple(float(v) for v in k), tuple(float(v) for v in theta0)
+        kind_a = np.array([self.KINDS[v] for v in kind], dtype=np.int32)
+        k_a, t0_a = np.array(self.k, dtype=np.float64), np.array(self.theta0, dtype=np.float64)
+        self._id = integrator.cpp_method.anglesCreate(integrator.system.n, triples.shape[0], triples.ctypes.data,
+                                                      0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, k_a.ctypes.data,
+                                                      t0_a.ctypes.data)
+        super().__init__(integrator, virial)
+
+    def compute(self, timestep):
+        s = self.integrator.system
+        out = self._out(timestep) if self._fused else None
+        self.integrator.cpp_method.angleForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, 0 if out is None else out.data_ptr())
+        if out is not None:
+            self._obs = out
+
+    @property
+    def nangles(self):
+        """The number of angles that acted at the most recent compute() (the count the pair providers call npairs)."""
+        return self.npairs
+
+
 def _sym3(w):
     import numpy as np
     xx, xy, xz, yy, yz, zz = (float(v) for v in w)
@@ -194,7 +253,7 @@ def _sym3(w):
 
 
 class StressLog:
-    """Energy and stress of a HarmonicRepulsion, TablePair or Bonds(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
+    """Energy and stress of a HarmonicRepulsion, TablePair, Bonds or Angles(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
     sample step the provider's fused call writes its eight doubles straight into the next row, the step number, the box tilt and the
     volume are noted on the host, and nothing waits for the device until table() is read.  Once full, the oldest rows are replaced."""
 
