@@ -13,6 +13,7 @@
 
 using namespace pse;
 
+struct Topology;
 struct pse_handle {
     pse_params par;
     Derived d;
@@ -21,21 +22,34 @@ struct pse_handle {
     int n_intervals = 0;
     unsigned long long steps = 0;
     int lz_op = PSE_LANCZOS_RECORDS16;
-    std::vector<pse_bonds *> bond_lists;
-    std::vector<pse_angles *> angle_lists;
+    std::vector<Topology *> topologies;
 };
-struct pse_angles {   // the REAL rows (pse_host_angle_rows), kept on the host
+struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows), kept on the host
     pse_handle *h;
     std::vector<int> row_off;
     std::vector<unsigned> entries;
+    Topology(pse_handle *h, size_t noff, size_t nent) : h(h), row_off(noff), entries(nent) {}
+    virtual ~Topology() {}
 };
-struct pse_bonds {   // the REAL rows (pse_host_bond_rows), kept on the host
-    pse_handle *h;
-    std::vector<int> row_off;
-    std::vector<unsigned> entries;
-};
+struct pse_bonds : Topology { using Topology::Topology; };
+struct pse_angles : Topology { using Topology::Topology; };
 struct pse_team { int unused; };
 
+// keeps t on its handle unless the row builder refused the list (rows_rc != 0)
+template <class T>
+static int topology_adopt(T *t, int rows_rc, T **out) {
+    if (rows_rc) { delete t; return rows_rc; }
+    t->h->topologies.push_back(t);
+    *out = t;
+    return 0;
+}
+static int topology_destroy(Topology *t) {
+    if (!t) return 0;
+    std::vector<Topology *> &l = t->h->topologies;
+    l.erase(std::remove(l.begin(), l.end(), t), l.end());
+    delete t;
+    return 0;
+}
 static int no_device(const char *what) { return fail(PSE_ERR_HIP, "%s: sanitizer build, there is no device behind this library", what); }
 
 extern "C" {
@@ -56,8 +70,7 @@ int pse_create(const pse_params *p, pse_handle **out) {
     return 0;
 }
 int pse_destroy(pse_handle *h) {
-    if (h) for (pse_bonds *b : h->bond_lists) delete b;
-    if (h) for (pse_angles *a : h->angle_lists) delete a;
+    if (h) for (Topology *t : h->topologies) delete t;
     delete h;
     return 0;
 }
@@ -84,36 +97,20 @@ int pse_step(pse_handle *h, pse_double4 *, pse_double4 *, pse_double3 *, pse_int
     if (lanczos_m && *lanczos_m < 2) *lanczos_m = 2;
     return 0;   // nothing is integrated: the arrays are device pointers and there is no device
 }
-int pse_pair_repulsion(pse_handle *h, const pse_double4 *, pse_double4 *, const unsigned *, unsigned N, double, double sigma, int) {
+// (pos, force, table and out8 are device pointers and there is no device: nothing is read or written)
+int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, double, double sigma, int) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
-    if (N == 0 || N > h->par.n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, h->par.n_max);
-    if (!(sigma > 0.0) || sigma > h->d.rcut) return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]", sigma, h->d.rcut);
-    return 0;
+    return pair_repulsion_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, false, nullptr, sigma);
 }
-int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *, pse_double4 *, const unsigned *, unsigned N, double, double sigma, int,
+int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, double, double sigma, int,
                               double *out8) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
-    if (N == 0 || N > h->par.n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, h->par.n_max);
-    if (!out8) return fail(PSE_ERR_INVALID, "null out8");
-    if (h->par.n_slabs > 1) return fail(PSE_ERR_INVALID, "pse_pair_repulsion_virial: this handle is a slab rank");
-    if (!(sigma > 0.0) || sigma > h->d.rcut) return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]", sigma, h->d.rcut);
-    return 0;   // out8 is a device pointer and there is no device: nothing is written
+    return pair_repulsion_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, true, out8, sigma);
 }
 int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, const double *table, int width,
                    double rmin, double rmax, int, double *out8) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
-    if (N == 0 || N > h->par.n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, h->par.n_max);
-    if (!pos) return fail(PSE_ERR_INVALID, "pse_pair_table: null pos");
-    if (!table) return fail(PSE_ERR_INVALID, "pse_pair_table: null table");
-    if (((uintptr_t)table & 15u) != 0) return fail(PSE_ERR_INVALID, "pse_pair_table: the table is not 16-byte aligned");
-    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_pair_table: force and out8 are both null: nothing to compute");
-    if (width < 2 || width > 2048) return fail(PSE_ERR_INVALID, "pse_pair_table: table width %d outside [2, 2048]", width);
-    if (!std::isfinite(rmin) || !std::isfinite(rmax)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g, rmax = %g must be finite", rmin, rmax);
-    if (rmin < 0.0) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g is negative", rmin);
-    if (!(rmax > rmin)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmax = %g must exceed rmin = %g", rmax, rmin);
-    if (rmax > h->d.rcut) return fail(PSE_ERR_INVALID, "pse_pair_table: table range rmax = %.4f beyond rcut = %.4f", rmax, h->d.rcut);
-    if (out8 && h->par.n_slabs > 1) return fail(PSE_ERR_INVALID, "pse_pair_table: this handle is a slab rank");
-    return 0;   // table, force and out8 are device pointers and there is no device: nothing is read or written
+    return pair_table_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, table, width, rmin, rmax, out8);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {
@@ -121,19 +118,10 @@ int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned 
     *out = nullptr;
     if (!h) return fail(PSE_ERR_INVALID, "pse_bonds_create: null handle");
     if (int rc = bonds_validate(h->par.n_max, n, nbonds, pairs_host, types_host, ntypes, kind_host, k_host, r0_host)) return rc;
-    pse_bonds *b = new pse_bonds{h, std::vector<int>((size_t)n + 1), std::vector<unsigned>((size_t)nbonds * 4)};
-    if (int rc = pse_host_bond_rows(n, nbonds, pairs_host, types_host, b->row_off.data(), b->entries.data())) { delete b; return rc; }
-    h->bond_lists.push_back(b);
-    *out = b;
-    return 0;
+    pse_bonds *b = new pse_bonds(h, (size_t)n + 1, (size_t)nbonds * 4);
+    return topology_adopt(b, pse_host_bond_rows(n, nbonds, pairs_host, types_host, b->row_off.data(), b->entries.data()), out);
 }
-int pse_bonds_destroy(pse_bonds *b) {
-    if (!b) return 0;
-    std::vector<pse_bonds *> &l = b->h->bond_lists;
-    l.erase(std::remove(l.begin(), l.end(), b), l.end());
-    delete b;
-    return 0;
-}
+int pse_bonds_destroy(pse_bonds *b) { return topology_destroy(b); }
 int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force, int, double *out8) {
     if (!b) return fail(PSE_ERR_INVALID, "pse_bond_forces: null bond object");
     if (!pos) return fail(PSE_ERR_INVALID, "pse_bond_forces: null pos");
@@ -151,19 +139,10 @@ int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, const unsigne
     *out = nullptr;
     if (!h) return fail(PSE_ERR_INVALID, "pse_angles_create: null handle");
     if (int rc = angles_validate(h->par.n_max, n, nangles, triples_host, types_host, ntypes, kind_host, k_host, theta0_host)) return rc;
-    pse_angles *a = new pse_angles{h, std::vector<int>((size_t)n + 1), std::vector<unsigned>((size_t)nangles * 12)};
-    if (int rc = pse_host_angle_rows(n, nangles, triples_host, types_host, a->row_off.data(), a->entries.data())) { delete a; return rc; }
-    h->angle_lists.push_back(a);
-    *out = a;
-    return 0;
+    pse_angles *a = new pse_angles(h, (size_t)n + 1, (size_t)nangles * 12);
+    return topology_adopt(a, pse_host_angle_rows(n, nangles, triples_host, types_host, a->row_off.data(), a->entries.data()), out);
 }
-int pse_angles_destroy(pse_angles *a) {
-    if (!a) return 0;
-    std::vector<pse_angles *> &l = a->h->angle_lists;
-    l.erase(std::remove(l.begin(), l.end(), a), l.end());
-    delete a;
-    return 0;
-}
+int pse_angles_destroy(pse_angles *a) { return topology_destroy(a); }
 int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, int, double *out8) {
     if (!a) return fail(PSE_ERR_INVALID, "pse_angle_forces: null angle object");
     if (!pos) return fail(PSE_ERR_INVALID, "pse_angle_forces: null pos");

@@ -23,8 +23,8 @@ Stokes::~Stokes() {
 
 void Stokes::setParams() {
     if (m_h) { pse_destroy(m_h); m_h = nullptr; }
-    m_bonds.clear();   // pse_destroy freed them
-    m_angles.clear();
+    m_bonds.objs.clear();   // pse_destroy freed them
+    m_angles.objs.clear();
     m_m_Lanczos = 2;   // "try two Lanczos iterations to start" (PSEv1/Stokes.cc:131-132)
     pse_params p{};
     p.n_max = m_n_total;
@@ -81,29 +81,22 @@ int Stokes::bondsCreate(unsigned int n, unsigned int nbonds, const unsigned int 
     if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
     pse_bonds *b = nullptr;
     check(pse_bonds_create(m_h, n, nbonds, pairs, types, ntypes, kind, k, r0, &b), "Stokes::bondsCreate");
-    m_bonds.push_back(b);
-    return (int)m_bonds.size() - 1;
-}
-
-pse_bonds *Stokes::bondObject(int id) const {
-    if (id < 0 || id >= (int)m_bonds.size() || !m_bonds[id])
-        throw std::invalid_argument("Stokes: no bond object with id " + std::to_string(id) + " (setParams invalidates the ids)");
-    return m_bonds[id];
+    return m_bonds.push(b);
 }
 
 void Stokes::bondForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8) {
-    check(pse_bond_forces(bondObject(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::bondForces");
+    check(pse_bond_forces(m_bonds.get(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::bondForces");
 }
 
 unsigned long long Stokes::bondsOverstretched(int id) {
     unsigned long long c = 0;
-    check(pse_bonds_overstretched(bondObject(id), &c), "Stokes::bondsOverstretched");
+    check(pse_bonds_overstretched(m_bonds.get(id), &c), "Stokes::bondsOverstretched");
     return c;
 }
 
 void Stokes::bondsDestroy(int id) {
-    check(pse_bonds_destroy(bondObject(id)), "Stokes::bondsDestroy");
-    m_bonds[id] = nullptr;
+    check(pse_bonds_destroy(m_bonds.get(id)), "Stokes::bondsDestroy");
+    m_bonds.drop(id);
 }
 
 int Stokes::anglesCreate(unsigned int n, unsigned int nangles, const unsigned int *triples, const unsigned int *types, int ntypes,
@@ -111,23 +104,16 @@ int Stokes::anglesCreate(unsigned int n, unsigned int nangles, const unsigned in
     if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
     pse_angles *a = nullptr;
     check(pse_angles_create(m_h, n, nangles, triples, types, ntypes, kind, k, theta0, &a), "Stokes::anglesCreate");
-    m_angles.push_back(a);
-    return (int)m_angles.size() - 1;
-}
-
-pse_angles *Stokes::angleObject(int id) const {
-    if (id < 0 || id >= (int)m_angles.size() || !m_angles[id])
-        throw std::invalid_argument("Stokes: no angle object with id " + std::to_string(id) + " (setParams invalidates the ids)");
-    return m_angles[id];
+    return m_angles.push(a);
 }
 
 void Stokes::angleForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8) {
-    check(pse_angle_forces(angleObject(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::angleForces");
+    check(pse_angle_forces(m_angles.get(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::angleForces");
 }
 
 void Stokes::anglesDestroy(int id) {
-    check(pse_angles_destroy(angleObject(id)), "Stokes::anglesDestroy");
-    m_angles[id] = nullptr;
+    check(pse_angles_destroy(m_angles.get(id)), "Stokes::anglesDestroy");
+    m_angles.drop(id);
 }
 
 pse_info Stokes::info() const {

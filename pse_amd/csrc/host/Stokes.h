@@ -3,6 +3,7 @@
 // the particle arrays stay with the caller (HOOMD's ParticleData in the reference, PSEv1/Stokes.cc:454-461).
 #pragma once
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -20,6 +21,20 @@ struct ParticleArrays {
     pse_double4 *pos; pse_double4 *vel; pse_double3 *accel; pse_int3 *image; const pse_double4 *net_force;
     const unsigned int *group_members;   // may be null: all particles
     unsigned int group_size;
+};
+
+// The objects of one kind that a Stokes made on its engine, by id -- the position in the table; null once destroyed.
+template <class T>
+struct IdTable {
+    const char *what;   // "bond", "angle": what the error calls them
+    std::vector<T *> objs;
+    int push(T *o) { objs.push_back(o); return (int)objs.size() - 1; }
+    T *get(int id) const {
+        if (id < 0 || id >= (int)objs.size() || !objs[id])
+            throw std::invalid_argument(std::string("Stokes: no ") + what + " object with id " + std::to_string(id) + " (setParams invalidates the ids)");
+        return objs[id];
+    }
+    void drop(int id) { objs[id] = nullptr; }
 };
 
 class Stokes {
@@ -85,10 +100,8 @@ private:
     int m_m_Lanczos = 2;                                                                   // Stokes.cc:132
     int m_lanczos_op = -1;
     pse_handle *m_h = nullptr;
-    std::vector<pse_bonds *> m_bonds;   // by id; null once destroyed
-    pse_bonds *bondObject(int id) const;
-    std::vector<pse_angles *> m_angles; // by id; null once destroyed
-    pse_angles *angleObject(int id) const;
+    IdTable<pse_bonds> m_bonds{"bond"};
+    IdTable<pse_angles> m_angles{"angle"};
 };
 
 }  // namespace pse_host

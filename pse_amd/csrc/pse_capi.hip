@@ -56,6 +56,7 @@ constexpr int PH_COUNT_ = 13;   // timed phases (enum PH_* below)
 struct Phase {
     hipEvent_t a = nullptr, b = nullptr;
 };
+struct Topology;
 
 struct pse_handle {
     pse_params par;
@@ -110,8 +111,7 @@ struct pse_handle {
     size_t sort_tmp_bytes = 0;
     int *cell_off = nullptr;
     double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
-    std::vector<pse_bonds *> bond_lists;   // the bond objects created on this handle and still alive (pse_destroy frees them)
-    std::vector<pse_angles *> angle_lists; // the same for the angle objects
+    std::vector<Topology *> topologies;   // the bond and angle objects created on this handle and still alive (pse_destroy frees them)
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
@@ -399,46 +399,30 @@ static int collect_times(pse_handle *h, unsigned mask) {
     return 0;
 }
 
-// A bond topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, the per-type parameters and the counter of
-// overstretched FENE bonds.  Owned by its handle.
-struct pse_bonds {
+// A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows or pse_host_angle_rows, the per-type parameters
+// and, for bonds, the counter of overstretched FENE bonds.  Owned by its handle; the destructor frees the device arrays.
+struct Topology {
     pse_handle *h = nullptr;
-    unsigned n = 0, nbonds = 0;
+    unsigned n = 0, count = 0;              // particles; bonds or angles
     int ntypes = 0;
-    unsigned *row_off = nullptr;            // n + 1
-    uint2 *entries = nullptr;               // 2 nbonds: (partner, type)
-    BondParam *par = nullptr;               // ntypes
-    unsigned long long *over = nullptr;     // FENE bonds seen at r >= r0 since creation
+    void *row_off = nullptr;                // n + 1 (bonds: unsigned, angles: int)
+    void *entries = nullptr;                // bonds: 2 count x uint2 (partner, type); angles: 3 count x uint4 (i, j, k, type), j the vertex, i < k
+    void *par = nullptr;                    // ntypes x BondParam or AngleParam
+    unsigned long long *over = nullptr;     // bonds: FENE bonds seen at r >= r0 since creation
+    virtual ~Topology() {
+        void *ptrs[] = {row_off, entries, par, over};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
 };
-static void bonds_free(pse_bonds *b) {
-    void *ptrs[] = {b->row_off, b->entries, b->par, b->over};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete b;
-}
-
-// An angle topology on the device (include/pse_amd.h): the rows of pse_host_angle_rows and the per-type parameters.  Owned by its handle.
-struct pse_angles {
-    pse_handle *h = nullptr;
-    unsigned n = 0, nangles = 0;
-    int ntypes = 0;
-    int *row_off = nullptr;                 // n + 1
-    uint4 *entries = nullptr;               // 3 nangles: (i, j, k, type), j the vertex, i < k
-    AngleParam *par = nullptr;              // ntypes
-};
-static void angles_free(pse_angles *a) {
-    void *ptrs[] = {a->row_off, a->entries, a->par};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete a;
-}
+struct pse_bonds : Topology {};
+struct pse_angles : Topology {};
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    for (pse_bonds *b : h->bond_lists) bonds_free(b);
-    h->bond_lists.clear();
-    for (pse_angles *a : h->angle_lists) angles_free(a);
-    h->angle_lists.clear();
+    for (Topology *t : h->topologies) delete t;
+    h->topologies.clear();
     if (h->plan_fwd) rocfft_plan_destroy(h->plan_fwd);
     if (h->plan_inv) rocfft_plan_destroy(h->plan_inv);
     if (h->plan_x_fwd) rocfft_plan_destroy(h->plan_x_fwd);
@@ -2573,59 +2557,35 @@ extern "C" int pse_sqrt_mreal(pse_handle *h, const pse_double4 *pos, const pse_d
     return 0;
 }
 
-extern "C" int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                                  double k, double sigma, int accumulate) {
-    TRY(check_n(h, N));
-    if (!pos || !force) return fail(PSE_ERR_INVALID, "null array");
-    if (!(sigma > 0.0) || sigma > h->d.rcut)
-        return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]: the cell list is built for the hydrodynamic cutoff",
-                    sigma, h->d.rcut);
+// pse_pair_repulsion and pse_pair_repulsion_virial (include/pse_amd.h): the force pass, and the same pass with the pair observables of
+// the repulsion -- energy, virial and pair count in eight device doubles.  Queue-only: nothing is read back, out8 is written by the stream.
+static int pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, double k, double sigma,
+                          int accumulate, bool virial, double *out8) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    TRY(pair_repulsion_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, virial, out8, sigma));
+    HIPCHK(hipSetDevice(h->device));
     TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    launch_pair_repulsion(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->stream);
+    launch_pair_repulsion(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->pv_rows, out8,
+                          h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
-
-// The same force pass with the pair observables of the repulsion (include/pse_amd.h): energy, virial and pair count in eight device
-// doubles.  Queue-only wherever pse_pair_repulsion is: nothing is read back, out8 is written by the stream.
+extern "C" int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                  double k, double sigma, int accumulate) {
+    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, false, nullptr);
+}
 extern "C" int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
                                          double k, double sigma, int accumulate, double *out8) {
-    TRY(check_n(h, N));
-    if (!pos) return fail(PSE_ERR_INVALID, "null array");
-    if (!out8) return fail(PSE_ERR_INVALID, "null out8: the observables need eight device doubles");
-    if (h->n_slabs > 1)
-        return fail(PSE_ERR_INVALID, "pse_pair_repulsion_virial: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums "
-                                     "would be partial", h->n_slabs);
-    if (!(sigma > 0.0) || sigma > h->d.rcut)
-        return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]: the cell list is built for the hydrodynamic cutoff",
-                    sigma, h->d.rcut);
-    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    launch_pair_repulsion_virial(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->pv_rows,
-                                 out8, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, true, out8);
 }
 
 // Tabulated pair potential on the same cell list (include/pse_amd.h), with or without the eight observables.  Queue-only wherever
 // pse_pair_repulsion is; the table is read by the stream.
 extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
                               const double *table, int width, double rmin, double rmax, int accumulate, double *out8) {
-    TRY(check_n(h, N));
-    if (!pos) return fail(PSE_ERR_INVALID, "pse_pair_table: null pos");
-    if (!table) return fail(PSE_ERR_INVALID, "pse_pair_table: null table");
-    if (((uintptr_t)table & 15u) != 0) return fail(PSE_ERR_INVALID, "pse_pair_table: the table is not 16-byte aligned (it is read as (V, F) entries)");
-    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_pair_table: force and out8 are both null: nothing to compute");
-    if (width < 2 || width > PAIR_TABLE_MAX_WIDTH)
-        return fail(PSE_ERR_INVALID, "pse_pair_table: table width %d outside [2, %d] (the table is staged in 32 KB of LDS)", width, PAIR_TABLE_MAX_WIDTH);
-    if (!std::isfinite(rmin) || !std::isfinite(rmax)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g, rmax = %g must be finite", rmin, rmax);
-    if (rmin < 0.0) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g is negative", rmin);
-    if (!(rmax > rmin)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmax = %g must exceed rmin = %g", rmax, rmin);
-    if (rmax > h->d.rcut)
-        return fail(PSE_ERR_INVALID, "pse_pair_table: table range rmax = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic cutoff",
-                    rmax, h->d.rcut);
-    if (out8 && h->n_slabs > 1)
-        return fail(PSE_ERR_INVALID, "pse_pair_table: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums would be "
-                                     "partial (out8 must be null here)", h->n_slabs);
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    TRY(pair_table_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, table, width, rmin, rmax, out8));
+    HIPCHK(hipSetDevice(h->device));
     TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
     launch_pair_table(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, table, width, rmin, rmax, accumulate, (double4 *)force,
                       h->pv_rows, out8, h->stream);
@@ -2633,7 +2593,43 @@ extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4
     return 0;
 }
 
-// ---- bonded forces (include/pse_amd.h) ----------------------------------------------------------------------------------------
+// ---- bonded forces and angle forces (include/pse_amd.h) ------------------------------------------------------------------------
+// The device copy of a topology: the host rows `off` and `ent`, ntypes 32-byte parameter sets and, with `counter`, a zeroed counter.
+// `what` is "bonds" or "angles".
+template <class T>
+static int topology_create(pse_handle *h, const char *what, unsigned n, unsigned count, int ntypes, const std::vector<int> &off,
+                           const std::vector<unsigned> &ent, const void *par, bool counter, T **out) {
+    static_assert(sizeof(BondParam) == sizeof(AngleParam), "one parameter set of either kind is 32 bytes");
+    T *t = new T();
+    t->h = h; t->n = n; t->count = count; t->ntypes = ntypes;
+    auto put = [](void **dst, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, bytes);
+        if (e != hipSuccess) return e;
+        return src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
+    };
+    hipError_t e = put(&t->row_off, off.data(), off.size() * sizeof(int));
+    if (e == hipSuccess) e = put(&t->entries, ent.data(), ent.size() * sizeof(unsigned));
+    if (e == hipSuccess) e = put(&t->par, par, (size_t)ntypes * sizeof(BondParam));
+    if (e == hipSuccess && counter) e = put((void **)&t->over, nullptr, sizeof(unsigned long long));
+    if (e == hipSuccess && counter) e = hipDeviceSynchronize();   // (the memset is the one call above that may return early)
+    if (e != hipSuccess) {
+        delete t;
+        return fail(PSE_ERR_HIP, "pse_%s_create: copying %u %s to the device failed: %s", what, count, what, hipGetErrorString(e));
+    }
+    h->topologies.push_back(t);
+    *out = t;
+    return 0;
+}
+static int topology_destroy(Topology *t) {
+    if (!t) return 0;
+    pse_handle *h = t->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
+    h->topologies.erase(std::remove(h->topologies.begin(), h->topologies.end(), t), h->topologies.end());
+    delete t;
+    return 0;
+}
+
 extern "C" int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                                 const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {
     if (!out) return fail(PSE_ERR_INVALID, "pse_bonds_create: null out");
@@ -2647,36 +2643,9 @@ extern "C" int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, cons
     std::vector<BondParam> par((size_t)ntypes);
     for (int t = 0; t < ntypes; ++t)
         par[t] = BondParam{k_host[t], r0_host[t], r0_host[t] > 0.0 ? 1.0 / (r0_host[t] * r0_host[t]) : 0.0, (double)kind_host[t]};
-    pse_bonds *b = new pse_bonds();
-    b->h = h; b->n = n; b->nbonds = nbonds; b->ntypes = ntypes;
-    auto put = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes);
-        if (e != hipSuccess) return e;
-        return src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
-    };
-    hipError_t e = put((void **)&b->row_off, off.data(), off.size() * sizeof(int));
-    if (e == hipSuccess) e = put((void **)&b->entries, ent.data(), ent.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = put((void **)&b->par, par.data(), par.size() * sizeof(BondParam));
-    if (e == hipSuccess) e = put((void **)&b->over, nullptr, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memset is the one call above that may return early)
-    if (e != hipSuccess) {
-        bonds_free(b);
-        return fail(PSE_ERR_HIP, "pse_bonds_create: copying %u bonds to the device failed: %s", nbonds, hipGetErrorString(e));
-    }
-    h->bond_lists.push_back(b);
-    *out = b;
-    return 0;
+    return topology_create(h, "bonds", n, nbonds, ntypes, off, ent, par.data(), true, out);
 }
-
-extern "C" int pse_bonds_destroy(pse_bonds *b) {
-    if (!b) return 0;
-    pse_handle *h = b->h;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
-    h->bond_lists.erase(std::remove(h->bond_lists.begin(), h->bond_lists.end(), b), h->bond_lists.end());
-    bonds_free(b);
-    return 0;
-}
+extern "C" int pse_bonds_destroy(pse_bonds *b) { return topology_destroy(b); }
 
 // Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
 extern "C" int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
@@ -2685,8 +2654,8 @@ extern "C" int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4
     if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_bond_forces: force and out8 are both null: nothing to compute");
     pse_handle *h = b->h;
     HIPCHK(hipSetDevice(h->device));
-    launch_bond_forces((const double4 *)pos, (int)b->n, b->row_off, b->entries, b->par, b->ntypes, h->dbox, accumulate, (double4 *)force,
-                       h->pv_rows, out8, b->over, h->stream);
+    launch_bond_forces((const double4 *)pos, (int)b->n, (const unsigned *)b->row_off, (const uint2 *)b->entries, (const BondParam *)b->par,
+                       b->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, b->over, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2700,7 +2669,6 @@ extern "C" int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) 
     return 0;
 }
 
-// ---- angle forces (include/pse_amd.h) ------------------------------------------------------------------------------------------
 extern "C" int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, const unsigned *triples_host, const unsigned *types_host,
                                  int ntypes, const int *kind_host, const double *k_host, const double *theta0_host, pse_angles **out) {
     if (!out) return fail(PSE_ERR_INVALID, "pse_angles_create: null out");
@@ -2713,34 +2681,9 @@ extern "C" int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, co
     TRY(pse_host_angle_rows(n, nangles, triples_host, types_host, off.data(), ent.data()));
     std::vector<AngleParam> par((size_t)ntypes);
     for (int t = 0; t < ntypes; ++t) par[t] = AngleParam{k_host[t], theta0_host[t], std::cos(theta0_host[t]), (double)kind_host[t]};
-    pse_angles *a = new pse_angles();
-    a->h = h; a->n = n; a->nangles = nangles; a->ntypes = ntypes;
-    auto put = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    };
-    hipError_t e = put((void **)&a->row_off, off.data(), off.size() * sizeof(int));
-    if (e == hipSuccess) e = put((void **)&a->entries, ent.data(), ent.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = put((void **)&a->par, par.data(), par.size() * sizeof(AngleParam));
-    if (e != hipSuccess) {
-        angles_free(a);
-        return fail(PSE_ERR_HIP, "pse_angles_create: copying %u angles to the device failed: %s", nangles, hipGetErrorString(e));
-    }
-    h->angle_lists.push_back(a);
-    *out = a;
-    return 0;
+    return topology_create(h, "angles", n, nangles, ntypes, off, ent, par.data(), false, out);
 }
-
-extern "C" int pse_angles_destroy(pse_angles *a) {
-    if (!a) return 0;
-    pse_handle *h = a->h;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
-    h->angle_lists.erase(std::remove(h->angle_lists.begin(), h->angle_lists.end(), a), h->angle_lists.end());
-    angles_free(a);
-    return 0;
-}
+extern "C" int pse_angles_destroy(pse_angles *a) { return topology_destroy(a); }
 
 // Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
 extern "C" int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
@@ -2749,8 +2692,8 @@ extern "C" int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_doubl
     if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_angle_forces: force and out8 are both null: nothing to compute");
     pse_handle *h = a->h;
     HIPCHK(hipSetDevice(h->device));
-    launch_angle_forces((const double4 *)pos, (int)a->n, a->row_off, a->entries, a->par, a->ntypes, h->dbox, accumulate, (double4 *)force,
-                        h->pv_rows, out8, h->stream);
+    launch_angle_forces((const double4 *)pos, (int)a->n, (const int *)a->row_off, (const uint4 *)a->entries, (const AngleParam *)a->par,
+                        a->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

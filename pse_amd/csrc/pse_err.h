@@ -17,6 +17,14 @@ void fill_info(const Derived &d, pse_info *o);
 // coarsest of the three grid spacings (an override the reference's rule cannot produce) -- shared by pse_create, pse_set_box,
 // pse_host_select_params and the sanitizer build's stand-in, so that all agree on which configurations are valid
 int gaussian_fits(const Derived &d, double hx, double hy, double hz);
+// 0, or PSE_ERR_INVALID with a message: the argument checks of pse_pair_repulsion (virial = false) and pse_pair_repulsion_virial
+// (virial = true) behind the null-handle check, with the handle's rcut, n_max and n_slabs -- shared by the device library and the
+// sanitizer build's stand-in, in the order include/pse_amd.h promises
+int pair_repulsion_validate(double rcut, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force, bool virial,
+                            const void *out8, double sigma);
+// the same for pse_pair_table
+int pair_table_validate(double rcut, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force, const double *table, int width,
+                        double rmin, double rmax, const void *out8);
 // 0, or PSE_ERR_INVALID with a message naming the offending value: the argument checks of pse_bonds_create that need no device
 // (include/pse_amd.h lists them) -- shared by the device library and the sanitizer build's stand-in
 int bonds_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types, int ntypes, const int *kind,

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -45,6 +46,45 @@ int gaussian_fits(const Derived &d, double hx, double hy, double hz) {
     if (!(worst < 700.0))
         return fail(PSE_ERR_INVALID, "grid spacings (%g, %g, %g) too unequal for the spreading Gaussian of P = %d points, eta = %g: "
                     "exp(+-%.0f) over its support on the coarsest axis", hx, hy, hz, d.P, d.eta, worst);
+    return 0;
+}
+
+static int count_in_range(unsigned n_max, unsigned N) {
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "N = %u outside (0, n_max = %u]", N, n_max);
+    return 0;
+}
+
+int pair_repulsion_validate(double rcut, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force, bool virial,
+                            const void *out8, double sigma) {
+    if (int rc = count_in_range(n_max, N)) return rc;
+    if (!pos || (!virial && !force)) return fail(PSE_ERR_INVALID, "null array");
+    if (virial && !out8) return fail(PSE_ERR_INVALID, "null out8: the observables need eight device doubles");
+    if (virial && n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "pse_pair_repulsion_virial: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums "
+                                     "would be partial", n_slabs);
+    if (!(sigma > 0.0) || sigma > rcut)
+        return fail(PSE_ERR_INVALID, "repulsion range %.4f outside (0, rcut = %.4f]: the cell list is built for the hydrodynamic cutoff", sigma, rcut);
+    return 0;
+}
+
+int pair_table_validate(double rcut, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force, const double *table, int width,
+                        double rmin, double rmax, const void *out8) {
+    if (int rc = count_in_range(n_max, N)) return rc;
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_pair_table: null pos");
+    if (!table) return fail(PSE_ERR_INVALID, "pse_pair_table: null table");
+    if (((uintptr_t)table & 15u) != 0) return fail(PSE_ERR_INVALID, "pse_pair_table: the table is not 16-byte aligned (it is read as (V, F) entries)");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_pair_table: force and out8 are both null: nothing to compute");
+    if (width < 2 || width > PAIR_TABLE_MAX_WIDTH)
+        return fail(PSE_ERR_INVALID, "pse_pair_table: table width %d outside [2, %d] (the table is staged in 32 KB of LDS)", width, PAIR_TABLE_MAX_WIDTH);
+    if (!std::isfinite(rmin) || !std::isfinite(rmax)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g, rmax = %g must be finite", rmin, rmax);
+    if (rmin < 0.0) return fail(PSE_ERR_INVALID, "pse_pair_table: rmin = %g is negative", rmin);
+    if (!(rmax > rmin)) return fail(PSE_ERR_INVALID, "pse_pair_table: rmax = %g must exceed rmin = %g", rmax, rmin);
+    if (rmax > rcut)
+        return fail(PSE_ERR_INVALID, "pse_pair_table: table range rmax = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic cutoff",
+                    rmax, rcut);
+    if (out8 && n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "pse_pair_table: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums would be "
+                                     "partial (out8 must be null here)", n_slabs);
     return 0;
 }
 

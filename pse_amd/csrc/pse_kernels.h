@@ -346,20 +346,17 @@ void launch_scatter_sum(const double4 *a, const double4 *b, const double4 *c, co
 void launch_integrate(double4 *pos, const double4 *vel, double3 *accel, int3 *image, const double4 *force,
                       const unsigned *group, int N, DBox box, double dt, double shear_rate, hipStream_t s);
 void launch_eval_fg(const double *r, int n, const double *coef, double *f, double *g, hipStream_t s);
-// soft pair repulsion from the cell list, scattered to the caller's order (force provider)
-void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
-                           double k, double sigma, int accumulate, double4 *force, hipStream_t s);
-// the same pass + the pair observables U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs over the rows j > i: one row of PAIR_VIRIAL_NOBS doubles
+// soft pair repulsion from the cell list, scattered to the caller's order (force provider).  out8 != null: the same
+// pass + the pair observables U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs over the rows j > i: one row of PAIR_VIRIAL_NOBS doubles
 // per workgroup into `rows` (pair_virial_rows(N) doubles), added up in a fixed order into out8 (device) by a second, one-workgroup
-// kernel; force may be null (observables only)
+// kernel; force may then be null (observables only).  out8 == null: forces only, no reduction (rows is not touched)
 constexpr int PAIR_VIRIAL_NOBS = 8;
 size_t pair_virial_rows(int n);
-void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
-                                  double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
+void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
+                           double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
 // tabulated central pair potential from the cell list (k_pair_table): table = width x (V, F) on the device, 16-byte aligned, nodes
 // r_e = rmin + e (rmax - rmin)/(width - 1), linear between them, staged in width * 16 bytes of LDS per workgroup.  out8 != null: the
 // eight observables through `rows` as above; out8 == null: forces only, no reduction (rows is not touched)
-constexpr int PAIR_TABLE_MAX_WIDTH = 2048;   // 32 KB of LDS
 void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
                        int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =

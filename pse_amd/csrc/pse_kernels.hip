@@ -2681,57 +2681,66 @@ void launch_basis_combine(const double4 *x0, const double4 *V, size_t stride, co
                        t_dev, m, scal, scale, use_norm, out_s, lo, hi, sink, st);
 }
 
-// Force provider next to the path (the step consumes net_force, PSEv1/Stokes.cc:447): soft repulsion
-// F_i = sum_j k (sigma - r) (r_i - r_j)/r over pairs closer than sigma, from the engine's own cell list.  One thread per
-// particle; the result is added to (or stored in) the caller's force array in the caller's order.
-__global__ void __launch_bounds__(TPB)
-k_pair_repulsion(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off,
-                 DBox box, DCells nc, double k, double sigma, int accumulate, double4 *__restrict__ force) {
-    const int i = xcd_block(blockIdx.x, gridDim.x) * TPB + threadIdx.x;
-    if (i >= N) return;
-    const double4 pi = pos_s[i];
-    double fx, fy, fz;
-    frac_coords(box, pi.x, pi.y, pi.z, fx, fy, fz);
-    const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
-    const double s2 = sigma * sigma;
-    double Fx = 0.0, Fy = 0.0, Fz = 0.0;
-    for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
-        for (int j = jb; j < je; ++j) {
-            const double4 pj = pos_s[j];
-            double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-            min_image(box, dx, dy, dz);
-            const double r2 = dx * dx + dy * dy + dz * dz;
-            if (r2 < s2 && j != i && r2 > 0.0) {
-                const double r = sqrt(r2), c = k * (sigma - r) / r;
-                Fx += c * dx; Fy += c * dy; Fz += c * dz;
-            }
-        }
-    });
-    const unsigned idx = tag_s[i];
+// Force providers next to the path (the step consumes net_force, PSEv1/Stokes.cc:447).  What the passes below share:
+constexpr int PV_NOBS = PAIR_VIRIAL_NOBS;
+typedef double pt_entry __attribute__((ext_vector_type(2)));   // a 16-byte LDS word (see k_pair_table)
+
+// The force row of one particle under `accumulate`: read before it is written, so that w is kept.
+__device__ __forceinline__ void force_row_store(double4 *__restrict__ force, unsigned idx, int accumulate, double Fx, double Fy, double Fz) {
     double4 f = force[idx];
     if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
     force[idx] = f;
 }
-void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
-                           double k, double sigma, int accumulate, double4 *force, hipStream_t s) {
-    hipLaunchKernelGGL(k_pair_repulsion, dim3(nblocks(N, TPB)), dim3(TPB), 0, s, pos_s, tag_s, N, cell_off, box, nc, k, sigma,
-                       accumulate, force);
+// The row of a particle without entries: accumulate != 0 neither reads nor writes it, accumulate == 0 overwrites its xyz, w kept.
+__device__ __forceinline__ void force_row_clear(double4 *__restrict__ force, unsigned idx, int accumulate) {
+    if (force && !accumulate) force_row_store(force, idx, 0, 0.0, 0.0, 0.0);
+}
+// One pair of a central force c d (d = r_i - r_j minimum image) with energy u: U, the six components W_ab = c d_a d_b of the
+// symmetric virial sum_{i<j} r_ij (x) F_ij, and a count.
+__device__ __forceinline__ void obs_add_central(double (&o)[PV_NOBS], double u, double c, double dx, double dy, double dz) {
+    const double cdx = c * dx, cdy = c * dy;
+    o[0] += u;
+    o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
+    o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
+    o[7] += 1.0;
+}
+// The reduction of the eight sums: over the wave with wave_sum, over the four waves through LDS with ONE barrier for the whole
+// 8-vector, and the workgroup writes row `blk` of eight doubles; k_pair_virial_finish adds the rows up.  No floating-point atomics:
+// every sum has a fixed order.  EVERY lane of the workgroup must arrive here (lanes past the last row with zeros).
+__device__ __forceinline__ void obs_rows_store(double (&o)[PV_NOBS], int blk, double *__restrict__ rows /* [gridDim.x][PV_NOBS] */) {
+    static_assert(TPB == 256, "the sum over the four waves of a workgroup is written out");
+    __shared__ double sh[TPB / 64][PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+}
+// Per-type parameters of the bonded passes: the type differs from lane to lane, so a wave-uniform (scalar) load cannot serve them;
+// they are staged in LDS instead, 32 bytes per type, at most 2 KB, copied by the first 2 ntypes lanes of each workgroup before one
+// barrier, and read as two 16-byte words per entry.  In the common case of one type every lane reads the same word, which the LDS
+// broadcasts.  EVERY lane must arrive here.
+__device__ __forceinline__ void stage_type_params(pt_entry *dst, const void *__restrict__ par, int ntypes) {
+    if ((int)threadIdx.x < 2 * ntypes) dst[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
+    __syncthreads();
 }
 
-// The same pass with the pair observables of a rheology run (no reference counterpart: the reference leaves forces and their
-// stress to HOOMD): besides the force on row i from ALL its neighbours, the rows j > i of the sorted order -- every unordered pair
-// once -- add U = k/2 (sigma - r)^2, the six components W_ab = c d_a d_b of the symmetric virial sum_{i<j} r_ij (x) F_ij
-// (d = r_i - r_j minimum image, c = k (sigma - r)/r: c d is the force on i from j) and a pair count.  The eight sums are reduced over
-// the wave with wave_sum, over the four waves through LDS with ONE barrier for the whole 8-vector, and each workgroup writes one
-// row of eight doubles; k_pair_virial_finish adds the rows up.  No floating-point atomics: every sum has a fixed order given the
-// sorted order, and the cell sort is a stable sort (k_cell_order), so the eight numbers are bit-reproducible from call to call on
-// equal inputs.  force == nullptr: observables only.
-constexpr int PV_NOBS = PAIR_VIRIAL_NOBS;
+// Soft repulsion F_i = sum_j k (sigma - r) (r_i - r_j)/r over pairs closer than sigma, from the engine's own cell list.  One thread
+// per particle; the result is added to (or stored in) the caller's force array in the caller's order.
+// (the cell walk is written out here and in k_pair_table: shared through a lambda-taking helper in the style of for_each_run it
+// compiled to another register allocation and cost the table pass 1 %, docs/HISTORY.md)
+// OBS: the same pass with the pair observables of a rheology run: besides the force on row i from ALL its neighbours, the rows
+// j > i of the sorted order -- every unordered pair once -- add U = k/2 (sigma - r)^2 and the virial of c = k (sigma - r)/r
+// (obs_add_central), reduced by obs_rows_store.  The sorted order fixes every sum, and the cell sort is a stable sort (k_cell_order),
+// so the eight numbers are bit-reproducible from call to call on equal inputs.  force == nullptr: observables only.
+template <bool OBS>
 __global__ void __launch_bounds__(TPB)
-k_pair_repulsion_virial(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off,
-                        DBox box, DCells nc, double k, double sigma, int accumulate, double4 *__restrict__ force,
-                        double *__restrict__ rows /* [gridDim.x][PV_NOBS] */) {
-    __shared__ double sh[TPB / 64][PV_NOBS];
+k_pair_repulsion(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off,
+                 DBox box, DCells nc, double k, double sigma, int accumulate, double4 *__restrict__ force,
+                 double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
     const int blk = xcd_block(blockIdx.x, gridDim.x);
     const int i = blk * TPB + threadIdx.x;
     double o[PV_NOBS];
@@ -2753,31 +2762,13 @@ k_pair_repulsion_virial(const double4 *__restrict__ pos_s, const unsigned *__res
                 if (r2 < s2 && j != i && r2 > 0.0) {
                     const double r = sqrt(r2), c = k * (sigma - r) / r;
                     Fx += c * dx; Fy += c * dy; Fz += c * dz;
-                    if (j > i) {
-                        const double cdx = c * dx, cdy = c * dy;
-                        o[0] += 0.5 * k * (sigma - r) * (sigma - r);
-                        o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
-                        o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
-                        o[7] += 1.0;
-                    }
+                    if (OBS && j > i) obs_add_central(o, 0.5 * k * (sigma - r) * (sigma - r), c, dx, dy, dz);
                 }
             }
         });
-        if (force) {
-            const unsigned idx = tag_s[i];
-            double4 f = force[idx];
-            if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
-            force[idx] = f;
-        }
+        if (force) force_row_store(force, tag_s[i], accumulate, Fx, Fy, Fz);
     }
-#pragma unroll
-    for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (OBS) obs_rows_store(o, blk, rows);
 }
 // One workgroup adds the nrows workgroup rows in a fixed order (the reduce_partials pattern, for the 8-vector at once): thread t
 // owns component t % 8 of the rows t / 8, t / 8 + 32, ...; then the 32 partial sums of a component are added in index order.
@@ -2795,12 +2786,24 @@ k_pair_virial_finish(const double *__restrict__ rows, int nrows, double *__restr
         out8[threadIdx.x] = s;
     }
 }
-void launch_pair_repulsion_virial(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
-                                  double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
+// The launch pair of every provider: out8 != null: launch(true, rows), then the rows are added up into out8; out8 == null:
+// launch(false, nullptr), no reduction.  `launch` takes the OBS flag as a std::bool_constant.
+template <class L>
+static void launch_with_obs(int nb, double *rows, double *out8, hipStream_t s, L &&launch) {
+    if (out8) {
+        launch(std::true_type{}, rows);
+        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
+    } else {
+        launch(std::false_type{}, (double *)nullptr);
+    }
+}
+void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
+                           double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
     const int nb = nblocks(N, TPB);
-    hipLaunchKernelGGL(k_pair_repulsion_virial, dim3(nb), dim3(TPB), 0, s, pos_s, tag_s, N, cell_off, box, nc, k, sigma, accumulate,
-                       force, rows);
-    hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
+    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+        hipLaunchKernelGGL(k_pair_repulsion<decltype(obs)::value>, dim3(nb), dim3(TPB), 0, s, pos_s, tag_s, N, cell_off, box, nc, k, sigma,
+                           accumulate, force, r);
+    });
 }
 size_t pair_virial_rows(int n) { return (size_t)nblocks(n, TPB) * PV_NOBS; }
 
@@ -2813,19 +2816,16 @@ size_t pair_virial_rows(int n) { return (size_t)nblocks(n, TPB) * PV_NOBS; }
 // coalesced), into `width` 16-byte entries -- 32 KB at the cap of PAIR_TABLE_MAX_WIDTH -- and a pair then makes two ds_read_b128, entries
 // e and e + 1: V and F of a node share one read, the LDS serves 16-byte reads at its full rate and an entry never straddles two
 // bank rows.  The lanes' e are unrelated, so these reads conflict; that is accepted, the pass is bound by the position gathers.
-// OBS: the eight sums of k_pair_repulsion_virial with U = V(r) and c = F(r)/r, over the rows j > i, reduced and written to `rows`
-// exactly as there (k_pair_virial_finish adds the rows up).  No lane leaves before the barrier behind the staging loop, nor, with
-// OBS, before the one of the reduction.
-// (the native vector type, not double2: hipcc splits a double2 read from LDS into its members and pairs them up again as ds_read2_b64,
-// which the LDS serves at a quarter of the rate of ds_read_b128)
-typedef double pt_entry __attribute__((ext_vector_type(2)));   // x = V, y = F
+// OBS: the eight sums of k_pair_repulsion<true> with U = V(r) and c = F(r)/r, over the rows j > i, reduced and written to `rows`
+// exactly as there.  No lane leaves before the barrier behind the staging loop, nor, with OBS, before the one of the reduction.
+// (pt_entry is the native vector type, not double2: hipcc splits a double2 read from LDS into its members and pairs them up again as
+// ds_read2_b64, which the LDS serves at a quarter of the rate of ds_read_b128; x = V, y = F)
 template <bool OBS>
 __global__ void __launch_bounds__(TPB)
 k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off, DBox box,
              DCells nc, const double2 *__restrict__ table, int width, double rmin, double rmax, double scale, int accumulate,
              double4 *__restrict__ force, double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
     extern __shared__ pt_entry pt_tab[];   // [width]
-    __shared__ double sh[OBS ? TPB / 64 : 1][PV_NOBS];
     for (int e = threadIdx.x; e < width; e += TPB) pt_tab[e] = ((const pt_entry *)table)[e];
     __syncthreads();
     const int blk = xcd_block(blockIdx.x, gridDim.x);
@@ -2856,48 +2856,24 @@ k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag
                         const pt_entry a = pt_tab[e], b = pt_tab[e + 1];
                         const double c = (a.y + w * (b.y - a.y)) * (1.0 / r);
                         Fx += c * dx; Fy += c * dy; Fz += c * dz;
-                        if (OBS && j > i) {
-                            const double cdx = c * dx, cdy = c * dy;
-                            o[0] += a.x + w * (b.x - a.x);
-                            o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
-                            o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
-                            o[7] += 1.0;
-                        }
+                        if (OBS && j > i) obs_add_central(o, a.x + w * (b.x - a.x), c, dx, dy, dz);
                     }
                 }
             }
         });
-        if (force) {
-            const unsigned idx = tag_s[i];
-            double4 f = force[idx];
-            if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
-            force[idx] = f;
-        }
+        if (force) force_row_store(force, tag_s[i], accumulate, Fx, Fy, Fz);
     }
-    if (OBS) {
-#pragma unroll
-        for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
-        }
-        __syncthreads();
-        if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-    }
+    if (OBS) obs_rows_store(o, blk, rows);
 }
 void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
                        int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
     const int nb = nblocks(N, TPB);
     const size_t lds = (size_t)width * sizeof(double2);
     const double scale = (double)(width - 1) / (rmax - rmin);
-    if (out8) {
-        hipLaunchKernelGGL(k_pair_table<true>, dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N, cell_off, box, nc, (const double2 *)table,
-                           width, rmin, rmax, scale, accumulate, force, rows);
-        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
-    } else {
-        hipLaunchKernelGGL(k_pair_table<false>, dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N, cell_off, box, nc, (const double2 *)table,
-                           width, rmin, rmax, scale, accumulate, force, nullptr);
-    }
+    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+        hipLaunchKernelGGL(k_pair_table<decltype(obs)::value>, dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N, cell_off, box, nc,
+                           (const double2 *)table, width, rmin, rmax, scale, accumulate, force, r);
+    });
 }
 
 // Bonded forces (HOOMD's bond.harmonic and bond.fene; no reference counterpart: the reference leaves forces to HOOMD).  One thread
@@ -2908,11 +2884,9 @@ void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const
 // of the bond SET -- forces and sums are bit-identical for any permutation of the bond list and either order of a bond's endpoints
 // (min_image is odd in d, so both ends see the same r).  A bond with r == 0 does nothing; a FENE bond with r >= r0 does nothing either
 // and is counted: its lower endpoint adds it to a per-thread count, and a thread that saw one makes ONE integer atomicAdd.
-// Per-type parameters: the type differs from lane to lane, so a wave-uniform (scalar) load cannot serve them; they are staged in
-// LDS instead, 32 bytes per type (k, r0, 1/r0^2, kind), at most 2 KB, copied by the first lanes of each workgroup before one barrier,
-// and read as two 16-byte words per bond.  In the common case of one type every lane reads the same entry, which the LDS broadcasts.
-// OBS: the endpoint with the LOWER index adds the bond to the eight sums U, W (six), count; reduction, row per workgroup and
-// k_pair_virial_finish as in k_pair_repulsion_virial.  No lane leaves before either barrier.
+// Per-type parameters (stage_type_params): (k, r0, 1/r0^2, kind).
+// OBS: the endpoint with the LOWER index adds the bond to the eight sums U, W (six), count (obs_add_central, obs_rows_store).  No lane
+// leaves before either barrier.
 // accumulate != 0: the rows of unbonded particles are neither read nor written; accumulate == 0: every row's xyz is overwritten, w kept.
 template <bool OBS>
 __global__ void __launch_bounds__(TPB)
@@ -2920,9 +2894,7 @@ k_bond_forces(const double4 *__restrict__ pos, int n, const unsigned *__restrict
               const BondParam *__restrict__ par, int ntypes, DBox box, int accumulate, double4 *__restrict__ force,
               double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */, unsigned long long *__restrict__ overstretched) {
     __shared__ pt_entry bp[2 * BOND_MAX_TYPES];   // [type][0] = (k, r0), [type][1] = (1/r0^2, kind)
-    __shared__ double sh[OBS ? TPB / 64 : 1][PV_NOBS];
-    if ((int)threadIdx.x < 2 * ntypes) bp[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
-    __syncthreads();
+    stage_type_params(bp, par, ntypes);
     const int blk = xcd_block(blockIdx.x, gridDim.x);
     const int i = blk * TPB + threadIdx.x;
     double o[PV_NOBS];
@@ -2958,51 +2930,26 @@ k_bond_forces(const double4 *__restrict__ pos, int n, const unsigned *__restrict
                     }
                     if (acts) {
                         Fx += c * dx; Fy += c * dy; Fz += c * dz;
-                        if (OBS && lower) {
-                            const double cdx = c * dx, cdy = c * dy;
-                            o[0] += u;
-                            o[1] += cdx * dx; o[2] += cdx * dy; o[3] += cdx * dz;
-                            o[4] += cdy * dy; o[5] += cdy * dz; o[6] += c * dz * dz;
-                            o[7] += 1.0;
-                        }
+                        if (OBS && lower) obs_add_central(o, u, c, dx, dy, dz);
                     }
                 }
             }
-            if (force) {
-                double4 f = force[i];
-                if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
-                force[i] = f;
-            }
+            if (force) force_row_store(force, i, accumulate, Fx, Fy, Fz);
             if (over) atomicAdd(overstretched, (unsigned long long)over);
-        } else if (force && !accumulate) {
-            double4 f = force[i];
-            f.x = 0.0; f.y = 0.0; f.z = 0.0;
-            force[i] = f;
+        } else {
+            force_row_clear(force, i, accumulate);
         }
     }
-    if (OBS) {
-#pragma unroll
-        for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
-        }
-        __syncthreads();
-        if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-    }
+    if (OBS) obs_rows_store(o, blk, rows);
 }
 void launch_bond_forces(const double4 *pos, int n, const unsigned *row_off, const uint2 *entries, const BondParam *par, int ntypes, DBox box,
                         int accumulate, double4 *force, double *rows, double *out8, unsigned long long *overstretched, hipStream_t s) {
     static_assert(sizeof(BondParam) == 2 * sizeof(pt_entry) && 2 * BOND_MAX_TYPES <= TPB, "one lane stages one 16-byte word of the parameters");
     const int nb = nblocks(n, TPB);
-    if (out8) {
-        hipLaunchKernelGGL(k_bond_forces<true>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, rows,
-                           overstretched);
-        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
-    } else {
-        hipLaunchKernelGGL(k_bond_forces<false>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, nullptr,
-                           overstretched);
-    }
+    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+        hipLaunchKernelGGL(k_bond_forces<decltype(obs)::value>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box,
+                           accumulate, force, r, overstretched);
+    });
 }
 
 // Angle forces (HOOMD's angle.harmonic and angle.cosinesq; no reference counterpart: the reference leaves forces to HOOMD).  One
@@ -3016,11 +2963,9 @@ void launch_bond_forces(const double4 *pos, int n, const unsigned *row_off, cons
 // the list and either order of an angle's ends.  harmonic: g = k (theta - theta0)/s with s = max(sqrt(1 - c^2), 1e-3) (HOOMD's floor
 // for the straight angle), the only branch that takes an acos; cosine-squared: g = -k (c - cos theta0).  An angle with r1 == 0 or
 // r2 == 0 does nothing.
-// Per-type parameters as in k_bond_forces: the type differs from lane to lane, so they are staged in LDS, 32 bytes per type
-// (k, theta0, cos theta0, kind), at most 2 KB, copied by the first lanes of each workgroup before one barrier and read as two 16-byte
-// words per angle; with one type every lane reads the same entry, which the LDS broadcasts.
-// OBS: the VERTEX thread alone adds the angle to the eight sums U, W_ab = d1_a F_i,b + d2_a F_k,b (six), count; reduction, row per
-// workgroup and k_pair_virial_finish as in k_pair_repulsion_virial.  No lane leaves before either barrier.
+// Per-type parameters (stage_type_params): (k, theta0, cos theta0, kind).
+// OBS: the VERTEX thread alone adds the angle to the eight sums U, W_ab = d1_a F_i,b + d2_a F_k,b (six), count (obs_rows_store).  No
+// lane leaves before either barrier.
 // accumulate != 0: the rows of particles in no angle are neither read nor written; accumulate == 0: every row's xyz is overwritten, w kept.
 template <bool OBS>
 __global__ void __launch_bounds__(TPB)
@@ -3028,9 +2973,7 @@ k_angle_forces(const double4 *__restrict__ pos, int n, const int *__restrict__ r
                const AngleParam *__restrict__ par, int ntypes, DBox box, int accumulate, double4 *__restrict__ force,
                double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
     __shared__ pt_entry ap[2 * ANGLE_MAX_TYPES];   // [type][0] = (k, theta0), [type][1] = (cos theta0, kind)
-    __shared__ double sh[OBS ? TPB / 64 : 1][PV_NOBS];
-    if ((int)threadIdx.x < 2 * ntypes) ap[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
-    __syncthreads();
+    stage_type_params(ap, par, ntypes);
     const int blk = xcd_block(blockIdx.x, gridDim.x);
     const int p = blk * TPB + threadIdx.x;
     double o[PV_NOBS];
@@ -3080,38 +3023,21 @@ k_angle_forces(const double4 *__restrict__ pos, int n, const int *__restrict__ r
                     }
                 }
             }
-            if (force) {
-                double4 f = force[p];
-                if (accumulate) { f.x += Fx; f.y += Fy; f.z += Fz; } else { f.x = Fx; f.y = Fy; f.z = Fz; }
-                force[p] = f;
-            }
-        } else if (force && !accumulate) {
-            double4 f = force[p];
-            f.x = 0.0; f.y = 0.0; f.z = 0.0;
-            force[p] = f;
+            if (force) force_row_store(force, p, accumulate, Fx, Fy, Fz);
+        } else {
+            force_row_clear(force, p, accumulate);
         }
     }
-    if (OBS) {
-#pragma unroll
-        for (int q = 0; q < PV_NOBS; ++q) o[q] = wave_sum(o[q]);
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < PV_NOBS; ++q) sh[threadIdx.x >> 6][q] = o[q];
-        }
-        __syncthreads();
-        if (threadIdx.x < PV_NOBS) rows[(size_t)blk * PV_NOBS + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-    }
+    if (OBS) obs_rows_store(o, blk, rows);
 }
 void launch_angle_forces(const double4 *pos, int n, const int *row_off, const uint4 *entries, const AngleParam *par, int ntypes, DBox box,
                          int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
     static_assert(sizeof(AngleParam) == 2 * sizeof(pt_entry) && 2 * ANGLE_MAX_TYPES <= TPB, "one lane stages one 16-byte word of the parameters");
     const int nb = nblocks(n, TPB);
-    if (out8) {
-        hipLaunchKernelGGL(k_angle_forces<true>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, rows);
-        hipLaunchKernelGGL(k_pair_virial_finish, dim3(1), dim3(TPB), 0, s, rows, nb, out8);
-    } else {
-        hipLaunchKernelGGL(k_angle_forces<false>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box, accumulate, force, nullptr);
-    }
+    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+        hipLaunchKernelGGL(k_angle_forces<decltype(obs)::value>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box,
+                           accumulate, force, r);
+    });
 }
 
 // K10 gpu_stokes_LinearCombination_kernel (PSEv1/Helper.cu:113-133) as the final un-sort: vel.xyz = a + b + c, keep w

@@ -72,11 +72,23 @@ def host_lanczos_sqrt_e1(alpha, beta):
     return t
 
 
-# the bond potentials of pse_bonds_create: name -> PSE_BOND_*
+def _chk_out8(out, pos):
+    """Where a pass writes its eight observables: `out`, checked, or a new tensor next to `pos` when out is None."""
+    import torch
+    if out is None:
+        return torch.empty(8, dtype=torch.float64, device=pos.device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
+            and out.is_contiguous()):
+        raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+    return out
+
+
+# the potentials of pse_bonds_create and pse_angles_create: name -> PSE_BOND_*, PSE_ANGLE_*
 BOND_KINDS = {"harmonic": 0, "fene": 1}
+ANGLE_KINDS = {"harmonic": 0, "cosinesq": 1}
 
 
-def _per_type(v, name):
+def _per_type(v):
     """A scalar or a sequence as a list (strings are scalars)."""
     import numpy as np
     if isinstance(v, str) or np.ndim(v) == 0:
@@ -84,141 +96,97 @@ def _per_type(v, name):
     return list(v)
 
 
-class BondList:
-    """Owner of a pse_bonds object: a fixed set of harmonic / FENE bonds among the rows of the caller-order arrays.  Holds a reference
-    to its engine, whose handle owns the device object."""
+def _topology_arrays(index, types, cols, name, what):
+    """The (count, cols) index array `name` of a list of `what`s ("bond" | "angle") and its optional type array, checked, as
+    contiguous uint32 arrays."""
+    import numpy as np
+    index = np.asarray(index)
+    if index.ndim != 2 or index.shape[1] != cols or index.shape[0] == 0 or not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"{name} must be a non-empty integer (n{what}s, {cols}) array of particle indices")
+    if index.min() < 0 or index.max() >= 2 ** 32:
+        raise ValueError(f"{name} holds an index outside [0, 2^32)")
+    if types is not None:
+        types = np.asarray(types)
+        if types.shape != (index.shape[0],) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0 or types.max() >= 2 ** 32:
+            raise ValueError(f"types must be an integer array in [0, 2^32) with one entry per {what}")
+        types = np.ascontiguousarray(types, dtype=np.uint32)
+    return np.ascontiguousarray(index, dtype=np.uint32), types
 
-    def __init__(self, engine, pairs, types, kinds, k, r0, n):
-        import numpy as np
-        pairs = np.asarray(pairs)
-        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0 or not np.issubdtype(pairs.dtype, np.integer):
-            raise ValueError("pairs must be a non-empty integer (nbonds, 2) array of particle indices")
-        if pairs.min() < 0 or pairs.max() >= 2 ** 32:
-            raise ValueError("pairs holds an index outside [0, 2^32)")
-        nb = pairs.shape[0]
-        if types is not None:
-            types = np.asarray(types)
-            if types.shape != (nb,) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0 or types.max() >= 2 ** 32:
-                raise ValueError("types must be a non-negative integer array with one entry per bond")
-            types = np.ascontiguousarray(types, dtype=np.uint32)
-        kinds, k, r0 = _per_type(kinds, "kinds"), _per_type(k, "k"), _per_type(r0, "r0")
-        if not (len(kinds) == len(k) == len(r0)) or not kinds:
-            raise ValueError("kinds, k and r0 must have one entry per bond type each")
-        for v in kinds:
-            if isinstance(v, str) and v not in BOND_KINDS:
-                raise ValueError(f"bond kind must be one of {sorted(BOND_KINDS)}, not {v!r}")
-        kind_a = np.array([BOND_KINDS[v] if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32)
-        k_a, r0_a = np.array(k, dtype=np.float64), np.array(r0, dtype=np.float64)
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+
+def _type_params(kinds, k, x, xname, table, what):
+    """The per-type parameters of a list of `what`s as (int32 kind codes, float64 k, float64 `xname`) arrays: scalars or sequences
+    with one entry per type each, a kind being a name of `table` or its code."""
+    import numpy as np
+    kinds, k, x = _per_type(kinds), _per_type(k), _per_type(x)
+    if not (len(kinds) == len(k) == len(x)) or not kinds:
+        raise ValueError(f"kinds, k and {xname} must have one entry per {what} type each")
+    for v in kinds:
+        if isinstance(v, str) and v not in table:
+            raise ValueError(f"{what} kind must be one of {sorted(table)}, not {v!r}")
+    return (np.array([table[v] if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32), np.array(k, dtype=np.float64),
+            np.array(x, dtype=np.float64))
+
+
+class _TopologyList:
+    """What BondList and AngleList share: the owner of a device topology among the rows of the caller-order arrays.  Holds a
+    reference to its engine, whose handle owns the device object.  A subclass names its entries (WHAT), its index array (INDEX, COLS
+    columns), its second parameter (X), its kind table and its three library functions."""
+
+    def __init__(self, engine, index, types, kinds, k, x, n):
+        index, types = _topology_arrays(index, types, self.COLS, self.INDEX, self.WHAT)
+        kind_a, k_a, x_a = _type_params(kinds, k, x, self.X, self.KINDS, self.WHAT)
         self.n = int(engine.params.n_max if n is None else n)
         if not 0 <= self.n < 2 ** 32:
             raise ValueError("n outside [0, 2^32)")
-        self.nbonds, self.engine, self._lib = nb, engine, engine._lib
-        self._b = ctypes.c_void_p()
+        self.count, self.engine, self._lib = index.shape[0], engine, engine._lib
+        self._obj = ctypes.c_void_p()
         vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        _lib.check(self._lib.pse_bonds_create(engine._h, self.n, nb, vp(pairs), vp(types), len(kind_a), vp(kind_a), vp(k_a), vp(r0_a),
-                                              ctypes.byref(self._b)))
+        _lib.check(getattr(self._lib, self.CREATE)(engine._h, self.n, self.count, vp(index), vp(types), len(kind_a), vp(kind_a), vp(k_a),
+                                                   vp(x_a), ctypes.byref(self._obj)))
 
     def forces(self, pos, force, accumulate=True, out=None, observables=True):
-        """The bonded forces on the first n rows of `pos` (pse_bond_forces), added to `force` (or stored: accumulate=False, which zeroes
-        the rows of unbonded particles), or force=None: observables only.  observables=True: returns the 8-element float64 CUDA tensor
-        U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nbonds, written to `out` when one is given (e.g. a row of a log tensor); observables=False:
-        forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
-        import torch
-        if self._b is None or not self._b.value:
-            raise ValueError("this BondList is closed")
+        """The forces of the list on the first n rows of `pos` (pse_bond_forces, pse_angle_forces), added to `force` (or stored:
+        accumulate=False, which zeroes the rows of particles in no entry), or force=None: observables only.  observables=True: returns
+        the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, count, written to `out` when one is given (e.g. a row of a
+        log tensor); observables=False: forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
+        if self._obj is None or not self._obj.value:
+            raise ValueError(f"this {type(self).__name__} is closed")
         _chk4(pos, "pos", self.n)
         if force is not None:
             _chk4(force, "force", self.n)
-        if observables:
-            if out is None:
-                out = torch.empty(8, dtype=torch.float64, device=pos.device)
-            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
-                    and out.is_contiguous()):
-                raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
-        _lib.check(self._lib.pse_bond_forces(self._b, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out) if observables else None))
-        return out if observables else None
+        out = _chk_out8(out, pos) if observables else None
+        _lib.check(getattr(self._lib, self.FORCES)(self._obj, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out)))
+        return out
+
+    def close(self):
+        o, self._obj = getattr(self, "_obj", None), None
+        if o is not None and o.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
+            getattr(self._lib, self.DESTROY)(o)
+
+    __del__ = close
+
+
+class BondList(_TopologyList):
+    """Owner of a pse_bonds object: a fixed set of harmonic / FENE bonds."""
+
+    WHAT, INDEX, COLS, X, KINDS = "bond", "pairs", 2, "r0", BOND_KINDS
+    CREATE, FORCES, DESTROY = "pse_bonds_create", "pse_bond_forces", "pse_bonds_destroy"
+    nbonds = property(lambda self: self.count)
 
     @property
     def overstretched(self):
         """FENE bonds found at r >= r0 by all calls since creation (pse_bonds_overstretched: waits for the stream)."""
         v = ctypes.c_ulonglong(0)
-        _lib.check(self._lib.pse_bonds_overstretched(self._b, ctypes.byref(v)))
+        _lib.check(self._lib.pse_bonds_overstretched(self._obj, ctypes.byref(v)))
         return int(v.value)
 
-    def close(self):
-        b, self._b = getattr(self, "_b", None), None
-        if b is not None and b.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
-            self._lib.pse_bonds_destroy(b)
 
-    __del__ = close
+class AngleList(_TopologyList):
+    """Owner of a pse_angles object: a fixed set of harmonic / cosine-squared angles (end, vertex, end)."""
 
-
-# the angle potentials of pse_angles_create: name -> PSE_ANGLE_*
-ANGLE_KINDS = {"harmonic": 0, "cosinesq": 1}
-
-
-class AngleList:
-    """Owner of a pse_angles object: a fixed set of harmonic / cosine-squared angles (end, vertex, end) among the rows of the
-    caller-order arrays.  Holds a reference to its engine, whose handle owns the device object."""
-
-    def __init__(self, engine, triples, types, kinds, k, theta0, n):
-        import numpy as np
-        triples = np.asarray(triples)
-        if triples.ndim != 2 or triples.shape[1] != 3 or triples.shape[0] == 0 or not np.issubdtype(triples.dtype, np.integer):
-            raise ValueError("triples must be a non-empty integer (nangles, 3) array of particle indices (end, vertex, end)")
-        if triples.min() < 0 or triples.max() >= 2 ** 32:
-            raise ValueError("triples holds an index outside [0, 2^32)")
-        na = triples.shape[0]
-        if types is not None:
-            types = np.asarray(types)
-            if types.shape != (na,) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0 or types.max() >= 2 ** 32:
-                raise ValueError("types must be a non-negative integer array with one entry per angle")
-            types = np.ascontiguousarray(types, dtype=np.uint32)
-        kinds, k, theta0 = _per_type(kinds, "kinds"), _per_type(k, "k"), _per_type(theta0, "theta0")
-        if not (len(kinds) == len(k) == len(theta0)) or not kinds:
-            raise ValueError("kinds, k and theta0 must have one entry per angle type each")
-        for v in kinds:
-            if isinstance(v, str) and v not in ANGLE_KINDS:
-                raise ValueError(f"angle kind must be one of {sorted(ANGLE_KINDS)}, not {v!r}")
-        kind_a = np.array([ANGLE_KINDS[v] if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32)
-        k_a, t0_a = np.array(k, dtype=np.float64), np.array(theta0, dtype=np.float64)
-        triples = np.ascontiguousarray(triples, dtype=np.uint32)
-        self.n = int(engine.params.n_max if n is None else n)
-        if not 0 <= self.n < 2 ** 32:
-            raise ValueError("n outside [0, 2^32)")
-        self.nangles, self.engine, self._lib = na, engine, engine._lib
-        self._a = ctypes.c_void_p()
-        vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        _lib.check(self._lib.pse_angles_create(engine._h, self.n, na, vp(triples), vp(types), len(kind_a), vp(kind_a), vp(k_a), vp(t0_a),
-                                               ctypes.byref(self._a)))
-
-    def forces(self, pos, force, accumulate=True, out=None, observables=True):
-        """The angle forces on the first n rows of `pos` (pse_angle_forces), added to `force` (or stored: accumulate=False, which zeroes
-        the rows of particles in no angle), or force=None: observables only.  observables=True: returns the 8-element float64 CUDA tensor
-        U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nangles, written to `out` when one is given (e.g. a row of a log tensor); observables=False:
-        forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
-        import torch
-        if self._a is None or not self._a.value:
-            raise ValueError("this AngleList is closed")
-        _chk4(pos, "pos", self.n)
-        if force is not None:
-            _chk4(force, "force", self.n)
-        if observables:
-            if out is None:
-                out = torch.empty(8, dtype=torch.float64, device=pos.device)
-            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
-                    and out.is_contiguous()):
-                raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
-        _lib.check(self._lib.pse_angle_forces(self._a, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out) if observables else None))
-        return out if observables else None
-
-    def close(self):
-        a, self._a = getattr(self, "_a", None), None
-        if a is not None and a.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
-            self._lib.pse_angles_destroy(a)
-
-    __del__ = close
+    WHAT, INDEX, COLS, X, KINDS = "angle", "triples", 3, "theta0", ANGLE_KINDS
+    CREATE, FORCES, DESTROY = "pse_angles_create", "pse_angle_forces", "pse_angles_destroy"
+    nangles = property(lambda self: self.count)
 
 
 class Engine:
@@ -388,16 +356,11 @@ class Engine:
         tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs (W_ab = sum_{i<j} d_a F_b, stress = -W / V; see include/pse_amd.h).  `force`
         may be None (observables only).  `out`: where to write them -- e.g. a row of a (samples, 8) log tensor; nothing is read
         back, the tensor is filled when the stream gets there."""
-        import torch
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
         if force is not None:
             _chk4(force, "force")
-        if out is None:
-            out = torch.empty(8, dtype=torch.float64, device=pos.device)
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
-                and out.is_contiguous()):
-            raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+        out = _chk_out8(out, pos)
         _lib.check(self._lib.pse_pair_repulsion_virial(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
                                                        1 if accumulate else 0, _ptr(out)))
         return out
@@ -418,15 +381,10 @@ class Engine:
         if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and table.dim() == 2
                 and table.shape[1] == 2 and table.is_contiguous()):
             raise ValueError("table must be a contiguous (width, 2) float64 CUDA tensor: V and F at the nodes")
-        if observables:
-            if out is None:
-                out = torch.empty(8, dtype=torch.float64, device=pos.device)
-            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
-                    and out.is_contiguous()):
-                raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
+        out = _chk_out8(out, pos) if observables else None
         _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
-                                            float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out) if observables else None))
-        return out if observables else None
+                                            float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out)))
+        return out
 
     def bonds(self, pairs, types=None, kinds=(0,), k=(1.0,), r0=(1.0,), n=None):
         """A bond topology on the device (pse_bonds_create; see include/pse_amd.h): `pairs` (nbonds, 2) particle indices into arrays of

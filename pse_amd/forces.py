@@ -2,9 +2,11 @@
 PSEv1/Stokes.cc:447; its example script has none).  SURVEY.md 8 f4: the step either side of the hot path, kept minimal."""
 import math
 
+from .engine import ANGLE_KINDS, BOND_KINDS, _per_type, _topology_arrays, _type_params
 
-class _PairProvider:
-    """What the pair providers share: the eight device doubles of the most recent fused call -- U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
+
+class _ObsProvider:
+    """What the pair, bond and angle providers share: the eight device doubles of the most recent fused call -- U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
     npairs -- where that call writes them (a row of a StressLog on a sample step, a buffer of the provider's own otherwise), and the
     host-side readers.  A subclass sets NAME (what its messages call it) and makes the call in compute()."""
 
@@ -24,14 +26,17 @@ class _PairProvider:
         m = g.members
         return s, 0 if m is None else m.data_ptr(), len(g)
 
-    def _out(self, timestep):
-        """The eight doubles the fused call of this step writes."""
+    def _fused_out(self, timestep):
+        """The eight doubles the call of this step writes, recorded as the most recent ones; None without virial=True."""
+        if not self._fused:
+            return None
         out = self.log.row(timestep) if self.log is not None else None
         if out is None:
             if self._own is None:
                 import torch
                 self._own = torch.zeros(8, dtype=torch.float64, device=self.integrator.system.pos.device)
             out = self._own
+        self._obs = out
         return out
 
     def _observables(self):
@@ -59,7 +64,7 @@ class _PairProvider:
         return -self.virial / (Lx * Ly * Lz)
 
 
-class HarmonicRepulsion(_PairProvider):
+class HarmonicRepulsion(_ObsProvider):
     """F_i = sum_j k (sigma - r)(r_i - r_j)/r for minimum-image pairs with r < sigma (sigma = 2a: contact of unit spheres).
     Evaluated on the integrator's own cell list; sigma must not exceed the hydrodynamic real-space cutoff.
 
@@ -78,13 +83,11 @@ class HarmonicRepulsion(_PairProvider):
         if not self._fused:
             self.integrator.cpp_method.pairRepulsion(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True)
             return
-        out = self._out(timestep)
         self.integrator.cpp_method.pairRepulsionVirial(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True,
-                                                       out.data_ptr())
-        self._obs = out
+                                                       self._fused_out(timestep).data_ptr())
 
 
-class TablePair(_PairProvider):
+class TablePair(_ObsProvider):
     """A tabulated central pair potential (pse_pair_table; HOOMD's pair.table for the one particle type here): `table` is a NumPy or
     torch (width, 2) array, 2 <= width <= 2048, of V and F -- the pair energy and the magnitude of the radial force, positive for a
     repulsion -- at the nodes r_k = rmin + k (rmax - rmin)/(width - 1); both are linear between the nodes.  Pairs with
@@ -121,14 +124,11 @@ class TablePair(_PairProvider):
 
     def compute(self, timestep):
         s, members, n = self._group_args()
-        out = self._out(timestep) if self._fused else None
         self.integrator.cpp_method.pairTable(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
-                                             int(self.table.shape[0]), self.rmin, self.rmax, True, 0 if out is None else out.data_ptr())
-        if out is not None:
-            self._obs = out
+                                             int(self.table.shape[0]), self.rmin, self.rmax, True, _addr(self._fused_out(timestep)))
 
 
-class Bonds(_PairProvider):
+class Bonds(_ObsProvider):
     """Harmonic and FENE bonds (pse_bond_forces; HOOMD's bond.harmonic and bond.fene): `pairs` is an (nbonds, 2) integer array of
     particle indices into the system's arrays.  kind = "harmonic": V = k/2 (r - r0)^2; "fene": V = -k/2 r0^2 ln(1 - (r/r0)^2), r < r0.
     `kind`, `k` and `r0` are scalars (one bond type) or sequences with one entry per type, and `types` then gives each bond's type
@@ -140,42 +140,16 @@ class Bonds(_PairProvider):
     `stress()`, `nbonds` and StressLog as for HarmonicRepulsion."""
 
     NAME = "Bonds"
-    KINDS = {"harmonic": 0, "fene": 1}
+    KINDS = BOND_KINDS
 
     def __init__(self, integrator, pairs, kind="harmonic", k=1.0, r0=1.0, types=None, virial=False):
-        import numpy as np
-        seq = lambda v: [v] if isinstance(v, str) or np.ndim(v) == 0 else list(v)
-        kind, k, r0 = seq(kind), seq(k), seq(r0)
-        nt = max(len(kind), len(k), len(r0))
-        kind, k, r0 = (v * nt if len(v) == 1 else v for v in (kind, k, r0))   # a scalar serves every type
-        if not len(kind) == len(k) == len(r0) == nt:
-            raise ValueError("kind, k and r0 must be scalars or sequences of one length (one entry per bond type)")
-        for v in kind:
-            if v not in self.KINDS:
-                raise ValueError(f"bond kind must be one of {sorted(self.KINDS)}, not {v!r}")
-        pairs = np.asarray(pairs)
-        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0 or not np.issubdtype(pairs.dtype, np.integer) or pairs.min() < 0:
-            raise ValueError("pairs must be a non-empty (nbonds, 2) array of non-negative integer particle indices")
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
-        if types is not None:
-            types = np.asarray(types)
-            if types.shape != (pairs.shape[0],) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
-                raise ValueError("types must be a non-negative integer array with one entry per bond")
-            types = np.ascontiguousarray(types, dtype=np.uint32)
-        self.kind, self.k, self.r0 = tuple(kind), tuple(float(v) for v in k), tuple(float(v) for v in r0)
-        kind_a = np.array([self.KINDS[v] for v in kind], dtype=np.int32)
-        k_a, r0_a = np.array(self.k, dtype=np.float64), np.array(self.r0, dtype=np.float64)
-        self._id = integrator.cpp_method.bondsCreate(integrator.system.n, pairs.shape[0], pairs.ctypes.data,
-                                                     0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, k_a.ctypes.data,
-                                                     r0_a.ctypes.data)
+        self.kind, self.k, self.r0, self._id = _topology(integrator.cpp_method.bondsCreate, integrator.system.n, pairs, "pairs", 2, types,
+                                                         kind, k, r0, "r0", self.KINDS, "bond")
         super().__init__(integrator, virial)
 
     def compute(self, timestep):
         s = self.integrator.system
-        out = self._out(timestep) if self._fused else None
-        self.integrator.cpp_method.bondForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, 0 if out is None else out.data_ptr())
-        if out is not None:
-            self._obs = out
+        self.integrator.cpp_method.bondForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, _addr(self._fused_out(timestep)))
 
     @property
     def nbonds(self):
@@ -188,7 +162,7 @@ class Bonds(_PairProvider):
         return int(self.integrator.cpp_method.bondsOverstretched(self._id))
 
 
-class Angles(_PairProvider):
+class Angles(_ObsProvider):
     """Harmonic and cosine-squared angles (pse_angle_forces; HOOMD's angle.harmonic and angle.cosinesq): `triples` is an (nangles, 3)
     integer array of particle indices into the system's arrays, (end, vertex, end).  With theta the angle at the vertex between the
     two arms, kind = "harmonic": V = k/2 (theta - theta0)^2; "cosinesq": V = k/2 (cos theta - cos theta0)^2.  `kind`, `k` and `theta0`
@@ -201,49 +175,44 @@ class Angles(_PairProvider):
     `virial`, `stress()`, `nangles` and StressLog as for HarmonicRepulsion."""
 
     NAME = "Angles"
-    KINDS = {"harmonic": 0, "cosinesq": 1}
+    KINDS = ANGLE_KINDS
 
     def __init__(self, integrator, triples, kind="harmonic", k=1.0, theta0=math.pi, types=None, virial=False):
-        import numpy as np
-        seq = lambda v: [v] if isinstance(v, str) or np.ndim(v) == 0 else list(v)
-        kind, k, theta0 = seq(kind), seq(k), seq(theta0)
-        nt = max(len(kind), len(k), len(theta0))
-        kind, k, theta0 = (v * nt if len(v) == 1 else v for v in (kind, k, theta0))   # a scalar serves every type
-        if not len(kind) == len(k) == len(theta0) == nt:
-            raise ValueError("kind, k and theta0 must be scalars or sequences of one length (one entry per angle type)")
-        for v in kind:
-            if v not in self.KINDS:
-                raise ValueError(f"angle kind must be one of {sorted(self.KINDS)}, not {v!r}")
-        triples = np.asarray(triples)
-        if (triples.ndim != 2 or triples.shape[1] != 3 or triples.shape[0] == 0 or not np.issubdtype(triples.dtype, np.integer)
-                or triples.min() < 0 or triples.max() >= 2 ** 32):
-            raise ValueError("triples must be a non-empty (nangles, 3) array of integer particle indices in [0, 2^32) (end, vertex, end)")
-        triples = np.ascontiguousarray(triples, dtype=np.uint32)
-        if types is not None:
-            types = np.asarray(types)
-            if (types.shape != (triples.shape[0],) or not np.issubdtype(types.dtype, np.integer) or types.min() < 0
-                    or types.max() >= 2 ** 32):
-                raise ValueError("types must be an integer array in [0, 2^32) with one entry per angle")
-            types = np.ascontiguousarray(types, dtype=np.uint32)
-        self.kind, self.k, self.theta0 = tuple(kind), tuple(float(v) for v in k), tuple(float(v) for v in theta0)
-        kind_a = np.array([self.KINDS[v] for v in kind], dtype=np.int32)
-        k_a, t0_a = np.array(self.k, dtype=np.float64), np.array(self.theta0, dtype=np.float64)
-        self._id = integrator.cpp_method.anglesCreate(integrator.system.n, triples.shape[0], triples.ctypes.data,
-                                                      0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, k_a.ctypes.data,
-                                                      t0_a.ctypes.data)
+        self.kind, self.k, self.theta0, self._id = _topology(integrator.cpp_method.anglesCreate, integrator.system.n, triples, "triples", 3,
+                                                             types, kind, k, theta0, "theta0", self.KINDS, "angle")
         super().__init__(integrator, virial)
 
     def compute(self, timestep):
         s = self.integrator.system
-        out = self._out(timestep) if self._fused else None
-        self.integrator.cpp_method.angleForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, 0 if out is None else out.data_ptr())
-        if out is not None:
-            self._obs = out
+        self.integrator.cpp_method.angleForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, _addr(self._fused_out(timestep)))
 
     @property
     def nangles(self):
         """The number of angles that acted at the most recent compute() (the count the pair providers call npairs)."""
         return self.npairs
+
+
+def _addr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _topology(create, n, index, name, cols, types, kind, k, x, xname, table, what):
+    """The checks and the device object of Bonds and Angles: `kind`, `k` and `x` (called `xname`) are scalars -- a scalar serves every
+    type -- or sequences of one length, a kind being a name of `table`; `index` is the (count, cols) array `name`.  Returns the three
+    per-type tuples and the id `create` gave the topology."""
+    kind, k, x = _per_type(kind), _per_type(k), _per_type(x)
+    nt = max(len(kind), len(k), len(x))
+    kind, k, x = (v * nt if len(v) == 1 else v for v in (kind, k, x))
+    if not len(kind) == len(k) == len(x) == nt:
+        raise ValueError(f"kind, k and {xname} must be scalars or sequences of one length (one entry per {what} type)")
+    for v in kind:
+        if v not in table:
+            raise ValueError(f"{what} kind must be one of {sorted(table)}, not {v!r}")
+    kind_a, k_a, x_a = _type_params(kind, k, x, xname, table, what)
+    index, types = _topology_arrays(index, types, cols, name, what)
+    tid = create(n, index.shape[0], index.ctypes.data, 0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, k_a.ctypes.data,
+                 x_a.ctypes.data)
+    return tuple(kind), tuple(k_a.tolist()), tuple(x_a.tolist()), tid
 
 
 def _sym3(w):
