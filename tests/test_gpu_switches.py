@@ -45,11 +45,15 @@ CASES = [
     ({"PSE_YSLAB_REGS": "0"}, ["test_gpu_local.py"], "velocities_match"),   # a slab rank's y pass by k_fft_cols also at Ny = 256
     # The cells are stored in blocks of b along z (x, z block, y, z in block; default b = 6 where an axis has at least twelve cells) so
     # that a wavefront's rows form a squat brick; PSE_CELL_BZ=0 is the plain (x, y, z) order.  Every near-field path (cell pass, pair
-    # list, overflow rows, kept neighbour list, pair repulsion) must give the same answers in either (the test boxes have 6-8 cells
-    # per axis: default = plain there, so b = 2 is what exercises the blocks).
-    ({"PSE_CELL_BZ": "0"}, ["test_gpu_parity.py", "test_gpu_nlist.py"], _NEAR := "mreal_matches_oracle or pair_list_overflow or brownian_velocity_matches_port "
-     "or step_integrates or pair_repulsion or reused_list or overflow_rows"),
-    ({"PSE_CELL_BZ": "2"}, ["test_gpu_parity.py", "test_gpu_nlist.py"], _NEAR),
+    # list, overflow rows, kept neighbour list, pair repulsion, pair table) must give the same answers in either.  The boxes of
+    # test_gpu_parity.py and test_gpu_nlist.py have 4-7 cells per axis: the default is the plain order there and b = 2 is what
+    # exercises the blocks; the boxes of test_gpu_cell_grids.py have 12-14 cells along z: the default is blocked there, 0 is what
+    # changes the order, 2 and 4 are other block heights (with and without a padded last block).
+    ({"PSE_CELL_BZ": "0"}, _NEAR_FILES := ["test_gpu_parity.py", "test_gpu_nlist.py", "test_gpu_cell_grids.py"],
+     _NEAR := "mreal_matches_oracle or pair_list_overflow or brownian_velocity_matches_port or step_integrates or pair_repulsion or reused_list "
+     "or overflow_rows or mreal_on_every_pass or pair_passes or two_calls_give_the_same_bits"),
+    ({"PSE_CELL_BZ": "2"}, _NEAR_FILES, _NEAR),
+    ({"PSE_CELL_BZ": "4"}, _NEAR_FILES, _NEAR),
 ]
 
 
