@@ -313,6 +313,57 @@ int pse_angles_destroy(pse_angles *a);
  * queues work on the handle's stream and reads nothing back; no floating-point atomics, bit-reproducible on equal inputs. */
 int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force /* may be NULL */,
                      int accumulate, double *out8 /* DEVICE, may be NULL */);
+
+/* ---- dihedral forces: HOOMD's dihedral.harmonic and dihedral.opls (no reference counterpart: the reference leaves forces to HOOMD) ----
+ * A pse_dihedrals object is a fixed set of ndihedrals quadruples (i, j, k, l) of four distinct particle indices into the caller-order
+ * arrays of n rows, each with one of ntypes <= 64 parameter sets (kind and four doubles).  Every difference is taken by minimum image
+ * in the handle's current box (pse_set_box), as for the bonds:
+ *   d1 = r_i - r_j,  d2 = r_k - r_j,  d3 = r_k - r_l,   m = d1 x d2,  nn = d2 x d3,  b = |d2|
+ *   phi = atan2(b (d1 . nn), m . nn)  in (-pi, pi]
+ * This is the IUPAC convention: the planar cis arrangement is phi = 0, trans is phi = pi, and i = (0,1,0), j = 0, k = (1,0,0),
+ * l = (1,0,1) has phi = +pi/2.  It is this convention whatever sign a given HOOMD version uses.  The pass takes no atan2: cos phi and
+ * sin phi are m.nn and b d1.nn over |m| |nn|, the multiple angles follow by the angle-addition recurrence.
+ *   PSE_DIHEDRAL_HARMONIC  params (k, d, mult, phi0):  V = k/2 (1 + d cos(mult phi - phi0)),  dV/dphi = -k d mult/2 sin(mult phi - phi0)
+ *   PSE_DIHEDRAL_OPLS      params (k1, k2, k3, k4):    V = 1/2 [k1 (1 + cos phi) + k2 (1 - cos 2phi) + k3 (1 + cos 3phi) + k4 (1 - cos 4phi)]
+ * Forces, with g = dV/dphi (the form without a division by sin phi):
+ *   F_i = -g b / |m|^2 m,   F_l = +g b / |nn|^2 nn,   s = d1.d2 / b^2,  t = d3.d2 / b^2
+ *   F_j = -F_i + s F_i - t F_l,   F_k = -F_l - s F_i + t F_l
+ * The four forces sum to zero; reversing a quadruple to (l, k, j, i) gives the same phi and the same forces on the same particles.
+ * A dihedral with |m|^2 == 0 or |nn|^2 == 0 -- a zero-length arm, three consecutive collinear particles -- contributes nothing and
+ * is not counted (the rule of the pair, bond and angle passes for r == 0).  Duplicate dihedrals are legal and act once each.  The
+ * minimum image is the nearest one only for arms (d1, d2, d3) shorter than half the smallest perpendicular box width: longer arms
+ * are the caller's error and are not detected.
+ * The object is stored as one row of (i, j, k, l) entries, with a parallel array of types, per particle, every dihedral in the rows
+ * of all four of its particles, oriented so that i < l and each row sorted (pse_host_dihedral_rows): forces and sums are therefore
+ * bit-identical for any order of the list and either direction a quadruple is written in.
+ * The object belongs to its handle: pse_destroy frees the dihedral objects still alive, pse_dihedrals_destroy after that is a caller
+ * error.
+ * pse_dihedrals_create returns PSE_ERR_INVALID, with a message naming the value, for: a null h, quads_host, out or parameter array,
+ * n == 0 or n > n_max, ndihedrals == 0 or ndihedrals > 2^28, an index >= n, a quadruple with two equal members, ntypes outside
+ * [1, 64], a type >= ntypes, an unknown kind, a non-finite parameter, a harmonic d that is not exactly -1 or +1, a harmonic mult that
+ * is not an integer in [1, 6].  *out is null after a refusal. */
+#define PSE_DIHEDRAL_HARMONIC 0   /* V = k/2 (1 + d cos(mult phi - phi0)) */
+#define PSE_DIHEDRAL_OPLS     1   /* V = 1/2 [k1 (1 + cos phi) + k2 (1 - cos 2phi) + k3 (1 + cos 3phi) + k4 (1 - cos 4phi)] */
+typedef struct pse_dihedrals pse_dihedrals;
+int pse_dihedrals_create(pse_handle *h, unsigned n, unsigned ndihedrals,
+                         const unsigned *quads_host /* ndihedrals x 4 particle indices: i, j, k, l */,
+                         const unsigned *types_host /* ndihedrals, or NULL: all type 0 */,
+                         int ntypes, const int *kind_host /* ntypes */, const double *params_host /* ntypes x 4 */,
+                         pse_dihedrals **out);
+int pse_dihedrals_destroy(pse_dihedrals *d);
+/* The dihedral forces of the object on the n rows of pos, and their observables.  force (n rows, or NULL: observables only):
+ * accumulate = 1 adds to .xyz of the particles that are in a dihedral, rows of the others are neither read nor written;
+ * accumulate = 0 overwrites .xyz of all n rows, with zero for particles in no dihedral; w is kept in every case.  out8 (DEVICE, 8
+ * doubles -- a row of a larger array will do -- or NULL: forces only, the reduction is not run) = U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
+ * ndihedrals with the signs of pse_pair_repulsion_virial: U = sum V, W_ab = sum (d1_a F_i,b + d2_a F_k,b + (d2 - d3)_a F_l,b) with
+ * each dihedral once, stress = -W / V, dU/d(xy) = -Wxy, ndihedrals = 1.0 per dihedral that acted.  W is symmetric and its trace is
+ * zero to rounding for both kinds (a dihedral angle does not change when everything is scaled or rotated).  force and out8 both
+ * NULL: PSE_ERR_INVALID.  The pass walks the object's rows, not the cell list: it does not sort, leaves the kept neighbour list and
+ * its counters alone, and works on a slab rank's handle too (positions are replicated there, the sums over all dihedrals are
+ * complete); owned-particle steps are not supported.  The call only queues work on the handle's stream and reads nothing back; no
+ * floating-point atomics, bit-reproducible on equal inputs. */
+int pse_dihedral_forces(pse_dihedrals *d, const pse_double4 *pos, pse_double4 *force /* may be NULL */,
+                        int accumulate, double *out8 /* DEVICE, may be NULL */);
 /* copy the three real-space grids (x-major, z fastest: idx = (x*Ny + y)*Nz + z, PSEv1/Mobility.cu:233) of the
  * most recent spread (stage 0) or inverse FFT (stage 1) to a host buffer of 3*nx_local*Ny*Nz doubles */
 int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out);
@@ -522,6 +573,18 @@ int pse_host_bond_rows(unsigned n, unsigned nbonds, const unsigned *pairs, const
  * offsets), an index >= n, an angle with two equal members. */
 int pse_host_angle_rows(unsigned n, unsigned nangles, const unsigned *triples, const unsigned *types /* or NULL */,
                         int *row_off /* n + 1 */, unsigned *entries /* 3 nangles x 4: i, j, k, type */);
+/* host-only: the per-particle rows a pse_dihedrals object stores (pse_dihedrals_create calls this after validating).  A CSR over
+ * the n particles, row p = entries row_off[p] .. row_off[p + 1) of TWO parallel sections of `entries`: the first holds one
+ * (i, j, k, l) quadruple of unsigned -- 16 bytes, entry e at entries[4 e] -- per dihedral p takes part in, the second, which starts
+ * at entries[16 ndihedrals], that entry's type at [e].  That is the 20 bytes of information per entry and no more: one aligned
+ * 16-byte load and one 4-byte load, both consecutive along a row, and no bits of an index are given up to the type.  A quadruple is
+ * stored as (l, k, j, i) where l < i, so that its first member is the smaller end; p is one of the four, which is its role.  Every
+ * dihedral appears in the rows of all four of its particles (duplicates as often as they are listed), each row sorted by
+ * (i, j, k, l, type), so the rows are a function of the dihedral SET, not of the list order or of the direction a quadruple is
+ * written in.  types == NULL: all type 0.  PSE_ERR_INVALID: a null array, n == 0, ndihedrals == 0 or > 2^28 (4 ndihedrals must fit
+ * the int offsets), an index >= n, a quadruple with two equal members. */
+int pse_host_dihedral_rows(unsigned n, unsigned ndihedrals, const unsigned *quads, const unsigned *types /* or NULL */,
+                           int *row_off /* n + 1 */, unsigned *entries /* 4 ndihedrals x 4: i, j, k, l; then 4 ndihedrals types */);
 
 #ifdef __cplusplus
 }

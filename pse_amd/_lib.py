@@ -132,6 +132,10 @@ SYMBOLS = {
     "pse_angles_destroy": (_i, [_vp]),
     "pse_angle_forces": (_i, [_vp, _vp, _vp, _i, _vp]),
     "pse_host_angle_rows": (_i, [_u, _u, _vp, _vp, _vp, _vp]),
+    "pse_dihedrals_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp]),
+    "pse_dihedrals_destroy": (_i, [_vp]),
+    "pse_dihedral_forces": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "pse_host_dihedral_rows": (_i, [_u, _u, _vp, _vp, _vp, _vp]),
     "pse_eval_realspace": (_i, [_vp, _dp, _i, _dp, _dp]),
     "pse_debug_copy_grid": (_i, [_vp, _i, _dp]),
     "pse_debug_spread": (_i, [_vp, _vp, _vp, _vp, _u]),

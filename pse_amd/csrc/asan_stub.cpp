@@ -2,7 +2,7 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, pse_bonds_*, pse_angles_*) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, pse_bonds_*, pse_angles_*, pse_dihedrals_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -24,7 +24,7 @@ struct pse_handle {
     int lz_op = PSE_LANCZOS_RECORDS16;
     std::vector<Topology *> topologies;
 };
-struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows), kept on the host
+struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows, pse_host_dihedral_rows), kept on the host
     pse_handle *h;
     std::vector<int> row_off;
     std::vector<unsigned> entries;
@@ -33,6 +33,7 @@ struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows), 
 };
 struct pse_bonds : Topology { using Topology::Topology; };
 struct pse_angles : Topology { using Topology::Topology; };
+struct pse_dihedrals : Topology { using Topology::Topology; };
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -147,6 +148,22 @@ int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, 
     if (!a) return fail(PSE_ERR_INVALID, "pse_angle_forces: null angle object");
     if (!pos) return fail(PSE_ERR_INVALID, "pse_angle_forces: null pos");
     if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_angle_forces: force and out8 are both null: nothing to compute");
+    return 0;   // pos, force and out8 are device pointers and there is no device: nothing is read or written
+}
+int pse_dihedrals_create(pse_handle *h, unsigned n, unsigned ndihedrals, const unsigned *quads_host, const unsigned *types_host, int ntypes,
+                         const int *kind_host, const double *params_host, pse_dihedrals **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null handle");
+    if (int rc = dihedrals_validate(h->par.n_max, n, ndihedrals, quads_host, types_host, ntypes, kind_host, params_host)) return rc;
+    pse_dihedrals *d = new pse_dihedrals(h, (size_t)n + 1, (size_t)ndihedrals * 20);
+    return topology_adopt(d, pse_host_dihedral_rows(n, ndihedrals, quads_host, types_host, d->row_off.data(), d->entries.data()), out);
+}
+int pse_dihedrals_destroy(pse_dihedrals *d) { return topology_destroy(d); }
+int pse_dihedral_forces(pse_dihedrals *d, const pse_double4 *pos, pse_double4 *force, int, double *out8) {
+    if (!d) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null dihedral object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: force and out8 are both null: nothing to compute");
     return 0;   // pos, force and out8 are device pointers and there is no device: nothing is read or written
 }
 

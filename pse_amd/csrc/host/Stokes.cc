@@ -25,6 +25,7 @@ void Stokes::setParams() {
     if (m_h) { pse_destroy(m_h); m_h = nullptr; }
     m_bonds.objs.clear();   // pse_destroy freed them
     m_angles.objs.clear();
+    m_dihedrals.objs.clear();
     m_m_Lanczos = 2;   // "try two Lanczos iterations to start" (PSEv1/Stokes.cc:131-132)
     pse_params p{};
     p.n_max = m_n_total;
@@ -114,6 +115,23 @@ void Stokes::angleForces(int id, const pse_double4 *pos, pse_double4 *force, boo
 void Stokes::anglesDestroy(int id) {
     check(pse_angles_destroy(m_angles.get(id)), "Stokes::anglesDestroy");
     m_angles.drop(id);
+}
+
+int Stokes::dihedralsCreate(unsigned int n, unsigned int ndihedrals, const unsigned int *quads, const unsigned int *types, int ntypes,
+                            const int *kind, const double *params) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    pse_dihedrals *d = nullptr;
+    check(pse_dihedrals_create(m_h, n, ndihedrals, quads, types, ntypes, kind, params, &d), "Stokes::dihedralsCreate");
+    return m_dihedrals.push(d);
+}
+
+void Stokes::dihedralForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8) {
+    check(pse_dihedral_forces(m_dihedrals.get(id), pos, force, accumulate ? 1 : 0, out8), "Stokes::dihedralForces");
+}
+
+void Stokes::dihedralsDestroy(int id) {
+    check(pse_dihedrals_destroy(m_dihedrals.get(id)), "Stokes::dihedralsDestroy");
+    m_dihedrals.drop(id);
 }
 
 pse_info Stokes::info() const {

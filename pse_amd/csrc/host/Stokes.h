@@ -26,7 +26,7 @@ struct ParticleArrays {
 // The objects of one kind that a Stokes made on its engine, by id -- the position in the table; null once destroyed.
 template <class T>
 struct IdTable {
-    const char *what;   // "bond", "angle": what the error calls them
+    const char *what;   // "bond", "angle", "dihedral": what the error calls them
     std::vector<T *> objs;
     int push(T *o) { objs.push_back(o); return (int)objs.size() - 1; }
     T *get(int id) const {
@@ -83,6 +83,14 @@ public:
     // force or out8 (eight DEVICE doubles: U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, nangles) may be null, not both
     void angleForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8);
     void anglesDestroy(int id);
+    // dihedral forces (pse_dihedrals_create / pse_dihedral_forces): dihedralsCreate copies the HOST arrays -- ndihedrals x 4 particle
+    // indices (i, j, k, l), ndihedrals types or null, ntypes kinds and ntypes x 4 parameters -- to the engine and returns the id the
+    // other calls take; the ids live and die as those of the bond objects do
+    int dihedralsCreate(unsigned int n, unsigned int ndihedrals, const unsigned int *quads, const unsigned int *types, int ntypes,
+                        const int *kind, const double *params);
+    // force or out8 (eight DEVICE doubles: U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, ndihedrals) may be null, not both
+    void dihedralForces(int id, const pse_double4 *pos, pse_double4 *force, bool accumulate, double *out8);
+    void dihedralsDestroy(int id);
     pse_info info() const;
     int lanczosIterations() const { return m_m_Lanczos; }
     unsigned int hashedSeed() const { return m_seed; }
@@ -102,6 +110,7 @@ private:
     pse_handle *m_h = nullptr;
     IdTable<pse_bonds> m_bonds{"bond"};
     IdTable<pse_angles> m_angles{"angle"};
+    IdTable<pse_dihedrals> m_dihedrals{"dihedral"};
 };
 
 }  // namespace pse_host

@@ -100,6 +100,16 @@ PYBIND11_MODULE(_PSEv1, m) {
             s.angleForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
         })
         .def("anglesDestroy", &Stokes::anglesDestroy)
+        // ndihedrals x 4 uint32 (i, j, k, l), ndihedrals uint32 or 0, ntypes int32, ntypes x 4 float64
+        .def("dihedralsCreate", [](Stokes &s, unsigned int n, unsigned int ndihedrals, std::uintptr_t quads, std::uintptr_t types, int ntypes,
+                                   std::uintptr_t kind, std::uintptr_t params) {
+            return s.dihedralsCreate(n, ndihedrals, ptr<const unsigned int>(quads), ptr<const unsigned int>(types), ntypes, ptr<const int>(kind),
+                                     ptr<const double>(params));
+        })
+        .def("dihedralForces", [](Stokes &s, int id, std::uintptr_t pos, std::uintptr_t force, bool accumulate, std::uintptr_t out8) {
+            s.dihedralForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
+        })
+        .def("dihedralsDestroy", &Stokes::dihedralsDestroy)
         .def("lanczosIterations", &Stokes::lanczosIterations)
         .def("hashedSeed", &Stokes::hashedSeed)
         .def("info", [](const Stokes &s) {

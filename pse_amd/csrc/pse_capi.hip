@@ -111,7 +111,7 @@ struct pse_handle {
     size_t sort_tmp_bytes = 0;
     int *cell_off = nullptr;
     double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
-    std::vector<Topology *> topologies;   // the bond and angle objects created on this handle and still alive (pse_destroy frees them)
+    std::vector<Topology *> topologies;   // the bond, angle and dihedral objects created on this handle and still alive (pse_destroy frees them)
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
@@ -399,15 +399,16 @@ static int collect_times(pse_handle *h, unsigned mask) {
     return 0;
 }
 
-// A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows or pse_host_angle_rows, the per-type parameters
+// A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
 // and, for bonds, the counter of overstretched FENE bonds.  Owned by its handle; the destructor frees the device arrays.
 struct Topology {
     pse_handle *h = nullptr;
-    unsigned n = 0, count = 0;              // particles; bonds or angles
+    unsigned n = 0, count = 0;              // particles; bonds, angles or dihedrals
     int ntypes = 0;
     void *row_off = nullptr;                // n + 1 (bonds: unsigned, angles: int)
-    void *entries = nullptr;                // bonds: 2 count x uint2 (partner, type); angles: 3 count x uint4 (i, j, k, type), j the vertex, i < k
-    void *par = nullptr;                    // ntypes x BondParam or AngleParam
+    void *entries = nullptr;                // bonds: 2 count x uint2 (partner, type); angles: 3 count x uint4 (i, j, k, type), j the vertex, i < k;
+                                            // dihedrals: 4 count x uint4 (i, j, k, l), i < l, then 4 count x unsigned types
+    void *par = nullptr;                    // ntypes x BondParam, AngleParam or DihedralParam
     unsigned long long *over = nullptr;     // bonds: FENE bonds seen at r >= r0 since creation
     virtual ~Topology() {
         void *ptrs[] = {row_off, entries, par, over};
@@ -416,6 +417,7 @@ struct Topology {
 };
 struct pse_bonds : Topology {};
 struct pse_angles : Topology {};
+struct pse_dihedrals : Topology {};
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
@@ -2594,12 +2596,11 @@ extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4
 }
 
 // ---- bonded forces and angle forces (include/pse_amd.h) ------------------------------------------------------------------------
-// The device copy of a topology: the host rows `off` and `ent`, ntypes 32-byte parameter sets and, with `counter`, a zeroed counter.
-// `what` is "bonds" or "angles".
+// The device copy of a topology: the host rows `off` and `ent`, the par_bytes of the ntypes parameter sets and, with `counter`, a
+// zeroed counter.  `what` is "bonds", "angles" or "dihedrals".
 template <class T>
 static int topology_create(pse_handle *h, const char *what, unsigned n, unsigned count, int ntypes, const std::vector<int> &off,
-                           const std::vector<unsigned> &ent, const void *par, bool counter, T **out) {
-    static_assert(sizeof(BondParam) == sizeof(AngleParam), "one parameter set of either kind is 32 bytes");
+                           const std::vector<unsigned> &ent, const void *par, size_t par_bytes, bool counter, T **out) {
     T *t = new T();
     t->h = h; t->n = n; t->count = count; t->ntypes = ntypes;
     auto put = [](void **dst, const void *src, size_t bytes) -> hipError_t {
@@ -2609,7 +2610,7 @@ static int topology_create(pse_handle *h, const char *what, unsigned n, unsigned
     };
     hipError_t e = put(&t->row_off, off.data(), off.size() * sizeof(int));
     if (e == hipSuccess) e = put(&t->entries, ent.data(), ent.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = put(&t->par, par, (size_t)ntypes * sizeof(BondParam));
+    if (e == hipSuccess) e = put(&t->par, par, par_bytes);
     if (e == hipSuccess && counter) e = put((void **)&t->over, nullptr, sizeof(unsigned long long));
     if (e == hipSuccess && counter) e = hipDeviceSynchronize();   // (the memset is the one call above that may return early)
     if (e != hipSuccess) {
@@ -2643,7 +2644,7 @@ extern "C" int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, cons
     std::vector<BondParam> par((size_t)ntypes);
     for (int t = 0; t < ntypes; ++t)
         par[t] = BondParam{k_host[t], r0_host[t], r0_host[t] > 0.0 ? 1.0 / (r0_host[t] * r0_host[t]) : 0.0, (double)kind_host[t]};
-    return topology_create(h, "bonds", n, nbonds, ntypes, off, ent, par.data(), true, out);
+    return topology_create(h, "bonds", n, nbonds, ntypes, off, ent, par.data(), par.size() * sizeof(BondParam), true, out);
 }
 extern "C" int pse_bonds_destroy(pse_bonds *b) { return topology_destroy(b); }
 
@@ -2681,7 +2682,7 @@ extern "C" int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, co
     TRY(pse_host_angle_rows(n, nangles, triples_host, types_host, off.data(), ent.data()));
     std::vector<AngleParam> par((size_t)ntypes);
     for (int t = 0; t < ntypes; ++t) par[t] = AngleParam{k_host[t], theta0_host[t], std::cos(theta0_host[t]), (double)kind_host[t]};
-    return topology_create(h, "angles", n, nangles, ntypes, off, ent, par.data(), false, out);
+    return topology_create(h, "angles", n, nangles, ntypes, off, ent, par.data(), par.size() * sizeof(AngleParam), false, out);
 }
 extern "C" int pse_angles_destroy(pse_angles *a) { return topology_destroy(a); }
 
@@ -2694,6 +2695,41 @@ extern "C" int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_doubl
     HIPCHK(hipSetDevice(h->device));
     launch_angle_forces((const double4 *)pos, (int)a->n, (const int *)a->row_off, (const uint4 *)a->entries, (const AngleParam *)a->par,
                         a->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pse_dihedrals_create(pse_handle *h, unsigned n, unsigned ndihedrals, const unsigned *quads_host, const unsigned *types_host,
+                                    int ntypes, const int *kind_host, const double *params_host, pse_dihedrals **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null handle");
+    TRY(dihedrals_validate((unsigned)h->n_max, n, ndihedrals, quads_host, types_host, ntypes, kind_host, params_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)ndihedrals * 20);
+    TRY(pse_host_dihedral_rows(n, ndihedrals, quads_host, types_host, off.data(), ent.data()));
+    std::vector<DihedralParam> par((size_t)ntypes);
+    for (int t = 0; t < ntypes; ++t) {
+        const double *p = params_host + 4 * (size_t)t;
+        // (d = +-1: the products with it are exact; mult >= 1 marks the harmonic kind, 0 the OPLS kind)
+        if (kind_host[t] == PSE_DIHEDRAL_HARMONIC) par[t] = DihedralParam{0.5 * p[0], p[1] * std::cos(p[3]), p[1] * std::sin(p[3]), 0.0, p[2], 0.0};
+        else par[t] = DihedralParam{p[0], p[1], p[2], p[3], 0.0, 0.0};
+    }
+    return topology_create(h, "dihedrals", n, ndihedrals, ntypes, off, ent, par.data(), par.size() * sizeof(DihedralParam), false, out);
+}
+extern "C" int pse_dihedrals_destroy(pse_dihedrals *d) { return topology_destroy(d); }
+
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_dihedral_forces(pse_dihedrals *d, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
+    if (!d) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null dihedral object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: force and out8 are both null: nothing to compute");
+    pse_handle *h = d->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_dihedral_forces((const double4 *)pos, (int)d->n, (const int *)d->row_off, (const uint4 *)d->entries,
+                           (const unsigned *)d->entries + 16 * (size_t)d->count, (const DihedralParam *)d->par, d->ntypes, h->dbox, accumulate,
+                           (double4 *)force, h->pv_rows, out8, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -32,5 +32,8 @@ int bonds_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *
 // the same for pse_angles_create
 int angles_validate(unsigned n_max, unsigned n, unsigned nangles, const unsigned *triples, const unsigned *types, int ntypes,
                     const int *kind, const double *k, const double *theta0);
+// the same for pse_dihedrals_create (params: ntypes x 4)
+int dihedrals_validate(unsigned n_max, unsigned n, unsigned ndihedrals, const unsigned *quads, const unsigned *types, int ntypes,
+                       const int *kind, const double *params);
 
 }  // namespace pse

@@ -13,6 +13,7 @@ constexpr int RS_PER_UNIT = 8;      // intervals of width 1/8 (in units of the p
 constexpr int PAIR_TABLE_MAX_WIDTH = 2048;   // entries of a pair table (pse_pair_table): staged in 32 KB of LDS
 constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS
 constexpr int ANGLE_MAX_TYPES = 64;  // parameter sets of an angle object (pse_angles_create): staged in 2 KB of LDS
+constexpr int DIHEDRAL_MAX_TYPES = 64;   // parameter sets of a dihedral object (pse_dihedrals_create): staged in 3 KB of LDS
 
 struct Box {
     double Lx, Ly, Lz, xy;

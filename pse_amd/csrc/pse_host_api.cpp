@@ -138,6 +138,39 @@ int angles_validate(unsigned n_max, unsigned n, unsigned nangles, const unsigned
     return 0;
 }
 
+int dihedrals_validate(unsigned n_max, unsigned n, unsigned ndihedrals, const unsigned *quads, const unsigned *types, int ntypes,
+                       const int *kind, const double *params) {
+    if (!quads) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null quads_host");
+    if (!kind || !params) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null parameter array (kind_host, params_host)");
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: n = %u outside (0, n_max = %u]", n, n_max);
+    if (ndihedrals == 0 || ndihedrals > (1u << 28))
+        return fail(PSE_ERR_INVALID, "pse_dihedrals_create: ndihedrals = %u outside (0, 2^28]", ndihedrals);
+    if (ntypes < 1 || ntypes > DIHEDRAL_MAX_TYPES)
+        return fail(PSE_ERR_INVALID, "pse_dihedrals_create: ntypes = %d outside [1, %d]", ntypes, DIHEDRAL_MAX_TYPES);
+    for (int t = 0; t < ntypes; ++t) {
+        const double *p = params + 4 * (size_t)t;
+        if (kind[t] != PSE_DIHEDRAL_HARMONIC && kind[t] != PSE_DIHEDRAL_OPLS)
+            return fail(PSE_ERR_INVALID, "pse_dihedrals_create: type %d has kind %d, neither PSE_DIHEDRAL_HARMONIC nor PSE_DIHEDRAL_OPLS", t, kind[t]);
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]))
+            return fail(PSE_ERR_INVALID, "pse_dihedrals_create: type %d has params = (%g, %g, %g, %g): all four must be finite", t, p[0], p[1], p[2], p[3]);
+        if (kind[t] == PSE_DIHEDRAL_HARMONIC) {
+            if (p[1] != -1.0 && p[1] != 1.0) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: harmonic type %d has d = %g, neither -1 nor +1", t, p[1]);
+            if (p[2] != std::floor(p[2]) || p[2] < 1.0 || p[2] > 6.0)
+                return fail(PSE_ERR_INVALID, "pse_dihedrals_create: harmonic type %d has mult = %g, not an integer in [1, 6]", t, p[2]);
+        }
+    }
+    for (unsigned a = 0; a < ndihedrals; ++a) {
+        const unsigned *q = quads + 4 * (size_t)a;
+        if (q[0] >= n || q[1] >= n || q[2] >= n || q[3] >= n)
+            return fail(PSE_ERR_INVALID, "pse_dihedrals_create: dihedral %u = (%u, %u, %u, %u) has an index >= n = %u", a, q[0], q[1], q[2], q[3], n);
+        if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
+            return fail(PSE_ERR_INVALID, "pse_dihedrals_create: dihedral %u = (%u, %u, %u, %u) has two equal members", a, q[0], q[1], q[2], q[3]);
+        if (types && types[a] >= (unsigned)ntypes)
+            return fail(PSE_ERR_INVALID, "pse_dihedrals_create: dihedral %u has type %u >= ntypes = %d", a, types[a], ntypes);
+    }
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -223,5 +256,50 @@ extern "C" int pse_host_angle_rows(unsigned n, unsigned nangles, const unsigned 
             if (a.k != b.k) return a.k < b.k;
             return a.type < b.type;
         });
+    return 0;
+}
+
+// Counting sort of the 4 ndihedrals memberships by particle, then each row sorted by the canonical (i, j, k, l, type), i < l.  The
+// rows are written as two sections: 4 ndihedrals x (i, j, k, l), then the 4 ndihedrals types in the same order.
+extern "C" int pse_host_dihedral_rows(unsigned n, unsigned ndihedrals, const unsigned *quads, const unsigned *types, int *row_off,
+                                      unsigned *entries) {
+    if (!quads || !row_off || !entries) return fail(PSE_ERR_INVALID, "pse_host_dihedral_rows: null array");
+    if (n == 0) return fail(PSE_ERR_INVALID, "pse_host_dihedral_rows: n = 0");
+    if (ndihedrals == 0 || ndihedrals > (1u << 28))
+        return fail(PSE_ERR_INVALID, "pse_host_dihedral_rows: ndihedrals = %u outside (0, 2^28]", ndihedrals);
+    for (unsigned a = 0; a < ndihedrals; ++a) {
+        const unsigned *q = quads + 4 * (size_t)a;
+        if (q[0] >= n || q[1] >= n || q[2] >= n || q[3] >= n)
+            return fail(PSE_ERR_INVALID, "pse_host_dihedral_rows: dihedral %u = (%u, %u, %u, %u) has an index >= n = %u", a, q[0], q[1], q[2], q[3], n);
+        if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
+            return fail(PSE_ERR_INVALID, "pse_host_dihedral_rows: dihedral %u = (%u, %u, %u, %u) has two equal members", a, q[0], q[1], q[2], q[3]);
+    }
+    std::fill(row_off, row_off + (size_t)n + 1, 0);   // (4 ndihedrals <= 2^30 < 2^31)
+    for (size_t m = 0; m < 4 * (size_t)ndihedrals; ++m) ++row_off[quads[m] + 1];
+    for (unsigned p = 0; p < n; ++p) row_off[p + 1] += row_off[p];
+    std::vector<int> fill(row_off, row_off + n);
+    struct Entry { unsigned i, j, k, l, type; };
+    std::vector<Entry> e(4 * (size_t)ndihedrals);
+    for (unsigned a = 0; a < ndihedrals; ++a) {
+        const unsigned *q = quads + 4 * (size_t)a, t = types ? types[a] : 0u;
+        const Entry en = q[3] < q[0] ? Entry{q[3], q[2], q[1], q[0], t} : Entry{q[0], q[1], q[2], q[3], t};
+        e[fill[en.i]++] = en;
+        e[fill[en.j]++] = en;
+        e[fill[en.k]++] = en;
+        e[fill[en.l]++] = en;
+    }
+    for (unsigned p = 0; p < n; ++p)
+        std::sort(e.begin() + row_off[p], e.begin() + row_off[p + 1], [](const Entry &a, const Entry &b) {
+            if (a.i != b.i) return a.i < b.i;
+            if (a.j != b.j) return a.j < b.j;
+            if (a.k != b.k) return a.k < b.k;
+            if (a.l != b.l) return a.l < b.l;
+            return a.type < b.type;
+        });
+    unsigned *ty = entries + 16 * (size_t)ndihedrals;
+    for (size_t m = 0; m < e.size(); ++m) {
+        entries[4 * m] = e[m].i; entries[4 * m + 1] = e[m].j; entries[4 * m + 2] = e[m].k; entries[4 * m + 3] = e[m].l;
+        ty[m] = e[m].type;
+    }
     return 0;
 }

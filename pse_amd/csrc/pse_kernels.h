@@ -380,5 +380,18 @@ struct AngleParam {   // 32 bytes, staged in LDS as two 16-byte words (the devic
 };
 void launch_angle_forces(const double4 *pos, int n, const int *row_off, const uint4 *entries, const AngleParam *par, int ntypes, DBox box,
                          int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
+// dihedral forces (k_dihedral_forces): one row of (i, j, k, l) entries per particle of the caller-order arrays, row p =
+// entries[row_off[p] .. row_off[p + 1]), i < l, sorted, and types[e] the type of entry e (the two sections pse_host_dihedral_rows
+// writes: 16 + 4 bytes per entry); par = ntypes <= DIHEDRAL_MAX_TYPES parameter sets.  out8 != null: the eight observables through
+// `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.
+struct DihedralParam {   // 48 bytes, staged in LDS as three 16-byte words (the device array is a hipMalloc of its own: aligned)
+    double p0, p1;   // harmonic: k/2, d cos(phi0);  OPLS: k1, k2
+    double p2, p3;   // harmonic: d sin(phi0), 0;    OPLS: k3, k4
+    double mult;     // harmonic: the multiplicity 1..6 as a double;  OPLS: 0, which is how the kernel tells the kinds apart
+    double pad;
+};
+void launch_dihedral_forces(const double4 *pos, int n, const int *row_off, const uint4 *entries, const unsigned *types,
+                            const DihedralParam *par, int ntypes, DBox box, int accumulate, double4 *force, double *rows, double *out8,
+                            hipStream_t s);
 
 }  // namespace pse

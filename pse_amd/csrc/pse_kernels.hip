@@ -2723,8 +2723,8 @@ __device__ __forceinline__ void obs_rows_store(double (&o)[PV_NOBS], int blk, do
 // they are staged in LDS instead, 32 bytes per type, at most 2 KB, copied by the first 2 ntypes lanes of each workgroup before one
 // barrier, and read as two 16-byte words per entry.  In the common case of one type every lane reads the same word, which the LDS
 // broadcasts.  EVERY lane must arrive here.
-__device__ __forceinline__ void stage_type_params(pt_entry *dst, const void *__restrict__ par, int ntypes) {
-    if ((int)threadIdx.x < 2 * ntypes) dst[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
+__device__ __forceinline__ void stage_type_params(pt_entry *dst, const void *__restrict__ par, int ntypes, int words = 2) {
+    if ((int)threadIdx.x < words * ntypes) dst[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
     __syncthreads();
 }
 
@@ -3037,6 +3037,122 @@ void launch_angle_forces(const double4 *pos, int n, const int *row_off, const ui
     launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
         hipLaunchKernelGGL(k_angle_forces<decltype(obs)::value>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, par, ntypes, box,
                            accumulate, force, r);
+    });
+}
+
+// Dihedral forces (HOOMD's dihedral.harmonic and dihedral.opls; no reference counterpart: the reference leaves forces to HOOMD).
+// One thread per particle of the CALLER-order arrays walks its row of the dihedral object -- entries (i, j, k, l), i < l, one 16-byte
+// load each, and the entry's type from the parallel array, sorted by (i, j, k, l, type) on the host.  The thread loads all four
+// positions from memory, its own included, and evaluates, by minimum image,
+//   d1 = r_i - r_j, d2 = r_k - r_j, d3 = r_k - r_l,  m = d1 x d2, nn = d2 x d3, b = |d2|,
+//   cos phi = m.nn / (|m| |nn|),  sin phi = b d1.nn / (|m| |nn|)   (phi = atan2(b d1.nn, m.nn): cis 0, trans pi; no atan2 is taken),
+//   g = dV/dphi,  F_i = -g b/|m|^2 m,  F_l = g b/|nn|^2 nn,  s = d1.d2/b^2, t = d3.d2/b^2,
+//   F_j = -F_i + s F_i - t F_l,  F_k = -F_l - s F_i + t F_l
+// in this CANONICAL order whatever its own role is, then takes the force of its role: the four threads of a dihedral run the same
+// arithmetic on the same numbers and hold bit-identical forces.  Each thread owns its force row: no atomics on forces, and the order
+// of the sum is the order of the row, a function of the dihedral SET -- forces and sums are bit-identical for any permutation of the
+// list and either direction of a quadruple.  cos and sin of the multiples of phi come from the angle-addition recurrence:
+// harmonic: (cm, sm) of mult phi by mult - 1 rotations, V = kh (1 + cd cm + sd sm), g = kh mult (sd cm - cd sm) with kh = k/2,
+// (cd, sd) = d (cos phi0, sin phi0); OPLS: the double-angle forms for 2 phi, 4 phi and one rotation for 3 phi.
+// A dihedral with |m|^2 == 0 or |nn|^2 == 0 does nothing.
+// Per-type parameters (stage_type_params, three words): harmonic (kh, cd), (sd, unused), (mult, 0); OPLS (k1, k2), (k3, k4), (0, 0):
+// mult == 0 is the OPLS kind.
+// OBS: the thread of j alone adds the dihedral to the eight sums U, W_ab = d1_a F_i,b + d2_a F_k,b + (d2 - d3)_a F_l,b (six), count
+// (obs_rows_store).  No lane leaves before either barrier.
+// accumulate != 0: the rows of particles in no dihedral are neither read nor written; accumulate == 0: every row's xyz is overwritten, w kept.
+template <bool OBS>
+__global__ void __launch_bounds__(TPB)
+k_dihedral_forces(const double4 *__restrict__ pos, int n, const int *__restrict__ row_off, const uint4 *__restrict__ entries,
+                  const unsigned *__restrict__ types, const DihedralParam *__restrict__ par, int ntypes, DBox box, int accumulate,
+                  double4 *__restrict__ force, double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
+    __shared__ pt_entry dp[3 * DIHEDRAL_MAX_TYPES];
+    stage_type_params(dp, par, ntypes, 3);
+    const int blk = xcd_block(blockIdx.x, gridDim.x);
+    const int p = blk * TPB + threadIdx.x;
+    double o[PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = 0.0;
+    if (p < n) {
+        const int eb = row_off[p], ee = row_off[p + 1];
+        if (ee > eb) {
+            double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+            for (int e = eb; e < ee; ++e) {
+                const uint4 en = entries[e];                  // x = i, y = j, z = k, w = l
+                const unsigned ty = types[e];
+                const double4 pi = pos[en.x], pj = pos[en.y], pk = pos[en.z], pl = pos[en.w];
+                double d1x = pi.x - pj.x, d1y = pi.y - pj.y, d1z = pi.z - pj.z;
+                double d2x = pk.x - pj.x, d2y = pk.y - pj.y, d2z = pk.z - pj.z;
+                double d3x = pk.x - pl.x, d3y = pk.y - pl.y, d3z = pk.z - pl.z;
+                min_image(box, d1x, d1y, d1z);
+                min_image(box, d2x, d2y, d2z);
+                min_image(box, d3x, d3y, d3z);
+                const double mx = d1y * d2z - d1z * d2y, my = d1z * d2x - d1x * d2z, mz = d1x * d2y - d1y * d2x;
+                const double nx = d2y * d3z - d2z * d3y, ny = d2z * d3x - d2x * d3z, nz = d2x * d3y - d2y * d3x;
+                const double m2 = mx * mx + my * my + mz * mz, n2 = nx * nx + ny * ny + nz * nz;
+                if (m2 > 0.0 && n2 > 0.0) {
+                    const double b2 = d2x * d2x + d2y * d2y + d2z * d2z, b = sqrt(b2);
+                    const double inv = 1.0 / sqrt(m2 * n2);
+                    const double c = (mx * nx + my * ny + mz * nz) * inv;
+                    const double sn = b * (d1x * nx + d1y * ny + d1z * nz) * inv;
+                    const pt_entry a0 = dp[3 * ty], a1 = dp[3 * ty + 1], a2 = dp[3 * ty + 2];
+                    double g, u;
+                    if (a2.x != 0.0) {                         // harmonic: a0 = (kh, cd), a1.x = sd, a2.x = mult
+                        double cm = c, sm = sn;
+                        const int mult = (int)a2.x;
+                        for (int q = 1; q < mult; ++q) {
+                            const double t = cm * c - sm * sn;
+                            sm = sm * c + cm * sn;
+                            cm = t;
+                        }
+                        u = a0.x * (1.0 + a0.y * cm + a1.x * sm);
+                        g = a0.x * a2.x * (a1.x * cm - a0.y * sm);
+                    } else {                                   // OPLS: a0 = (k1, k2), a1 = (k3, k4)
+                        const double c2 = 2.0 * c * c - 1.0, s2 = 2.0 * sn * c;
+                        const double c3 = c2 * c - s2 * sn, s3 = s2 * c + c2 * sn;
+                        const double c4 = 2.0 * c2 * c2 - 1.0, s4 = 2.0 * s2 * c2;
+                        u = 0.5 * (a0.x * (1.0 + c) + a0.y * (1.0 - c2) + a1.x * (1.0 + c3) + a1.y * (1.0 - c4));
+                        g = 0.5 * (-a0.x * sn + 2.0 * a0.y * s2 - 3.0 * a1.x * s3 + 4.0 * a1.y * s4);
+                    }
+                    const double gi = -g * b / m2, gl = g * b / n2;
+                    const double Fix = gi * mx, Fiy = gi * my, Fiz = gi * mz;
+                    const double Flx = gl * nx, Fly = gl * ny, Flz = gl * nz;
+                    const double ib2 = 1.0 / b2;
+                    const double s = (d1x * d2x + d1y * d2y + d1z * d2z) * ib2, t = (d3x * d2x + d3y * d2y + d3z * d2z) * ib2;
+                    const double Sx = s * Fix - t * Flx, Sy = s * Fiy - t * Fly, Sz = s * Fiz - t * Flz;   // F_j = S - F_i, F_k = -S - F_l
+                    if ((unsigned)p == en.y) {                 // j
+                        Fx += Sx - Fix; Fy += Sy - Fiy; Fz += Sz - Fiz;
+                        if (OBS) {
+                            const double Fkx = -Sx - Flx, Fky = -Sy - Fly, Fkz = -Sz - Flz;
+                            const double ex = d2x - d3x, ey = d2y - d3y, ez = d2z - d3z;   // r_l - r_j
+                            o[0] += u;
+                            o[1] += d1x * Fix + d2x * Fkx + ex * Flx; o[2] += d1x * Fiy + d2x * Fky + ex * Fly;
+                            o[3] += d1x * Fiz + d2x * Fkz + ex * Flz; o[4] += d1y * Fiy + d2y * Fky + ey * Fly;
+                            o[5] += d1y * Fiz + d2y * Fkz + ey * Flz; o[6] += d1z * Fiz + d2z * Fkz + ez * Flz;
+                            o[7] += 1.0;
+                        }
+                    } else if ((unsigned)p == en.z) {          // k
+                        Fx -= Sx + Flx; Fy -= Sy + Fly; Fz -= Sz + Flz;
+                    } else {
+                        const bool first = (unsigned)p == en.x;
+                        Fx += first ? Fix : Flx; Fy += first ? Fiy : Fly; Fz += first ? Fiz : Flz;
+                    }
+                }
+            }
+            if (force) force_row_store(force, p, accumulate, Fx, Fy, Fz);
+        } else {
+            force_row_clear(force, p, accumulate);
+        }
+    }
+    if (OBS) obs_rows_store(o, blk, rows);
+}
+void launch_dihedral_forces(const double4 *pos, int n, const int *row_off, const uint4 *entries, const unsigned *types,
+                            const DihedralParam *par, int ntypes, DBox box, int accumulate, double4 *force, double *rows, double *out8,
+                            hipStream_t s) {
+    static_assert(sizeof(DihedralParam) == 3 * sizeof(pt_entry) && 3 * DIHEDRAL_MAX_TYPES <= TPB, "one lane stages one 16-byte word of the parameters");
+    const int nb = nblocks(n, TPB);
+    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+        hipLaunchKernelGGL(k_dihedral_forces<decltype(obs)::value>, dim3(nb), dim3(TPB), 0, s, pos, n, row_off, entries, types, par, ntypes,
+                           box, accumulate, force, r);
     });
 }
 

@@ -83,9 +83,10 @@ def _chk_out8(out, pos):
     return out
 
 
-# the potentials of pse_bonds_create and pse_angles_create: name -> PSE_BOND_*, PSE_ANGLE_*
+# the potentials of pse_bonds_create, pse_angles_create and pse_dihedrals_create: name -> PSE_BOND_*, PSE_ANGLE_*, PSE_DIHEDRAL_*
 BOND_KINDS = {"harmonic": 0, "fene": 1}
 ANGLE_KINDS = {"harmonic": 0, "cosinesq": 1}
+DIHEDRAL_KINDS = {"harmonic": 0, "opls": 1}
 
 
 def _per_type(v):
@@ -97,7 +98,7 @@ def _per_type(v):
 
 
 def _topology_arrays(index, types, cols, name, what):
-    """The (count, cols) index array `name` of a list of `what`s ("bond" | "angle") and its optional type array, checked, as
+    """The (count, cols) index array `name` of a list of `what`s ("bond" | "angle" | "dihedral") and its optional type array, checked, as
     contiguous uint32 arrays."""
     import numpy as np
     index = np.asarray(index)
@@ -113,39 +114,51 @@ def _topology_arrays(index, types, cols, name, what):
     return np.ascontiguousarray(index, dtype=np.uint32), types
 
 
-def _type_params(kinds, k, x, xname, table, what):
+def _type_params(kinds, k, x, xname, table, what, width=None):
     """The per-type parameters of a list of `what`s as (int32 kind codes, float64 k, float64 `xname`) arrays: scalars or sequences
-    with one entry per type each, a kind being a name of `table` or its code."""
+    with one entry per type each, a kind being a name of `table` or its code.  width = w: a type has w parameters and not two: `k`
+    holds them, one w-tuple or one per type, `x` is not used, and the result is (kind codes, (ntypes, w) float64 array, None)."""
     import numpy as np
-    kinds, k, x = _per_type(kinds), _per_type(k), _per_type(x)
-    if not (len(kinds) == len(k) == len(x)) or not kinds:
-        raise ValueError(f"kinds, k and {xname} must have one entry per {what} type each")
+    if width is not None:
+        kinds, p = _per_type(kinds), np.array(k, dtype=np.float64)
+        p = p[None] if p.ndim == 1 else p
+        if p.ndim != 2 or p.shape[1] != width or len(kinds) != p.shape[0] or not kinds:
+            raise ValueError(f"kinds and {xname} must have one entry and one {width}-tuple per {what} type")
+        k, x = np.ascontiguousarray(p), None
+    else:
+        kinds, k, x = _per_type(kinds), _per_type(k), _per_type(x)
+        if not (len(kinds) == len(k) == len(x)) or not kinds:
+            raise ValueError(f"kinds, k and {xname} must have one entry per {what} type each")
     for v in kinds:
         if isinstance(v, str) and v not in table:
             raise ValueError(f"{what} kind must be one of {sorted(table)}, not {v!r}")
     return (np.array([table[v] if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32), np.array(k, dtype=np.float64),
-            np.array(x, dtype=np.float64))
+            None if x is None else np.array(x, dtype=np.float64))
 
 
 class _TopologyList:
-    """What BondList and AngleList share: the owner of a device topology among the rows of the caller-order arrays.  Holds a
-    reference to its engine, whose handle owns the device object.  A subclass names its entries (WHAT), its index array (INDEX, COLS
-    columns), its second parameter (X), its kind table and its three library functions."""
+    """What BondList, AngleList and DihedralList share: the owner of a device topology among the rows of the caller-order arrays.
+    Holds a reference to its engine, whose handle owns the device object.  A subclass names its entries (WHAT), its index array
+    (INDEX, COLS columns), its second parameter (X) -- or, with WIDTH parameters per type, the one array of them -- its kind table and
+    its three library functions."""
+
+    WIDTH = None
 
     def __init__(self, engine, index, types, kinds, k, x, n):
         index, types = _topology_arrays(index, types, self.COLS, self.INDEX, self.WHAT)
-        kind_a, k_a, x_a = _type_params(kinds, k, x, self.X, self.KINDS, self.WHAT)
+        kind_a, k_a, x_a = _type_params(kinds, k, x, self.X, self.KINDS, self.WHAT, self.WIDTH)
         self.n = int(engine.params.n_max if n is None else n)
         if not 0 <= self.n < 2 ** 32:
             raise ValueError("n outside [0, 2^32)")
         self.count, self.engine, self._lib = index.shape[0], engine, engine._lib
         self._obj = ctypes.c_void_p()
         vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        _lib.check(getattr(self._lib, self.CREATE)(engine._h, self.n, self.count, vp(index), vp(types), len(kind_a), vp(kind_a), vp(k_a),
-                                                   vp(x_a), ctypes.byref(self._obj)))
+        par = (vp(k_a),) if x_a is None else (vp(k_a), vp(x_a))
+        _lib.check(getattr(self._lib, self.CREATE)(engine._h, self.n, self.count, vp(index), vp(types), len(kind_a), vp(kind_a), *par,
+                                                   ctypes.byref(self._obj)))
 
     def forces(self, pos, force, accumulate=True, out=None, observables=True):
-        """The forces of the list on the first n rows of `pos` (pse_bond_forces, pse_angle_forces), added to `force` (or stored:
+        """The forces of the list on the first n rows of `pos` (pse_bond_forces, pse_angle_forces, pse_dihedral_forces), added to `force` (or stored:
         accumulate=False, which zeroes the rows of particles in no entry), or force=None: observables only.  observables=True: returns
         the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, count, written to `out` when one is given (e.g. a row of a
         log tensor); observables=False: forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
@@ -187,6 +200,14 @@ class AngleList(_TopologyList):
     WHAT, INDEX, COLS, X, KINDS = "angle", "triples", 3, "theta0", ANGLE_KINDS
     CREATE, FORCES, DESTROY = "pse_angles_create", "pse_angle_forces", "pse_angles_destroy"
     nangles = property(lambda self: self.count)
+
+
+class DihedralList(_TopologyList):
+    """Owner of a pse_dihedrals object: a fixed set of harmonic / OPLS dihedrals (i, j, k, l)."""
+
+    WHAT, INDEX, COLS, X, KINDS, WIDTH = "dihedral", "quads", 4, "params", DIHEDRAL_KINDS, 4
+    CREATE, FORCES, DESTROY = "pse_dihedrals_create", "pse_dihedral_forces", "pse_dihedrals_destroy"
+    ndihedrals = property(lambda self: self.count)
 
 
 class Engine:
@@ -397,6 +418,13 @@ class Engine:
         vertex, end) into arrays of `n` rows (default: n_max), `types` (nangles,) indices into the per-type sequences `kinds`
         ("harmonic" | "cosinesq" or ANGLE_KINDS codes), `k`, `theta0` (radians, in [0, pi]), or None: all type 0.  Returns an AngleList."""
         return AngleList(self, triples, types, kinds, k, theta0, n)
+
+    def dihedrals(self, quads, types=None, kinds=(0,), params=((1.0, 1.0, 1.0, 0.0),), n=None):
+        """A dihedral topology on the device (pse_dihedrals_create; see include/pse_amd.h): `quads` (ndihedrals, 4) particle indices
+        (i, j, k, l) into arrays of `n` rows (default: n_max), `types` (ndihedrals,) indices into the per-type sequences `kinds`
+        ("harmonic" | "opls" or DIHEDRAL_KINDS codes) and `params` (one 4-tuple per type: harmonic (k, d, mult, phi0), OPLS
+        (k1, k2, k3, k4)), or None: all type 0.  phi is the IUPAC dihedral angle: cis 0, trans pi.  Returns a DihedralList."""
+        return DihedralList(self, quads, types, kinds, params, None, n)
 
     def random_psi(self, n, timestep, group=None):
         import torch

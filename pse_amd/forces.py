@@ -2,11 +2,11 @@
 PSEv1/Stokes.cc:447; its example script has none).  SURVEY.md 8 f4: the step either side of the hot path, kept minimal."""
 import math
 
-from .engine import ANGLE_KINDS, BOND_KINDS, _per_type, _topology_arrays, _type_params
+from .engine import ANGLE_KINDS, BOND_KINDS, DIHEDRAL_KINDS, _per_type, _topology_arrays, _type_params
 
 
 class _ObsProvider:
-    """What the pair, bond and angle providers share: the eight device doubles of the most recent fused call -- U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
+    """What the pair, bond, angle and dihedral providers share: the eight device doubles of the most recent fused call -- U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
     npairs -- where that call writes them (a row of a StressLog on a sample step, a buffer of the provider's own otherwise), and the
     host-side readers.  A subclass sets NAME (what its messages call it) and makes the call in compute()."""
 
@@ -192,14 +192,53 @@ class Angles(_ObsProvider):
         return self.npairs
 
 
+class Dihedrals(_ObsProvider):
+    """Harmonic and OPLS dihedrals (pse_dihedral_forces; HOOMD's dihedral.harmonic and dihedral.opls): `quads` is an (ndihedrals, 4)
+    integer array of particle indices (i, j, k, l) into the system's arrays.  phi is the IUPAC dihedral angle of the three arms
+    i-j, j-k, k-l: the planar cis arrangement is 0, trans is pi (this convention whatever sign a given HOOMD version uses).
+    kind = "harmonic": params (k, d, mult, phi0), V = k/2 (1 + d cos(mult phi - phi0)), d = -1 or +1, mult an integer in 1..6;
+    "opls": params (k1, k2, k3, k4), V = 1/2 [k1 (1 + cos phi) + k2 (1 - cos 2phi) + k3 (1 + cos 3phi) + k4 (1 - cos 4phi)].  `kind` is
+    a scalar or a sequence with one entry per type, `params` one 4-tuple or one per type, and `types` then gives each dihedral's type
+    (None: all type 0).  The topology is copied to the device once, here.  Duplicate dihedrals act once each.  An arm must stay
+    shorter than half the smallest perpendicular box width: the minimum image is the nearest one only there.  A dihedral with three
+    consecutive collinear particles has no angle and does nothing.
+
+    virial=True: the same call also writes the dihedral energy, the virial (traceless) and the number of dihedrals that acted:
+    `energy`, `virial`, `stress()`, `ndihedrals` and StressLog as for HarmonicRepulsion."""
+
+    NAME = "Dihedrals"
+    KINDS = DIHEDRAL_KINDS
+
+    def __init__(self, integrator, quads, kind="harmonic", params=(1.0, 1.0, 1.0, 0.0), types=None, virial=False):
+        self.kind, self.params, _, self._id = _topology(integrator.cpp_method.dihedralsCreate, integrator.system.n, quads, "quads", 4,
+                                                        types, kind, params, None, "params", self.KINDS, "dihedral", width=4)
+        super().__init__(integrator, virial)
+
+    def compute(self, timestep):
+        s = self.integrator.system
+        self.integrator.cpp_method.dihedralForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, _addr(self._fused_out(timestep)))
+
+    @property
+    def ndihedrals(self):
+        """The number of dihedrals that acted at the most recent compute() (the count the pair providers call npairs)."""
+        return self.npairs
+
+
 def _addr(t):
     return 0 if t is None else t.data_ptr()
 
 
-def _topology(create, n, index, name, cols, types, kind, k, x, xname, table, what):
-    """The checks and the device object of Bonds and Angles: `kind`, `k` and `x` (called `xname`) are scalars -- a scalar serves every
-    type -- or sequences of one length, a kind being a name of `table`; `index` is the (count, cols) array `name`.  Returns the three
-    per-type tuples and the id `create` gave the topology."""
+def _topology(create, n, index, name, cols, types, kind, k, x, xname, table, what, width=None):
+    """The checks and the device object of Bonds, Angles and Dihedrals: `kind`, `k` and `x` (called `xname`) are scalars -- a scalar
+    serves every type -- or sequences of one length, a kind being a name of `table`; `index` is the (count, cols) array `name`.
+    width = w: a type has w parameters: `k` is one w-tuple or a sequence of them, x is not used (None).  Returns the three per-type
+    tuples (the third None with a width) and the id `create` gave the topology."""
+    if width is not None:
+        import numpy as np
+        if np.ndim(k) not in (1, 2) or np.shape(k)[-1] != width:
+            raise ValueError(f"{xname} must be one {width}-tuple or a sequence of them (one per {what} type)")
+        k = [tuple(k)] if np.ndim(k) == 1 else [tuple(v) for v in k]
+        x = [None] * len(k)
     kind, k, x = _per_type(kind), _per_type(k), _per_type(x)
     nt = max(len(kind), len(k), len(x))
     kind, k, x = (v * nt if len(v) == 1 else v for v in (kind, k, x))
@@ -208,11 +247,11 @@ def _topology(create, n, index, name, cols, types, kind, k, x, xname, table, wha
     for v in kind:
         if v not in table:
             raise ValueError(f"{what} kind must be one of {sorted(table)}, not {v!r}")
-    kind_a, k_a, x_a = _type_params(kind, k, x, xname, table, what)
+    kind_a, k_a, x_a = _type_params(kind, k, x, xname, table, what, width)
     index, types = _topology_arrays(index, types, cols, name, what)
-    tid = create(n, index.shape[0], index.ctypes.data, 0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, k_a.ctypes.data,
-                 x_a.ctypes.data)
-    return tuple(kind), tuple(k_a.tolist()), tuple(x_a.tolist()), tid
+    par = (k_a.ctypes.data,) if x_a is None else (k_a.ctypes.data, x_a.ctypes.data)
+    tid = create(n, index.shape[0], index.ctypes.data, 0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, *par)
+    return tuple(kind), tuple(map(tuple, k_a.tolist())) if width else tuple(k_a.tolist()), None if x_a is None else tuple(x_a.tolist()), tid
 
 
 def _sym3(w):
@@ -222,7 +261,7 @@ def _sym3(w):
 
 
 class StressLog:
-    """Energy and stress of a HarmonicRepulsion, TablePair, Bonds or Angles(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
+    """Energy and stress of a HarmonicRepulsion, TablePair, Bonds, Angles or Dihedrals(..., virial=True) every `period` steps, in a device ring of `capacity` rows: on a
     sample step the provider's fused call writes its eight doubles straight into the next row, the step number, the box tilt and the
     volume are noted on the host, and nothing waits for the device until table() is read.  Once full, the oldest rows are replaced."""
 
