@@ -231,6 +231,39 @@ int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* 
                    const double *table /* DEVICE, width x 2: V_k, F_k interleaved */, int width, double rmin, double rmax,
                    int accumulate, double *out8 /* DEVICE, may be NULL */);
 
+/* ---- pair exclusions: HOOMD's nlist.reset_exclusions (no reference counterpart: the reference leaves forces to HOOMD) ----
+ * In HOOMD the neighbour list drops bonded pairs from the pair potentials by default (nlist.reset_exclusions(['bond']), optionally
+ * 'angle' and 'dihedral'): force fields are fitted with that understanding.  A pse_exclusions object is such a SET of npairs particle
+ * pairs, and the two passes below are pse_pair_table and pse_pair_repulsion with the pairs of the set contributing nothing -- not to
+ * the forces, not to U or W, not to npairs.  The indices are CALLER-order particle indices: rows of pos and force, the values of
+ * `group` -- not positions in the group, not rows of the engine's sorted order.  A particle whose index is >= the object's n has no
+ * exclusions.  A pair may be listed more than once and in either order: it is one exclusion (a set, unlike a bond list).  Which
+ * pairs to put in it is the caller's choice: HOOMD's sets are both members of a bond, the two ends of an angle, the two ends of a
+ * dihedral.  Scaled 1-4 interactions ("special pairs") are not provided, and neither the hydrodynamic near field nor the kept
+ * neighbour list knows exclusions: the mobility acts between all particles.
+ * The object is stored as one sorted row of partners per particle, every pair in both rows (pse_host_exclusion_rows): results are
+ * bit-identical for any order of the list and either order of a pair's members.  It belongs to its handle: pse_destroy frees the
+ * objects still alive, pse_exclusions_destroy after that is a caller error.
+ * pse_exclusions_create returns PSE_ERR_INVALID, with a message naming the value, for: a null h, pairs_host or out, n == 0 or
+ * n > n_max, npairs == 0 or npairs > 2^30, an index >= n, a pair with i == j.  *out is null after a refusal. */
+typedef struct pse_exclusions pse_exclusions;
+int pse_exclusions_create(pse_handle *h, unsigned n, unsigned npairs, const unsigned *pairs_host /* npairs x 2 particle indices */,
+                          pse_exclusions **out);
+int pse_exclusions_destroy(pse_exclusions *ex);
+/* pse_pair_table with the pairs of ex excluded.  Arguments, results, refusals and their order are those of pse_pair_table (its
+ * checks run first); in addition PSE_ERR_INVALID for a null ex and for an ex created on another handle.  The kept pairs are summed
+ * in the order of pse_pair_table: with an object none of whose pairs is in range, forces and out8 equal pse_pair_table's bit for
+ * bit.  Queue-only wherever pse_pair_table is, no atomics, bit-reproducible; ex must stay alive until the stream has passed the call
+ * (pse_exclusions_destroy waits for the stream). */
+int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* may be NULL */, const unsigned *group, unsigned N,
+                        const double *table /* DEVICE, width x 2: V_k, F_k interleaved */, int width, double rmin, double rmax,
+                        int accumulate, double *out8 /* DEVICE, may be NULL */, const pse_exclusions *ex);
+/* The harmonic repulsion with the pairs of ex excluded: out8 == NULL is pse_pair_repulsion (force is required), out8 != NULL is
+ * pse_pair_repulsion_virial (force may be NULL, refused on a slab rank); the checks of the one or the other run first, then those of
+ * ex as above.  Summation order, reproducibility and queueing as for pse_pair_table_excl. */
+int pse_pair_repulsion_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                            double k, double sigma, int accumulate, double *out8 /* DEVICE, may be NULL */, const pse_exclusions *ex);
+
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,
@@ -585,6 +618,14 @@ int pse_host_angle_rows(unsigned n, unsigned nangles, const unsigned *triples, c
  * the int offsets), an index >= n, a quadruple with two equal members. */
 int pse_host_dihedral_rows(unsigned n, unsigned ndihedrals, const unsigned *quads, const unsigned *types /* or NULL */,
                            int *row_off /* n + 1 */, unsigned *entries /* 4 ndihedrals x 4: i, j, k, l; then 4 ndihedrals types */);
+/* host-only: the per-particle rows a pse_exclusions object stores (pse_exclusions_create calls this after validating).  A CSR over
+ * the n particles: row i is entries[row_off[i]] .. entries[row_off[i + 1]), the indices excluded from i, one unsigned each, sorted
+ * ascending.  An exclusion is a set: a pair listed several times, in either order, is kept once; every pair appears in both members'
+ * rows; row_off[n] is the number of entries kept (twice the number of distinct pairs, at most 2 npairs).  The rows are a function of
+ * the pair SET, not of the list order or of the order of a pair's members.  PSE_ERR_INVALID: a null array, n == 0, npairs == 0 or
+ * > 2^30, an index >= n, a pair with i == j. */
+int pse_host_exclusion_rows(unsigned n, unsigned npairs, const unsigned *pairs, int *row_off /* n + 1 */,
+                            unsigned *entries /* room for 2 npairs */);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,11 @@ SYMBOLS = {
     "pse_pair_repulsion": (_i, [_vp, _vp, _vp, _vp, _u, _d, _d, _i]),
     "pse_pair_repulsion_virial": (_i, [_vp, _vp, _vp, _vp, _u, _d, _d, _i, _vp]),
     "pse_pair_table": (_i, [_vp, _vp, _vp, _vp, _u, _vp, _i, _d, _d, _i, _vp]),
+    "pse_exclusions_create": (_i, [_vp, _u, _u, _vp, _vp]),
+    "pse_exclusions_destroy": (_i, [_vp]),
+    "pse_pair_table_excl": (_i, [_vp, _vp, _vp, _vp, _u, _vp, _i, _d, _d, _i, _vp, _vp]),
+    "pse_pair_repulsion_excl": (_i, [_vp, _vp, _vp, _vp, _u, _d, _d, _i, _vp, _vp]),
+    "pse_host_exclusion_rows": (_i, [_u, _u, _vp, _vp, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

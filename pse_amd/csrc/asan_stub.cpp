@@ -2,7 +2,7 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, pse_bonds_*, pse_angles_*, pse_dihedrals_*) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*, pse_dihedrals_*, pse_exclusions_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -24,7 +24,7 @@ struct pse_handle {
     int lz_op = PSE_LANCZOS_RECORDS16;
     std::vector<Topology *> topologies;
 };
-struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows, pse_host_dihedral_rows), kept on the host
+struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows, pse_host_dihedral_rows, pse_host_exclusion_rows), kept on the host
     pse_handle *h;
     std::vector<int> row_off;
     std::vector<unsigned> entries;
@@ -34,6 +34,7 @@ struct Topology {   // the REAL rows (pse_host_bond_rows, pse_host_angle_rows, p
 struct pse_bonds : Topology { using Topology::Topology; };
 struct pse_angles : Topology { using Topology::Topology; };
 struct pse_dihedrals : Topology { using Topology::Topology; };
+struct pse_exclusions : Topology { using Topology::Topology; };
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -112,6 +113,27 @@ int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, co
                    double rmin, double rmax, int, double *out8) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
     return pair_table_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, table, width, rmin, rmax, out8);
+}
+int pse_exclusions_create(pse_handle *h, unsigned n, unsigned npairs, const unsigned *pairs_host, pse_exclusions **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null handle");
+    if (int rc = exclusions_validate(h->par.n_max, n, npairs, pairs_host)) return rc;
+    pse_exclusions *ex = new pse_exclusions(h, (size_t)n + 1, (size_t)npairs * 2);
+    return topology_adopt(ex, pse_host_exclusion_rows(n, npairs, pairs_host, ex->row_off.data(), ex->entries.data()), out);
+}
+int pse_exclusions_destroy(pse_exclusions *ex) { return topology_destroy(ex); }
+int pse_pair_repulsion_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, double, double sigma, int,
+                            double *out8, const pse_exclusions *ex) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    if (int rc = pair_repulsion_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, out8 != nullptr, out8, sigma)) return rc;
+    return pair_excl_validate("pse_pair_repulsion_excl", ex, ex ? ex->h : nullptr, h);
+}
+int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, const double *table, int width,
+                        double rmin, double rmax, int, double *out8, const pse_exclusions *ex) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    if (int rc = pair_table_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, table, width, rmin, rmax, out8)) return rc;
+    return pair_excl_validate("pse_pair_table_excl", ex, ex ? ex->h : nullptr, h);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -26,6 +26,7 @@ void Stokes::setParams() {
     m_bonds.objs.clear();   // pse_destroy freed them
     m_angles.objs.clear();
     m_dihedrals.objs.clear();
+    m_exclusions.objs.clear();
     m_m_Lanczos = 2;   // "try two Lanczos iterations to start" (PSEv1/Stokes.cc:131-132)
     pse_params p{};
     p.n_max = m_n_total;
@@ -75,6 +76,33 @@ void Stokes::pairTable(const pse_double4 *pos, pse_double4 *force, const unsigne
                        int width, double rmin, double rmax, bool accumulate, double *out8) {
     if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
     check(pse_pair_table(m_h, pos, force, group, n, table, width, rmin, rmax, accumulate ? 1 : 0, out8), "Stokes::pairTable");
+}
+
+int Stokes::exclusionsCreate(unsigned int n, unsigned int npairs, const unsigned int *pairs) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    pse_exclusions *ex = nullptr;
+    check(pse_exclusions_create(m_h, n, npairs, pairs, &ex), "Stokes::exclusionsCreate");
+    return m_exclusions.push(ex);
+}
+
+void Stokes::exclusionsDestroy(int id) {
+    check(pse_exclusions_destroy(m_exclusions.get(id)), "Stokes::exclusionsDestroy");
+    m_exclusions.drop(id);
+}
+
+void Stokes::pairTableExcl(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, const double *table,
+                           int width, double rmin, double rmax, bool accumulate, double *out8, int ex) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    check(pse_pair_table_excl(m_h, pos, force, group, n, table, width, rmin, rmax, accumulate ? 1 : 0, out8, m_exclusions.get(ex)),
+          "Stokes::pairTableExcl");
+}
+
+void Stokes::pairRepulsionExcl(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k,
+                               double sigma, bool accumulate, double *out8, int ex) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    if (n == 0 && !out8) return;   // (as pairRepulsion; with out8 an empty group is refused by the C-ABI, as in pairRepulsionVirial)
+    check(pse_pair_repulsion_excl(m_h, pos, force, group, n, k, sigma, accumulate ? 1 : 0, out8, m_exclusions.get(ex)),
+          "Stokes::pairRepulsionExcl");
 }
 
 int Stokes::bondsCreate(unsigned int n, unsigned int nbonds, const unsigned int *pairs, const unsigned int *types, int ntypes, const int *kind,

@@ -26,7 +26,7 @@ struct ParticleArrays {
 // The objects of one kind that a Stokes made on its engine, by id -- the position in the table; null once destroyed.
 template <class T>
 struct IdTable {
-    const char *what;   // "bond", "angle", "dihedral": what the error calls them
+    const char *what;   // "bond", "angle", "dihedral", "exclusion": what the error calls them
     std::vector<T *> objs;
     int push(T *o) { objs.push_back(o); return (int)objs.size() - 1; }
     T *get(int id) const {
@@ -66,6 +66,17 @@ public:
     // rmin + k (rmax - rmin)/(width - 1), linear in between; force or out8 may be null (observables only / forces only), not both
     void pairTable(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, const double *table, int width,
                    double rmin, double rmax, bool accumulate, double *out8);
+    // pair exclusions (pse_exclusions_create; HOOMD's nlist.reset_exclusions): exclusionsCreate copies the HOST array of npairs x 2
+    // caller-order particle indices to the engine and returns the id the two passes below take; the ids live and die as those of the
+    // bond objects do
+    int exclusionsCreate(unsigned int n, unsigned int npairs, const unsigned int *pairs);
+    void exclusionsDestroy(int id);
+    // pairTable with the pairs of exclusion object `ex` contributing nothing (pse_pair_table_excl)
+    void pairTableExcl(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, const double *table, int width,
+                       double rmin, double rmax, bool accumulate, double *out8, int ex);
+    // the repulsion likewise (pse_pair_repulsion_excl): out8 null is pairRepulsion, out8 given is pairRepulsionVirial
+    void pairRepulsionExcl(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k, double sigma,
+                           bool accumulate, double *out8, int ex);
     // bonded forces (pse_bonds_create / pse_bond_forces / pse_bonds_overstretched): bondsCreate copies the HOST arrays -- nbonds x 2
     // particle indices, nbonds types or null, ntypes x (kind, k, r0) -- to the engine and returns the id the other calls take.  The
     // bond objects belong to the engine: setParams, which makes a new one, invalidates every id
@@ -111,6 +122,7 @@ private:
     IdTable<pse_bonds> m_bonds{"bond"};
     IdTable<pse_angles> m_angles{"angle"};
     IdTable<pse_dihedrals> m_dihedrals{"dihedral"};
+    IdTable<pse_exclusions> m_exclusions{"exclusion"};
 };
 
 }  // namespace pse_host

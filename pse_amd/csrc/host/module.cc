@@ -79,6 +79,21 @@ PYBIND11_MODULE(_PSEv1, m) {
             s.pairTable(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, ptr<const double>(table), width,
                         rmin, rmax, accumulate, ptr<double>(out8));
         })
+        // pair exclusions: npairs x 2 uint32 HOST indices by address (numpy .ctypes.data); the _excl passes take the id
+        .def("exclusionsCreate", [](Stokes &s, unsigned int n, unsigned int npairs, std::uintptr_t pairs) {
+            return s.exclusionsCreate(n, npairs, ptr<const unsigned int>(pairs));
+        })
+        .def("exclusionsDestroy", &Stokes::exclusionsDestroy)
+        .def("pairTableExcl", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, std::uintptr_t table,
+                                 int width, double rmin, double rmax, bool accumulate, std::uintptr_t out8, int ex) {
+            s.pairTableExcl(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, ptr<const double>(table),
+                            width, rmin, rmax, accumulate, ptr<double>(out8), ex);
+        })
+        .def("pairRepulsionExcl", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, double k,
+                                     double sigma, bool accumulate, std::uintptr_t out8, int ex) {
+            s.pairRepulsionExcl(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate,
+                                ptr<double>(out8), ex);
+        })
         // host arrays by address too (numpy .ctypes.data): nbonds x 2 uint32, nbonds uint32 or 0, ntypes int32 / float64 / float64
         .def("bondsCreate", [](Stokes &s, unsigned int n, unsigned int nbonds, std::uintptr_t pairs, std::uintptr_t types, int ntypes,
                                std::uintptr_t kind, std::uintptr_t k, std::uintptr_t r0) {

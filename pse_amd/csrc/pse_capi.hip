@@ -418,6 +418,7 @@ struct Topology {
 struct pse_bonds : Topology {};
 struct pse_angles : Topology {};
 struct pse_dihedrals : Topology {};
+struct pse_exclusions : Topology {};   // row_off: unsigned, entries: the partners, one unsigned each (pse_host_exclusion_rows); no parameters
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
@@ -2561,14 +2562,21 @@ extern "C" int pse_sqrt_mreal(pse_handle *h, const pse_double4 *pos, const pse_d
 
 // pse_pair_repulsion and pse_pair_repulsion_virial (include/pse_amd.h): the force pass, and the same pass with the pair observables of
 // the repulsion -- energy, virial and pair count in eight device doubles.  Queue-only: nothing is read back, out8 is written by the stream.
+// The rows of an exclusion object as the launches take them.
+static PairExclusions excl_rows(const pse_exclusions *ex) {
+    return PairExclusions{(const unsigned *)ex->row_off, (const unsigned *)ex->entries, ex->n};
+}
+// `excl`: the name of the entry point that takes an exclusion object `ex`, checked behind the plain pass's own arguments; null: a plain pass.
 static int pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, double k, double sigma,
-                          int accumulate, bool virial, double *out8) {
+                          int accumulate, bool virial, double *out8, const char *excl = nullptr, const pse_exclusions *ex = nullptr) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
     TRY(pair_repulsion_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, virial, out8, sigma));
+    if (excl) TRY(pair_excl_validate(excl, ex, ex ? ex->h : nullptr, h));
     HIPCHK(hipSetDevice(h->device));
     TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
     launch_pair_repulsion(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->pv_rows, out8,
-                          h->stream);
+                          h->stream, ex ? &er : nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2580,24 +2588,39 @@ extern "C" int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, 
                                          double k, double sigma, int accumulate, double *out8) {
     return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, true, out8);
 }
+extern "C" int pse_pair_repulsion_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                       double k, double sigma, int accumulate, double *out8, const pse_exclusions *ex) {
+    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, out8 != nullptr, out8, "pse_pair_repulsion_excl", ex);
+}
 
 // Tabulated pair potential on the same cell list (include/pse_amd.h), with or without the eight observables.  Queue-only wherever
 // pse_pair_repulsion is; the table is read by the stream.
-extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                              const double *table, int width, double rmin, double rmax, int accumulate, double *out8) {
+static int pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, const double *table,
+                      int width, double rmin, double rmax, int accumulate, double *out8, const char *excl, const pse_exclusions *ex) {
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
     TRY(pair_table_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, table, width, rmin, rmax, out8));
+    if (excl) TRY(pair_excl_validate(excl, ex, ex ? ex->h : nullptr, h));
     HIPCHK(hipSetDevice(h->device));
     TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
     launch_pair_table(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, table, width, rmin, rmax, accumulate, (double4 *)force,
-                      h->pv_rows, out8, h->stream);
+                      h->pv_rows, out8, h->stream, ex ? &er : nullptr);
     HIPCHK(hipGetLastError());
     return 0;
+}
+extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                              const double *table, int width, double rmin, double rmax, int accumulate, double *out8) {
+    return pair_table(h, pos, force, group, N, table, width, rmin, rmax, accumulate, out8, nullptr, nullptr);
+}
+extern "C" int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                   const double *table, int width, double rmin, double rmax, int accumulate, double *out8,
+                                   const pse_exclusions *ex) {
+    return pair_table(h, pos, force, group, N, table, width, rmin, rmax, accumulate, out8, "pse_pair_table_excl", ex);
 }
 
 // ---- bonded forces and angle forces (include/pse_amd.h) ------------------------------------------------------------------------
 // The device copy of a topology: the host rows `off` and `ent`, the par_bytes of the ntypes parameter sets and, with `counter`, a
-// zeroed counter.  `what` is "bonds", "angles" or "dihedrals".
+// zeroed counter.  `what` is "bonds", "angles", "dihedrals" or "exclusions".
 template <class T>
 static int topology_create(pse_handle *h, const char *what, unsigned n, unsigned count, int ntypes, const std::vector<int> &off,
                            const std::vector<unsigned> &ent, const void *par, size_t par_bytes, bool counter, T **out) {
@@ -2610,7 +2633,7 @@ static int topology_create(pse_handle *h, const char *what, unsigned n, unsigned
     };
     hipError_t e = put(&t->row_off, off.data(), off.size() * sizeof(int));
     if (e == hipSuccess) e = put(&t->entries, ent.data(), ent.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = put(&t->par, par, par_bytes);
+    if (e == hipSuccess && par_bytes) e = put(&t->par, par, par_bytes);   // (pair exclusions have no parameters)
     if (e == hipSuccess && counter) e = put((void **)&t->over, nullptr, sizeof(unsigned long long));
     if (e == hipSuccess && counter) e = hipDeviceSynchronize();   // (the memset is the one call above that may return early)
     if (e != hipSuccess) {
@@ -2733,6 +2756,21 @@ extern "C" int pse_dihedral_forces(pse_dihedrals *d, const pse_double4 *pos, pse
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// Pair exclusions (include/pse_amd.h): the rows of pse_host_exclusion_rows on the device, read by the _excl pair passes.
+extern "C" int pse_exclusions_create(pse_handle *h, unsigned n, unsigned npairs, const unsigned *pairs_host, pse_exclusions **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null handle");
+    TRY(exclusions_validate((unsigned)h->n_max, n, npairs, pairs_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)npairs * 2);
+    TRY(pse_host_exclusion_rows(n, npairs, pairs_host, off.data(), ent.data()));
+    ent.resize((size_t)(unsigned)off[n]);   // duplicates are gone
+    return topology_create(h, "exclusions", n, (unsigned)off[n] / 2, 0, off, ent, nullptr, 0, false, out);
+}
+extern "C" int pse_exclusions_destroy(pse_exclusions *ex) { return topology_destroy(ex); }
 
 extern "C" int pse_random_psi(pse_handle *h, pse_double4 *psi, const unsigned *group, unsigned N, unsigned timestep) {
     TRY(check_n(h, N));

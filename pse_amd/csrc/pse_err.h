@@ -35,5 +35,10 @@ int angles_validate(unsigned n_max, unsigned n, unsigned nangles, const unsigned
 // the same for pse_dihedrals_create (params: ntypes x 4)
 int dihedrals_validate(unsigned n_max, unsigned n, unsigned ndihedrals, const unsigned *quads, const unsigned *types, int ntypes,
                        const int *kind, const double *params);
+// the same for pse_exclusions_create
+int exclusions_validate(unsigned n_max, unsigned n, unsigned npairs, const unsigned *pairs);
+// what pse_pair_table_excl and pse_pair_repulsion_excl (`who`) check behind the validators of the plain passes: an exclusion object,
+// and one of this handle (ex_handle: the handle it was created on)
+int pair_excl_validate(const char *who, const void *ex, const void *ex_handle, const void *h);
 
 }  // namespace pse

@@ -171,6 +171,24 @@ int dihedrals_validate(unsigned n_max, unsigned n, unsigned ndihedrals, const un
     return 0;
 }
 
+int exclusions_validate(unsigned n_max, unsigned n, unsigned npairs, const unsigned *pairs) {
+    if (!pairs) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null pairs_host");
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "pse_exclusions_create: n = %u outside (0, n_max = %u]", n, n_max);
+    if (npairs == 0 || npairs > (1u << 30)) return fail(PSE_ERR_INVALID, "pse_exclusions_create: npairs = %u outside (0, 2^30]", npairs);
+    for (unsigned b = 0; b < npairs; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1];
+        if (i >= n || j >= n) return fail(PSE_ERR_INVALID, "pse_exclusions_create: pair %u = (%u, %u) has an index >= n = %u", b, i, j, n);
+        if (i == j) return fail(PSE_ERR_INVALID, "pse_exclusions_create: pair %u excludes particle %u from itself", b, i);
+    }
+    return 0;
+}
+
+int pair_excl_validate(const char *who, const void *ex, const void *ex_handle, const void *h) {
+    if (!ex) return fail(PSE_ERR_INVALID, "%s: null exclusion object", who);
+    if (ex_handle != h) return fail(PSE_ERR_INVALID, "%s: the exclusion object was created on another handle", who);
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -300,6 +318,39 @@ extern "C" int pse_host_dihedral_rows(unsigned n, unsigned ndihedrals, const uns
     for (size_t m = 0; m < e.size(); ++m) {
         entries[4 * m] = e[m].i; entries[4 * m + 1] = e[m].j; entries[4 * m + 2] = e[m].k; entries[4 * m + 3] = e[m].l;
         ty[m] = e[m].type;
+    }
+    return 0;
+}
+
+// The pairs as sorted, unique (min, max) keys; walked in that order, row p receives its partners below p (from the keys whose first
+// member they are, ascending) before its partners above p (from the keys that start with p, ascending): every row comes out sorted
+// without a sort of its own.  O(npairs log npairs).
+extern "C" int pse_host_exclusion_rows(unsigned n, unsigned npairs, const unsigned *pairs, int *row_off, unsigned *entries) {
+    if (!pairs || !row_off || !entries) return fail(PSE_ERR_INVALID, "pse_host_exclusion_rows: null array");
+    if (n == 0) return fail(PSE_ERR_INVALID, "pse_host_exclusion_rows: n = 0");
+    if (npairs == 0 || npairs > (1u << 30)) return fail(PSE_ERR_INVALID, "pse_host_exclusion_rows: npairs = %u outside (0, 2^30]", npairs);
+    for (unsigned b = 0; b < npairs; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1];
+        if (i >= n || j >= n) return fail(PSE_ERR_INVALID, "pse_host_exclusion_rows: pair %u = (%u, %u) has an index >= n = %u", b, i, j, n);
+        if (i == j) return fail(PSE_ERR_INVALID, "pse_host_exclusion_rows: pair %u excludes particle %u from itself", b, i);
+    }
+    std::vector<uint64_t> key(npairs);
+    for (unsigned b = 0; b < npairs; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1];
+        key[b] = ((uint64_t)std::min(i, j) << 32) | std::max(i, j);
+    }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    // (offsets are counted as unsigned: at the cap of 2^30 distinct pairs the last one is 2^31, which the device reads as unsigned too)
+    unsigned *off = reinterpret_cast<unsigned *>(row_off);
+    std::fill(off, off + (size_t)n + 1, 0u);
+    for (uint64_t k : key) { ++off[(unsigned)(k >> 32) + 1]; ++off[(unsigned)k + 1]; }
+    for (unsigned i = 0; i < n; ++i) off[i + 1] += off[i];
+    std::vector<unsigned> fill(off, off + n);
+    for (uint64_t k : key) {
+        const unsigned lo = (unsigned)(k >> 32), hi = (unsigned)k;
+        entries[fill[lo]++] = hi;
+        entries[fill[hi]++] = lo;
     }
     return 0;
 }

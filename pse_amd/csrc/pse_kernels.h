@@ -352,13 +352,23 @@ void launch_eval_fg(const double *r, int n, const double *coef, double *f, doubl
 // kernel; force may then be null (observables only).  out8 == null: forces only, no reduction (rows is not touched)
 constexpr int PAIR_VIRIAL_NOBS = 8;
 size_t pair_virial_rows(int n);
+// pair exclusions of the two cell-list passes (pse_exclusions_create): the device copy of the rows of pse_host_exclusion_rows, a CSR
+// over the first n caller-order indices, row t = entries[row_off[t] .. row_off[t + 1]) the partners excluded from t, ascending.
+// ex != null: the pairs in it contribute nothing to forces or sums (k_pair_repulsion<OBS, true>, k_pair_table<OBS, true>); ex == null:
+// the plain kernels
+struct PairExclusions {
+    const unsigned *row_off, *entries;
+    unsigned n;
+};
 void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
-                           double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
+                           double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
+                           const PairExclusions *ex = nullptr);
 // tabulated central pair potential from the cell list (k_pair_table): table = width x (V, F) on the device, 16-byte aligned, nodes
 // r_e = rmin + e (rmax - rmin)/(width - 1), linear between them, staged in width * 16 bytes of LDS per workgroup.  out8 != null: the
 // eight observables through `rows` as above; out8 == null: forces only, no reduction (rows is not touched)
 void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
-                       int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s);
+                       int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
+                       const PairExclusions *ex = nullptr);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
 // entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
 // eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does

@@ -2728,6 +2728,41 @@ __device__ __forceinline__ void stage_type_params(pt_entry *dst, const void *__r
     __syncthreads();
 }
 
+// Pair exclusions of the two cell-list passes below (HOOMD's nlist.reset_exclusions): ExclRows is the device copy of the rows of
+// pse_host_exclusion_rows -- a CSR over the first n CALLER-order particle indices, row t the partners excluded from t, sorted
+// ascending, without duplicates, every pair in both rows.  The rows are indexed by tags (tag_s), never by sorted-order rows.
+struct ExclRows {
+    const unsigned *__restrict__ off;   // n + 1
+    const unsigned *__restrict__ ent;   // off[n] partners
+    unsigned n;
+};
+constexpr unsigned EXCL_LINEAR = 8;   // rows (or what the bisection leaves of one) up to this length are compared in one batch of loads
+// The row bounds [eb, ee) of the particle with tag t: a tag >= n has no exclusions and reads nothing.
+__device__ __forceinline__ void excl_row(const ExclRows &ex, unsigned t, unsigned &eb, unsigned &ee) {
+    eb = ee = 0u;
+    if (t < ex.n) { eb = ex.off[t]; ee = ex.off[t + 1]; }
+}
+// Is tag tj in the sorted row [eb, ee), eb < ee?  Called for a pair that has passed the distance test, a few per particle, and only
+// by a lane whose row is not empty (the caller tests eb < ee before it loads tag_s[j]).  Search: rows are typically the 2-6 partners
+// of a chain's 1-2, 1-3 and 1-4 neighbours, so a row of at most EXCL_LINEAR = 8 entries is compared whole: eight 4-byte loads along
+// the row, indices past the end clamped to the last entry, issued back to back and waited for once -- one or two cache lines, ONE
+// memory latency behind the load of tag_s[j].  (A scan in ascending order with an early exit at the first entry >= tj makes fewer
+// loads but waits for each before it decides on the next: three to four latencies in a row per pair, measured 1.40x the plain table
+// pass on six-entry rows against 1.28x for this form, docs/HISTORY.md.)  A longer row (a hub, a cross-linker) uses the sorted
+// order: it is bisected until at most 8 candidates are left, log2(len / 8) dependent loads, and the same batch finishes -- a row of
+// 500 costs 6 loads and a batch instead of 500 loads.  The lanes of a wave diverge here; the pass is bound by the position gathers.
+__device__ __forceinline__ bool excl_has(const unsigned *__restrict__ ent, unsigned eb, unsigned ee, unsigned tj) {
+    while (ee - eb > EXCL_LINEAR) {   // tj, if present, stays in [eb, ee)
+        const unsigned mid = eb + ((ee - eb) >> 1);
+        if (ent[mid] <= tj) eb = mid; else ee = mid;
+    }
+    const unsigned last = ee - 1u;
+    bool hit = false;
+#pragma unroll
+    for (unsigned q = 0; q < EXCL_LINEAR; ++q) hit |= ent[min(eb + q, last)] == tj;
+    return hit;
+}
+
 // Soft repulsion F_i = sum_j k (sigma - r) (r_i - r_j)/r over pairs closer than sigma, from the engine's own cell list.  One thread
 // per particle; the result is added to (or stored in) the caller's force array in the caller's order.
 // (the cell walk is written out here and in k_pair_table: shared through a lambda-taking helper in the style of for_each_run it
@@ -2736,11 +2771,16 @@ __device__ __forceinline__ void stage_type_params(pt_entry *dst, const void *__r
 // j > i of the sorted order -- every unordered pair once -- add U = k/2 (sigma - r)^2 and the virial of c = k (sigma - r)/r
 // (obs_add_central), reduced by obs_rows_store.  The sorted order fixes every sum, and the cell sort is a stable sort (k_cell_order),
 // so the eight numbers are bit-reproducible from call to call on equal inputs.  force == nullptr: observables only.
-template <bool OBS>
+// EXCL: the pairs of `ex` contribute nothing (pse_pair_repulsion_excl).  The lane reads its tag and its row bounds once; a pair
+// that has passed the distance test -- a few per particle -- is looked up by the partner's tag (excl_has), and only by a lane whose row
+// is not empty: the others load neither tag_s[j] nor an entry.  The test is symmetric (every pair is in both rows), so the forces stay
+// equal and opposite and the rule j > i of the sums stays; the kept pairs are summed in the order of the plain pass.  EXCL = false
+// is the plain pass: `ex` is not read.
+template <bool OBS, bool EXCL>
 __global__ void __launch_bounds__(TPB)
 k_pair_repulsion(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off,
                  DBox box, DCells nc, double k, double sigma, int accumulate, double4 *__restrict__ force,
-                 double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
+                 double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */, ExclRows ex) {
     const int blk = xcd_block(blockIdx.x, gridDim.x);
     const int i = blk * TPB + threadIdx.x;
     double o[PV_NOBS];
@@ -2753,13 +2793,15 @@ k_pair_repulsion(const double4 *__restrict__ pos_s, const unsigned *__restrict__
         const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
         const double s2 = sigma * sigma;
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        unsigned eb = 0u, ee = 0u;
+        if (EXCL) excl_row(ex, tag_s[i], eb, ee);
         for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
             for (int j = jb; j < je; ++j) {
                 const double4 pj = pos_s[j];
                 double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
                 min_image(box, dx, dy, dz);
                 const double r2 = dx * dx + dy * dy + dz * dz;
-                if (r2 < s2 && j != i && r2 > 0.0) {
+                if (r2 < s2 && j != i && r2 > 0.0 && !(EXCL && eb < ee && excl_has(ex.ent, eb, ee, tag_s[j]))) {
                     const double r = sqrt(r2), c = k * (sigma - r) / r;
                     Fx += c * dx; Fy += c * dy; Fz += c * dz;
                     if (OBS && j > i) obs_add_central(o, 0.5 * k * (sigma - r) * (sigma - r), c, dx, dy, dz);
@@ -2797,12 +2839,21 @@ static void launch_with_obs(int nb, double *rows, double *out8, hipStream_t s, L
         launch(std::false_type{}, (double *)nullptr);
     }
 }
+// The exclusion flag of a launch as a std::bool_constant, as launch_with_obs hands over OBS: `launch` is instantiated for both.
+template <class L>
+static void launch_with_excl(const PairExclusions *ex, L &&launch) {
+    if (ex) launch(std::true_type{}, ExclRows{ex->row_off, ex->entries, ex->n});
+    else launch(std::false_type{}, ExclRows{nullptr, nullptr, 0u});
+}
 void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
-                           double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
+                           double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
+                           const PairExclusions *ex) {
     const int nb = nblocks(N, TPB);
-    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
-        hipLaunchKernelGGL(k_pair_repulsion<decltype(obs)::value>, dim3(nb), dim3(TPB), 0, s, pos_s, tag_s, N, cell_off, box, nc, k, sigma,
-                           accumulate, force, r);
+    launch_with_excl(ex, [&](auto excl, ExclRows er) {
+        launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+            hipLaunchKernelGGL((k_pair_repulsion<decltype(obs)::value, decltype(excl)::value>), dim3(nb), dim3(TPB), 0, s, pos_s, tag_s, N,
+                               cell_off, box, nc, k, sigma, accumulate, force, r, er);
+        });
     });
 }
 size_t pair_virial_rows(int n) { return (size_t)nblocks(n, TPB) * PV_NOBS; }
@@ -2820,11 +2871,13 @@ size_t pair_virial_rows(int n) { return (size_t)nblocks(n, TPB) * PV_NOBS; }
 // exactly as there.  No lane leaves before the barrier behind the staging loop, nor, with OBS, before the one of the reduction.
 // (pt_entry is the native vector type, not double2: hipcc splits a double2 read from LDS into its members and pairs them up again as
 // ds_read2_b64, which the LDS serves at a quarter of the rate of ds_read_b128; x = V, y = F)
-template <bool OBS>
+// EXCL: the pairs of `ex` contribute nothing (pse_pair_table_excl), exactly as in k_pair_repulsion<OBS, true>: tag and row bounds
+// once per lane, the lookup (excl_has) behind both distance tests and only in a lane with a row; EXCL = false does not read `ex`.
+template <bool OBS, bool EXCL>
 __global__ void __launch_bounds__(TPB)
 k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, int N, const int *__restrict__ cell_off, DBox box,
              DCells nc, const double2 *__restrict__ table, int width, double rmin, double rmax, double scale, int accumulate,
-             double4 *__restrict__ force, double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */) {
+             double4 *__restrict__ force, double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */, ExclRows ex) {
     extern __shared__ pt_entry pt_tab[];   // [width]
     for (int e = threadIdx.x; e < width; e += TPB) pt_tab[e] = ((const pt_entry *)table)[e];
     __syncthreads();
@@ -2841,6 +2894,8 @@ k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag
         const double rmax2 = rmax * rmax;
         const int elast = width - 2;
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        unsigned eb = 0u, ee = 0u;
+        if (EXCL) excl_row(ex, tag_s[i], eb, ee);
         for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
             for (int j = jb; j < je; ++j) {
                 const double4 pj = pos_s[j];
@@ -2849,7 +2904,7 @@ k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag
                 const double r2 = dx * dx + dy * dy + dz * dz;
                 if (r2 < rmax2 && j != i && r2 > 0.0) {
                     const double r = sqrt(r2);
-                    if (r >= rmin) {
+                    if (r >= rmin && !(EXCL && eb < ee && excl_has(ex.ent, eb, ee, tag_s[j]))) {
                         const double t = (r - rmin) * scale;        // 0 <= t <= width - 1 (+ an ulp): e stays inside the table
                         const int e = min((int)t, elast);
                         const double w = t - (double)e;
@@ -2866,13 +2921,16 @@ k_pair_table(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag
     if (OBS) obs_rows_store(o, blk, rows);
 }
 void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
-                       int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s) {
+                       int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
+                       const PairExclusions *ex) {
     const int nb = nblocks(N, TPB);
     const size_t lds = (size_t)width * sizeof(double2);
     const double scale = (double)(width - 1) / (rmax - rmin);
-    launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
-        hipLaunchKernelGGL(k_pair_table<decltype(obs)::value>, dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N, cell_off, box, nc,
-                           (const double2 *)table, width, rmin, rmax, scale, accumulate, force, r);
+    launch_with_excl(ex, [&](auto excl, ExclRows er) {
+        launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+            hipLaunchKernelGGL((k_pair_table<decltype(obs)::value, decltype(excl)::value>), dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, N,
+                               cell_off, box, nc, (const double2 *)table, width, rmin, rmax, scale, accumulate, force, r, er);
+        });
     });
 }
 

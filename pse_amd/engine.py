@@ -210,6 +210,35 @@ class DihedralList(_TopologyList):
     ndihedrals = property(lambda self: self.count)
 
 
+class ExclusionList:
+    """Owner of a pse_exclusions object: a set of particle pairs that the pair passes skip (HOOMD's nlist.reset_exclusions).  `pairs`
+    is an (npairs, 2) integer array of caller-order particle indices below `n` (default: n_max); a pair listed twice or in either
+    order is one exclusion.  Pass it as `exclusions=` to Engine.pair_table, pair_repulsion or pair_repulsion_virial.  Holds a
+    reference to its engine, whose handle owns the device object."""
+
+    DESTROY = "pse_exclusions_destroy"
+
+    def __init__(self, engine, pairs, n=None):
+        pairs, _ = _topology_arrays(pairs, None, 2, "pairs", "pair")
+        self.n = int(engine.params.n_max if n is None else n)
+        if not 0 <= self.n < 2 ** 32:
+            raise ValueError("n outside [0, 2^32)")
+        self.count, self.engine, self._lib = pairs.shape[0], engine, engine._lib
+        self._obj = ctypes.c_void_p()
+        _lib.check(self._lib.pse_exclusions_create(engine._h, self.n, self.count, ctypes.c_void_p(pairs.ctypes.data), ctypes.byref(self._obj)))
+
+    def _handle(self, engine):
+        """The device object, for a pass of `engine`."""
+        if self._obj is None or not self._obj.value:
+            raise ValueError("this ExclusionList is closed")
+        if engine is not self.engine:
+            raise ValueError("this ExclusionList belongs to another engine")
+        return self._obj
+
+    close = _TopologyList.close
+    __del__ = close
+
+
 class Engine:
     """One PSE engine instance == one `Stokes` object's device state (PSEv1/Stokes.h:128-150)."""
 
@@ -364,36 +393,47 @@ class Engine:
                                             ctypes.byref(m)))
         return out, m.value
 
-    def pair_repulsion(self, pos, force, k, sigma=2.0, group=None, accumulate=True):
-        """Soft repulsion k (sigma - r) r_hat for r < sigma added to (or stored in) `force`."""
+    def pair_repulsion(self, pos, force, k, sigma=2.0, group=None, accumulate=True, exclusions=None):
+        """Soft repulsion k (sigma - r) r_hat for r < sigma added to (or stored in) `force`.  exclusions: an
+        ExclusionList (Engine.exclusions) whose pairs contribute nothing (pse_pair_repulsion_excl); None: every pair in range acts."""
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk4(force, "force"); _chk_group(group)
+        if exclusions is not None:
+            _lib.check(self._lib.pse_pair_repulsion_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                         1 if accumulate else 0, None, exclusions._handle(self)))
+            return force
         _lib.check(self._lib.pse_pair_repulsion(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
                                                 1 if accumulate else 0))
         return force
 
-    def pair_repulsion_virial(self, pos, force, k, sigma=2.0, group=None, accumulate=True, out=None):
+    def pair_repulsion_virial(self, pos, force, k, sigma=2.0, group=None, accumulate=True, out=None, exclusions=None):
         """pair_repulsion plus the pair observables of the same pass (pse_pair_repulsion_virial): returns the 8-element float64 CUDA
         tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs (W_ab = sum_{i<j} d_a F_b, stress = -W / V; see include/pse_amd.h).  `force`
         may be None (observables only).  `out`: where to write them -- e.g. a row of a (samples, 8) log tensor; nothing is read
-        back, the tensor is filled when the stream gets there."""
+        back, the tensor is filled when the stream gets there.  exclusions: as for pair_repulsion; the excluded pairs are in none of
+        the eight numbers."""
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
         if force is not None:
             _chk4(force, "force")
         out = _chk_out8(out, pos)
+        if exclusions is not None:
+            _lib.check(self._lib.pse_pair_repulsion_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                         1 if accumulate else 0, _ptr(out), exclusions._handle(self)))
+            return out
         _lib.check(self._lib.pse_pair_repulsion_virial(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
                                                        1 if accumulate else 0, _ptr(out)))
         return out
 
-    def pair_table(self, pos, force, table, rmin, rmax, group=None, accumulate=True, out=None, observables=True):
+    def pair_table(self, pos, force, table, rmin, rmax, group=None, accumulate=True, out=None, observables=True, exclusions=None):
         """A tabulated central pair potential on the engine's cell list (pse_pair_table; see include/pse_amd.h).  `table`: contiguous
         (width, 2) float64 CUDA tensor, V and F (magnitude of the radial force, positive for a repulsion) at the nodes
         rmin + k (rmax - rmin)/(width - 1), linear in between; pairs with rmin <= r < rmax act.  `force` is incremented (or stored,
         accumulate=False), or None: observables only.  observables=True: returns the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz,
         Wyy, Wyz, Wzz, npairs, written to `out` when one is given (e.g. a row of a log tensor).  observables=False: forces only, the
         reduction is not run, `out` is left alone and None is returned.  Nothing is read back; the stream reads `table`, so keep it
-        alive and unchanged until the stream has passed the call."""
+        alive and unchanged until the stream has passed the call.  exclusions: an ExclusionList (Engine.exclusions) whose pairs
+        contribute nothing to the forces or the eight numbers (pse_pair_table_excl); None: every pair in range acts."""
         import torch
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
@@ -403,9 +443,18 @@ class Engine:
                 and table.shape[1] == 2 and table.is_contiguous()):
             raise ValueError("table must be a contiguous (width, 2) float64 CUDA tensor: V and F at the nodes")
         out = _chk_out8(out, pos) if observables else None
+        if exclusions is not None:
+            _lib.check(self._lib.pse_pair_table_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
+                                                     float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out), exclusions._handle(self)))
+            return out
         _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
                                             float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out)))
         return out
+
+    def exclusions(self, pairs, n=None):
+        """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
+        caller-order particle indices below `n` (default: n_max).  Returns an ExclusionList: the `exclusions=` of the pair passes."""
+        return ExclusionList(self, pairs, n)
 
     def bonds(self, pairs, types=None, kinds=(0,), k=(1.0,), r0=(1.0,), n=None):
         """A bond topology on the device (pse_bonds_create; see include/pse_amd.h): `pairs` (nbonds, 2) particle indices into arrays of

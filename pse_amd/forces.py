@@ -64,22 +64,75 @@ class _ObsProvider:
         return -self.virial / (Lx * Ly * Lz)
 
 
+def exclusion_pairs(bonds=None, angles=None, dihedrals=None):
+    """HOOMD's exclusion sets (nlist.reset_exclusions(['bond', 'angle', 'dihedral'])) of the index arrays that are given: both
+    members of a bond (nb, 2), the two ends of an angle (na, 3: columns 0 and 2), the two ends of a dihedral (nd, 4: columns 0 and
+    3).  Returns their union as an (npairs, 2) int64 array of (smaller, larger) index pairs, each once, in ascending order.  Needs no
+    device; ValueError if nothing was passed."""
+    import numpy as np
+    parts = []
+    for name, a, cols, ends in (("bonds", bonds, 2, (0, 1)), ("angles", angles, 3, (0, 2)), ("dihedrals", dihedrals, 4, (0, 3))):
+        if a is None:
+            continue
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != cols or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer (count, {cols}) array of particle indices")
+        parts.append(a[:, ends].astype(np.int64))
+    if not parts:
+        raise ValueError("from_topology needs at least one of bonds, angles, dihedrals")
+    p = np.concatenate(parts, axis=0)
+    return np.unique(np.stack([p.min(axis=1), p.max(axis=1)], axis=1), axis=0)
+
+
+class Exclusions:
+    """Pairs that the pair providers skip (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` is an (npairs, 2) integer
+    array of particle indices into the system's arrays; order and duplicates do not matter.  Pass the object as `exclusions=` to
+    TablePair or HarmonicRepulsion: the excluded pairs then add nothing to the forces, the energy, the virial or npairs.  In HOOMD
+    bonded pairs are excluded by default; here nothing is excluded unless asked for.  The set is copied to the device once, here."""
+
+    def __init__(self, integrator, pairs):
+        pairs, _ = _topology_arrays(pairs, None, 2, "pairs", "pair")
+        self.integrator, self.npairs_listed = integrator, pairs.shape[0]
+        self._id = integrator.cpp_method.exclusionsCreate(integrator.system.n, pairs.shape[0], pairs.ctypes.data)
+
+    @classmethod
+    def from_topology(cls, integrator, bonds=None, angles=None, dihedrals=None):
+        """The exclusions HOOMD derives from a topology (exclusion_pairs): the union of what is passed."""
+        return cls(integrator, exclusion_pairs(bonds, angles, dihedrals))
+
+
+def _excl_id(integrator, exclusions):
+    """The id of an Exclusions object for a provider of `integrator`, or None."""
+    if exclusions is None:
+        return None
+    if not isinstance(exclusions, Exclusions) or exclusions.integrator is not integrator:
+        raise ValueError("exclusions must be a forces.Exclusions made on the same integrator")
+    return exclusions._id
+
+
 class HarmonicRepulsion(_ObsProvider):
     """F_i = sum_j k (sigma - r)(r_i - r_j)/r for minimum-image pairs with r < sigma (sigma = 2a: contact of unit spheres).
     Evaluated on the integrator's own cell list; sigma must not exceed the hydrodynamic real-space cutoff.
 
     virial=True: compute() makes the fused call (pse_pair_repulsion_virial) instead -- the same forces, plus the potential energy
     and the virial of the same pass in eight device doubles.  `energy`, `virial` and `stress()` copy them to the host when they are
-    read (that waits for the stream); a StressLog samples them without any wait."""
+    read (that waits for the stream); a StressLog samples them without any wait.
+
+    exclusions: an Exclusions object whose pairs do not repel (pse_pair_repulsion_excl); None: every pair in range acts."""
 
     NAME = "HarmonicRepulsion"
 
-    def __init__(self, integrator, k, sigma=2.0, virial=False):
+    def __init__(self, integrator, k, sigma=2.0, virial=False, exclusions=None):
         self.k, self.sigma = float(k), float(sigma)
+        self._excl = _excl_id(integrator, exclusions)
         super().__init__(integrator, virial)
 
     def compute(self, timestep):
         s, members, n = self._group_args()
+        if self._excl is not None:
+            self.integrator.cpp_method.pairRepulsionExcl(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True,
+                                                         _addr(self._fused_out(timestep)), self._excl)
+            return
         if not self._fused:
             self.integrator.cpp_method.pairRepulsion(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True)
             return
@@ -95,11 +148,14 @@ class TablePair(_ObsProvider):
     to the device once, here.
 
     virial=True: the same call also writes the potential energy, the virial and the pair count: `energy`, `virial`, `stress()`,
-    `npairs` and StressLog as for HarmonicRepulsion."""
+    `npairs` and StressLog as for HarmonicRepulsion.
+
+    exclusions: an Exclusions object whose pairs the table does not act on (pse_pair_table_excl) -- what HOOMD does by default for
+    bonded pairs; None: every pair in range acts."""
 
     NAME = "TablePair"
 
-    def __init__(self, integrator, table, rmin, rmax, virial=False):
+    def __init__(self, integrator, table, rmin, rmax, virial=False, exclusions=None):
         import torch
         t = torch.as_tensor(table).detach().to(dtype=torch.float64)
         if t.dim() != 2 or t.shape[1] != 2 or not 2 <= t.shape[0] <= 2048:
@@ -110,20 +166,26 @@ class TablePair(_ObsProvider):
         if not 0.0 <= self.rmin < self.rmax < float("inf"):
             raise ValueError("need 0 <= rmin < rmax, both finite")
         self.table = t.to(integrator.system.pos.device).contiguous().clone()
+        self._excl = _excl_id(integrator, exclusions)
         super().__init__(integrator, virial)
 
     @classmethod
-    def from_functions(cls, integrator, V, F, rmin, rmax, width, virial=False):
+    def from_functions(cls, integrator, V, F, rmin, rmax, width, virial=False, exclusions=None):
         """Sample the callables V(r) and F(r) = -dV/dr (one float in, one float out) at the `width` nodes."""
         import numpy as np
         width, rmin, rmax = int(width), float(rmin), float(rmax)
         if width < 2:
             raise ValueError("width must be at least 2")
         r = rmin + np.arange(width) * ((rmax - rmin) / (width - 1))
-        return cls(integrator, np.array([[float(V(x)), float(F(x))] for x in r]), rmin, rmax, virial=virial)
+        return cls(integrator, np.array([[float(V(x)), float(F(x))] for x in r]), rmin, rmax, virial=virial, exclusions=exclusions)
 
     def compute(self, timestep):
         s, members, n = self._group_args()
+        if self._excl is not None:
+            self.integrator.cpp_method.pairTableExcl(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
+                                                     int(self.table.shape[0]), self.rmin, self.rmax, True, _addr(self._fused_out(timestep)),
+                                                     self._excl)
+            return
         self.integrator.cpp_method.pairTable(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
                                              int(self.table.shape[0]), self.rmin, self.rmax, True, _addr(self._fused_out(timestep)))
 
