@@ -226,7 +226,8 @@ int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4
  * in 32 KB of LDS per workgroup), rmin or rmax not finite, rmin < 0, rmax <= rmin, rmax > rcut (the cell list is built for the
  * hydrodynamic cutoff), a table that is not 16-byte aligned, out8 on a slab rank (n_slabs >= 2: its sums would be partial).  The
  * call only queues work on the handle's stream wherever pse_pair_repulsion does and reads nothing back: the table is read by the
- * stream, the caller keeps it alive and unchanged until the stream has passed the call. */
+ * stream, the caller keeps it alive and unchanged until the stream has passed the call.  Particles of several types, with one
+ * table per pair of types: pse_pair_table_typed below. */
 int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force /* may be NULL */, const unsigned *group, unsigned N,
                    const double *table /* DEVICE, width x 2: V_k, F_k interleaved */, int width, double rmin, double rmax,
                    int accumulate, double *out8 /* DEVICE, may be NULL */);
@@ -263,6 +264,41 @@ int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *forc
  * ex as above.  Summation order, reproducibility and queueing as for pse_pair_table_excl. */
 int pse_pair_repulsion_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
                             double k, double sigma, int accumulate, double *out8 /* DEVICE, may be NULL */, const pse_exclusions *ex);
+
+/* ---- typed pair tables: HOOMD's pair.table with pair_coeff.set('A', 'B', ...) (no reference counterpart: the reference leaves forces to HOOMD) ----
+ * Equal-radius beads that differ only in how they interact -- the blocks of a copolymer, sticky end groups, a binary mixture: every
+ * particle has one of ntypes <= 8 types, and every unordered pair of types its own table.  The hydrodynamics knows no types.
+ * Pair types: npt = ntypes (ntypes + 1)/2 of them; the pair of types a <= b has the index p(a, b) = a ntypes - a (a - 1)/2 + (b - a),
+ * the upper triangle row by row: AA, AB, AC, ..., BB, BC, ...; a pair of particles with types (b, a) uses p(a, b).
+ * Tables: pair type p has width_host[p] nodes between rmin_host[p] and rmax_host[p], with exactly the meaning of pse_pair_table: V and
+ * F linear between the nodes, acting on rmin <= r, r^2 < rmax^2, r > 0, no extrapolation.  tables_host holds the (V_k, F_k) entries
+ * of the pair types one after another in the order of p, sum(width) x 2 doubles.  width_host[p] == 0 switches pair type p off: it
+ * contributes nothing, its rmin and rmax are ignored, it takes no room in tables_host.  All tables together are staged in LDS by every
+ * workgroup: sum(width) <= 3584 entries = 56 KB, which with the kernel's 1.4 KB of static LDS stays inside the 64 KB a workgroup gets
+ * without raising a limit (pse_host_typed_table_layout is the one place that computes where each table lies).
+ * Types: types_host[t] is the type of CALLER-order particle t -- a row of pos and force, a value of `group` -- not of a position in the
+ * group or of a row of the engine's sorted order.  A particle whose index is >= the object's n acts as type 0.
+ * The object belongs to its handle: pse_destroy frees the objects still alive, pse_typed_table_destroy after that is a caller error;
+ * pse_typed_table_destroy waits for the stream.  Everything is copied at creation: the host arrays may go afterwards.
+ * pse_typed_table_create returns PSE_ERR_INVALID, with a message naming the value, for: a null argument, n == 0 or n > n_max, ntypes
+ * outside [1, 8], a type >= ntypes, a width of 1, a negative width or a width > 2048, all widths zero, a sum of widths > 3584, and for
+ * a pair type that is on: rmin or rmax not finite, rmin < 0, rmax <= rmin, rmax > rcut, a table entry that is not finite.  *out is
+ * null after a refusal. */
+typedef struct pse_typed_table pse_typed_table;
+int pse_typed_table_create(pse_handle *h, unsigned n, const unsigned *types_host /* n: type of caller-order row t */, int ntypes,
+                           const int *width_host, const double *rmin_host, const double *rmax_host /* npt each */,
+                           const double *tables_host /* sum(width) x 2: V_k, F_k, the pair types' tables one after another */,
+                           pse_typed_table **out);
+int pse_typed_table_destroy(pse_typed_table *t);
+/* The pass of pse_pair_table_excl on the handle of t with, for every pair, the table and the range of its pair type.  force,
+ * accumulate, w, out8 (meaning and signs of its eight numbers), group and N as there; ex == NULL: nothing is excluded, otherwise the
+ * pairs of ex contribute nothing.  No floating-point atomics, every sum in the engine's sorted order: bit-reproducible on equal
+ * inputs, and unchanged bit for bit when two types swap their labels together with their tables.  Against pse_pair_table with the one
+ * table for all pair types the results agree to rounding, not bit for bit (another kernel).  Queue-only wherever pse_pair_table is:
+ * t (and ex) must stay alive until the stream has passed the call.  PSE_ERR_INVALID, in this order: a null t, N == 0 or N > n_max,
+ * a null pos, force and out8 both null, out8 on a slab rank, an ex created on another handle than t. */
+int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4 *force /* may be NULL */, const unsigned *group,
+                         unsigned N, int accumulate, double *out8 /* DEVICE, may be NULL */, const pse_exclusions *ex /* may be NULL */);
 
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
@@ -626,6 +662,15 @@ int pse_host_dihedral_rows(unsigned n, unsigned ndihedrals, const unsigned *quad
  * > 2^30, an index >= n, a pair with i == j. */
 int pse_host_exclusion_rows(unsigned n, unsigned npairs, const unsigned *pairs, int *row_off /* n + 1 */,
                             unsigned *entries /* room for 2 npairs */);
+/* host-only: where the tables of a typed pair table lie and what the kernel uses of each (pse_typed_table_create calls this).  For
+ * the npt = ntypes (ntypes + 1)/2 pair types in the order p(a, b) of pse_typed_table_create: base[p] = the offset of table p in the
+ * concatenated stage = the sum of the widths before it (an off pair type takes no room), scale[p] = (double)(width - 1)/(rmax - rmin)
+ * -- the expression of pse_pair_table --, rmax2[p] = rmax rmax; scale and rmax2 are 0 for an off pair type (width 0), whose rmin and
+ * rmax are not looked at.  *total = the sum of the widths.  PSE_ERR_INVALID: a null array, ntypes outside [1, 8], a width of 1, a
+ * negative width or a width > 2048, all widths zero, a sum of widths > 3584, and for a pair type that is on: rmin or rmax not finite,
+ * rmin < 0, rmax <= rmin.  Nothing is written after a refusal. */
+int pse_host_typed_table_layout(int ntypes, const int *width, const double *rmin, const double *rmax,
+                                int *base /* npt */, double *scale /* npt */, double *rmax2 /* npt */, int *total);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,10 @@ SYMBOLS = {
     "pse_pair_table_excl": (_i, [_vp, _vp, _vp, _vp, _u, _vp, _i, _d, _d, _i, _vp, _vp]),
     "pse_pair_repulsion_excl": (_i, [_vp, _vp, _vp, _vp, _u, _d, _d, _i, _vp, _vp]),
     "pse_host_exclusion_rows": (_i, [_u, _u, _vp, _vp, _vp]),
+    "pse_typed_table_create": (_i, [_vp, _u, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pse_typed_table_destroy": (_i, [_vp]),
+    "pse_pair_table_typed": (_i, [_vp, _vp, _vp, _vp, _u, _i, _vp, _vp]),
+    "pse_host_typed_table_layout": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

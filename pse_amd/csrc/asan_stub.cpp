@@ -2,7 +2,7 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*, pse_dihedrals_*, pse_exclusions_*) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*, pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -35,6 +35,7 @@ struct pse_bonds : Topology { using Topology::Topology; };
 struct pse_angles : Topology { using Topology::Topology; };
 struct pse_dihedrals : Topology { using Topology::Topology; };
 struct pse_exclusions : Topology { using Topology::Topology; };
+struct pse_typed_table : Topology { using Topology::Topology; };   // row_off: the REAL layout (pse_host_typed_table_layout), entries: the types
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -134,6 +135,26 @@ int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *forc
     if (!h) return fail(PSE_ERR_INVALID, "null handle");
     if (int rc = pair_table_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, N, pos, force, table, width, rmin, rmax, out8)) return rc;
     return pair_excl_validate("pse_pair_table_excl", ex, ex ? ex->h : nullptr, h);
+}
+int pse_typed_table_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const int *width_host, const double *rmin_host,
+                           const double *rmax_host, const double *tables_host, pse_typed_table **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_typed_table_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_typed_table_create: null handle");
+    if (int rc = typed_table_validate(h->d.rcut, h->par.n_max, n, types_host, ntypes, width_host, rmin_host, rmax_host, tables_host)) return rc;
+    const int npt = ntypes * (ntypes + 1) / 2;
+    pse_typed_table *t = new pse_typed_table(h, (size_t)npt, (size_t)n);
+    std::vector<double> scale(npt), rmax2(npt);
+    int total = 0;
+    std::copy(types_host, types_host + n, t->entries.begin());
+    return topology_adopt(t, pse_host_typed_table_layout(ntypes, width_host, rmin_host, rmax_host, t->row_off.data(), scale.data(), rmax2.data(), &total),
+                          out);
+}
+int pse_typed_table_destroy(pse_typed_table *t) { return topology_destroy(t); }
+int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4 *force, const unsigned *, unsigned N, int, double *out8,
+                         const pse_exclusions *ex) {
+    pse_handle *h = t ? t->h : nullptr;
+    return pair_typed_validate(t, h, h ? h->par.n_max : 0u, h ? h->par.n_slabs : 1, N, pos, force, out8, ex, ex ? ex->h : nullptr);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -27,6 +27,7 @@ void Stokes::setParams() {
     m_angles.objs.clear();
     m_dihedrals.objs.clear();
     m_exclusions.objs.clear();
+    m_typed.objs.clear();
     m_m_Lanczos = 2;   // "try two Lanczos iterations to start" (PSEv1/Stokes.cc:131-132)
     pse_params p{};
     p.n_max = m_n_total;
@@ -103,6 +104,26 @@ void Stokes::pairRepulsionExcl(const pse_double4 *pos, pse_double4 *force, const
     if (n == 0 && !out8) return;   // (as pairRepulsion; with out8 an empty group is refused by the C-ABI, as in pairRepulsionVirial)
     check(pse_pair_repulsion_excl(m_h, pos, force, group, n, k, sigma, accumulate ? 1 : 0, out8, m_exclusions.get(ex)),
           "Stokes::pairRepulsionExcl");
+}
+
+int Stokes::typedTableCreate(unsigned int n, const unsigned int *types, int ntypes, const int *width, const double *rmin, const double *rmax,
+                             const double *tables) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    pse_typed_table *t = nullptr;
+    check(pse_typed_table_create(m_h, n, types, ntypes, width, rmin, rmax, tables, &t), "Stokes::typedTableCreate");
+    return m_typed.push(t);
+}
+
+void Stokes::typedTableDestroy(int id) {
+    check(pse_typed_table_destroy(m_typed.get(id)), "Stokes::typedTableDestroy");
+    m_typed.drop(id);
+}
+
+void Stokes::pairTableTyped(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, bool accumulate,
+                            double *out8, int typed, int ex) {
+    if (!m_h) throw std::runtime_error("Stokes::setParams() has not been called");
+    check(pse_pair_table_typed(m_typed.get(typed), pos, force, group, n, accumulate ? 1 : 0, out8, ex < 0 ? nullptr : m_exclusions.get(ex)),
+          "Stokes::pairTableTyped");
 }
 
 int Stokes::bondsCreate(unsigned int n, unsigned int nbonds, const unsigned int *pairs, const unsigned int *types, int ntypes, const int *kind,

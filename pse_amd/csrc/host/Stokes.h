@@ -26,7 +26,7 @@ struct ParticleArrays {
 // The objects of one kind that a Stokes made on its engine, by id -- the position in the table; null once destroyed.
 template <class T>
 struct IdTable {
-    const char *what;   // "bond", "angle", "dihedral", "exclusion": what the error calls them
+    const char *what;   // "bond", "angle", "dihedral", "exclusion", "typed table": what the error calls them
     std::vector<T *> objs;
     int push(T *o) { objs.push_back(o); return (int)objs.size() - 1; }
     T *get(int id) const {
@@ -77,6 +77,15 @@ public:
     // the repulsion likewise (pse_pair_repulsion_excl): out8 null is pairRepulsion, out8 given is pairRepulsionVirial
     void pairRepulsionExcl(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, double k, double sigma,
                            bool accumulate, double *out8, int ex);
+    // typed pair tables (pse_typed_table_create; HOOMD's pair.table with one pair_coeff per pair of types): typedTableCreate copies the
+    // HOST arrays -- n types, and per pair type p(a, b) of the header a width (0: off), rmin and rmax, then the (V, F) tables one after
+    // another -- to the engine and returns the id that pairTableTyped takes; the ids live and die as those of the bond objects do
+    int typedTableCreate(unsigned int n, const unsigned int *types, int ntypes, const int *width, const double *rmin, const double *rmax,
+                         const double *tables);
+    void typedTableDestroy(int id);
+    // the pass of typed table `typed` (pse_pair_table_typed); ex: the id of an exclusion object, or negative: nothing is excluded
+    void pairTableTyped(const pse_double4 *pos, pse_double4 *force, const unsigned int *group, unsigned int n, bool accumulate, double *out8,
+                        int typed, int ex);
     // bonded forces (pse_bonds_create / pse_bond_forces / pse_bonds_overstretched): bondsCreate copies the HOST arrays -- nbonds x 2
     // particle indices, nbonds types or null, ntypes x (kind, k, r0) -- to the engine and returns the id the other calls take.  The
     // bond objects belong to the engine: setParams, which makes a new one, invalidates every id
@@ -123,6 +132,7 @@ private:
     IdTable<pse_angles> m_angles{"angle"};
     IdTable<pse_dihedrals> m_dihedrals{"dihedral"};
     IdTable<pse_exclusions> m_exclusions{"exclusion"};
+    IdTable<pse_typed_table> m_typed{"typed table"};
 };
 
 }  // namespace pse_host

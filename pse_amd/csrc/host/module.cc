@@ -94,6 +94,19 @@ PYBIND11_MODULE(_PSEv1, m) {
             s.pairRepulsionExcl(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate,
                                 ptr<double>(out8), ex);
         })
+        // typed pair tables: HOST arrays by address (numpy .ctypes.data): n uint32 types, npt int32 widths, npt float64 rmin and rmax,
+        // sum(width) x 2 float64 table entries; pairTableTyped takes the id, and the id of an exclusion object or -1
+        .def("typedTableCreate", [](Stokes &s, unsigned int n, std::uintptr_t types, int ntypes, std::uintptr_t width, std::uintptr_t rmin,
+                                    std::uintptr_t rmax, std::uintptr_t tables) {
+            return s.typedTableCreate(n, ptr<const unsigned int>(types), ntypes, ptr<const int>(width), ptr<const double>(rmin),
+                                      ptr<const double>(rmax), ptr<const double>(tables));
+        })
+        .def("typedTableDestroy", &Stokes::typedTableDestroy)
+        .def("pairTableTyped", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, bool accumulate,
+                                  std::uintptr_t out8, int typed, int ex) {
+            s.pairTableTyped(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, accumulate,
+                             ptr<double>(out8), typed, ex);
+        })
         // host arrays by address too (numpy .ctypes.data): nbonds x 2 uint32, nbonds uint32 or 0, ntypes int32 / float64 / float64
         .def("bondsCreate", [](Stokes &s, unsigned int n, unsigned int nbonds, std::uintptr_t pairs, std::uintptr_t types, int ntypes,
                                std::uintptr_t kind, std::uintptr_t k, std::uintptr_t r0) {

@@ -419,6 +419,18 @@ struct pse_bonds : Topology {};
 struct pse_angles : Topology {};
 struct pse_dihedrals : Topology {};
 struct pse_exclusions : Topology {};   // row_off: unsigned, entries: the partners, one unsigned each (pse_host_exclusion_rows); no parameters
+// A typed pair table (include/pse_amd.h): n = particles with a type, count = entries of all tables; `par` holds the two 16-byte words per
+// pair type that k_pair_table_typed stages.  The other arrays are its own: row_off and entries stay null.
+struct pse_typed_table : Topology {
+    unsigned char *types = nullptr;         // n: the type of caller-order particle t
+    unsigned char *type_s = nullptr;        // n_max: the types in sorted order, written by every call (k_type_mirror)
+    double *tables = nullptr;               // count x (V, F)
+    double rmax2_all = 0.0;                 // the largest rmax^2 of the pair types that are on
+    ~pse_typed_table() override {
+        void *ptrs[] = {types, type_s, tables};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
+};
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
@@ -2771,6 +2783,63 @@ extern "C" int pse_exclusions_create(pse_handle *h, unsigned n, unsigned npairs,
     return topology_create(h, "exclusions", n, (unsigned)off[n] / 2, 0, off, ent, nullptr, 0, false, out);
 }
 extern "C" int pse_exclusions_destroy(pse_exclusions *ex) { return topology_destroy(ex); }
+
+// Typed pair tables (include/pse_amd.h): the types, the concatenated tables and the per-pair-type words on the device, and the pass.
+extern "C" int pse_typed_table_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const int *width_host,
+                                      const double *rmin_host, const double *rmax_host, const double *tables_host, pse_typed_table **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_typed_table_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_typed_table_create: null handle");
+    TRY(typed_table_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, width_host, rmin_host, rmax_host, tables_host));
+    HIPCHK(hipSetDevice(h->device));
+    const int npt = ntypes * (ntypes + 1) / 2;
+    std::vector<int> base(npt);
+    std::vector<double> scale(npt), rmax2(npt);
+    int total = 0;
+    TRY(pse_host_typed_table_layout(ntypes, width_host, rmin_host, rmax_host, base.data(), scale.data(), rmax2.data(), &total));
+    std::vector<double> par((size_t)4 * npt);   // (rmin, rmax2), (scale, {base, width - 2}): an off pair type is all zeros
+    double rmax2_all = 0.0;
+    for (int p = 0; p < npt; ++p) {
+        if (width_host[p] == 0) continue;
+        const long long bw = (long long)(unsigned)base[p] | ((long long)(width_host[p] - 2) << 32);
+        par[4 * p] = rmin_host[p]; par[4 * p + 1] = rmax2[p]; par[4 * p + 2] = scale[p];
+        memcpy(&par[4 * p + 3], &bw, sizeof bw);
+        rmax2_all = std::max(rmax2_all, rmax2[p]);
+    }
+    std::vector<unsigned char> types(n);
+    for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
+    pse_typed_table *t = new pse_typed_table();
+    t->h = h; t->n = n; t->count = (unsigned)total; t->ntypes = ntypes; t->rmax2_all = rmax2_all;
+    hipError_t e = hipMalloc((void **)&t->types, n);
+    if (e == hipSuccess) e = hipMemcpy(t->types, types.data(), n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->type_s, (size_t)h->n_max);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->tables, (size_t)total * 2 * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(t->tables, tables_host, (size_t)total * 2 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&t->par, par.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(t->par, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete t;
+        return fail(PSE_ERR_HIP, "pse_typed_table_create: copying %d table entries and %u types to the device failed: %s", total, n,
+                    hipGetErrorString(e));
+    }
+    h->topologies.push_back(t);
+    *out = t;
+    return 0;
+}
+extern "C" int pse_typed_table_destroy(pse_typed_table *t) { return topology_destroy(t); }
+extern "C" int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                    int accumulate, double *out8, const pse_exclusions *ex) {
+    pse_handle *h = t ? t->h : nullptr;
+    TRY(pair_typed_validate(t, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, N, pos, force, out8, ex, ex ? ex->h : nullptr));
+    HIPCHK(hipSetDevice(h->device));
+    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
+    const PairTypedTables tt{t->types, t->type_s, t->tables, (const double *)t->par, t->n, t->ntypes, (int)t->count, t->rmax2_all};
+    launch_pair_table_typed(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, tt, accumulate, (double4 *)force, h->pv_rows, out8,
+                            h->stream, ex ? &er : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
 extern "C" int pse_random_psi(pse_handle *h, pse_double4 *psi, const unsigned *group, unsigned N, unsigned timestep) {
     TRY(check_n(h, N));

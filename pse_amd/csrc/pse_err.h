@@ -40,5 +40,15 @@ int exclusions_validate(unsigned n_max, unsigned n, unsigned npairs, const unsig
 // what pse_pair_table_excl and pse_pair_repulsion_excl (`who`) check behind the validators of the plain passes: an exclusion object,
 // and one of this handle (ex_handle: the handle it was created on)
 int pair_excl_validate(const char *who, const void *ex, const void *ex_handle, const void *h);
+// the same for pse_typed_table_create behind its null-out and null-handle checks: the null arrays, n, the types, and -- through the
+// checks of pse_host_typed_table_layout under the caller's name -- ntypes, the widths, the ranges and the sum of the widths; then
+// rmax against rcut and the table entries
+int typed_table_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const int *width, const double *rmin,
+                         const double *rmax, const double *tables);
+// the argument checks of pse_pair_table_typed, in the order of pse_pair_table_excl: the object (t_handle: the handle it was created
+// on, n_max and n_slabs that handle's), N, pos, force and out8, out8 on a slab rank; then an exclusion object, if one is given, of
+// the same handle
+int pair_typed_validate(const void *t, const void *t_handle, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force,
+                        const void *out8, const void *ex, const void *ex_handle);
 
 }  // namespace pse

@@ -189,6 +189,71 @@ int pair_excl_validate(const char *who, const void *ex, const void *ex_handle, c
     return 0;
 }
 
+// What pse_host_typed_table_layout computes and refuses, under the name `who` of the entry point that asks.
+static int typed_layout(const char *who, int ntypes, const int *width, const double *rmin, const double *rmax, int *base, double *scale,
+                        double *rmax2, int *total) {
+    if (!width || !rmin || !rmax) return fail(PSE_ERR_INVALID, "%s: null array (width, rmin, rmax)", who);
+    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    const int npt = ntypes * (ntypes + 1) / 2;
+    long long sum = 0;
+    for (int p = 0; p < npt; ++p) {
+        if (width[p] < 0 || width[p] == 1 || width[p] > PAIR_TABLE_MAX_WIDTH)
+            return fail(PSE_ERR_INVALID, "%s: pair type %d has width %d, neither 0 (off) nor in [2, %d]", who, p, width[p], PAIR_TABLE_MAX_WIDTH);
+        sum += width[p];
+        if (width[p] == 0) continue;
+        if (!std::isfinite(rmin[p]) || !std::isfinite(rmax[p]))
+            return fail(PSE_ERR_INVALID, "%s: pair type %d: rmin = %g, rmax = %g must be finite", who, p, rmin[p], rmax[p]);
+        if (rmin[p] < 0.0) return fail(PSE_ERR_INVALID, "%s: pair type %d: rmin = %g is negative", who, p, rmin[p]);
+        if (!(rmax[p] > rmin[p])) return fail(PSE_ERR_INVALID, "%s: pair type %d: rmax = %g must exceed rmin = %g", who, p, rmax[p], rmin[p]);
+    }
+    if (sum == 0) return fail(PSE_ERR_INVALID, "%s: all widths are zero: every pair type is off", who);
+    if (sum > PAIR_TYPED_MAX_ENTRIES)
+        return fail(PSE_ERR_INVALID, "%s: the widths sum to %lld entries, more than %d (the tables are staged together in 56 KB of LDS)", who, sum,
+                    PAIR_TYPED_MAX_ENTRIES);
+    int at = 0;
+    for (int p = 0; p < npt; ++p) {
+        const bool on = width[p] != 0;
+        if (base) base[p] = at;
+        if (scale) scale[p] = on ? (double)(width[p] - 1) / (rmax[p] - rmin[p]) : 0.0;
+        if (rmax2) rmax2[p] = on ? rmax[p] * rmax[p] : 0.0;
+        at += width[p];
+    }
+    if (total) *total = at;
+    return 0;
+}
+
+int typed_table_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const int *width, const double *rmin,
+                         const double *rmax, const double *tables) {
+    const char *who = "pse_typed_table_create";
+    if (!types) return fail(PSE_ERR_INVALID, "%s: null types_host", who);
+    if (!tables) return fail(PSE_ERR_INVALID, "%s: null tables_host", who);
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    int total = 0;
+    if (int rc = typed_layout(who, ntypes, width, rmin, rmax, nullptr, nullptr, nullptr, &total)) return rc;
+    for (unsigned i = 0; i < n; ++i)
+        if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    for (int p = 0; p < ntypes * (ntypes + 1) / 2; ++p)
+        if (width[p] != 0 && rmax[p] > rcut)
+            return fail(PSE_ERR_INVALID, "%s: pair type %d: table range rmax = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic "
+                                         "cutoff", who, p, rmax[p], rcut);
+    for (int e = 0; e < 2 * total; ++e)
+        if (!std::isfinite(tables[e])) return fail(PSE_ERR_INVALID, "%s: table entry %d (%s) = %g is not finite", who, e / 2, e % 2 ? "F" : "V", tables[e]);
+    return 0;
+}
+
+int pair_typed_validate(const void *t, const void *t_handle, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force,
+                        const void *out8, const void *ex, const void *ex_handle) {
+    if (!t) return fail(PSE_ERR_INVALID, "pse_pair_table_typed: null typed table");
+    if (int rc = count_in_range(n_max, N)) return rc;
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_pair_table_typed: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_pair_table_typed: force and out8 are both null: nothing to compute");
+    if (out8 && n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "pse_pair_table_typed: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the sums would "
+                                     "be partial (out8 must be null here)", n_slabs);
+    if (ex) return pair_excl_validate("pse_pair_table_typed", ex, ex_handle, t_handle);
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -353,4 +418,11 @@ extern "C" int pse_host_exclusion_rows(unsigned n, unsigned npairs, const unsign
         entries[fill[hi]++] = lo;
     }
     return 0;
+}
+
+// One table after another in the order of the pair types, an off pair type taking no room (see include/pse_amd.h).
+extern "C" int pse_host_typed_table_layout(int ntypes, const int *width, const double *rmin, const double *rmax, int *base, double *scale,
+                                           double *rmax2, int *total) {
+    if (!base || !scale || !rmax2 || !total) return fail(PSE_ERR_INVALID, "pse_host_typed_table_layout: null array (base, scale, rmax2, total)");
+    return typed_layout("pse_host_typed_table_layout", ntypes, width, rmin, rmax, base, scale, rmax2, total);
 }

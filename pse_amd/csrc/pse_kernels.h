@@ -369,6 +369,23 @@ void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, c
 void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const double *table,
                        int width, double rmin, double rmax, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
                        const PairExclusions *ex = nullptr);
+// typed pair tables (k_pair_table_typed; pse_typed_table_create): the device arrays of one object.  types: n bytes, the type of
+// caller-order particle t (a tag >= n acts as type 0); type_s: room for one byte per sorted row, written by every launch behind the
+// sort (k_type_mirror); tables: total x (V, F), the pair types' tables one after another, 16-byte aligned, staged in total * 16 bytes
+// of LDS; par: two 16-byte words per pair type, (rmin, rmax^2) and (scale, {base, width - 2} as two ints in one double's bits), an
+// off pair type with rmax^2 = 0; rmax2_all: the largest rmax^2, the wave-uniform prefilter.  rows, out8, ex as for launch_pair_table
+constexpr int PAIR_TYPED_MAX_PAIR_TYPES = pse::PAIR_TYPED_MAX_TYPES * (pse::PAIR_TYPED_MAX_TYPES + 1) / 2;
+struct PairTypedTables {
+    const unsigned char *types;
+    unsigned char *type_s;
+    const double *tables, *par;
+    unsigned n;
+    int ntypes, total;
+    double rmax2_all;
+};
+void launch_pair_table_typed(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
+                             const PairTypedTables &tt, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
+                             const PairExclusions *ex = nullptr);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
 // entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
 // eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does

@@ -2934,6 +2934,107 @@ void launch_pair_table(const double4 *pos_s, const unsigned *tag_s, int N, const
     });
 }
 
+// Typed pair tables (pse_pair_table_typed; HOOMD's pair.table with one pair_coeff per pair of types): k_pair_table with, for every
+// pair, the table and the range of its pair type p(a, b) = a ntypes - a (a - 1)/2 + (b - a), a <= b.  A kernel of its own and not a
+// third flag of k_pair_table: the plain pass keeps its instruction stream (see the note on shared code above k_pair_repulsion).
+// LDS: the tables of all pair types lie one after another in `total` <= PAIR_TYPED_MAX_ENTRIES 16-byte entries of dynamic LDS (56 KB at
+// the cap), staged as in k_pair_table; the pair type differs from lane to lane, so its parameters cannot come from a scalar load and
+// are staged too (stage_type_params): two 16-byte words per pair type, (rmin, rmax^2) and (scale, {base, width - 2} as two ints in the
+// bits of one double), at most 36 pair types = 1152 bytes of static LDS.  With the 256 bytes of obs_rows_store that is 1408 bytes of
+// static LDS: 57344 + 1408 = 58752 <= 65536.  In the common case of few types most lanes read the same parameter word, which the LDS
+// broadcasts.  An off pair type has rmax^2 = 0 and fails the range test.
+// Where the types come from: a one-byte-per-row mirror in sorted order, type_s[i] = types[tag_s[i]] (0 for a tag >= n), filled by
+// k_type_mirror behind the sort on every call.  A pair in range then costs one byte load at type_s[j], issued next to pos_s[j] and
+// on a line that the neighbouring rows of the run share (64 rows per 64 bytes), where types[tag_s[j]] would be two dependent loads,
+// the second a scattered one -- the chain that makes the exclusion lookup cost what it does.  The mirror pass reads 4 + 1 bytes and
+// writes one per row, against the 32-byte position gathers of some tens of partners per row here.  Nobody has measured the other form.
+// Per pair: the wave-uniform prefilter r^2 < max_p rmax^2, j != i, r^2 > 0 first; only behind it the partner's type and the
+// parameter words; then the pair type's own rmax^2 and rmin and, with EXCL, the lookup of k_pair_table<OBS, true> (the tag is read
+// only by lanes that have a row).  From t on the arithmetic is k_pair_table's line for line.  No lane leaves before a barrier.
+__global__ void __launch_bounds__(TPB)
+k_type_mirror(const unsigned *__restrict__ tag_s, int N, const unsigned char *__restrict__ types, unsigned n, unsigned char *__restrict__ type_s) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i < N) {
+        const unsigned t = tag_s[i];
+        type_s[i] = t < n ? types[t] : (unsigned char)0;   // never past n
+    }
+}
+template <bool OBS, bool EXCL>
+__global__ void __launch_bounds__(TPB)
+k_pair_table_typed(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, const unsigned char *__restrict__ type_s, int N,
+                   const int *__restrict__ cell_off, DBox box, DCells nc, const double2 *__restrict__ tables, int total,
+                   const double2 *__restrict__ par /* 2 npt words */, int ntypes, double rmax2_all, int accumulate,
+                   double4 *__restrict__ force, double *__restrict__ rows /* OBS: [gridDim.x][PV_NOBS] */, ExclRows ex) {
+    extern __shared__ pt_entry pt_tab[];   // [total]
+    __shared__ pt_entry tp[2 * PAIR_TYPED_MAX_PAIR_TYPES];   // [pair type][0] = (rmin, rmax2), [1] = (scale, {base, width - 2})
+    for (int e = threadIdx.x; e < total; e += TPB) pt_tab[e] = ((const pt_entry *)tables)[e];
+    stage_type_params(tp, par, ntypes * (ntypes + 1) / 2);   // (its barrier is the one behind both stages)
+    const int blk = xcd_block(blockIdx.x, gridDim.x);
+    const int i = blk * TPB + threadIdx.x;
+    double o[PV_NOBS];
+#pragma unroll
+    for (int q = 0; q < PV_NOBS; ++q) o[q] = 0.0;
+    if (i < N) {
+        const double4 pi = pos_s[i];
+        double fx, fy, fz;
+        frac_coords(box, pi.x, pi.y, pi.z, fx, fy, fz);
+        const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
+        const int ti = type_s[i];
+        double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        unsigned eb = 0u, ee = 0u;
+        if (EXCL) excl_row(ex, tag_s[i], eb, ee);
+        for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
+            for (int j = jb; j < je; ++j) {
+                const double4 pj = pos_s[j];
+                double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                min_image(box, dx, dy, dz);
+                const double r2 = dx * dx + dy * dy + dz * dz;
+                if (r2 < rmax2_all && j != i && r2 > 0.0) {
+                    const int tj = type_s[j];
+                    const int lo = min(ti, tj), hi = max(ti, tj);
+                    const int p = lo * ntypes - ((lo * (lo - 1)) >> 1) + (hi - lo);
+                    const pt_entry q0 = tp[2 * p];
+                    if (r2 < q0.y) {
+                        const double r = sqrt(r2), rmin = q0.x;
+                        if (r >= rmin && !(EXCL && eb < ee && excl_has(ex.ent, eb, ee, tag_s[j]))) {
+                            const pt_entry q1 = tp[2 * p + 1];
+                            const double scale = q1.x;
+                            const long long bw = __double_as_longlong(q1.y);
+                            const int base = (int)(unsigned)bw, elast = (int)(bw >> 32);
+                            const double t = (r - rmin) * scale;        // 0 <= t <= width - 1 (+ an ulp): e stays inside the table
+                            const int e = min((int)t, elast);
+                            const double w = t - (double)e;
+                            const pt_entry a = pt_tab[base + e], b = pt_tab[base + e + 1];
+                            const double c = (a.y + w * (b.y - a.y)) * (1.0 / r);
+                            Fx += c * dx; Fy += c * dy; Fz += c * dz;
+                            if (OBS && j > i) obs_add_central(o, a.x + w * (b.x - a.x), c, dx, dy, dz);
+                        }
+                    }
+                }
+            }
+        });
+        if (force) force_row_store(force, tag_s[i], accumulate, Fx, Fy, Fz);
+    }
+    if (OBS) obs_rows_store(o, blk, rows);
+}
+void launch_pair_table_typed(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
+                             const PairTypedTables &tt, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
+                             const PairExclusions *ex) {
+    static_assert(2 * PAIR_TYPED_MAX_PAIR_TYPES <= TPB, "one lane stages one 16-byte word of the parameters");
+    static_assert((size_t)PAIR_TYPED_MAX_ENTRIES * sizeof(pt_entry) + 2 * PAIR_TYPED_MAX_PAIR_TYPES * sizeof(pt_entry)
+                  + (TPB / 64) * PV_NOBS * sizeof(double) <= 65536, "tables, parameters and the reduction share 64 KB of LDS");
+    const int nb = nblocks(N, TPB);
+    const size_t lds = (size_t)tt.total * sizeof(pt_entry);
+    hipLaunchKernelGGL(k_type_mirror, dim3(nb), dim3(TPB), 0, s, tag_s, N, tt.types, tt.n, tt.type_s);
+    launch_with_excl(ex, [&](auto excl, ExclRows er) {
+        launch_with_obs(nb, rows, out8, s, [&](auto obs, double *r) {
+            hipLaunchKernelGGL((k_pair_table_typed<decltype(obs)::value, decltype(excl)::value>), dim3(nb), dim3(TPB), lds, s, pos_s, tag_s,
+                               tt.type_s, N, cell_off, box, nc, (const double2 *)tt.tables, tt.total, (const double2 *)tt.par, tt.ntypes,
+                               tt.rmax2_all, accumulate, force, r, er);
+        });
+    });
+}
+
 // Bonded forces (HOOMD's bond.harmonic and bond.fene; no reference counterpart: the reference leaves forces to HOOMD).  One thread
 // per particle of the CALLER-order arrays walks its row of the bond object -- entries (partner, type), one 8-byte load each, sorted by
 // (partner, type) on the host -- and gathers each partner's position with one double4 load.  With d = r_i - r_j (minimum image),

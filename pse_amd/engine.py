@@ -239,6 +239,95 @@ class ExclusionList:
     __del__ = close
 
 
+PAIR_TYPED_MAX_TYPES = 8   # pse_typed_table_create: particle types, and with them at most 36 pair types
+
+
+def pair_type_index(a, b, ntypes):
+    """The index of the pair of types (a, b), either order, among the ntypes (ntypes + 1)/2 pair types (include/pse_amd.h): the
+    upper triangle row by row."""
+    a, b = (a, b) if a <= b else (b, a)
+    return a * ntypes - a * (a - 1) // 2 + (b - a)
+
+
+def _typed_tables(tables, ntypes):
+    """The `tables` dictionary {(a, b): (table, rmin, rmax)} of a typed pair table as the arrays of pse_typed_table_create: (widths
+    int32 (npt,), rmin float64 (npt,), rmax float64 (npt,), entries float64 (sum of widths, 2)).  A key may name its types in either
+    order; both orders of one pair are a ValueError; a pair that is missing is off (width 0).  Needs no device."""
+    import numpy as np
+    if not isinstance(tables, dict) or not tables:
+        raise ValueError("tables must be a non-empty dict {(a, b): (table, rmin, rmax)}")
+    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
+        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    npt = ntypes * (ntypes + 1) // 2
+    width, rmin, rmax, parts = np.zeros(npt, dtype=np.int32), np.zeros(npt), np.zeros(npt), [None] * npt
+    for key, value in tables.items():
+        if not (isinstance(key, tuple) and len(key) == 2 and all(isinstance(t, (int, np.integer)) for t in key)):
+            raise ValueError(f"tables key {key!r} is not a pair (a, b) of integer types")
+        a, b = int(key[0]), int(key[1])
+        if not (0 <= a < ntypes and 0 <= b < ntypes):
+            raise ValueError(f"tables key {key!r} names a type outside [0, {ntypes})")
+        p = pair_type_index(a, b, ntypes)
+        if parts[p] is not None:
+            raise ValueError(f"tables holds both ({a}, {b}) and ({b}, {a}): one pair of types, one table")
+        if not (isinstance(value, (tuple, list)) and len(value) == 3):
+            raise ValueError(f"tables[{key!r}] must be (table, rmin, rmax)")
+        t = value[0].detach().cpu().numpy() if hasattr(value[0], "detach") else value[0]
+        t = np.array(t, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != 2 or not 2 <= t.shape[0] <= 2048:
+            raise ValueError(f"tables[{key!r}]: the table must be (width, 2) with 2 <= width <= 2048: V and F at the nodes")
+        if not np.isfinite(t).all():
+            raise ValueError(f"tables[{key!r}]: table entries must be finite")
+        lo, hi = float(value[1]), float(value[2])
+        if not 0.0 <= lo < hi < float("inf"):
+            raise ValueError(f"tables[{key!r}]: need 0 <= rmin < rmax, both finite")
+        width[p], rmin[p], rmax[p], parts[p] = t.shape[0], lo, hi, t
+    return width, rmin, rmax, np.ascontiguousarray(np.concatenate([t for t in parts if t is not None], axis=0))
+
+
+def _typed_types(types, tables):
+    """(uint32 types, ntypes): the type array of a typed pair table, checked; ntypes is one more than the largest type in `types`
+    or in a key of `tables`."""
+    import numpy as np
+    types = np.asarray(types)
+    if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
+        raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
+    keys = [int(t) for key in tables for t in key] if isinstance(tables, dict) and all(isinstance(k, tuple) for k in tables) else []
+    return np.ascontiguousarray(types, dtype=np.uint32), max([int(types.max())] + keys) + 1
+
+
+class TypedTable:
+    """Owner of a pse_typed_table object: one type per particle and one tabulated potential per pair of types (HOOMD's pair.table with
+    a pair_coeff per type pair).  `types`: (n,) integers, the type of caller-order particle t; a particle past them acts as type 0.
+    `tables`: {(a, b): (table, rmin, rmax)} with `table` a (width, 2) array of V and F at the nodes as for Engine.pair_table; either
+    order of a key, a missing pair is off.  Pass it as `typed` to Engine.pair_table_typed.  Holds a reference to its engine, whose
+    handle owns the device object."""
+
+    DESTROY = "pse_typed_table_destroy"
+
+    def __init__(self, engine, types, tables, n=None):
+        types, self.ntypes = _typed_types(types, tables)
+        width, rmin, rmax, entries = _typed_tables(tables, self.ntypes)
+        self.n = int(types.shape[0] if n is None else n)
+        if not 0 <= self.n <= types.shape[0]:
+            raise ValueError("n outside [0, len(types)]")
+        self.count, self.engine, self._lib = int(width.sum()), engine, engine._lib
+        self._obj = ctypes.c_void_p()
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+        _lib.check(self._lib.pse_typed_table_create(engine._h, self.n, vp(types), self.ntypes, vp(width), vp(rmin), vp(rmax), vp(entries),
+                                                    ctypes.byref(self._obj)))
+
+    def _handle(self, engine):
+        """The device object, for a pass of `engine`."""
+        if self._obj is None or not self._obj.value:
+            raise ValueError("this TypedTable is closed")
+        if engine is not self.engine:
+            raise ValueError("this TypedTable belongs to another engine")
+        return self._obj
+
+    close = _TopologyList.close
+    __del__ = close
+
+
 class Engine:
     """One PSE engine instance == one `Stokes` object's device state (PSEv1/Stokes.h:128-150)."""
 
@@ -449,6 +538,26 @@ class Engine:
             return out
         _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
                                             float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out)))
+        return out
+
+    def typed_table(self, types, tables, n=None):
+        """A typed pair table on the device (pse_typed_table_create; see include/pse_amd.h): `types` (n,) the type of every
+        caller-order particle, `tables` {(a, b): (table, rmin, rmax)} one tabulated potential per pair of types, either order of a
+        key, a missing pair off; `n`: how many of `types` to use (default: all).  Returns a TypedTable: the `typed` of
+        pair_table_typed."""
+        return TypedTable(self, types, tables, n)
+
+    def pair_table_typed(self, pos, force, typed, group=None, accumulate=True, out=None, observables=True, exclusions=None):
+        """Engine.pair_table with, for every pair, the table and the range of its pair of types (pse_pair_table_typed).  `typed`: a
+        TypedTable (Engine.typed_table).  `force`, `group`, `accumulate`, `out`, `observables` and what is returned as for
+        pair_table; exclusions: an ExclusionList whose pairs contribute nothing, None: every pair in range acts."""
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if force is not None:
+            _chk4(force, "force")
+        out = _chk_out8(out, pos) if observables else None
+        _lib.check(self._lib.pse_pair_table_typed(typed._handle(self), _ptr(pos), _ptr(force), _ptr(group), n, 1 if accumulate else 0,
+                                                  _ptr(out), None if exclusions is None else exclusions._handle(self)))
         return out
 
     def exclusions(self, pairs, n=None):

@@ -2,7 +2,7 @@
 PSEv1/Stokes.cc:447; its example script has none).  SURVEY.md 8 f4: the step either side of the hot path, kept minimal."""
 import math
 
-from .engine import ANGLE_KINDS, BOND_KINDS, DIHEDRAL_KINDS, _per_type, _topology_arrays, _type_params
+from .engine import ANGLE_KINDS, BOND_KINDS, DIHEDRAL_KINDS, _per_type, _topology_arrays, _type_params, _typed_tables, _typed_types
 
 
 class _ObsProvider:
@@ -188,6 +188,90 @@ class TablePair(_ObsProvider):
             return
         self.integrator.cpp_method.pairTable(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
                                              int(self.table.shape[0]), self.rmin, self.rmax, True, _addr(self._fused_out(timestep)))
+
+
+def _typed_arguments(types, tables, type_names):
+    """What TypedTablePair checks before it touches the device: `types` and the keys of `tables` as integers -- a name is its
+    position in `type_names` --, then the arrays of pse_typed_table_create (engine._typed_tables).  Returns (types uint32, ntypes,
+    widths, rmin, rmax, entries)."""
+    if not isinstance(tables, dict) or not tables:
+        raise ValueError("tables must be a non-empty dict {(a, b): (table, rmin, rmax)}")
+    names = None if type_names is None else list(type_names)
+    if names is not None and (len(set(names)) != len(names) or not all(isinstance(v, str) for v in names)):
+        raise ValueError("type_names must be distinct strings")
+
+    def code(v):
+        if not isinstance(v, str):
+            return v
+        if names is None:
+            raise ValueError(f"type name {v!r}: names need a type_names= list")
+        if v not in names:
+            raise ValueError(f"unknown type name {v!r}: type_names is {names}")
+        return names.index(v)
+
+    types = [code(v) for v in (types.tolist() if hasattr(types, "tolist") else list(types))]
+    coded = {}
+    for key, value in tables.items():
+        k = tuple(code(v) for v in key) if isinstance(key, tuple) else key
+        if k in coded:
+            raise ValueError(f"tables names the pair {key!r} twice, by name and by number")
+        coded[k] = value
+    types, ntypes = _typed_types(types, coded)
+    return (types, max(ntypes, len(names or ()))) + _typed_tables(coded, max(ntypes, len(names or ())))
+
+
+class TypedTablePair(_ObsProvider):
+    """One tabulated pair potential per pair of particle types (pse_pair_table_typed; HOOMD's pair.table with pair_coeff.set('A', 'B',
+    ...)): `types` gives every particle of the system its type -- integers, or names with a `type_names=` list, whose order numbers
+    them --, `tables` is a dict {(a, b): (table, rmin, rmax)} with `table`, `rmin` and `rmax` as for TablePair.  A key may name its two
+    types in either order (both orders of one pair are a ValueError); a pair of types without a key does not interact.  At most 8
+    types, and at most 3584 table entries over all pairs of types.  Types and tables are copied to the device once, here.
+
+    virial=True: `energy`, `virial`, `stress()`, `npairs` and StressLog as for TablePair -- with all pair types but one off, `npairs`
+    counts the contacts of that pair of types.  exclusions: as for TablePair."""
+
+    NAME = "TypedTablePair"
+
+    def __init__(self, integrator, types, tables, virial=False, exclusions=None, type_names=None):
+        types, self.ntypes, width, rmin, rmax, entries = _typed_arguments(types, tables, type_names)   # (raises before the device is touched)
+        n = integrator.system.n
+        if types.shape[0] != n:
+            raise ValueError(f"types has {types.shape[0]} entries, the system {n} particles")
+        self.types, self.widths, self.rmin, self.rmax, self.tables = types, width, rmin, rmax, entries
+        self._excl = _excl_id(integrator, exclusions)
+        self._id = integrator.cpp_method.typedTableCreate(n, types.ctypes.data, self.ntypes, width.ctypes.data, rmin.ctypes.data,
+                                                          rmax.ctypes.data, entries.ctypes.data)
+        super().__init__(integrator, virial)
+
+    @classmethod
+    def from_functions(cls, integrator, types, functions, virial=False, exclusions=None, type_names=None):
+        """`functions`: {(a, b): (V, F, rmin, rmax, width)} -- the callables V(r) and F(r) = -dV/dr (one float in, one float out) of
+        each pair of types, sampled at `width` nodes as TablePair.from_functions samples them."""
+        import numpy as np
+        if not isinstance(functions, dict) or not functions:
+            raise ValueError("functions must be a non-empty dict {(a, b): (V, F, rmin, rmax, width)}")
+        tables = {}
+        for key, value in functions.items():
+            if not (isinstance(value, (tuple, list)) and len(value) == 5):
+                raise ValueError(f"functions[{key!r}] must be (V, F, rmin, rmax, width)")
+            V, F, rmin, rmax, width = value[0], value[1], float(value[2]), float(value[3]), int(value[4])
+            if width < 2:
+                raise ValueError("width must be at least 2")
+            r = rmin + np.arange(width) * ((rmax - rmin) / (width - 1))
+            tables[key] = (np.array([[float(V(x)), float(F(x))] for x in r]), rmin, rmax)
+        return cls(integrator, types, tables, virial=virial, exclusions=exclusions, type_names=type_names)
+
+    def table(self, a, b):
+        """The (width, 2) table of the pair of types (a, b), integers, as it was copied to the device; None if the pair is off."""
+        from .engine import pair_type_index
+        p = pair_type_index(int(a), int(b), self.ntypes)
+        first = int(self.widths[:p].sum())
+        return self.tables[first:first + int(self.widths[p])] if self.widths[p] else None
+
+    def compute(self, timestep):
+        s, members, n = self._group_args()
+        self.integrator.cpp_method.pairTableTyped(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, True, _addr(self._fused_out(timestep)),
+                                                  self._id, -1 if self._excl is None else self._excl)
 
 
 class Bonds(_ObsProvider):
