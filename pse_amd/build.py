@@ -1,6 +1,6 @@
 """Builds libpse_amd.so (HIP kernels + C-ABI) and the pybind11 host module in-tree with hipcc for gfx950.
 
-Run as `python -m pse_amd.build` or through __graft_entry__.build(). No cmake: three translation units.
+Run as `python -m pse_amd.build` or through __graft_entry__.build(). No cmake: one hipcc call per translation unit (LIB_UNITS) and one link.
 """
 import os
 import subprocess
@@ -48,6 +48,7 @@ def _all_sources():
 
 
 LIB_UNITS = (("pse_kernels.hip", HIPFLAGS), ("pse_farfield.hip", HIPFLAGS + FARFLAGS), ("pse_capi.hip", HIPFLAGS), ("pse_local.hip", HIPFLAGS), ("pse_zfft.hip", HIPFLAGS),
+             ("pse_forces.hip", HIPFLAGS),
              ("pse_params.cpp", ["-x", "c++"]), ("pse_host_api.cpp", ["-x", "c++"]))
 _report = []   # what build_all did, one entry per artefact: (name, "compiled" | "reused")
 

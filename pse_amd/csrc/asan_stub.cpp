@@ -2,7 +2,9 @@
 // libpse_amd.so): GPU AddressSanitizer is not available on the MI355X pool, so the host-side code -- the parameter rule and the
 // real-space table builder (pse_params.cpp), the tridiagonal solver, and the C++ host classes (csrc/host/) -- is
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
-// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*, pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed) keep a small host object that runs the REAL parameter
+// pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
+// ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>

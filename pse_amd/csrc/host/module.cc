@@ -65,81 +65,11 @@ PYBIND11_MODULE(_PSEv1, m) {
                                                        ptr<const unsigned int>(group), n});
         })
         .def("integrateStepTwo", &Stokes::integrateStepTwo)
-        .def("pairRepulsion", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, double k,
-                                 double sigma, bool accumulate) {
-            s.pairRepulsion(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate);
-        })
-        .def("pairRepulsionVirial", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, double k,
-                                       double sigma, bool accumulate, std::uintptr_t out8) {
-            s.pairRepulsionVirial(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate,
-                                  ptr<double>(out8));
-        })
-        .def("pairTable", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, std::uintptr_t table,
-                             int width, double rmin, double rmax, bool accumulate, std::uintptr_t out8) {
-            s.pairTable(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, ptr<const double>(table), width,
-                        rmin, rmax, accumulate, ptr<double>(out8));
-        })
-        // pair exclusions: npairs x 2 uint32 HOST indices by address (numpy .ctypes.data); the _excl passes take the id
-        .def("exclusionsCreate", [](Stokes &s, unsigned int n, unsigned int npairs, std::uintptr_t pairs) {
-            return s.exclusionsCreate(n, npairs, ptr<const unsigned int>(pairs));
-        })
-        .def("exclusionsDestroy", &Stokes::exclusionsDestroy)
-        .def("pairTableExcl", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, std::uintptr_t table,
-                                 int width, double rmin, double rmax, bool accumulate, std::uintptr_t out8, int ex) {
-            s.pairTableExcl(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, ptr<const double>(table),
-                            width, rmin, rmax, accumulate, ptr<double>(out8), ex);
-        })
-        .def("pairRepulsionExcl", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, double k,
-                                     double sigma, bool accumulate, std::uintptr_t out8, int ex) {
-            s.pairRepulsionExcl(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, k, sigma, accumulate,
-                                ptr<double>(out8), ex);
-        })
-        // typed pair tables: HOST arrays by address (numpy .ctypes.data): n uint32 types, npt int32 widths, npt float64 rmin and rmax,
-        // sum(width) x 2 float64 table entries; pairTableTyped takes the id, and the id of an exclusion object or -1
-        .def("typedTableCreate", [](Stokes &s, unsigned int n, std::uintptr_t types, int ntypes, std::uintptr_t width, std::uintptr_t rmin,
-                                    std::uintptr_t rmax, std::uintptr_t tables) {
-            return s.typedTableCreate(n, ptr<const unsigned int>(types), ntypes, ptr<const int>(width), ptr<const double>(rmin),
-                                      ptr<const double>(rmax), ptr<const double>(tables));
-        })
-        .def("typedTableDestroy", &Stokes::typedTableDestroy)
-        .def("pairTableTyped", [](Stokes &s, std::uintptr_t pos, std::uintptr_t force, std::uintptr_t group, unsigned int n, bool accumulate,
-                                  std::uintptr_t out8, int typed, int ex) {
-            s.pairTableTyped(ptr<const pse_double4>(pos), ptr<pse_double4>(force), ptr<const unsigned int>(group), n, accumulate,
-                             ptr<double>(out8), typed, ex);
-        })
-        // host arrays by address too (numpy .ctypes.data): nbonds x 2 uint32, nbonds uint32 or 0, ntypes int32 / float64 / float64
-        .def("bondsCreate", [](Stokes &s, unsigned int n, unsigned int nbonds, std::uintptr_t pairs, std::uintptr_t types, int ntypes,
-                               std::uintptr_t kind, std::uintptr_t k, std::uintptr_t r0) {
-            return s.bondsCreate(n, nbonds, ptr<const unsigned int>(pairs), ptr<const unsigned int>(types), ntypes, ptr<const int>(kind),
-                                 ptr<const double>(k), ptr<const double>(r0));
-        })
-        .def("bondForces", [](Stokes &s, int id, std::uintptr_t pos, std::uintptr_t force, bool accumulate, std::uintptr_t out8) {
-            s.bondForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
-        })
-        .def("bondsOverstretched", &Stokes::bondsOverstretched)
-        .def("bondsDestroy", &Stokes::bondsDestroy)
-        // nangles x 3 uint32 (end, vertex, end), nangles uint32 or 0, ntypes int32 / float64 / float64
-        .def("anglesCreate", [](Stokes &s, unsigned int n, unsigned int nangles, std::uintptr_t triples, std::uintptr_t types, int ntypes,
-                                std::uintptr_t kind, std::uintptr_t k, std::uintptr_t theta0) {
-            return s.anglesCreate(n, nangles, ptr<const unsigned int>(triples), ptr<const unsigned int>(types), ntypes, ptr<const int>(kind),
-                                  ptr<const double>(k), ptr<const double>(theta0));
-        })
-        .def("angleForces", [](Stokes &s, int id, std::uintptr_t pos, std::uintptr_t force, bool accumulate, std::uintptr_t out8) {
-            s.angleForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
-        })
-        .def("anglesDestroy", &Stokes::anglesDestroy)
-        // ndihedrals x 4 uint32 (i, j, k, l), ndihedrals uint32 or 0, ntypes int32, ntypes x 4 float64
-        .def("dihedralsCreate", [](Stokes &s, unsigned int n, unsigned int ndihedrals, std::uintptr_t quads, std::uintptr_t types, int ntypes,
-                                   std::uintptr_t kind, std::uintptr_t params) {
-            return s.dihedralsCreate(n, ndihedrals, ptr<const unsigned int>(quads), ptr<const unsigned int>(types), ntypes, ptr<const int>(kind),
-                                     ptr<const double>(params));
-        })
-        .def("dihedralForces", [](Stokes &s, int id, std::uintptr_t pos, std::uintptr_t force, bool accumulate, std::uintptr_t out8) {
-            s.dihedralForces(id, ptr<const pse_double4>(pos), ptr<pse_double4>(force), accumulate, ptr<double>(out8));
-        })
-        .def("dihedralsDestroy", &Stokes::dihedralsDestroy)
         .def("lanczosIterations", &Stokes::lanczosIterations)
         .def("hashedSeed", &Stokes::hashedSeed)
+        // the engine for callers of the C-ABI beside this class (pse_amd.engine.StokesEngine): its address, 0 before setParams
+        .def("handle", [](const Stokes &s) { return reinterpret_cast<std::uintptr_t>(s.handle()); })
+        .def("engineSerial", &Stokes::engineSerial)
         .def("info", [](const Stokes &s) {
             const pse_info i = s.info();
             py::dict d;

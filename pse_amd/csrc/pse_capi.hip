@@ -29,6 +29,7 @@
 #include "pse_err.h"
 #include "pse_host.h"
 #include "pse_kernels.h"
+#include "pse_forces.h"
 #include "pse_local.h"
 
 using namespace pse;

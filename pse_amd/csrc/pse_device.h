@@ -107,6 +107,15 @@ __device__ __forceinline__ void vq_unpack(vq4 w, double &x, double &y, double &z
     z = fma((double)hz, 4294967296.0, (double)w.z) * sc;
 }
 
+// ---- launch geometry and the wave reduction that the kernel files share ----------------------------------------------------------
+constexpr int TPB = 256;   // threads per workgroup of the one-thread-per-row kernels: four waves
+static inline int nblocks(long n, int tpb) { return (int)((n + tpb - 1) / tpb); }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 __device__ __forceinline__ int wrapi(int a, int n) { a %= n; return a < 0 ? a + n : a; }
 
 // ---- Philox4x32-10 ------------------------------------------------------------------------------------

@@ -21,9 +21,6 @@
 
 namespace pse {
 
-static inline int nblocks(long n, int tpb) { return (int)((n + tpb - 1) / tpb); }
-
-
 struct FarRec {
     int ox, oy, oz;          // support origin (first node per axis), wrapped into the grid
     unsigned idx;            // index in the cell-sorted arrays; bit 31: owned by another slab rank

@@ -4,9 +4,7 @@
 
 namespace pse {
 
-constexpr int TPB = 256;
 constexpr unsigned KEY_FOREIGN = 0xFFFFFFFFu;
-static inline int nblocks(long n, int tpb) { return (int)((n + tpb - 1) / tpb); }
 
 // cell layer cx relative to the first layer of the rank's slab, nearest periodic image around the slab's centre:
 // 0 .. per - 1 = own layers, negative = towards the left neighbour, >= per = towards the right one

@@ -136,47 +136,75 @@ def _type_params(kinds, k, x, xname, table, what, width=None):
             None if x is None else np.array(x, dtype=np.float64))
 
 
-class _TopologyList:
+class _DeviceObject:
+    """What the owners of a device object share.  The object belongs to one handle, which frees it when it goes: the owner holds a
+    reference to its engine (an Engine, or the StokesEngine of an integrator) and the engine's serial at creation, and a changed
+    serial -- Engine.close(), or a setParams() of the integrator, which makes a new handle -- says that the object went with its
+    handle.  A subclass names the library function that frees the object (DESTROY)."""
+
+    def _create(self, engine, create, *args):
+        """create(handle, *args, &object) on the handle of `engine`."""
+        self.engine, self._lib, self._obj = engine, engine._lib, ctypes.c_void_p()
+        _lib.check(getattr(self._lib, create)(engine._h, *args, ctypes.byref(self._obj)))
+        self._serial = engine.serial
+
+    def _handle(self, engine=None):
+        """The device object, for a pass of `engine` (None: of its own engine)."""
+        if self._obj is None or not self._obj.value:
+            raise ValueError(f"this {type(self).__name__} is closed")
+        if engine is not None and engine is not self.engine:
+            raise ValueError(f"this {type(self).__name__} belongs to another engine")
+        if self.engine.serial != self._serial:
+            raise ValueError(f"this {type(self).__name__} went with the engine it was made on (setParams makes a new engine, close() ends "
+                             "one): make it again")
+        return self._obj
+
+    def close(self):
+        o, self._obj = getattr(self, "_obj", None), None
+        if o is not None and o.value and self.engine.serial == self._serial:   # (otherwise the handle freed it already)
+            getattr(self._lib, self.DESTROY)(o)
+
+    __del__ = close
+
+
+def _rows(engine, n):
+    """How many rows of the caller-order arrays an object covers: `n`, or the engine's n_max."""
+    n = int(engine.n_max if n is None else n)
+    if not 0 <= n < 2 ** 32:
+        raise ValueError("n outside [0, 2^32)")
+    return n
+
+
+def _vp(a):
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+class _TopologyList(_DeviceObject):
     """What BondList, AngleList and DihedralList share: the owner of a device topology among the rows of the caller-order arrays.
-    Holds a reference to its engine, whose handle owns the device object.  A subclass names its entries (WHAT), its index array
-    (INDEX, COLS columns), its second parameter (X) -- or, with WIDTH parameters per type, the one array of them -- its kind table and
-    its three library functions."""
+    A subclass names its entries (WHAT), its index array (INDEX, COLS columns), its second parameter (X) -- or, with WIDTH
+    parameters per type, the one array of them -- its kind table and its three library functions."""
 
     WIDTH = None
 
     def __init__(self, engine, index, types, kinds, k, x, n):
         index, types = _topology_arrays(index, types, self.COLS, self.INDEX, self.WHAT)
         kind_a, k_a, x_a = _type_params(kinds, k, x, self.X, self.KINDS, self.WHAT, self.WIDTH)
-        self.n = int(engine.params.n_max if n is None else n)
-        if not 0 <= self.n < 2 ** 32:
-            raise ValueError("n outside [0, 2^32)")
-        self.count, self.engine, self._lib = index.shape[0], engine, engine._lib
-        self._obj = ctypes.c_void_p()
-        vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        par = (vp(k_a),) if x_a is None else (vp(k_a), vp(x_a))
-        _lib.check(getattr(self._lib, self.CREATE)(engine._h, self.n, self.count, vp(index), vp(types), len(kind_a), vp(kind_a), *par,
-                                                   ctypes.byref(self._obj)))
+        self.n, self.count = _rows(engine, n), index.shape[0]
+        par = (_vp(k_a),) if x_a is None else (_vp(k_a), _vp(x_a))
+        self._create(engine, self.CREATE, self.n, self.count, _vp(index), _vp(types), len(kind_a), _vp(kind_a), *par)
 
     def forces(self, pos, force, accumulate=True, out=None, observables=True):
         """The forces of the list on the first n rows of `pos` (pse_bond_forces, pse_angle_forces, pse_dihedral_forces), added to `force` (or stored:
         accumulate=False, which zeroes the rows of particles in no entry), or force=None: observables only.  observables=True: returns
         the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, count, written to `out` when one is given (e.g. a row of a
         log tensor); observables=False: forces only, the reduction is not run and None is returned.  Queue-only: nothing is read back."""
-        if self._obj is None or not self._obj.value:
-            raise ValueError(f"this {type(self).__name__} is closed")
+        obj = self._handle()
         _chk4(pos, "pos", self.n)
         if force is not None:
             _chk4(force, "force", self.n)
         out = _chk_out8(out, pos) if observables else None
-        _lib.check(getattr(self._lib, self.FORCES)(self._obj, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out)))
+        _lib.check(getattr(self._lib, self.FORCES)(obj, _ptr(pos), _ptr(force), 1 if accumulate else 0, _ptr(out)))
         return out
-
-    def close(self):
-        o, self._obj = getattr(self, "_obj", None), None
-        if o is not None and o.value and self.engine._h is not None and self.engine._h.value:   # (a closed engine freed it already)
-            getattr(self._lib, self.DESTROY)(o)
-
-    __del__ = close
 
 
 class BondList(_TopologyList):
@@ -190,7 +218,7 @@ class BondList(_TopologyList):
     def overstretched(self):
         """FENE bonds found at r >= r0 by all calls since creation (pse_bonds_overstretched: waits for the stream)."""
         v = ctypes.c_ulonglong(0)
-        _lib.check(self._lib.pse_bonds_overstretched(self._obj, ctypes.byref(v)))
+        _lib.check(self._lib.pse_bonds_overstretched(self._handle(), ctypes.byref(v)))
         return int(v.value)
 
 
@@ -210,33 +238,17 @@ class DihedralList(_TopologyList):
     ndihedrals = property(lambda self: self.count)
 
 
-class ExclusionList:
+class ExclusionList(_DeviceObject):
     """Owner of a pse_exclusions object: a set of particle pairs that the pair passes skip (HOOMD's nlist.reset_exclusions).  `pairs`
     is an (npairs, 2) integer array of caller-order particle indices below `n` (default: n_max); a pair listed twice or in either
-    order is one exclusion.  Pass it as `exclusions=` to Engine.pair_table, pair_repulsion or pair_repulsion_virial.  Holds a
-    reference to its engine, whose handle owns the device object."""
+    order is one exclusion.  Pass it as `exclusions=` to Engine.pair_table, pair_repulsion or pair_repulsion_virial."""
 
     DESTROY = "pse_exclusions_destroy"
 
     def __init__(self, engine, pairs, n=None):
         pairs, _ = _topology_arrays(pairs, None, 2, "pairs", "pair")
-        self.n = int(engine.params.n_max if n is None else n)
-        if not 0 <= self.n < 2 ** 32:
-            raise ValueError("n outside [0, 2^32)")
-        self.count, self.engine, self._lib = pairs.shape[0], engine, engine._lib
-        self._obj = ctypes.c_void_p()
-        _lib.check(self._lib.pse_exclusions_create(engine._h, self.n, self.count, ctypes.c_void_p(pairs.ctypes.data), ctypes.byref(self._obj)))
-
-    def _handle(self, engine):
-        """The device object, for a pass of `engine`."""
-        if self._obj is None or not self._obj.value:
-            raise ValueError("this ExclusionList is closed")
-        if engine is not self.engine:
-            raise ValueError("this ExclusionList belongs to another engine")
-        return self._obj
-
-    close = _TopologyList.close
-    __del__ = close
+        self.n, self.count = _rows(engine, n), pairs.shape[0]
+        self._create(engine, "pse_exclusions_create", self.n, self.count, _vp(pairs))
 
 
 PAIR_TYPED_MAX_TYPES = 8   # pse_typed_table_create: particle types, and with them at most 36 pair types
@@ -295,41 +307,166 @@ def _typed_types(types, tables):
     return np.ascontiguousarray(types, dtype=np.uint32), max([int(types.max())] + keys) + 1
 
 
-class TypedTable:
+class TypedTable(_DeviceObject):
     """Owner of a pse_typed_table object: one type per particle and one tabulated potential per pair of types (HOOMD's pair.table with
     a pair_coeff per type pair).  `types`: (n,) integers, the type of caller-order particle t; a particle past them acts as type 0.
     `tables`: {(a, b): (table, rmin, rmax)} with `table` a (width, 2) array of V and F at the nodes as for Engine.pair_table; either
-    order of a key, a missing pair is off.  Pass it as `typed` to Engine.pair_table_typed.  Holds a reference to its engine, whose
-    handle owns the device object."""
+    order of a key, a missing pair is off.  Pass it as `typed` to Engine.pair_table_typed."""
 
     DESTROY = "pse_typed_table_destroy"
 
     def __init__(self, engine, types, tables, n=None):
-        types, self.ntypes = _typed_types(types, tables)
-        width, rmin, rmax, entries = _typed_tables(tables, self.ntypes)
-        self.n = int(types.shape[0] if n is None else n)
+        types, ntypes = _typed_types(types, tables)
+        self._create_from(engine, types, ntypes, *_typed_tables(tables, ntypes), n)
+
+    @classmethod
+    def from_arrays(cls, engine, types, ntypes, width, rmin, rmax, entries):
+        """The object of arrays that are checked already: what _typed_types and _typed_tables return (forces.TypedTablePair, which
+        numbers its types by name and may know more types than the particles show)."""
+        self = cls.__new__(cls)
+        self._create_from(engine, types, ntypes, width, rmin, rmax, entries, None)
+        return self
+
+    def _create_from(self, engine, types, ntypes, width, rmin, rmax, entries, n):
+        self.n, self.ntypes, self.count = int(types.shape[0] if n is None else n), ntypes, int(width.sum())
         if not 0 <= self.n <= types.shape[0]:
             raise ValueError("n outside [0, len(types)]")
-        self.count, self.engine, self._lib = int(width.sum()), engine, engine._lib
-        self._obj = ctypes.c_void_p()
-        vp = lambda a: ctypes.c_void_p(a.ctypes.data)
-        _lib.check(self._lib.pse_typed_table_create(engine._h, self.n, vp(types), self.ntypes, vp(width), vp(rmin), vp(rmax), vp(entries),
-                                                    ctypes.byref(self._obj)))
-
-    def _handle(self, engine):
-        """The device object, for a pass of `engine`."""
-        if self._obj is None or not self._obj.value:
-            raise ValueError("this TypedTable is closed")
-        if engine is not self.engine:
-            raise ValueError("this TypedTable belongs to another engine")
-        return self._obj
-
-    close = _TopologyList.close
-    __del__ = close
+        self._create(engine, "pse_typed_table_create", self.n, _vp(types), ntypes, _vp(width), _vp(rmin), _vp(rmax), _vp(entries))
 
 
-class Engine:
+class _ForcePasses:
+    """The force providers of the C-ABI on one handle, for whoever holds one: an Engine, which owns its handle, and the
+    StokesEngine of an integrator, whose handle the C++ Stokes object owns.  Needs `_lib`, `_h` (the handle; raises where there is
+    none), `n_max`, and `serial`: a number that changes when the handle goes, by which the objects made here know (_DeviceObject)."""
+
+    def pair_repulsion(self, pos, force, k, sigma=2.0, group=None, accumulate=True, exclusions=None):
+        """Soft repulsion k (sigma - r) r_hat for r < sigma added to (or stored in) `force` (SURVEY.md 8 f4).  exclusions: an
+        ExclusionList (Engine.exclusions) whose pairs contribute nothing (pse_pair_repulsion_excl); None: every pair in range acts."""
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk4(force, "force"); _chk_group(group)
+        if exclusions is not None:
+            _lib.check(self._lib.pse_pair_repulsion_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                         1 if accumulate else 0, None, exclusions._handle(self)))
+            return force
+        _lib.check(self._lib.pse_pair_repulsion(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                1 if accumulate else 0))
+        return force
+
+    def pair_repulsion_virial(self, pos, force, k, sigma=2.0, group=None, accumulate=True, out=None, exclusions=None):
+        """pair_repulsion plus the pair observables of the same pass (pse_pair_repulsion_virial): returns the 8-element float64 CUDA
+        tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs (W_ab = sum_{i<j} d_a F_b, stress = -W / V; see include/pse_amd.h).  `force`
+        may be None (observables only).  `out`: where to write them -- e.g. a row of a (samples, 8) log tensor; nothing is read
+        back, the tensor is filled when the stream gets there.  exclusions: as for pair_repulsion; the excluded pairs are in none of
+        the eight numbers."""
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if force is not None:
+            _chk4(force, "force")
+        out = _chk_out8(out, pos)
+        if exclusions is not None:
+            _lib.check(self._lib.pse_pair_repulsion_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                         1 if accumulate else 0, _ptr(out), exclusions._handle(self)))
+            return out
+        _lib.check(self._lib.pse_pair_repulsion_virial(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
+                                                       1 if accumulate else 0, _ptr(out)))
+        return out
+
+    def pair_table(self, pos, force, table, rmin, rmax, group=None, accumulate=True, out=None, observables=True, exclusions=None):
+        """A tabulated central pair potential on the engine's cell list (pse_pair_table; see include/pse_amd.h).  `table`: contiguous
+        (width, 2) float64 CUDA tensor, V and F (magnitude of the radial force, positive for a repulsion) at the nodes
+        rmin + k (rmax - rmin)/(width - 1), linear in between; pairs with rmin <= r < rmax act.  `force` is incremented (or stored,
+        accumulate=False), or None: observables only.  observables=True: returns the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz,
+        Wyy, Wyz, Wzz, npairs, written to `out` when one is given (e.g. a row of a log tensor).  observables=False: forces only, the
+        reduction is not run, `out` is left alone and None is returned.  Nothing is read back; the stream reads `table`, so keep it
+        alive and unchanged until the stream has passed the call.  exclusions: an ExclusionList (Engine.exclusions) whose pairs
+        contribute nothing to the forces or the eight numbers (pse_pair_table_excl); None: every pair in range acts."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if force is not None:
+            _chk4(force, "force")
+        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and table.dim() == 2
+                and table.shape[1] == 2 and table.is_contiguous()):
+            raise ValueError("table must be a contiguous (width, 2) float64 CUDA tensor: V and F at the nodes")
+        out = _chk_out8(out, pos) if observables else None
+        if exclusions is not None:
+            _lib.check(self._lib.pse_pair_table_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
+                                                     float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out), exclusions._handle(self)))
+            return out
+        _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
+                                            float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out)))
+        return out
+
+    def typed_table(self, types, tables, n=None):
+        """A typed pair table on the device (pse_typed_table_create; see include/pse_amd.h): `types` (n,) the type of every
+        caller-order particle, `tables` {(a, b): (table, rmin, rmax)} one tabulated potential per pair of types, either order of a
+        key, a missing pair off; `n`: how many of `types` to use (default: all).  Returns a TypedTable: the `typed` of
+        pair_table_typed."""
+        return TypedTable(self, types, tables, n)
+
+    def pair_table_typed(self, pos, force, typed, group=None, accumulate=True, out=None, observables=True, exclusions=None):
+        """Engine.pair_table with, for every pair, the table and the range of its pair of types (pse_pair_table_typed).  `typed`: a
+        TypedTable (Engine.typed_table).  `force`, `group`, `accumulate`, `out`, `observables` and what is returned as for
+        pair_table; exclusions: an ExclusionList whose pairs contribute nothing, None: every pair in range acts."""
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if force is not None:
+            _chk4(force, "force")
+        out = _chk_out8(out, pos) if observables else None
+        _lib.check(self._lib.pse_pair_table_typed(typed._handle(self), _ptr(pos), _ptr(force), _ptr(group), n, 1 if accumulate else 0,
+                                                  _ptr(out), None if exclusions is None else exclusions._handle(self)))
+        return out
+
+    def exclusions(self, pairs, n=None):
+        """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
+        caller-order particle indices below `n` (default: n_max).  Returns an ExclusionList: the `exclusions=` of the pair passes."""
+        return ExclusionList(self, pairs, n)
+
+    def bonds(self, pairs, types=None, kinds=(0,), k=(1.0,), r0=(1.0,), n=None):
+        """A bond topology on the device (pse_bonds_create; see include/pse_amd.h): `pairs` (nbonds, 2) particle indices into arrays of
+        `n` rows (default: n_max), `types` (nbonds,) indices into the per-type sequences `kinds` ("harmonic" | "fene" or
+        BOND_KINDS codes), `k`, `r0`, or None: all type 0.  Returns a BondList."""
+        return BondList(self, pairs, types, kinds, k, r0, n)
+
+    def angles(self, triples, types=None, kinds=(0,), k=(1.0,), theta0=(math.pi,), n=None):
+        """An angle topology on the device (pse_angles_create; see include/pse_amd.h): `triples` (nangles, 3) particle indices (end,
+        vertex, end) into arrays of `n` rows (default: n_max), `types` (nangles,) indices into the per-type sequences `kinds`
+        ("harmonic" | "cosinesq" or ANGLE_KINDS codes), `k`, `theta0` (radians, in [0, pi]), or None: all type 0.  Returns an AngleList."""
+        return AngleList(self, triples, types, kinds, k, theta0, n)
+
+    def dihedrals(self, quads, types=None, kinds=(0,), params=((1.0, 1.0, 1.0, 0.0),), n=None):
+        """A dihedral topology on the device (pse_dihedrals_create; see include/pse_amd.h): `quads` (ndihedrals, 4) particle indices
+        (i, j, k, l) into arrays of `n` rows (default: n_max), `types` (ndihedrals,) indices into the per-type sequences `kinds`
+        ("harmonic" | "opls" or DIHEDRAL_KINDS codes) and `params` (one 4-tuple per type: harmonic (k, d, mult, phi0), OPLS
+        (k1, k2, k3, k4)), or None: all type 0.  phi is the IUPAC dihedral angle: cis 0, trans pi.  Returns a DihedralList."""
+        return DihedralList(self, quads, types, kinds, params, None, n)
+
+
+class StokesEngine(_ForcePasses):
+    """The force passes on the engine of an integrator (integrate.PSEv1.engine): `cpp_method` is the C++ Stokes object, which owns
+    the handle and replaces it in setParams().  Holds a reference to it, so that it outlives every object made here, and never
+    destroys the handle."""
+
+    def __init__(self, cpp_method, n_max):
+        self.cpp_method, self.n_max, self._lib = cpp_method, int(n_max), _lib.load()
+
+    @property
+    def _h(self):
+        h = self.cpp_method.handle()
+        if not h:
+            raise RuntimeError("Stokes::setParams() has not been called")
+        return ctypes.c_void_p(h)
+
+    @property
+    def serial(self):
+        return self.cpp_method.engineSerial()
+
+
+class Engine(_ForcePasses):
     """One PSE engine instance == one `Stokes` object's device state (PSEv1/Stokes.h:128-150)."""
+
+    serial = 0   # (_ForcePasses) close() is the one change
+    n_max = property(lambda self: self.params.n_max)
 
     def __init__(self, n_max, box, xi=0.5, error=1e-3, max_strain=0.5, seed=0, grid=(0, 0, 0), P=0, rcut=0.0,
                  device=-1, n_slabs=1, slab_rank=0, local_rows=0, lanczos_operator=None):
@@ -364,6 +501,7 @@ class Engine:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.pse_destroy(self._h)
             self._h = ctypes.c_void_p()
+            self.serial = 1
 
     __del__ = close
 
@@ -481,108 +619,6 @@ class Engine:
         _lib.check(self._lib.pse_sqrt_mreal(self._h, _ptr(pos), _ptr(psi), _ptr(out), _ptr(group), n, float(tol),
                                             ctypes.byref(m)))
         return out, m.value
-
-    def pair_repulsion(self, pos, force, k, sigma=2.0, group=None, accumulate=True, exclusions=None):
-        """Soft repulsion k (sigma - r) r_hat for r < sigma added to (or stored in) `force` (SURVEY.md 8 f4).  exclusions: an
-        ExclusionList (Engine.exclusions) whose pairs contribute nothing (pse_pair_repulsion_excl); None: every pair in range acts."""
-        n = pos.shape[0] if group is None else group.shape[0]
-        _chk4(pos, "pos"); _chk4(force, "force"); _chk_group(group)
-        if exclusions is not None:
-            _lib.check(self._lib.pse_pair_repulsion_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
-                                                         1 if accumulate else 0, None, exclusions._handle(self)))
-            return force
-        _lib.check(self._lib.pse_pair_repulsion(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
-                                                1 if accumulate else 0))
-        return force
-
-    def pair_repulsion_virial(self, pos, force, k, sigma=2.0, group=None, accumulate=True, out=None, exclusions=None):
-        """pair_repulsion plus the pair observables of the same pass (pse_pair_repulsion_virial): returns the 8-element float64 CUDA
-        tensor U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz, npairs (W_ab = sum_{i<j} d_a F_b, stress = -W / V; see include/pse_amd.h).  `force`
-        may be None (observables only).  `out`: where to write them -- e.g. a row of a (samples, 8) log tensor; nothing is read
-        back, the tensor is filled when the stream gets there.  exclusions: as for pair_repulsion; the excluded pairs are in none of
-        the eight numbers."""
-        n = pos.shape[0] if group is None else group.shape[0]
-        _chk4(pos, "pos"); _chk_group(group)
-        if force is not None:
-            _chk4(force, "force")
-        out = _chk_out8(out, pos)
-        if exclusions is not None:
-            _lib.check(self._lib.pse_pair_repulsion_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
-                                                         1 if accumulate else 0, _ptr(out), exclusions._handle(self)))
-            return out
-        _lib.check(self._lib.pse_pair_repulsion_virial(self._h, _ptr(pos), _ptr(force), _ptr(group), n, float(k), float(sigma),
-                                                       1 if accumulate else 0, _ptr(out)))
-        return out
-
-    def pair_table(self, pos, force, table, rmin, rmax, group=None, accumulate=True, out=None, observables=True, exclusions=None):
-        """A tabulated central pair potential on the engine's cell list (pse_pair_table; see include/pse_amd.h).  `table`: contiguous
-        (width, 2) float64 CUDA tensor, V and F (magnitude of the radial force, positive for a repulsion) at the nodes
-        rmin + k (rmax - rmin)/(width - 1), linear in between; pairs with rmin <= r < rmax act.  `force` is incremented (or stored,
-        accumulate=False), or None: observables only.  observables=True: returns the 8-element float64 CUDA tensor U, Wxx, Wxy, Wxz,
-        Wyy, Wyz, Wzz, npairs, written to `out` when one is given (e.g. a row of a log tensor).  observables=False: forces only, the
-        reduction is not run, `out` is left alone and None is returned.  Nothing is read back; the stream reads `table`, so keep it
-        alive and unchanged until the stream has passed the call.  exclusions: an ExclusionList (Engine.exclusions) whose pairs
-        contribute nothing to the forces or the eight numbers (pse_pair_table_excl); None: every pair in range acts."""
-        import torch
-        n = pos.shape[0] if group is None else group.shape[0]
-        _chk4(pos, "pos"); _chk_group(group)
-        if force is not None:
-            _chk4(force, "force")
-        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and table.dim() == 2
-                and table.shape[1] == 2 and table.is_contiguous()):
-            raise ValueError("table must be a contiguous (width, 2) float64 CUDA tensor: V and F at the nodes")
-        out = _chk_out8(out, pos) if observables else None
-        if exclusions is not None:
-            _lib.check(self._lib.pse_pair_table_excl(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
-                                                     float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out), exclusions._handle(self)))
-            return out
-        _lib.check(self._lib.pse_pair_table(self._h, _ptr(pos), _ptr(force), _ptr(group), n, _ptr(table), int(table.shape[0]),
-                                            float(rmin), float(rmax), 1 if accumulate else 0, _ptr(out)))
-        return out
-
-    def typed_table(self, types, tables, n=None):
-        """A typed pair table on the device (pse_typed_table_create; see include/pse_amd.h): `types` (n,) the type of every
-        caller-order particle, `tables` {(a, b): (table, rmin, rmax)} one tabulated potential per pair of types, either order of a
-        key, a missing pair off; `n`: how many of `types` to use (default: all).  Returns a TypedTable: the `typed` of
-        pair_table_typed."""
-        return TypedTable(self, types, tables, n)
-
-    def pair_table_typed(self, pos, force, typed, group=None, accumulate=True, out=None, observables=True, exclusions=None):
-        """Engine.pair_table with, for every pair, the table and the range of its pair of types (pse_pair_table_typed).  `typed`: a
-        TypedTable (Engine.typed_table).  `force`, `group`, `accumulate`, `out`, `observables` and what is returned as for
-        pair_table; exclusions: an ExclusionList whose pairs contribute nothing, None: every pair in range acts."""
-        n = pos.shape[0] if group is None else group.shape[0]
-        _chk4(pos, "pos"); _chk_group(group)
-        if force is not None:
-            _chk4(force, "force")
-        out = _chk_out8(out, pos) if observables else None
-        _lib.check(self._lib.pse_pair_table_typed(typed._handle(self), _ptr(pos), _ptr(force), _ptr(group), n, 1 if accumulate else 0,
-                                                  _ptr(out), None if exclusions is None else exclusions._handle(self)))
-        return out
-
-    def exclusions(self, pairs, n=None):
-        """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
-        caller-order particle indices below `n` (default: n_max).  Returns an ExclusionList: the `exclusions=` of the pair passes."""
-        return ExclusionList(self, pairs, n)
-
-    def bonds(self, pairs, types=None, kinds=(0,), k=(1.0,), r0=(1.0,), n=None):
-        """A bond topology on the device (pse_bonds_create; see include/pse_amd.h): `pairs` (nbonds, 2) particle indices into arrays of
-        `n` rows (default: n_max), `types` (nbonds,) indices into the per-type sequences `kinds` ("harmonic" | "fene" or
-        BOND_KINDS codes), `k`, `r0`, or None: all type 0.  Returns a BondList."""
-        return BondList(self, pairs, types, kinds, k, r0, n)
-
-    def angles(self, triples, types=None, kinds=(0,), k=(1.0,), theta0=(math.pi,), n=None):
-        """An angle topology on the device (pse_angles_create; see include/pse_amd.h): `triples` (nangles, 3) particle indices (end,
-        vertex, end) into arrays of `n` rows (default: n_max), `types` (nangles,) indices into the per-type sequences `kinds`
-        ("harmonic" | "cosinesq" or ANGLE_KINDS codes), `k`, `theta0` (radians, in [0, pi]), or None: all type 0.  Returns an AngleList."""
-        return AngleList(self, triples, types, kinds, k, theta0, n)
-
-    def dihedrals(self, quads, types=None, kinds=(0,), params=((1.0, 1.0, 1.0, 0.0),), n=None):
-        """A dihedral topology on the device (pse_dihedrals_create; see include/pse_amd.h): `quads` (ndihedrals, 4) particle indices
-        (i, j, k, l) into arrays of `n` rows (default: n_max), `types` (ndihedrals,) indices into the per-type sequences `kinds`
-        ("harmonic" | "opls" or DIHEDRAL_KINDS codes) and `params` (one 4-tuple per type: harmonic (k, d, mult, phi0), OPLS
-        (k1, k2, k3, k4)), or None: all type 0.  phi is the IUPAC dihedral angle: cis 0, trans pi.  Returns a DihedralList."""
-        return DihedralList(self, quads, types, kinds, params, None, n)
 
     def random_psi(self, n, timestep, group=None):
         import torch

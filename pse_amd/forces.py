@@ -2,13 +2,15 @@
 PSEv1/Stokes.cc:447; its example script has none).  SURVEY.md 8 f4: the step either side of the hot path, kept minimal."""
 import math
 
-from .engine import ANGLE_KINDS, BOND_KINDS, DIHEDRAL_KINDS, _per_type, _topology_arrays, _type_params, _typed_tables, _typed_types
+from .engine import (ANGLE_KINDS, BOND_KINDS, DIHEDRAL_KINDS, AngleList, BondList, DihedralList, ExclusionList, TypedTable, _per_type,
+                     _topology_arrays, _type_params, _typed_tables, _typed_types)
 
 
 class _ObsProvider:
     """What the pair, bond, angle and dihedral providers share: the eight device doubles of the most recent fused call -- U, Wxx, Wxy, Wxz, Wyy, Wyz, Wzz,
     npairs -- where that call writes them (a row of a StressLog on a sample step, a buffer of the provider's own otherwise), and the
-    host-side readers.  A subclass sets NAME (what its messages call it) and makes the call in compute()."""
+    host-side readers.  A subclass sets NAME (what its messages call it) and makes the call in compute(): one force pass of the
+    integrator's engine (integrate.PSEv1.engine, engine._ForcePasses), added to net_force."""
 
     NAME = "pair provider"
 
@@ -20,11 +22,9 @@ class _ObsProvider:
         self.log = None      # a StressLog registers itself here
         integrator.system.forces.append(self)
 
-    def _group_args(self):
-        """(system, address of the group's members or 0, number of members)"""
-        s, g = self.integrator.system, self.integrator.group
-        m = g.members
-        return s, 0 if m is None else m.data_ptr(), len(g)
+    def _pass(self, timestep):
+        """The keywords every pass takes: the forces are added, and the eight doubles go where _fused_out says."""
+        return dict(accumulate=True, out=self._fused_out(timestep), observables=self._fused)
 
     def _fused_out(self, timestep):
         """The eight doubles the call of this step writes, recorded as the most recent ones; None without virial=True."""
@@ -93,7 +93,7 @@ class Exclusions:
     def __init__(self, integrator, pairs):
         pairs, _ = _topology_arrays(pairs, None, 2, "pairs", "pair")
         self.integrator, self.npairs_listed = integrator, pairs.shape[0]
-        self._id = integrator.cpp_method.exclusionsCreate(integrator.system.n, pairs.shape[0], pairs.ctypes.data)
+        self.list = ExclusionList(integrator.engine, pairs, integrator.system.n)
 
     @classmethod
     def from_topology(cls, integrator, bonds=None, angles=None, dihedrals=None):
@@ -101,13 +101,13 @@ class Exclusions:
         return cls(integrator, exclusion_pairs(bonds, angles, dihedrals))
 
 
-def _excl_id(integrator, exclusions):
-    """The id of an Exclusions object for a provider of `integrator`, or None."""
+def _excl_list(integrator, exclusions):
+    """The ExclusionList of an Exclusions object for a provider of `integrator`, or None."""
     if exclusions is None:
         return None
     if not isinstance(exclusions, Exclusions) or exclusions.integrator is not integrator:
         raise ValueError("exclusions must be a forces.Exclusions made on the same integrator")
-    return exclusions._id
+    return exclusions.list
 
 
 class HarmonicRepulsion(_ObsProvider):
@@ -124,20 +124,17 @@ class HarmonicRepulsion(_ObsProvider):
 
     def __init__(self, integrator, k, sigma=2.0, virial=False, exclusions=None):
         self.k, self.sigma = float(k), float(sigma)
-        self._excl = _excl_id(integrator, exclusions)
+        self._excl = _excl_list(integrator, exclusions)
         super().__init__(integrator, virial)
 
     def compute(self, timestep):
-        s, members, n = self._group_args()
-        if self._excl is not None:
-            self.integrator.cpp_method.pairRepulsionExcl(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True,
-                                                         _addr(self._fused_out(timestep)), self._excl)
-            return
+        s, g, eng = self.integrator.system, self.integrator.group, self.integrator.engine
         if not self._fused:
-            self.integrator.cpp_method.pairRepulsion(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True)
+            if len(g):   # (with virial=True an empty group is refused by the C-ABI: no device code here could write zeros to the eight doubles)
+                eng.pair_repulsion(s.pos, s.net_force, self.k, self.sigma, group=g.members, accumulate=True, exclusions=self._excl)
             return
-        self.integrator.cpp_method.pairRepulsionVirial(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.k, self.sigma, True,
-                                                       self._fused_out(timestep).data_ptr())
+        eng.pair_repulsion_virial(s.pos, s.net_force, self.k, self.sigma, group=g.members, accumulate=True, out=self._fused_out(timestep),
+                                  exclusions=self._excl)
 
 
 class TablePair(_ObsProvider):
@@ -166,7 +163,7 @@ class TablePair(_ObsProvider):
         if not 0.0 <= self.rmin < self.rmax < float("inf"):
             raise ValueError("need 0 <= rmin < rmax, both finite")
         self.table = t.to(integrator.system.pos.device).contiguous().clone()
-        self._excl = _excl_id(integrator, exclusions)
+        self._excl = _excl_list(integrator, exclusions)
         super().__init__(integrator, virial)
 
     @classmethod
@@ -180,14 +177,9 @@ class TablePair(_ObsProvider):
         return cls(integrator, np.array([[float(V(x)), float(F(x))] for x in r]), rmin, rmax, virial=virial, exclusions=exclusions)
 
     def compute(self, timestep):
-        s, members, n = self._group_args()
-        if self._excl is not None:
-            self.integrator.cpp_method.pairTableExcl(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
-                                                     int(self.table.shape[0]), self.rmin, self.rmax, True, _addr(self._fused_out(timestep)),
-                                                     self._excl)
-            return
-        self.integrator.cpp_method.pairTable(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, self.table.data_ptr(),
-                                             int(self.table.shape[0]), self.rmin, self.rmax, True, _addr(self._fused_out(timestep)))
+        s = self.integrator.system
+        self.integrator.engine.pair_table(s.pos, s.net_force, self.table, self.rmin, self.rmax, group=self.integrator.group.members,
+                                          exclusions=self._excl, **self._pass(timestep))
 
 
 def _typed_arguments(types, tables, type_names):
@@ -238,9 +230,8 @@ class TypedTablePair(_ObsProvider):
         if types.shape[0] != n:
             raise ValueError(f"types has {types.shape[0]} entries, the system {n} particles")
         self.types, self.widths, self.rmin, self.rmax, self.tables = types, width, rmin, rmax, entries
-        self._excl = _excl_id(integrator, exclusions)
-        self._id = integrator.cpp_method.typedTableCreate(n, types.ctypes.data, self.ntypes, width.ctypes.data, rmin.ctypes.data,
-                                                          rmax.ctypes.data, entries.ctypes.data)
+        self._excl = _excl_list(integrator, exclusions)
+        self._typed = TypedTable.from_arrays(integrator.engine, types, self.ntypes, width, rmin, rmax, entries)
         super().__init__(integrator, virial)
 
     @classmethod
@@ -269,12 +260,44 @@ class TypedTablePair(_ObsProvider):
         return self.tables[first:first + int(self.widths[p])] if self.widths[p] else None
 
     def compute(self, timestep):
-        s, members, n = self._group_args()
-        self.integrator.cpp_method.pairTableTyped(s.pos.data_ptr(), s.net_force.data_ptr(), members, n, True, _addr(self._fused_out(timestep)),
-                                                  self._id, -1 if self._excl is None else self._excl)
+        s = self.integrator.system
+        self.integrator.engine.pair_table_typed(s.pos, s.net_force, self._typed, group=self.integrator.group.members, exclusions=self._excl,
+                                                **self._pass(timestep))
 
 
-class Bonds(_ObsProvider):
+class _TopologyProvider(_ObsProvider):
+    """What Bonds, Angles and Dihedrals share: the provider holds a BondList, AngleList or DihedralList of the integrator's engine."""
+
+    def _create(self, integrator, List, index, types, kind, k, x):
+        """The checks, all before the integrator is touched, and the list: `kind`, `k` and `x` are scalars -- a scalar serves every
+        type -- or sequences of one length; with List.WIDTH = w parameters per type `k` is one w-tuple or a sequence of them and `x`
+        is None.  Returns the three per-type tuples as the provider shows them (the third None with a width)."""
+        xname, what, width = List.X, List.WHAT, List.WIDTH
+        if width is not None:
+            import numpy as np
+            if np.ndim(k) not in (1, 2) or np.shape(k)[-1] != width:
+                raise ValueError(f"{xname} must be one {width}-tuple or a sequence of them (one per {what} type)")
+            k = [tuple(k)] if np.ndim(k) == 1 else [tuple(v) for v in k]
+            x = [None] * len(k)
+        kind, k, x = _per_type(kind), _per_type(k), _per_type(x)
+        nt = max(len(kind), len(k), len(x))
+        kind, k, x = (v * nt if len(v) == 1 else v for v in (kind, k, x))
+        if not len(kind) == len(k) == len(x) == nt:
+            raise ValueError(f"kind, k and {xname} must be scalars or sequences of one length (one entry per {what} type)")
+        for v in kind:
+            if v not in List.KINDS:
+                raise ValueError(f"{what} kind must be one of {sorted(List.KINDS)}, not {v!r}")
+        _, k_a, x_a = _type_params(kind, k, x, xname, List.KINDS, what, width)
+        index, types = _topology_arrays(index, types, List.COLS, List.INDEX, what)
+        self._list = List(integrator.engine, index, types, kind, k_a, x_a, integrator.system.n)
+        return tuple(kind), tuple(map(tuple, k_a.tolist())) if width else tuple(k_a.tolist()), None if x_a is None else tuple(x_a.tolist())
+
+    def compute(self, timestep):
+        s = self.integrator.system
+        self._list.forces(s.pos, s.net_force, **self._pass(timestep))
+
+
+class Bonds(_TopologyProvider):
     """Harmonic and FENE bonds (pse_bond_forces; HOOMD's bond.harmonic and bond.fene): `pairs` is an (nbonds, 2) integer array of
     particle indices into the system's arrays.  kind = "harmonic": V = k/2 (r - r0)^2; "fene": V = -k/2 r0^2 ln(1 - (r/r0)^2), r < r0.
     `kind`, `k` and `r0` are scalars (one bond type) or sequences with one entry per type, and `types` then gives each bond's type
@@ -289,13 +312,8 @@ class Bonds(_ObsProvider):
     KINDS = BOND_KINDS
 
     def __init__(self, integrator, pairs, kind="harmonic", k=1.0, r0=1.0, types=None, virial=False):
-        self.kind, self.k, self.r0, self._id = _topology(integrator.cpp_method.bondsCreate, integrator.system.n, pairs, "pairs", 2, types,
-                                                         kind, k, r0, "r0", self.KINDS, "bond")
+        self.kind, self.k, self.r0 = self._create(integrator, BondList, pairs, types, kind, k, r0)
         super().__init__(integrator, virial)
-
-    def compute(self, timestep):
-        s = self.integrator.system
-        self.integrator.cpp_method.bondForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, _addr(self._fused_out(timestep)))
 
     @property
     def nbonds(self):
@@ -305,10 +323,10 @@ class Bonds(_ObsProvider):
     @property
     def overstretched(self):
         """FENE bonds found at r >= r0 by all compute() calls so far (waits for the stream)."""
-        return int(self.integrator.cpp_method.bondsOverstretched(self._id))
+        return self._list.overstretched
 
 
-class Angles(_ObsProvider):
+class Angles(_TopologyProvider):
     """Harmonic and cosine-squared angles (pse_angle_forces; HOOMD's angle.harmonic and angle.cosinesq): `triples` is an (nangles, 3)
     integer array of particle indices into the system's arrays, (end, vertex, end).  With theta the angle at the vertex between the
     two arms, kind = "harmonic": V = k/2 (theta - theta0)^2; "cosinesq": V = k/2 (cos theta - cos theta0)^2.  `kind`, `k` and `theta0`
@@ -324,13 +342,8 @@ class Angles(_ObsProvider):
     KINDS = ANGLE_KINDS
 
     def __init__(self, integrator, triples, kind="harmonic", k=1.0, theta0=math.pi, types=None, virial=False):
-        self.kind, self.k, self.theta0, self._id = _topology(integrator.cpp_method.anglesCreate, integrator.system.n, triples, "triples", 3,
-                                                             types, kind, k, theta0, "theta0", self.KINDS, "angle")
+        self.kind, self.k, self.theta0 = self._create(integrator, AngleList, triples, types, kind, k, theta0)
         super().__init__(integrator, virial)
-
-    def compute(self, timestep):
-        s = self.integrator.system
-        self.integrator.cpp_method.angleForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, _addr(self._fused_out(timestep)))
 
     @property
     def nangles(self):
@@ -338,7 +351,7 @@ class Angles(_ObsProvider):
         return self.npairs
 
 
-class Dihedrals(_ObsProvider):
+class Dihedrals(_TopologyProvider):
     """Harmonic and OPLS dihedrals (pse_dihedral_forces; HOOMD's dihedral.harmonic and dihedral.opls): `quads` is an (ndihedrals, 4)
     integer array of particle indices (i, j, k, l) into the system's arrays.  phi is the IUPAC dihedral angle of the three arms
     i-j, j-k, k-l: the planar cis arrangement is 0, trans is pi (this convention whatever sign a given HOOMD version uses).
@@ -356,48 +369,13 @@ class Dihedrals(_ObsProvider):
     KINDS = DIHEDRAL_KINDS
 
     def __init__(self, integrator, quads, kind="harmonic", params=(1.0, 1.0, 1.0, 0.0), types=None, virial=False):
-        self.kind, self.params, _, self._id = _topology(integrator.cpp_method.dihedralsCreate, integrator.system.n, quads, "quads", 4,
-                                                        types, kind, params, None, "params", self.KINDS, "dihedral", width=4)
+        self.kind, self.params, _ = self._create(integrator, DihedralList, quads, types, kind, params, None)
         super().__init__(integrator, virial)
-
-    def compute(self, timestep):
-        s = self.integrator.system
-        self.integrator.cpp_method.dihedralForces(self._id, s.pos.data_ptr(), s.net_force.data_ptr(), True, _addr(self._fused_out(timestep)))
 
     @property
     def ndihedrals(self):
         """The number of dihedrals that acted at the most recent compute() (the count the pair providers call npairs)."""
         return self.npairs
-
-
-def _addr(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def _topology(create, n, index, name, cols, types, kind, k, x, xname, table, what, width=None):
-    """The checks and the device object of Bonds, Angles and Dihedrals: `kind`, `k` and `x` (called `xname`) are scalars -- a scalar
-    serves every type -- or sequences of one length, a kind being a name of `table`; `index` is the (count, cols) array `name`.
-    width = w: a type has w parameters: `k` is one w-tuple or a sequence of them, x is not used (None).  Returns the three per-type
-    tuples (the third None with a width) and the id `create` gave the topology."""
-    if width is not None:
-        import numpy as np
-        if np.ndim(k) not in (1, 2) or np.shape(k)[-1] != width:
-            raise ValueError(f"{xname} must be one {width}-tuple or a sequence of them (one per {what} type)")
-        k = [tuple(k)] if np.ndim(k) == 1 else [tuple(v) for v in k]
-        x = [None] * len(k)
-    kind, k, x = _per_type(kind), _per_type(k), _per_type(x)
-    nt = max(len(kind), len(k), len(x))
-    kind, k, x = (v * nt if len(v) == 1 else v for v in (kind, k, x))
-    if not len(kind) == len(k) == len(x) == nt:
-        raise ValueError(f"kind, k and {xname} must be scalars or sequences of one length (one entry per {what} type)")
-    for v in kind:
-        if v not in table:
-            raise ValueError(f"{what} kind must be one of {sorted(table)}, not {v!r}")
-    kind_a, k_a, x_a = _type_params(kind, k, x, xname, table, what, width)
-    index, types = _topology_arrays(index, types, cols, name, what)
-    par = (k_a.ctypes.data,) if x_a is None else (k_a.ctypes.data, x_a.ctypes.data)
-    tid = create(n, index.shape[0], index.ctypes.data, 0 if types is None else types.ctypes.data, nt, kind_a.ctypes.data, *par)
-    return tuple(kind), tuple(map(tuple, k_a.tolist())) if width else tuple(k_a.tolist()), None if x_a is None else tuple(x_a.tolist()), tid
 
 
 def _sym3(w):

@@ -3,7 +3,7 @@ function_form, max_strain, nlist_type)`, `.set_params`, `.stop_shear`, backed by
 import math
 
 from . import _PSEv1, context, shear_function
-from .engine import _lanczos_operator_code
+from .engine import StokesEngine, _lanczos_operator_code
 
 
 class _const_or_variant:
@@ -41,6 +41,8 @@ class PSEv1:
         if lz_op is not None:
             self.cpp_method.setLanczosOperator(lz_op)
         self.cpp_method.setParams()                                                     # integrate.py:96
+        # what the force providers (pse_amd.forces) call: the C-ABI's force passes on the handle cpp_method owns
+        self.engine = StokesEngine(self.cpp_method, s.n)
         s.integrators.append(self)
 
     def set_params(self, T=None, function_form=None, max_strain=0.5):                  # integrate.py:108-118

@@ -85,6 +85,16 @@ def test_seed_hash_matches_reference_arithmetic(mod, oracle):
         assert s.hashedSeed() == oracle.hash_seed(seed)
 
 
+def test_stokes_is_the_integrator_and_nothing_else(mod):
+    """The C++ Stokes class takes net_force from outside and knows no potential, like the reference's: its Python surface is the
+    integrator's, plus the two accessors through which the force providers reach the engine over the ctypes binding."""
+    public = {name for name in dir(mod.Stokes) if not name.startswith("_")}
+    assert public == {"setT", "setShear", "setDeltaT", "setOverrides", "setLanczosOperator", "setParams", "setBox", "integrateStepOne",
+                      "integrateStepTwo", "info", "lanczosIterations", "hashedSeed", "handle", "engineSerial"}
+    s = mod.Stokes(10, 20.0, 20.0, 20.0, 0.0, mod.VariantConst(1.0), 1, 0.5, 1e-3, 1e-3)
+    assert s.handle() == 0 and s.engineSerial() == 0              # no engine before setParams
+
+
 def test_hoomd_shim_covers_the_reference_example():
     """Every `hoomd....` name the reference's examples/run.py touches resolves on the stand-in package (the script itself
     needs a GPU; it is not copied into this repo).  The names are tests/golden/reference_example_names.json, which
