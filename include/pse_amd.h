@@ -300,6 +300,34 @@ int pse_typed_table_destroy(pse_typed_table *t);
 int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4 *force /* may be NULL */, const unsigned *group,
                          unsigned N, int accumulate, double *out8 /* DEVICE, may be NULL */, const pse_exclusions *ex /* may be NULL */);
 
+/* ---- pair-distance histograms: the counts behind g(r), the partial g_ab(r) and coordination numbers (no reference counterpart) ----
+ * A pse_pair_hist object fixes the types of the particles and the bins: every particle has one of ntypes <= 8 types (types_host[t]: the
+ * type of CALLER-order particle t, as for pse_typed_table_create; NULL: all of type 0; a
+ * particle whose index is >= n acts as type 0), and every pair type p(a, b) = a ntypes - a (a - 1)/2 + (b - a), a <= b, of the
+ * npt = ntypes (ntypes + 1)/2 has one row of nbins uniform bins on [rmin, rmax), shared by all pair types.
+ * pse_pair_hist_accumulate walks the handle's cell list once: every unordered minimum-image pair among the N group members with
+ * rmin <= r, r^2 < rmax^2, r > 0 that is not in ex adds 1 to counts[p nbins + b], b = min((int)((r - rmin) nbins/(rmax - rmin)),
+ * nbins - 1) -- bin b covers [rmin + b w, rmin + (b + 1) w), w = (rmax - rmin)/nbins.  counts (DEVICE, npt x nbins unsigned 64-bit words,
+ * 8-byte aligned) is ADDED to: the caller zeroes it once and accumulates as many samples as it likes; nothing is read back and the
+ * host never waits (queue-only wherever pse_pair_table is).  Only integers are summed (32-bit counters in LDS per workgroup, 64-bit
+ * atomics into counts): the result is exact, independent of the order of the particles and of the launch, and bit-reproducible.
+ * From the counts of S samples: g_ab(r_b) = counts / (S P_ab V_shell / V) with P_aa = N_a (N_a - 1)/2, P_ab = N_a N_b,
+ * V_shell = 4 pi/3 (r_hi^3 - r_lo^3), V = Lx Ly Lz (pse_amd.analyze.RDF does this).
+ * npt x nbins <= 8192 (32 KB of LDS).  rmax may not exceed rcut: the cell list is built for the hydrodynamic cutoff.  A slab rank
+ * (n_slabs >= 2) orders only its own cells, its counts would be partial: refused.
+ * The object belongs to its handle: pse_destroy frees the objects still alive, pse_pair_hist_destroy after that is a caller error;
+ * pse_pair_hist_destroy waits for the stream.  The types are copied at creation.
+ * pse_pair_hist_create returns PSE_ERR_INVALID, with a message naming the value, for, in this order: a null out or h, n == 0 or
+ * n > n_max, ntypes outside [1, 8], nbins < 1, npt x nbins > 8192, rmin or rmax not finite, rmin < 0, rmax <= rmin, rmax > rcut, a slab
+ * rank, a type >= ntypes.  *out is null after a refusal.  pse_pair_hist_accumulate, in this order: a null g, N == 0 or N > n_max, a
+ * null pos, a null counts or one that is not 8-byte aligned, an ex created on another handle than g; counts is untouched then. */
+typedef struct pse_pair_hist pse_pair_hist;
+int pse_pair_hist_create(pse_handle *h, unsigned n, const unsigned *types_host /* n, or NULL: one type */, int ntypes, int nbins,
+                         double rmin, double rmax, pse_pair_hist **out);
+int pse_pair_hist_destroy(pse_pair_hist *g);
+int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const unsigned *group, unsigned N,
+                             unsigned long long *counts /* DEVICE, npt x nbins, ADDED to */, const pse_exclusions *ex /* may be NULL */);
+
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -38,6 +38,7 @@ struct pse_angles : Topology { using Topology::Topology; };
 struct pse_dihedrals : Topology { using Topology::Topology; };
 struct pse_exclusions : Topology { using Topology::Topology; };
 struct pse_typed_table : Topology { using Topology::Topology; };   // row_off: the REAL layout (pse_host_typed_table_layout), entries: the types
+struct pse_pair_hist : Topology { using Topology::Topology; };     // entries: the types (zeros where none were given)
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -157,6 +158,21 @@ int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4
                          const pse_exclusions *ex) {
     pse_handle *h = t ? t->h : nullptr;
     return pair_typed_validate(t, h, h ? h->par.n_max : 0u, h ? h->par.n_slabs : 1, N, pos, force, out8, ex, ex ? ex->h : nullptr);
+}
+int pse_pair_hist_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int nbins, double rmin, double rmax, pse_pair_hist **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_pair_hist_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_pair_hist_create: null handle");
+    if (int rc = pair_hist_create_validate(h->d.rcut, h->par.n_max, h->par.n_slabs, n, types_host, ntypes, nbins, rmin, rmax)) return rc;
+    pse_pair_hist *g = new pse_pair_hist(h, 0, (size_t)n);
+    if (types_host) std::copy(types_host, types_host + n, g->entries.begin());
+    return topology_adopt(g, 0, out);
+}
+int pse_pair_hist_destroy(pse_pair_hist *g) { return topology_destroy(g); }
+int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const unsigned *, unsigned N, unsigned long long *counts,
+                             const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;   // (pos and counts are device pointers and there is no device: nothing is read or written)
+    return pair_hist_validate(g, h, h ? h->par.n_max : 0u, N, pos, counts, ex, ex ? ex->h : nullptr);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

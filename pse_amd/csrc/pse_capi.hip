@@ -432,6 +432,18 @@ struct pse_typed_table : Topology {
         for (void *p : ptrs) if (p) (void)hipFree(p);
     }
 };
+// A pair-distance histogram (include/pse_amd.h): n = particles with a type, ntypes, and the bins; types and type_s as in pse_typed_table.
+// The arrays of Topology stay null.
+struct pse_pair_hist : Topology {
+    unsigned char *types = nullptr;         // n: the type of caller-order particle t
+    unsigned char *type_s = nullptr;        // n_max: the types in sorted order, written by every call (k_type_mirror)
+    int nbins = 0;
+    double rmin = 0.0, rmax = 0.0;
+    ~pse_pair_hist() override {
+        void *ptrs[] = {types, type_s};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
+};
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
@@ -2838,6 +2850,45 @@ extern "C" int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, 
     const PairTypedTables tt{t->types, t->type_s, t->tables, (const double *)t->par, t->n, t->ntypes, (int)t->count, t->rmax2_all};
     launch_pair_table_typed(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, tt, accumulate, (double4 *)force, h->pv_rows, out8,
                             h->stream, ex ? &er : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Pair-distance histograms (include/pse_amd.h): the types on the device, and the pass.  Queue-only: the sort, the type mirror, the
+// pass; nothing is read back, the counters are added to by the stream.
+extern "C" int pse_pair_hist_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int nbins, double rmin, double rmax,
+                                    pse_pair_hist **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_pair_hist_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_pair_hist_create: null handle");
+    TRY(pair_hist_create_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, n, types_host, ntypes, nbins, rmin, rmax));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
+    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
+    pse_pair_hist *g = new pse_pair_hist();
+    g->h = h; g->n = n; g->count = (unsigned)(ntypes * (ntypes + 1) / 2 * nbins); g->ntypes = ntypes;
+    g->nbins = nbins; g->rmin = rmin; g->rmax = rmax;
+    hipError_t e = hipMalloc((void **)&g->types, n);
+    if (e == hipSuccess) e = hipMemcpy(g->types, types.data(), n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&g->type_s, (size_t)h->n_max);
+    if (e != hipSuccess) {
+        delete g;
+        return fail(PSE_ERR_HIP, "pse_pair_hist_create: copying %u types to the device failed: %s", n, hipGetErrorString(e));
+    }
+    h->topologies.push_back(g);
+    *out = g;
+    return 0;
+}
+extern "C" int pse_pair_hist_destroy(pse_pair_hist *g) { return topology_destroy(g); }
+extern "C" int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned long long *counts,
+                                        const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;
+    TRY(pair_hist_validate(g, h, h ? (unsigned)h->n_max : 0u, N, pos, counts, ex, ex ? ex->h : nullptr));
+    HIPCHK(hipSetDevice(h->device));
+    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
+    const PairHist ph{g->types, g->type_s, g->n, g->ntypes, g->nbins, g->rmin, g->rmax};
+    launch_pair_hist(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, ph, counts, h->stream, ex ? &er : nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -50,5 +50,13 @@ int typed_table_validate(double rcut, unsigned n_max, unsigned n, const unsigned
 // the same handle
 int pair_typed_validate(const void *t, const void *t_handle, unsigned n_max, int n_slabs, unsigned N, const void *pos, const void *force,
                         const void *out8, const void *ex, const void *ex_handle);
+// the argument checks of pse_pair_hist_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them
+// (types may be null: one type), with the handle's rcut, n_max and n_slabs
+int pair_hist_create_validate(double rcut, unsigned n_max, int n_slabs, unsigned n, const unsigned *types, int ntypes, int nbins, double rmin,
+                              double rmax);
+// the argument checks of pse_pair_hist_accumulate: the object (g_handle: the handle it was created on, n_max that handle's), N, pos,
+// counts; then an exclusion object, if one is given, of the same handle
+int pair_hist_validate(const void *g, const void *g_handle, unsigned n_max, unsigned N, const void *pos, const void *counts, const void *ex,
+                       const void *ex_handle);
 
 }  // namespace pse

@@ -47,6 +47,19 @@ struct PairTypedTables {
 void launch_pair_table_typed(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
                              const PairTypedTables &tt, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
                              const PairExclusions *ex = nullptr);
+// pair-distance histogram (k_pair_hist; pse_pair_hist_create): the device arrays and the bins of one object.  types, type_s: as in
+// PairTypedTables (type_s is written by every launch, k_type_mirror).  Every unordered pair of sorted rows with rmin <= r, r^2 < rmax^2,
+// r > 0 that is not in `ex` adds 1 to counts[p nbins + b]: p the pair type p(a, b), b = min((int)((r - rmin) scale), nbins - 1),
+// scale = nbins/(rmax - rmin).  counts (device, npt x nbins) is ADDED to with integer atomics: exact, whatever the order.
+struct PairHist {
+    const unsigned char *types;
+    unsigned char *type_s;
+    unsigned n;
+    int ntypes, nbins;
+    double rmin, rmax;
+};
+void launch_pair_hist(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const PairHist &ph,
+                      unsigned long long *counts, hipStream_t s, const PairExclusions *ex = nullptr);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
 // entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
 // eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does

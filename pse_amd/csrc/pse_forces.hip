@@ -1,5 +1,5 @@
-// Kernels of the force providers (pse_forces.h): pair repulsion, tabulated and typed pair tables with exclusions on the engine's
-// cell list, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
+// Kernels of the force providers (pse_forces.h): pair repulsion, tabulated and typed pair tables with exclusions and the pair-distance
+// histogram on the engine's cell list, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
 // they leave in net_force.  gfx950, wave64, fp64.
 #include "pse_forces.h"
 
@@ -358,6 +358,76 @@ void launch_pair_table_typed(const double4 *pos_s, const unsigned *tag_s, int N,
                                tt.type_s, N, cell_off, box, nc, (const double2 *)tt.tables, tt.total, (const double2 *)tt.par, tt.ntypes,
                                tt.rmax2_all, accumulate, force, r, er);
         });
+    });
+}
+
+// Pair-distance histogram (pse_pair_hist_accumulate): the distances of all unordered pairs, one row of nbins uniform bins on
+// [rmin, rmax) per pair type p(a, b) -- the raw counts of the radial distribution functions g_ab(r).  A kernel of its own, as
+// k_pair_table_typed is (see the note on shared code above k_pair_repulsion); the walk, the type mirror (k_type_mirror) and the
+// exclusion lookup are those of k_pair_table_typed.  One thread per sorted row i; a pair j > i -- every unordered pair once, the
+// rule of the OBS sums -- with r^2 < rmax^2, r^2 > 0, r = sqrt(r^2) >= rmin that is not excluded adds 1 to counter p nbins + b,
+// b = min((int)((r - rmin) scale), nbins - 1): r within an ulp of rmax may give t = nbins, the clamp keeps it in the last bin.
+// Counters: `ncount` = npt nbins <= PAIR_HIST_MAX_COUNTERS unsigned words of dynamic LDS (at most 32 KB), zeroed by the workgroup
+// before one barrier and added to by ds_add_u32 without a returned value.  Behind the walk and ONE more barrier the workgroup adds
+// its non-zero counters to the caller's 64-bit counters with global integer atomics without a returned value.  An LDS counter holds
+// the pairs of 256 rows: no overflow.  No floating point is summed: every count is exact and independent of the order, equal inputs
+// give equal bits.  No lane leaves before either barrier.
+// Measured and dropped (docs/HISTORY.md): a copy of the counters per wave (no difference, at one bin as at 128), and several row
+// blocks per workgroup before the flush (slower at 10^6 and 10^7 rows: fewer workgroups hide the gathers worse than the flush costs).
+template <bool EXCL>
+__global__ void __launch_bounds__(TPB)
+k_pair_hist(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, const unsigned char *__restrict__ type_s, int N,
+            const int *__restrict__ cell_off, DBox box, DCells nc, int ntypes, int nbins, int ncount, double rmin, double rmax2, double scale,
+            unsigned long long *__restrict__ counts /* [ncount], added to */, ExclRows ex) {
+    extern __shared__ unsigned ph_cnt[];   // [ncount]
+    for (int c = threadIdx.x; c < ncount; c += TPB) ph_cnt[c] = 0u;
+    __syncthreads();
+    const int blast = nbins - 1;
+    const int i = xcd_block(blockIdx.x, gridDim.x) * TPB + threadIdx.x;
+    if (i < N) {
+        const double4 pi = pos_s[i];
+        double fx, fy, fz;
+        frac_coords(box, pi.x, pi.y, pi.z, fx, fy, fz);
+        const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
+        const int ti = type_s[i];
+        unsigned eb = 0u, ee = 0u;
+        if (EXCL) excl_row(ex, tag_s[i], eb, ee);
+        for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
+            for (int j = max(jb, i + 1); j < je; ++j) {
+                const double4 pj = pos_s[j];
+                double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                min_image(box, dx, dy, dz);
+                const double r2 = dx * dx + dy * dy + dz * dz;
+                if (r2 < rmax2 && r2 > 0.0) {
+                    const double r = sqrt(r2);
+                    if (r >= rmin && !(EXCL && eb < ee && excl_has(ex.ent, eb, ee, tag_s[j]))) {
+                        const int tj = type_s[j];
+                        const int lo = min(ti, tj), hi = max(ti, tj);
+                        const int p = lo * ntypes - ((lo * (lo - 1)) >> 1) + (hi - lo);
+                        const int bin = min((int)((r - rmin) * scale), blast);
+                        atomicAdd(ph_cnt + p * nbins + bin, 1u);
+                    }
+                }
+            }
+        });
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < ncount; c += TPB) {
+        const unsigned v = ph_cnt[c];
+        if (v) atomicAdd(counts + c, (unsigned long long)v);
+    }
+}
+void launch_pair_hist(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const PairHist &ph,
+                      unsigned long long *counts, hipStream_t s, const PairExclusions *ex) {
+    static_assert((size_t)PAIR_HIST_MAX_COUNTERS * sizeof(unsigned) <= 32768, "the counters take at most 32 KB of LDS");
+    const int nb = nblocks(N, TPB);
+    const int ncount = ph.ntypes * (ph.ntypes + 1) / 2 * ph.nbins;
+    const size_t lds = (size_t)ncount * sizeof(unsigned);
+    const double scale = (double)ph.nbins / (ph.rmax - ph.rmin);
+    hipLaunchKernelGGL(k_type_mirror, dim3(nb), dim3(TPB), 0, s, tag_s, N, ph.types, ph.n, ph.type_s);
+    launch_with_excl(ex, [&](auto excl, ExclRows er) {
+        hipLaunchKernelGGL((k_pair_hist<decltype(excl)::value>), dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, ph.type_s, N, cell_off, box,
+                           nc, ph.ntypes, ph.nbins, ncount, ph.rmin, ph.rmax * ph.rmax, scale, counts, er);
     });
 }
 

@@ -254,6 +254,43 @@ int pair_typed_validate(const void *t, const void *t_handle, unsigned n_max, int
     return 0;
 }
 
+int pair_hist_create_validate(double rcut, unsigned n_max, int n_slabs, unsigned n, const unsigned *types, int ntypes, int nbins, double rmin,
+                              double rmax) {
+    const char *who = "pse_pair_hist_create";
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (nbins < 1) return fail(PSE_ERR_INVALID, "%s: nbins = %d, need at least one bin", who, nbins);
+    const long long npt = ntypes * (ntypes + 1) / 2;
+    if (npt * nbins > PAIR_HIST_MAX_COUNTERS)
+        return fail(PSE_ERR_INVALID, "%s: %lld pair types x %d bins = %lld counters, more than %d (the counters are kept in 32 KB of LDS)", who, npt,
+                    nbins, npt * nbins, PAIR_HIST_MAX_COUNTERS);
+    if (!std::isfinite(rmin) || !std::isfinite(rmax)) return fail(PSE_ERR_INVALID, "%s: rmin = %g, rmax = %g must be finite", who, rmin, rmax);
+    if (rmin < 0.0) return fail(PSE_ERR_INVALID, "%s: rmin = %g is negative", who, rmin);
+    if (!(rmax > rmin)) return fail(PSE_ERR_INVALID, "%s: rmax = %g must exceed rmin = %g", who, rmax, rmin);
+    if (rmax > rcut)
+        return fail(PSE_ERR_INVALID, "%s: histogram range rmax = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic cutoff", who,
+                    rmax, rcut);
+    if (n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "%s: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the counts would be partial", who,
+                    n_slabs);
+    if (types)
+        for (unsigned i = 0; i < n; ++i)
+            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    return 0;
+}
+
+int pair_hist_validate(const void *g, const void *g_handle, unsigned n_max, unsigned N, const void *pos, const void *counts, const void *ex,
+                       const void *ex_handle) {
+    const char *who = "pse_pair_hist_accumulate";
+    if (!g) return fail(PSE_ERR_INVALID, "%s: null histogram object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!counts) return fail(PSE_ERR_INVALID, "%s: null counts", who);
+    if (((uintptr_t)counts & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: counts is not 8-byte aligned (64-bit counters)", who);
+    if (ex) return pair_excl_validate(who, ex, ex_handle, g_handle);
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;

@@ -334,6 +334,52 @@ class TypedTable(_DeviceObject):
         self._create(engine, "pse_typed_table_create", self.n, _vp(types), ntypes, _vp(width), _vp(rmin), _vp(rmax), _vp(entries))
 
 
+PAIR_HIST_MAX_COUNTERS = 8192   # pse_pair_hist_create: pair types x bins
+
+
+def _pair_hist_arguments(types, ntypes, nbins, rmin, rmax):
+    """The arguments of a pair histogram, checked before the device is touched: (types uint32 (n,) or None, ntypes, nbins, rmin,
+    rmax).  `types`: None (one type) or a 1-D array of integers in [0, ntypes)."""
+    import numpy as np
+    ntypes, nbins, rmin, rmax = int(ntypes), int(nbins), float(rmin), float(rmax)
+    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
+        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    if nbins < 1:
+        raise ValueError(f"nbins = {nbins}: need at least one bin")
+    npt = ntypes * (ntypes + 1) // 2
+    if npt * nbins > PAIR_HIST_MAX_COUNTERS:
+        raise ValueError(f"{npt} pair types x {nbins} bins = {npt * nbins} counters, more than {PAIR_HIST_MAX_COUNTERS}")
+    if not 0.0 <= rmin < rmax < float("inf"):
+        raise ValueError("need 0 <= rmin < rmax, both finite")
+    if types is not None:
+        types = np.asarray(types)
+        if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
+            raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
+        if types.max() >= ntypes:
+            raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
+        types = np.ascontiguousarray(types, dtype=np.uint32)
+    return types, ntypes, nbins, rmin, rmax
+
+
+class PairHistogram(_DeviceObject):
+    """Owner of a pse_pair_hist object: one type per particle and nbins uniform bins on [rmin, rmax) for every pair of types.
+    `types`: (n,) integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts as type 0.
+    Pass it as `hist` to Engine.pair_hist_accumulate."""
+
+    DESTROY = "pse_pair_hist_destroy"
+
+    def __init__(self, engine, types, ntypes, nbins, rmin, rmax, n=None):
+        types, self.ntypes, self.nbins, self.rmin, self.rmax = _pair_hist_arguments(types, ntypes, nbins, rmin, rmax)
+        self.npt = self.ntypes * (self.ntypes + 1) // 2
+        if types is None:
+            self.n = _rows(engine, n)
+        else:
+            self.n = int(types.shape[0] if n is None else n)
+            if not 0 <= self.n <= types.shape[0]:
+                raise ValueError("n outside [0, len(types)]")
+        self._create(engine, "pse_pair_hist_create", self.n, _vp(types), self.ntypes, self.nbins, self.rmin, self.rmax)
+
+
 class _ForcePasses:
     """The force providers of the C-ABI on one handle, for whoever holds one: an Engine, which owns its handle, and the
     StokesEngine of an integrator, whose handle the C++ Stokes object owns.  Needs `_lib`, `_h` (the handle; raises where there is
@@ -416,6 +462,28 @@ class _ForcePasses:
         _lib.check(self._lib.pse_pair_table_typed(typed._handle(self), _ptr(pos), _ptr(force), _ptr(group), n, 1 if accumulate else 0,
                                                   _ptr(out), None if exclusions is None else exclusions._handle(self)))
         return out
+
+    def pair_histogram(self, types, ntypes, nbins, rmin, rmax, n=None):
+        """A pair-distance histogram on the device (pse_pair_hist_create; see include/pse_amd.h): `types` (n,) the type of every
+        caller-order particle, below `ntypes` <= 8, or None: one type; `nbins` uniform bins on [rmin, rmax), rmax <= rcut, for each of
+        the ntypes (ntypes + 1)/2 pair types, at most 8192 counters in all; `n`: how many of `types` to use (default: all; without
+        types: n_max).  Returns a PairHistogram: the `hist` of pair_hist_accumulate."""
+        return PairHistogram(self, types, ntypes, nbins, rmin, rmax, n)
+
+    def pair_hist_accumulate(self, pos, hist, counts, group=None, exclusions=None):
+        """One sample of the pair distances (pse_pair_hist_accumulate): every unordered pair with rmin <= r < rmax, r > 0 adds 1 to
+        counts[p, b], p = pair_type_index of its types, b its bin.  `counts`: a contiguous (npt, nbins) int64 CUDA tensor, ADDED to --
+        zero it once, accumulate as many samples as you like.  exclusions: an ExclusionList whose pairs are not counted.  Queue-only:
+        nothing is read back; integers only, so the counts are exact and do not depend on the order of the particles.  Returns counts."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()
+                and tuple(counts.shape) == (hist.npt, hist.nbins)):
+            raise ValueError(f"counts must be a contiguous ({hist.npt}, {hist.nbins}) int64 CUDA tensor")
+        _lib.check(self._lib.pse_pair_hist_accumulate(hist._handle(self), _ptr(pos), _ptr(group), n, _ptr(counts),
+                                                      None if exclusions is None else exclusions._handle(self)))
+        return counts
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
