@@ -328,6 +328,47 @@ int pse_pair_hist_destroy(pse_pair_hist *g);
 int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const unsigned *group, unsigned N,
                              unsigned long long *counts /* DEVICE, npt x nbins, ADDED to */, const pse_exclusions *ex /* may be NULL */);
 
+/* ---- static structure factors: the densities rho_a(k) on the box's reciprocal lattice and their products S_ab(k) (no reference counterpart) ----
+ * A pse_structure_factor object fixes the types of the particles (types_host, ntypes <= 8, exactly as for pse_pair_hist_create:
+ * CALLER-order, NULL: all of type 0, a particle whose index is >= n acts as type 0) and a list of nk integer triples m = (mx, my, mz),
+ * |m_i| <= PSE_SF_MAX_INDEX, nk <= PSE_SF_MAX_MODES.  (0, 0, 0), a mode and its negative, and duplicates are allowed
+ * (a mode listed twice is computed once: equal bits in both places).
+ * With the handle's CURRENT box (Lx, Ly, Lz, xy) -- whatever pse_set_box last set -- and the fractional coordinates s_x = (x - xy y)/Lx,
+ * s_y = y/Ly, s_z = z/Lz (not shifted, not wrapped), pse_structure_factor_accumulate computes, over the N group members j,
+ *   rho_a(m) = sum_{type(j) = a} exp(-2 pi i (mx s_x + my s_y + mz s_z)),
+ * the density of type a at k = 2 pi (mx/Lx, my/Ly - xy mx/Lx, mz/Lz).  A particle moved by any lattice vector, the tilted
+ * (xy Ly, Ly, 0) included, gives the same rho.  The phase is reduced exactly before it is evaluated (every product m_i s_i loses its
+ * integer part in one fused operation, the sum its own, then sincospi): no sine or cosine of a large argument is taken, and the error
+ * of one term is that of s itself -- two roundings in s_x, one in s_y and s_z, times 2 pi |m_i| -- plus a few 1e-16.
+ * rho (DEVICE, ntypes x nk x 2 doubles, (re, im) interleaved, or NULL) is OVERWRITTEN; sums (DEVICE, npt x nk doubles, or NULL) is ADDED
+ * to: sums[p nk + q] += Re(rho_a(m_q) conj rho_b(m_q)) for the pair type p(a, b) = a ntypes - a (a - 1)/2 + (b - a), a <= b, of the
+ * npt = ntypes (ntypes + 1)/2, with the rho of this call: the caller zeroes it once and accumulates as many samples as it likes,
+ * S_ab(k) = sums / (samples sqrt(N_a N_b)) (pse_amd.analyze.StructureFactor does this).  Both are in the caller's order of the modes.
+ * A type without particles has rho exactly 0, and (0, 0, 0) gives rho_a = N_a exactly.
+ * No floating-point atomics: every sum has a fixed order, equal inputs give equal bits.  The distinct modes are sorted at creation (mx, then
+ * my, then mz) and cut into arithmetic progressions m0 + t d of at most 8 modes, each seeded from the exactly reduced phase and
+ * continued by one complex multiplication per mode: the value of a mode is a function of the mode SET, not of the order of the list,
+ * and a permuted list gives the same bits, permuted.  A permuted particle order changes the order of the sums: equal to rounding.
+ * The call only queues work on the handle's stream and reads nothing back.  It does not sort and does not touch the cell list, the
+ * kept neighbour list or its counters, and it works on a slab rank's handle (n_slabs >= 2: positions are replicated there, the sums
+ * are complete), as the bonded passes do.
+ * The object belongs to its handle: pse_destroy frees the objects still alive, pse_structure_factor_destroy after that is a caller
+ * error; pse_structure_factor_destroy waits for the stream.  Types and modes are copied at creation, and the object holds the
+ * workspace of the partial sums, sized from n_max, ntypes and nk (at most 256 MB).
+ * pse_structure_factor_create returns PSE_ERR_INVALID, with a message naming the value, for, in this order: a null out or h, n == 0
+ * or n > n_max, ntypes outside [1, 8], nk == 0 or nk > 32768, a null modes_host, an index beyond +-4096, a type >= ntypes.  *out is
+ * null after a refusal.  pse_structure_factor_accumulate, in this order: a null f, N == 0 or N > n_max, a null pos, rho and sums both
+ * null, either of them not 8-byte aligned; nothing is launched and nothing is written then. */
+#define PSE_SF_MAX_INDEX 4096    /* |mx|, |my|, |mz| */
+#define PSE_SF_MAX_MODES 32768   /* nk */
+typedef struct pse_structure_factor pse_structure_factor;
+int pse_structure_factor_create(pse_handle *h, unsigned n, const unsigned *types_host /* n, or NULL: one type */, int ntypes,
+                                unsigned nk, const int *modes_host /* nk x 3 */, pse_structure_factor **out);
+int pse_structure_factor_destroy(pse_structure_factor *f);
+int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *pos, const unsigned *group, unsigned N,
+                                    double *rho  /* DEVICE, ntypes x nk x 2 (re, im), OVERWRITTEN, may be NULL */,
+                                    double *sums /* DEVICE, npt x nk, ADDED to, may be NULL */);
+
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,

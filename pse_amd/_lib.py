@@ -135,6 +135,9 @@ SYMBOLS = {
     "pse_pair_hist_create": (_i, [_vp, _u, _vp, _i, _i, _d, _d, _vp]),
     "pse_pair_hist_destroy": (_i, [_vp]),
     "pse_pair_hist_accumulate": (_i, [_vp, _vp, _vp, _u, _vp, _vp]),
+    "pse_structure_factor_create": (_i, [_vp, _u, _vp, _i, _u, _vp, _vp]),
+    "pse_structure_factor_destroy": (_i, [_vp]),
+    "pse_structure_factor_accumulate": (_i, [_vp, _vp, _vp, _u, _vp, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -39,6 +39,7 @@ struct pse_dihedrals : Topology { using Topology::Topology; };
 struct pse_exclusions : Topology { using Topology::Topology; };
 struct pse_typed_table : Topology { using Topology::Topology; };   // row_off: the REAL layout (pse_host_typed_table_layout), entries: the types
 struct pse_pair_hist : Topology { using Topology::Topology; };     // entries: the types (zeros where none were given)
+struct pse_structure_factor : Topology { using Topology::Topology; };   // row_off: the REAL plan (structure_factor_plan), entries: its permutation
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -173,6 +174,22 @@ int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const uns
                              const pse_exclusions *ex) {
     pse_handle *h = g ? g->h : nullptr;   // (pos and counts are device pointers and there is no device: nothing is read or written)
     return pair_hist_validate(g, h, h ? h->par.n_max : 0u, N, pos, counts, ex, ex ? ex->h : nullptr);
+}
+int pse_structure_factor_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, unsigned nk, const int *modes_host,
+                                pse_structure_factor **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_structure_factor_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_structure_factor_create: null handle");
+    if (int rc = structure_factor_create_validate(h->par.n_max, n, types_host, ntypes, nk, modes_host)) return rc;
+    pse_structure_factor *f = new pse_structure_factor(h, 0, 0);
+    std::vector<unsigned> uoff;
+    structure_factor_plan(nk, modes_host, f->entries, uoff, f->row_off);
+    return topology_adopt(f, 0, out);
+}
+int pse_structure_factor_destroy(pse_structure_factor *f) { return topology_destroy(f); }
+int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *pos, const unsigned *, unsigned N, double *rho, double *sums) {
+    pse_handle *h = f ? f->h : nullptr;   // (pos, rho and sums are device pointers and there is no device: nothing is read or written)
+    return structure_factor_validate(f, h ? h->par.n_max : 0u, N, pos, rho, sums);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -444,6 +444,20 @@ struct pse_pair_hist : Topology {
         for (void *p : ptrs) if (p) (void)hipFree(p);
     }
 };
+// A static structure factor (include/pse_amd.h): n = particles with a type, count = nk modes, ntypes; the plan of the modes
+// (structure_factor_plan) and the workspace of the partial sums.  The arrays of Topology stay null.
+struct pse_structure_factor : Topology {
+    unsigned char *types = nullptr;         // n: the type of caller-order particle t
+    int4 *segs = nullptr;                   // 2 nseg: the segments of the canonical order
+    unsigned *perm = nullptr;               // nk: the caller's indices in the canonical order
+    unsigned *uoff = nullptr;               // nu + 1: where the u-th distinct mode begins in perm
+    double2 *rows = nullptr;                // sf_workspace(n_max, ntypes, nk)
+    int nseg = 0, nlong = 0, nu = 0, span = 0;
+    ~pse_structure_factor() override {
+        void *ptrs[] = {types, segs, perm, uoff, rows};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
+};
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
@@ -2889,6 +2903,56 @@ extern "C" int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos
     const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
     const PairHist ph{g->types, g->type_s, g->n, g->ntypes, g->nbins, g->rmin, g->rmax};
     launch_pair_hist(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, ph, counts, h->stream, ex ? &er : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Static structure factors (include/pse_amd.h): the types, the plan of the modes and the workspace on the device, and the pass.
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
+extern "C" int pse_structure_factor_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, unsigned nk, const int *modes_host,
+                                           pse_structure_factor **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_structure_factor_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_structure_factor_create: null handle");
+    TRY(structure_factor_create_validate((unsigned)h->n_max, n, types_host, ntypes, nk, modes_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
+    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
+    std::vector<unsigned> perm, uoff;
+    std::vector<int> segs;
+    structure_factor_plan(nk, modes_host, perm, uoff, segs);
+    pse_structure_factor *f = new pse_structure_factor();
+    f->h = h; f->n = n; f->count = nk; f->ntypes = ntypes;
+    f->nseg = (int)(segs.size() / 8);
+    for (size_t g = 0; g < segs.size(); g += 8) f->nlong += segs[g + 3] > SF_SHORT;
+    f->nu = (int)uoff.size() - 1; f->span = sf_span((unsigned)h->n_max, ntypes, (int)nk);
+    const size_t work = sf_workspace((unsigned)h->n_max, ntypes, (int)nk) * sizeof(double2);
+    hipError_t e = hipMalloc((void **)&f->types, n);
+    if (e == hipSuccess) e = hipMemcpy(f->types, types.data(), n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&f->segs, segs.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(f->segs, segs.data(), segs.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&f->perm, (size_t)nk * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemcpy(f->perm, perm.data(), (size_t)nk * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&f->uoff, uoff.size() * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemcpy(f->uoff, uoff.data(), uoff.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&f->rows, work);
+    if (e != hipSuccess) {
+        delete f;
+        return fail(PSE_ERR_HIP, "pse_structure_factor_create: %u types, %u modes and a workspace of %zu bytes on the device failed: %s", n, nk,
+                    work, hipGetErrorString(e));
+    }
+    h->topologies.push_back(f);
+    *out = f;
+    return 0;
+}
+extern "C" int pse_structure_factor_destroy(pse_structure_factor *f) { return topology_destroy(f); }
+extern "C" int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *pos, const unsigned *group, unsigned N, double *rho,
+                                               double *sums) {
+    pse_handle *h = f ? f->h : nullptr;
+    TRY(structure_factor_validate(f, h ? (unsigned)h->n_max : 0u, N, pos, rho, sums));
+    HIPCHK(hipSetDevice(h->device));
+    const StructureFactor sf{f->types, f->n, f->ntypes, f->segs, f->nseg, f->nlong, f->perm, f->uoff, f->nu, (int)f->count, f->rows, f->span};
+    launch_structure_factor((const double4 *)pos, group, (int)N, h->dbox, sf, rho, sums, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -4,6 +4,7 @@
 // (python -m pse_amd.build --asan).
 #pragma once
 #include <string>
+#include <vector>
 
 #include "../../include/pse_amd.h"
 #include "pse_host.h"
@@ -58,5 +59,17 @@ int pair_hist_create_validate(double rcut, unsigned n_max, int n_slabs, unsigned
 // counts; then an exclusion object, if one is given, of the same handle
 int pair_hist_validate(const void *g, const void *g_handle, unsigned n_max, unsigned N, const void *pos, const void *counts, const void *ex,
                        const void *ex_handle);
+// the argument checks of pse_structure_factor_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists
+// them (types may be null: one type), with the handle's n_max
+int structure_factor_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes);
+// the argument checks of pse_structure_factor_accumulate: the object (n_max its handle's), N, pos, rho and sums
+int structure_factor_validate(const void *f, unsigned n_max, unsigned N, const void *pos, const void *rho, const void *sums);
+// The plan of a mode list (nk x 3), a function of the mode SET: perm = the caller's indices in the canonical order (ascending mx,
+// then my, then mz; equal modes by index); uoff (nu + 1) = where the u-th DISTINCT mode begins in perm -- a duplicate is computed once
+// and written to every place that asked for it; and the segments that cover the nu distinct modes in that order: greedy arithmetic
+// progressions m0 + t d, d the difference of a segment's first two modes (any integer vector), cut after SF_RUN modes and in front of (0, 0, 0), which is always a seed (rho = N_a exactly).  segs holds
+// eight ints per segment: m0x, m0y, m0z, len, dx, dy, dz, first (the position of m0 among the distinct modes); the segments of more
+// than SF_SHORT modes come first, the short ones behind them, each class in the canonical order.
+void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> &perm, std::vector<unsigned> &uoff, std::vector<int> &segs);
 
 }  // namespace pse

@@ -60,6 +60,28 @@ struct PairHist {
 };
 void launch_pair_hist(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const PairHist &ph,
                       unsigned long long *counts, hipStream_t s, const PairExclusions *ex = nullptr);
+// static structure factor (k_sf_partial, k_sf_finish; pse_structure_factor_create): the device arrays of one object.  types: n bytes
+// as in PairTypedTables (a caller index >= n acts as type 0); segs: two int4 per segment of the mode plan (structure_factor_plan):
+// (m0x, m0y, m0z, len), (dx, dy, dz, first); perm: nk, the caller's indices in the canonical order, uoff: nu + 1, where the u-th of the nu
+// DISTINCT modes begins in perm (its value goes to every caller index there); rows: the workspace of sf_workspace(n_max, ntypes, nk)
+// complex numbers, one row of nu per (span of `span` particles, type); span = sf_span(n_max, ntypes, nk),
+// a multiple of the staged chunk, the smallest with which the workspace stays within 256 MB.  rho (ntypes x nk x 2, overwritten) and
+// sums (npt x nk, added to) are the caller's device arrays in its order of the modes, either may be null.
+struct StructureFactor {
+    const unsigned char *types;
+    unsigned n;
+    int ntypes;
+    const int4 *segs;
+    int nseg, nlong;   // segments in all, and those of more than SF_SHORT modes, which come first
+    const unsigned *perm, *uoff;
+    int nu, nk;
+    double2 *rows;
+    int span;
+};
+int sf_span(unsigned n_max, int ntypes, int nk);
+size_t sf_workspace(unsigned n_max, int ntypes, int nk);
+void launch_structure_factor(const double4 *pos, const unsigned *group, int N, DBox box, const StructureFactor &sf, double *rho, double *sums,
+                             hipStream_t s);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
 // entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
 // eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does

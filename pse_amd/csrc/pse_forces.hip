@@ -1,5 +1,5 @@
 // Kernels of the force providers (pse_forces.h): pair repulsion, tabulated and typed pair tables with exclusions and the pair-distance
-// histogram on the engine's cell list, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
+// histogram on the engine's cell list, the static structure factor on the caller-order positions, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
 // they leave in net_force.  gfx950, wave64, fp64.
 #include "pse_forces.h"
 
@@ -429,6 +429,172 @@ void launch_pair_hist(const double4 *pos_s, const unsigned *tag_s, int N, const 
         hipLaunchKernelGGL((k_pair_hist<decltype(excl)::value>), dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, ph.type_s, N, cell_off, box,
                            nc, ph.ntypes, ph.nbins, ncount, ph.rmin, ph.rmax * ph.rmax, scale, counts, er);
     });
+}
+
+// Static structure factor (pse_structure_factor_accumulate): rho_a(m) = sum_{j of type a} exp(-2 pi i m.s_j) over a list of integer
+// modes m, s the fractional coordinates (x - xy y)/Lx, y/Ly, z/Lz without the 1/2 and without wrapping, and the products
+// Re(rho_a conj rho_b).  N x nk complex exponentials, no cell list, nothing sorted: the pass reads pos through `group`.
+// Pass 1, k_sf_partial.  The modes come as SEGMENTS (structure_factor_plan): arithmetic progressions m0 + t d of len <= SF_RUN modes of
+// the canonically sorted list.  A LANE owns a segment and keeps its SF_RUN complex sums in registers; a workgroup is ONE wave, 64
+// segments (a tile), and walks a span of particles -- row `row` of the workspace -- in chunks of SF_CHUNK staged in LDS: each lane
+// computes s for four particles (two divisions and a fused multiply-add, so that s_x has two roundings and s_y, s_z one) and
+// stores s and the type; then all lanes walk the chunk together.  The particle index is wave-uniform, the LDS reads broadcast, and
+// there is NO reduction across lanes: the sum of a mode is formed by one lane in particle order.  Per particle and segment:
+// f_c = fma(m_c, s_c, -rint(m_c s_c)) takes the integer part off every product EXACTLY (the fused operation rounds once, a value
+// below 1/2), t = f_x + f_y + f_z, t -= rint(t), and sincospi(2 t) is the seed; the same for the step d; then SF_RUN - 1 complex
+// multiplications.  Sums past len continue the progression and are not written.  The segments of at most SF_SHORT = 2 modes -- all
+// of a scattered list, the ends of runs -- are walked by a second launch of the same kernel with two sums per lane (R = SF_SHORT): one
+// step of the recurrence instead of seven.  Nothing takes sin or cos of a large argument.
+// Types: the pass runs once per type over the span and skips the particles of the other types -- a wave-uniform branch on a byte
+// from LDS, two instructions against the ~150 of a particle that counts -- and restages the chunks per type (1.3 % of the walk per
+// type).  Row (row, a) of the workspace, one complex number per distinct mode at its canonical position, is written whole, zeros for a type that is
+// absent: the finish reads no stale word.  Two barriers per chunk; no lane leaves before a barrier: a lane past the last segment
+// walks a segment of len 0 and writes nothing.
+// Pass 2, k_sf_finish: one thread column per distinct mode of the canonical order, SF_FIN_WAVES waves per workgroup that share the rows r = w, w + W, ...;
+// each adds its rows in ascending order (four at a time in flight), the waves' sums are added in wave order through LDS: a fixed
+// order, no floating-point atomics, equal inputs give equal bits.  Wave 0 then holds rho_a of its mode for all types, writes rho
+// and adds the products to sums, at every caller position of the mode (perm[uoff[q] .. uoff[q + 1]): a mode listed twice is computed
+// once and has the same bits in both places).
+// Measured (docs/HISTORY.md, N = 10^6): 768 modes on the three axes 0.77 ms, 4096 scattered modes 7.6 ms, one type or two.  Measured
+// and dropped: one launch with eight sums per lane for every segment -- 9.8 ms on the scattered list, whose segments are pairs.  Not
+// built, so not measured: lanes over particles with a tile of mode sums per lane and a wave + LDS reduction per tile, and a
+// deterministic partition of the chunk by type.
+constexpr int SF_CHUNK = 256;       // particles staged per barrier pair: 6.25 KB of LDS
+constexpr int SF_TILE = 64;         // segments per workgroup of k_sf_partial: one wave
+constexpr int SF_FIN_WAVES = 16;    // waves of a workgroup of k_sf_finish
+__device__ __forceinline__ void sf_phase(double mx, double my, double mz, double sx, double sy, double sz, double &c, double &s) {
+    const double fx = fma(mx, sx, -rint(mx * sx)), fy = fma(my, sy, -rint(my * sy)), fz = fma(mz, sz, -rint(mz * sz));
+    double t = fx + fy + fz;
+    t -= rint(t);
+    sincospi(-2.0 * t, &s, &c);   // exp(-2 pi i t)
+}
+template <int R>
+__global__ void __launch_bounds__(SF_TILE)
+k_sf_partial(const double4 *__restrict__ pos, const unsigned *__restrict__ group, int N, const unsigned char *__restrict__ types, unsigned ntyped,
+             int ntypes, DBox box, const int4 *__restrict__ segs, int nseg, int ntiles, int span, int nu,
+             double2 *__restrict__ rows /* [nrows][ntypes][nu] */) {
+    __shared__ double sx[SF_CHUNK], sy[SF_CHUNK], sz[SF_CHUNK];
+    __shared__ unsigned char st[SF_CHUNK];
+    const int lane = threadIdx.x, tile = blockIdx.x % ntiles, row = blockIdx.x / ntiles;
+    const int seg = tile * SF_TILE + lane;
+    int4 a0 = make_int4(0, 0, 0, 0), a1 = make_int4(0, 0, 0, 0);
+    if (seg < nseg) { a0 = segs[2 * seg]; a1 = segs[2 * seg + 1]; }
+    const double mx = a0.x, my = a0.y, mz = a0.z, dx = a1.x, dy = a1.y, dz = a1.z;
+    const int len = a0.w, first = a1.w;
+    const long jb = (long)row * span, je = min((long)N, jb + span);
+    for (int a = 0; a < ntypes; ++a) {
+        double re[R], im[R];
+#pragma unroll
+        for (int t = 0; t < R; ++t) re[t] = im[t] = 0.0;
+        for (long base = jb; base < je; base += SF_CHUNK) {
+            const int cnt = (int)min((long)SF_CHUNK, je - base);
+            __syncthreads();   // the walk of the chunk before is over
+            for (int q = lane; q < cnt; q += SF_TILE) {
+                const unsigned idx = group ? group[base + q] : (unsigned)(base + q);
+                const double4 p = pos[idx];
+                sx[q] = fma(-box.xy, p.y, p.x) / box.Lx;
+                sy[q] = p.y / box.Ly;
+                sz[q] = p.z / box.Lz;
+                st[q] = idx < ntyped ? types[idx] : (unsigned char)0;
+            }
+            __syncthreads();
+            for (int q = 0; q < cnt; ++q) {
+                if (__builtin_amdgcn_readfirstlane((int)st[q]) != a) continue;   // (wave-uniform: a scalar branch)
+                const double x = sx[q], y = sy[q], z = sz[q];
+                double cr, ci, wr, wi;
+                sf_phase(mx, my, mz, x, y, z, cr, ci);
+                sf_phase(dx, dy, dz, x, y, z, wr, wi);
+#pragma unroll
+                for (int t = 0; t < R; ++t) {
+                    re[t] += cr; im[t] += ci;
+                    const double nr = cr * wr - ci * wi;
+                    ci = cr * wi + ci * wr;
+                    cr = nr;
+                }
+            }
+        }
+        double2 *__restrict__ out = rows + ((size_t)row * ntypes + a) * nu + first;
+#pragma unroll
+        for (int t = 0; t < R; ++t)
+            if (t < len) out[t] = make_double2(re[t], im[t]);
+    }
+}
+__global__ void __launch_bounds__(SF_TILE * SF_FIN_WAVES)
+k_sf_finish(const double2 *__restrict__ rows, int nrows, int ntypes, int nu, int nk, const unsigned *__restrict__ perm,
+            const unsigned *__restrict__ uoff, double *__restrict__ rho, double *__restrict__ sums) {
+    __shared__ double2 sh[SF_FIN_WAVES][SF_TILE];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int q = blockIdx.x * SF_TILE + lane;
+    const bool live = q < nu;
+    double rr[PAIR_TYPED_MAX_TYPES], ri[PAIR_TYPED_MAX_TYPES];
+#pragma unroll
+    for (int a = 0; a < PAIR_TYPED_MAX_TYPES; ++a) {
+        rr[a] = ri[a] = 0.0;
+        if (a < ntypes) {   // (uniform: no lane leaves before a barrier)
+            double2 s0 = make_double2(0.0, 0.0), s1 = s0, s2 = s0, s3 = s0;
+            if (live) {
+                const double2 *__restrict__ col = rows + (size_t)a * nu + q;
+                const size_t stride = (size_t)ntypes * nu;
+                int r = w;
+                for (; r + 3 * SF_FIN_WAVES < nrows; r += 4 * SF_FIN_WAVES) {
+                    const double2 v0 = col[(size_t)r * stride], v1 = col[(size_t)(r + SF_FIN_WAVES) * stride],
+                                  v2 = col[(size_t)(r + 2 * SF_FIN_WAVES) * stride], v3 = col[(size_t)(r + 3 * SF_FIN_WAVES) * stride];
+                    s0.x += v0.x; s0.y += v0.y; s1.x += v1.x; s1.y += v1.y; s2.x += v2.x; s2.y += v2.y; s3.x += v3.x; s3.y += v3.y;
+                }
+                for (; r < nrows; r += SF_FIN_WAVES) { const double2 v = col[(size_t)r * stride]; s0.x += v.x; s0.y += v.y; }
+            }
+            sh[w][lane] = make_double2((s0.x + s1.x) + (s2.x + s3.x), (s0.y + s1.y) + (s2.y + s3.y));
+            __syncthreads();
+            if (w == 0) {
+                double x = 0.0, y = 0.0;
+#pragma unroll
+                for (int v = 0; v < SF_FIN_WAVES; ++v) { x += sh[v][lane].x; y += sh[v][lane].y; }
+                rr[a] = x; ri[a] = y;
+            }
+            __syncthreads();
+        }
+    }
+    if (w != 0 || !live) return;   // (behind the last barrier)
+    for (unsigned e = uoff[q]; e < uoff[q + 1]; ++e) {   // (one place, or every place of a mode that is listed more than once)
+        const unsigned o = perm[e];
+        int p = 0;
+#pragma unroll
+        for (int a = 0; a < PAIR_TYPED_MAX_TYPES; ++a) {
+            if (a >= ntypes) break;
+            if (rho) { rho[2 * ((size_t)a * nk + o)] = rr[a]; rho[2 * ((size_t)a * nk + o) + 1] = ri[a]; }
+#pragma unroll
+            for (int b = a; b < PAIR_TYPED_MAX_TYPES; ++b) {
+                if (b >= ntypes) break;
+                if (sums) sums[(size_t)p * nk + o] += rr[a] * rr[b] + ri[a] * ri[b];
+                ++p;
+            }
+        }
+    }
+}
+int sf_span(unsigned n_max, int ntypes, int nk) {
+    const long chunks = nblocks((long)n_max, SF_CHUNK);
+    const long per = ((long)1 << 24) / ((long)ntypes * nk);   // rows that fit 2^24 complex numbers = 256 MB (>= 64: ntypes nk <= 2^18)
+    return (int)(SF_CHUNK * ((chunks + per - 1) / per));
+}
+size_t sf_workspace(unsigned n_max, int ntypes, int nk) {
+    return (size_t)nblocks((long)n_max, sf_span(n_max, ntypes, nk)) * ntypes * nk;
+}
+void launch_structure_factor(const double4 *pos, const unsigned *group, int N, DBox box, const StructureFactor &sf, double *rho, double *sums,
+                             hipStream_t s) {
+    static_assert(SF_TILE == 64, "a workgroup of k_sf_partial is one wave");
+    const int nrows = nblocks(N, sf.span), nshort = sf.nseg - sf.nlong;
+    if (sf.nlong) {
+        const int ntiles = nblocks(sf.nlong, SF_TILE);
+        hipLaunchKernelGGL(k_sf_partial<SF_RUN>, dim3((unsigned)(nrows * ntiles)), dim3(SF_TILE), 0, s, pos, group, N, sf.types, sf.n, sf.ntypes,
+                           box, sf.segs, sf.nlong, ntiles, sf.span, sf.nu, sf.rows);
+    }
+    if (nshort) {
+        const int ntiles = nblocks(nshort, SF_TILE);
+        hipLaunchKernelGGL(k_sf_partial<SF_SHORT>, dim3((unsigned)(nrows * ntiles)), dim3(SF_TILE), 0, s, pos, group, N, sf.types, sf.n,
+                           sf.ntypes, box, sf.segs + 2 * sf.nlong, nshort, ntiles, sf.span, sf.nu, sf.rows);
+    }
+    hipLaunchKernelGGL(k_sf_finish, dim3(nblocks(sf.nu, SF_TILE)), dim3(SF_TILE * SF_FIN_WAVES), 0, s, sf.rows, nrows, sf.ntypes, sf.nu,
+                       sf.nk, sf.perm, sf.uoff, rho, sums);
 }
 
 // Bonded forces (HOOMD's bond.harmonic and bond.fene; no reference counterpart: the reference leaves forces to HOOMD).  One thread

@@ -12,6 +12,10 @@ constexpr int RS_PER_UNIT = 8;      // intervals of width 1/8 (in units of the p
 
 constexpr int PAIR_TABLE_MAX_WIDTH = 2048;   // entries of a pair table (pse_pair_table): staged in 32 KB of LDS
 constexpr int PAIR_HIST_MAX_COUNTERS = 8192;   // counters of a pair histogram (pse_pair_hist_create), pair types x bins: 32 KB of LDS
+constexpr int SF_MAX_INDEX = 4096;     // |mx|, |my|, |mz| of a structure-factor mode (pse_structure_factor_create; PSE_SF_MAX_INDEX)
+constexpr int SF_MAX_MODES = 32768;    // modes of one structure-factor object (PSE_SF_MAX_MODES)
+constexpr int SF_RUN = 8;              // modes of one segment: a lane of k_sf_partial keeps their sums in registers, seeded exactly, 7 steps
+constexpr int SF_SHORT = 2;            // a segment of at most this many modes is walked by the short form of the kernel (k_sf_partial<SF_SHORT>)
 constexpr int PAIR_TYPED_MAX_TYPES = 8;      // particle types of a typed pair table (pse_typed_table_create): at most 36 pair types
 constexpr int PAIR_TYPED_MAX_ENTRIES = 3584; // entries of all its tables together: 56 KB of LDS, next to 1.4 KB of static LDS, inside 64 KB
 constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS

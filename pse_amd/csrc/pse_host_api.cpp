@@ -291,6 +291,78 @@ int pair_hist_validate(const void *g, const void *g_handle, unsigned n_max, unsi
     return 0;
 }
 
+int structure_factor_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes) {
+    const char *who = "pse_structure_factor_create";
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (nk == 0 || nk > (unsigned)SF_MAX_MODES) return fail(PSE_ERR_INVALID, "%s: nk = %u outside [1, %d]", who, nk, SF_MAX_MODES);
+    if (!modes) return fail(PSE_ERR_INVALID, "%s: null modes_host", who);
+    for (unsigned q = 0; q < nk; ++q)
+        for (int c = 0; c < 3; ++c)
+            if (modes[3 * (size_t)q + c] > SF_MAX_INDEX || modes[3 * (size_t)q + c] < -SF_MAX_INDEX)
+                return fail(PSE_ERR_INVALID, "%s: mode %u has the index m%c = %d beyond +-%d", who, q, "xyz"[c], modes[3 * (size_t)q + c], SF_MAX_INDEX);
+    if (types)
+        for (unsigned i = 0; i < n; ++i)
+            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    return 0;
+}
+
+int structure_factor_validate(const void *f, unsigned n_max, unsigned N, const void *pos, const void *rho, const void *sums) {
+    const char *who = "pse_structure_factor_accumulate";
+    if (!f) return fail(PSE_ERR_INVALID, "%s: null structure-factor object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!rho && !sums) return fail(PSE_ERR_INVALID, "%s: rho and sums are both null: nothing to compute", who);
+    if (((uintptr_t)rho & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: rho = %p is not 8-byte aligned (doubles)", who, rho);
+    if (((uintptr_t)sums & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sums = %p is not 8-byte aligned (doubles)", who, sums);
+    return 0;
+}
+
+void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> &perm, std::vector<unsigned> &uoff, std::vector<int> &segs) {
+    perm.resize(nk);
+    for (unsigned q = 0; q < nk; ++q) perm[q] = q;
+    auto differ = [&](unsigned a, unsigned b) {
+        for (int c = 0; c < 3; ++c)
+            if (modes[3 * (size_t)a + c] != modes[3 * (size_t)b + c]) return true;
+        return false;
+    };
+    std::sort(perm.begin(), perm.end(), [&](unsigned a, unsigned b) {
+        for (int c = 0; c < 3; ++c)
+            if (modes[3 * (size_t)a + c] != modes[3 * (size_t)b + c]) return modes[3 * (size_t)a + c] < modes[3 * (size_t)b + c];
+        return a < b;
+    });
+    uoff.clear();
+    for (unsigned e = 0; e < nk; ++e)
+        if (e == 0 || differ(perm[e - 1], perm[e])) uoff.push_back(e);
+    const unsigned nu = (unsigned)uoff.size();
+    uoff.push_back(nk);
+    auto m = [&](unsigned u, int c) { return modes[3 * (size_t)perm[uoff[u]] + c]; };
+    segs.clear();
+    for (unsigned q = 0; q < nu;) {
+        int d[3] = {0, 0, 0};
+        unsigned len = 1;
+        auto zero = [&](unsigned u) { return m(u, 0) == 0 && m(u, 1) == 0 && m(u, 2) == 0; };   // (0, 0, 0) is always a seed: rho = N_a exactly
+        if (q + 1 < nu && !zero(q + 1)) {
+            for (int c = 0; c < 3; ++c) d[c] = m(q + 1, c) - m(q, c);
+            len = 2;
+            while (len < (unsigned)SF_RUN && q + len < nu && !zero(q + len) && m(q + len, 0) - m(q + len - 1, 0) == d[0] &&
+                   m(q + len, 1) - m(q + len - 1, 1) == d[1] && m(q + len, 2) - m(q + len - 1, 2) == d[2])
+                ++len;
+        }
+        const int sg[8] = {m(q, 0), m(q, 1), m(q, 2), (int)len, d[0], d[1], d[2], (int)q};
+        segs.insert(segs.end(), sg, sg + 8);
+        q += len;
+    }
+    // the segments of more than SF_SHORT modes first, the short ones behind them, each class in the canonical order: the pass runs
+    // the classes as two launches (a scattered list is all pairs and single modes: seven of eight recurrence steps would be wasted)
+    std::vector<int> sorted;
+    sorted.reserve(segs.size());
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t g = 0; g < segs.size(); g += 8)
+            if ((segs[g + 3] > SF_SHORT) == (pass == 0)) sorted.insert(sorted.end(), segs.begin() + g, segs.begin() + g + 8);
+    segs.swap(sorted);
+}
+
 }  // namespace pse
 
 using namespace pse;

@@ -380,6 +380,54 @@ class PairHistogram(_DeviceObject):
         self._create(engine, "pse_pair_hist_create", self.n, _vp(types), self.ntypes, self.nbins, self.rmin, self.rmax)
 
 
+SF_MAX_INDEX = 4096    # pse_structure_factor_create: |mx|, |my|, |mz|
+SF_MAX_MODES = 32768   # ... and the number of modes
+
+
+def _structure_factor_arguments(types, ntypes, modes):
+    """The arguments of a structure-factor object, checked before the device is touched: (types uint32 (n,) or None, ntypes, modes
+    int32 (nk, 3)).  `types`: None (one type) or a 1-D array of integers in [0, ntypes); `modes`: integer triples within
+    +-SF_MAX_INDEX, at most SF_MAX_MODES of them."""
+    import numpy as np
+    ntypes = int(ntypes)
+    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
+        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    modes = np.asarray(modes)
+    if modes.ndim != 2 or modes.shape[1] != 3 or modes.shape[0] == 0 or not np.issubdtype(modes.dtype, np.integer):
+        raise ValueError("modes must be a non-empty integer (nk, 3) array of reciprocal-lattice indices (mx, my, mz)")
+    if modes.shape[0] > SF_MAX_MODES:
+        raise ValueError(f"{modes.shape[0]} modes, more than {SF_MAX_MODES}")
+    if np.abs(modes).max() > SF_MAX_INDEX:
+        raise ValueError(f"modes holds the index {int(np.abs(modes).max())} beyond +-{SF_MAX_INDEX}")
+    if types is not None:
+        types = np.asarray(types)
+        if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
+            raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
+        if types.max() >= ntypes:
+            raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
+        types = np.ascontiguousarray(types, dtype=np.uint32)
+    return types, ntypes, np.ascontiguousarray(modes, dtype=np.int32)
+
+
+class StructureFactorModes(_DeviceObject):
+    """Owner of a pse_structure_factor object: one type per particle and a list of integer modes (mx, my, mz) of the box's reciprocal
+    lattice.  `types`: (n,) integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts
+    as type 0.  Pass it as `sf` to Engine.structure_factor_accumulate."""
+
+    DESTROY = "pse_structure_factor_destroy"
+
+    def __init__(self, engine, types, ntypes, modes, n=None):
+        types, self.ntypes, self.modes = _structure_factor_arguments(types, ntypes, modes)
+        self.npt, self.nk = self.ntypes * (self.ntypes + 1) // 2, int(self.modes.shape[0])
+        if types is None:
+            self.n = _rows(engine, n)
+        else:
+            self.n = int(types.shape[0] if n is None else n)
+            if not 0 <= self.n <= types.shape[0]:
+                raise ValueError("n outside [0, len(types)]")
+        self._create(engine, "pse_structure_factor_create", self.n, _vp(types), self.ntypes, self.nk, _vp(self.modes))
+
+
 class _ForcePasses:
     """The force providers of the C-ABI on one handle, for whoever holds one: an Engine, which owns its handle, and the
     StokesEngine of an integrator, whose handle the C++ Stokes object owns.  Needs `_lib`, `_h` (the handle; raises where there is
@@ -484,6 +532,32 @@ class _ForcePasses:
         _lib.check(self._lib.pse_pair_hist_accumulate(hist._handle(self), _ptr(pos), _ptr(group), n, _ptr(counts),
                                                       None if exclusions is None else exclusions._handle(self)))
         return counts
+
+    def structure_factor(self, types, ntypes, modes, n=None):
+        """A static structure factor on the device (pse_structure_factor_create; see include/pse_amd.h): `types` (n,) the type of
+        every caller-order particle, below `ntypes` <= 8, or None: one type; `modes` (nk, 3) integers (mx, my, mz) within +-4096, at
+        most 32768, of the reciprocal lattice of whatever box the engine has when a sample is taken; `n`: how many of `types` to use
+        (default: all; without types: n_max).  Returns a StructureFactorModes with nk, ntypes, npt and close(): the `sf` of
+        structure_factor_accumulate."""
+        return StructureFactorModes(self, types, ntypes, modes, n)
+
+    def structure_factor_accumulate(self, pos, sf, rho=None, sums=None, group=None):
+        """One sample of the densities rho_a(m) = sum_{j of type a} exp(-2 pi i m.s_j) in the engine's current box
+        (pse_structure_factor_accumulate).  `rho`: a contiguous (ntypes, nk, 2) float64 CUDA tensor, (re, im), OVERWRITTEN; `sums`: a
+        contiguous (npt, nk) float64 CUDA tensor, ADDED to: sums[p, q] += Re(rho_a conj rho_b), p = pair_type_index(a, b) -- zero it
+        once, accumulate as many samples as you like.  Either may be None, not both.  Queue-only: nothing is read back, the sort and
+        the neighbour list are not touched; no atomics, equal inputs give equal bits.  Returns (rho, sums)."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        for t, name, shape in ((rho, "rho", (sf.ntypes, sf.nk, 2)), (sums, "sums", (sf.npt, sf.nk))):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                                      and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {shape} float64 CUDA tensor")
+        if rho is None and sums is None:
+            raise ValueError("rho and sums are both None: nothing to compute")
+        _lib.check(self._lib.pse_structure_factor_accumulate(sf._handle(self), _ptr(pos), _ptr(group), n, _ptr(rho), _ptr(sums)))
+        return rho, sums
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
