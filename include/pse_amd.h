@@ -369,6 +369,58 @@ int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *
                                     double *rho  /* DEVICE, ntypes x nk x 2 (re, im), OVERWRITTEN, may be NULL */,
                                     double *sums /* DEVICE, npt x nk, ADDED to, may be NULL */);
 
+/* ---- displacement moments: the drift, the mean-squared displacement tensor and the fourth moment per type, against up to 64 time origins (no reference counterpart) ----
+ * A pse_msd object fixes the types of the particles (types_host, ntypes <= 8, exactly as for pse_pair_hist_create: CALLER-order, NULL:
+ * all of type 0, a particle whose index is >= n acts as type 0; copied at creation) and holds norigins <= PSE_MSD_MAX_ORIGINS slots of
+ * n_max UNWRAPPED positions in fp64, three planes (x, y, z) of n_max doubles per slot, zeroed at creation, indexed by the caller-order
+ * particle index.  The unwrapped position of a particle at (x, y, z) with image (ix, iy, iz) in the box (Lx, Ly, Lz) is
+ *   x_u = x + ix Lx + iy (strain Ly),   y_u = y + iy Ly,   z_u = z + iz Lz,
+ * where `strain` is the ACCUMULATED tilt: the current xy plus the whole lattice vectors that Lees-Edwards flips have removed so far
+ * (pse_amd.system.System.strain).  It stands where xy would: position + image . box with the current xy jumps by iy Lx at every flip;
+ * r_u with the strain is the same point before and after a flip and through every re-wrap of x behind a changed tilt, every x and z
+ * wrap of pse_integrate and every y wrap BEFORE the first flip.  LIMIT: it is NOT continuous through a y image gained after a flip --
+ * the wrap of pse_integrate takes xy Ly, the CURRENT tilt, off x, the formula adds strain Ly, so x_u shifts by flips Ly per such
+ * image.  y_u and z_u are always right: the moments without x (dy, dz, dy^2, dz^2, dy dz) hold for any run; those with x (dx, dx^2,
+ * dx dy, dx dz, |d|^4) and the x of pse_msd_displacement hold for a sheared run only while no particle gains a y image after a flip.
+ * Lx, Ly, Lz are the handle's CURRENT box lengths (pse_set_box); its xy is not used.  sLy = strain Ly is formed once on the host, in
+ * double; the device evaluates x_u = fma(iy, sLy, fma(ix, Lx, x)), y_u = fma(iy, Ly, y), z_u = fma(iz, Lz, z): two roundings in x_u,
+ * one in y_u and z_u.
+ * pse_msd_store writes r_u of the N group members into `slot` and marks the slot stored (host bookkeeping: no device wait).
+ * pse_msd_accumulate computes r_u(now) of every group member once and, for every listed pair q = (slots_host[q], rows_host[q]) and
+ * every type a, with d = r_u(now) - r_u(slot),
+ *   sums[(rows_host[q] ntypes + a) PSE_MSD_MOMENTS + c] += sum over the members of type a of moment_c(d),
+ * c = 0..2: dx, dy, dz;  3..8: dx^2, dy^2, dz^2, dx dy, dx dz, dy dz;  9: (dx^2 + dy^2 + dz^2)^2.  A type without members adds exactly
+ * +0.0; rows of sums that no pair names are not touched.  The two host lists (at most 64 pairs) travel by value as a kernel argument:
+ * no copy, no wait.  The caller must use the same group for the store and the accumulate of one slot (documented, not checked).
+ * pse_msd_displacement writes, for every group member t, out[t] = (d.x, d.y, d.z, |d|^2) against `slot`; rows outside the group are
+ * not touched.
+ * No floating-point atomics: a wave owns 256 consecutive group members, four per lane; a lane adds the moments of its particles in
+ * registers, the wave adds the lanes' sums with a fixed halving tree and writes one row per listed pair and type into a workspace the
+ * object owns (sized for 64 pairs, whatever norigins is: a slot may be listed for several rows); a finishing kernel adds the rows of
+ * the waves in a fixed interleaved order and then adds to sums: equal inputs give equal bits.  All calls only queue work on the handle's stream and read nothing back.  They do
+ * not sort and do not touch the cell list, the kept neighbour list or its counters, and they work on a slab rank's handle
+ * (n_slabs >= 2: positions are replicated there, the sums are complete).
+ * The object belongs to its handle: pse_destroy frees the objects still alive, pse_msd_destroy after that is a caller error;
+ * pse_msd_destroy waits for the stream.  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_msd_create, in this order: a null out or
+ * h, n == 0 or n > n_max, ntypes outside [1, 8], norigins outside [1, 64], a type >= ntypes (*out is null after a refusal).
+ * pse_msd_store and pse_msd_displacement, in this order: a null m, slot outside [0, norigins), N == 0 or N > n_max, a null pos, a null
+ * image, a strain that is not finite; pse_msd_displacement then: a slot never stored, a null out or one that is not 8-byte aligned.
+ * pse_msd_accumulate, in this order: a null m, N == 0 or N > n_max, a null pos, a null image, a strain that is not finite, npairs
+ * outside [1, 64], a null slots_host or rows_host, nrows < 1, a slot out of range, a slot never stored, a row outside [0, nrows), a
+ * row listed twice in this call (the finishing pass would race), a null sums or one that is not 8-byte aligned. */
+#define PSE_MSD_MAX_ORIGINS 64
+#define PSE_MSD_MOMENTS     10
+typedef struct pse_msd pse_msd;
+int pse_msd_create(pse_handle *h, unsigned n, const unsigned *types_host /* n, or NULL: one type */, int ntypes, int norigins, pse_msd **out);
+int pse_msd_destroy(pse_msd *m);
+int pse_msd_store(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain);
+int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
+                       int npairs, const int *slots_host, const int *rows_host, int nrows,
+                       double *sums /* DEVICE, nrows x ntypes x 10, ADDED to */);
+int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
+                         pse_double4 *out /* DEVICE, caller order: d.xyz, |d|^2 in w; rows outside the group untouched */);
+
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,

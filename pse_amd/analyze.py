@@ -3,11 +3,13 @@ of the integrator's engine (pse_pair_hist_accumulate: one walk of the cell list 
 the counts into the radial distribution functions g_ab(r) and coordination numbers when they are read.  StructureFactor is the other
 half of how structure is reported: the densities rho_a(k) on the reciprocal lattice of the (tilted) box, summed directly and exactly
 on the device (pse_structure_factor_accumulate), and their products S_ab(k) -- at any k the box admits, far below 2 pi / rcut, and
-resolved in direction."""
+resolved in direction.  MSD is the dynamic counterpart: the engine keeps up to 64 time origins of unwrapped positions
+(pse_msd_store) and one streaming pass per sample sums the first, second and fourth moments of the displacement per type and per
+origin (pse_msd_accumulate): the drift, the mean-squared displacement tensor and the non-Gaussian parameter over many time origins."""
 import math
 
-from .engine import (SF_MAX_MODES, PairHistogram, StructureFactorModes, _pair_hist_arguments, _structure_factor_arguments,
-                     pair_type_index)
+from .engine import (MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, DisplacementOrigins, PairHistogram, StructureFactorModes, _msd_arguments,
+                     _pair_hist_arguments, _structure_factor_arguments, pair_type_index)
 from .forces import _excl_list
 
 
@@ -365,3 +367,208 @@ class StructureFactor:
     def shell_average(self, nbins, kmax=None, a=None, b=None):
         k = self.k   # (the differing-box check comes first)
         return shell_average_of(k, self.S(a, b), nbins, kmax)
+
+
+def unwrap(pos, image, box, strain):
+    """The unwrapped positions (N, 3) of wrapped positions `pos` (N, >= 3) with images `image` (N, 3) in the box (Lx, Ly, Lz[, xy]):
+    x + ix Lx + iy strain Ly, y + iy Ly, z + iz Lz.  `strain` is the ACCUMULATED tilt -- the box's xy plus the lattice vectors that
+    Lees-Edwards flips have taken off it so far (System.strain) -- and stands where xy would: with the current xy the result jumps by
+    iy Lx at every flip; with the strain it is the same point before and after a flip, through every re-wrap behind a changed tilt,
+    every x and z wrap and every y wrap before the first flip.  LIMIT: a y image gained AFTER a flip shifts x_u by flips Ly (the
+    step's wrap takes xy Ly, the current tilt, off x; the formula adds strain Ly): x_u of a sheared run is right only while no
+    particle gains a y image after a flip; y_u and z_u are always right.
+    NumPy only; the device restates it (pse_msd_store), with the same order of operations up to the fused roundings."""
+    import numpy as np
+    pos, image = np.asarray(pos, dtype=np.float64), np.asarray(image)
+    Lx, Ly, Lz = float(box[0]), float(box[1]), float(box[2])
+    sLy = float(strain) * Ly
+    out = np.empty((pos.shape[0], 3))
+    out[:, 0] = image[:, 1] * sLy + (image[:, 0] * Lx + pos[:, 0])
+    out[:, 1] = image[:, 1] * Ly + pos[:, 1]
+    out[:, 2] = image[:, 2] * Lz + pos[:, 2]
+    return out
+
+
+class MSDSchedule:
+    """Which origins an MSD sample is taken against and where the next origin goes; integers only.  Sample s = 0, 1, ... (1) is
+    accumulated against every origin j = 0, 1, ... with 1 <= s - j origin_every <= nlags, into row lag - 1, and then (2), if s is a
+    multiple of origin_every, is stored as origin s / origin_every in slot (s / origin_every) % norigins, norigins =
+    ceil(nlags / origin_every): a slot is overwritten only after its origin's lag nlags has been taken.  `counts[lag - 1]`: the origins
+    that lag has been taken against so far; `live[slot]`: the sample stored in that slot since the last reset()."""
+
+    def __init__(self, nlags, origin_every=1):
+        self.nlags, self.origin_every = int(nlags), int(origin_every)
+        if self.nlags < 1 or self.origin_every < 1:
+            raise ValueError("nlags and origin_every must be positive")
+        self.norigins = -(-self.nlags // self.origin_every)
+        if self.norigins > MSD_MAX_ORIGINS:
+            raise ValueError(f"nlags / origin_every = {self.nlags} / {self.origin_every} needs {self.norigins} origins, more than "
+                             f"{MSD_MAX_ORIGINS}")
+        self.reset()
+
+    def reset(self):
+        self.samples, self.counts, self.live = 0, [0] * self.nlags, {}
+
+    def pairs(self, s=None):
+        """[(slot, row)] of sample s (default: the next one), oldest origin first."""
+        s = self.samples if s is None else int(s)
+        oe = self.origin_every
+        first = max(0, -(-(s - self.nlags) // oe))          # the smallest j with s - j oe <= nlags
+        last = (s - 1) // oe if s >= 1 else -1               # the largest j with s - j oe >= 1
+        return [(j % self.norigins, s - j * oe - 1) for j in range(first, last + 1)]
+
+    def sample(self, accumulate, store):
+        """One sample: accumulate(slots, rows) if there is a live origin, then store(slot) if this sample is an origin."""
+        s, pairs = self.samples, self.pairs()
+        if pairs:
+            accumulate([p[0] for p in pairs], [p[1] for p in pairs])
+            for _, row in pairs:
+                self.counts[row] += 1
+        if s % self.origin_every == 0:
+            store((s // self.origin_every) % self.norigins)
+            self.live[(s // self.origin_every) % self.norigins] = s
+        self.samples = s + 1
+
+    def slot_of_lag(self, lag):
+        """The slot of the origin that was `lag` samples old at the last sample; ValueError if there is none."""
+        s = self.samples - 1
+        j, rem = divmod(s - int(lag), self.origin_every)
+        if s < 0 or not 1 <= int(lag) <= self.nlags or rem or j < 0:
+            raise ValueError(f"no live origin {lag} samples before the last sample")
+        return j % self.norigins
+
+
+def _msd_analyzer_arguments(nlags, origin_every, types, type_names, period):
+    """What MSD checks before it touches the device.  Returns (schedule, types uint32 or None, ntypes, names or None, period)."""
+    schedule = MSDSchedule(nlags, origin_every)
+    types, ntypes, names, period = _typed_arguments(types, type_names, period)
+    types, ntypes, _ = _msd_arguments(types, ntypes, schedule.norigins)
+    return schedule, types, ntypes, names, period
+
+
+def moments_of_sums(sums, counts, type_counts, a=None):
+    """The mean moments per lag of accumulated sums (nlags, ntypes, 10): sums[:, a] / (counts N_a), or with a = None those of all types
+    together, sum_a sums[:, a] / (counts N); nan where a lag has no origin yet or the type no particle.  NumPy only."""
+    import numpy as np
+    sums, counts = np.asarray(sums, dtype=np.float64), np.asarray(counts, dtype=np.float64)
+    tot, n = (sums.sum(axis=1), float(np.sum(type_counts))) if a is None else (sums[:, a], float(type_counts[a]))
+    den = counts * n
+    return np.divide(tot, den[:, None], out=np.full(tot.shape, np.nan), where=den[:, None] > 0.0)
+
+
+class MSD:
+    """Displacement moments of a run over many time origins: every `period` steps (a sample) the displacements d of the integrator's
+    group since each live origin are reduced on the device (pse_msd_accumulate) to ten sums per particle type and lag -- dx dy dz,
+    dx^2 dy^2 dz^2 dxdy dxdz dydz, |d|^4 -- in a float64 CUDA tensor of this object, and every `origin_every` samples the unwrapped
+    positions become a new origin (pse_msd_store).  Lags run from 1 to `nlags` samples; ceil(nlags / origin_every) <= 64 origins are
+    kept.  Sampling only queues work; the readers below are the only places that wait for the device.  `types`, `type_names`: as for
+    RDF; at most 8 types.  Positions are unwrapped with the system's accumulated strain (System.strain, analyze.unwrap): a flip of
+    the box does not move them.
+
+    Under shear the displacement contains the affine advection dx = rate * integral of y_u dt: the xx, xy and xz entries of the
+    tensor, the x component of the mean displacement and the trace contain it; yy, zz and yz do not (read msd_tensor()[:, 1, 1] +
+    msd_tensor()[:, 2, 2] for the diffusion across the flow).  LIMIT (analyze.unwrap): once the box has flipped, every y image a
+    particle gains shifts its unwrapped x by flips * Ly, so everything that contains x -- xx, xy, xz, the trace msd(), alpha2(), the x
+    of mean_displacement() and of displacement() -- is wrong from then on; yy, zz, yz and the y, z drift stay right.  msd() and
+    alpha2() warn (RuntimeWarning) when a sample was taken in a flipped box.
+
+    lags -- in steps;  counts -- origins per lag;  sums -- (nlags, ntypes, 10);  mean_displacement(a) -- (nlags, 3);  msd(a) -- the
+    trace, (nlags,);  msd_tensor(a) -- (nlags, 3, 3);  alpha2(a) = 3 <d^4> / (5 <d^2>^2) - 1;  displacement(slot=, lag=) -- (N, 4) per
+    particle against the CURRENT positions: d and |d|^2;  reset().  a = None: all types together."""
+
+    def __init__(self, integrator, nlags, origin_every=1, types=None, type_names=None, period=1):
+        import numpy as np
+        import torch
+        self._schedule, types, self.ntypes, self.type_names, self.period = _msd_analyzer_arguments(
+            nlags, origin_every, types, type_names, period)   # (raises before the device is touched)
+        system = integrator.system
+        if types is not None and types.shape[0] != system.n:
+            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
+        self.integrator, self.system = integrator, system
+        self.nlags, self.origin_every, self.norigins = self._schedule.nlags, self._schedule.origin_every, self._schedule.norigins
+        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
+        self._origins = DisplacementOrigins(integrator.engine, types, self.ntypes, self.norigins, system.n)
+        self._sums = torch.zeros((self.nlags, self.ntypes, MSD_MOMENTS), dtype=torch.float64, device=system.pos.device)
+        self.flipped = False      # a sample was taken with tilt_flips != 0: the moments that contain x are not to be trusted
+        system.analyzers.append(self)
+
+    def analyze(self, timestep):
+        if timestep % self.period:
+            return
+        s, e, g = self.system, self.integrator.engine, self.integrator.group.members
+        self.flipped = self.flipped or s.tilt_flips != 0
+        self._schedule.sample(lambda slots, rows: e.msd_accumulate(s.pos, s.image, self._origins, s.strain, slots, rows, self._sums, group=g),
+                              lambda slot: e.msd_store(s.pos, s.image, self._origins, slot, s.strain, group=g))
+
+    def reset(self):
+        """Forget the sums, the counts and the origins."""
+        self._sums.zero_()
+        self._schedule.reset()
+        self.flipped = False
+
+    def _warn_x(self, what):
+        if self.flipped:
+            import warnings
+            warnings.warn(f"{what} contains the unwrapped x, which is shifted by flips * Ly for every y image gained after a "
+                          "Lees-Edwards flip (analyze.unwrap): samples were taken in a flipped box; use the yy, zz, yz entries of "
+                          "msd_tensor()", RuntimeWarning, stacklevel=3)
+
+    _code = RDF._code
+    _type_counts = RDF._type_counts
+
+    @property
+    def samples(self):
+        return self._schedule.samples
+
+    @property
+    def lags(self):
+        import numpy as np
+        return np.arange(1, self.nlags + 1) * self.period
+
+    @property
+    def counts(self):
+        import numpy as np
+        return np.array(self._schedule.counts, dtype=np.int64)
+
+    @property
+    def sums(self):
+        return self._sums.cpu().numpy()
+
+    def _moments(self, a):
+        return moments_of_sums(self.sums, self.counts, self._type_counts(), None if a is None else self._code(a))
+
+    def mean_displacement(self, a=None):
+        return self._moments(a)[:, 0:3]
+
+    def msd_tensor(self, a=None):
+        import numpy as np
+        m = self._moments(a)
+        t = np.empty((self.nlags, 3, 3))
+        for (i, j), c in {(0, 0): 3, (1, 1): 4, (2, 2): 5, (0, 1): 6, (0, 2): 7, (1, 2): 8}.items():
+            t[:, i, j] = t[:, j, i] = m[:, c]
+        return t
+
+    def msd(self, a=None):
+        self._warn_x("msd()")
+        m = self._moments(a)
+        return m[:, 3] + m[:, 4] + m[:, 5]
+
+    def alpha2(self, a=None):
+        import numpy as np
+        self._warn_x("alpha2()")
+        m = self._moments(a)
+        d2 = m[:, 3] + m[:, 4] + m[:, 5]
+        return np.divide(3.0 * m[:, 9], 5.0 * d2 * d2, out=np.full(self.nlags, np.nan), where=d2 > 0.0) - 1.0
+
+    def displacement(self, slot=None, lag=None):
+        """(N, 4): d and |d|^2 of every particle of the group from the origin in `slot` -- or the one that was `lag` samples old at the
+        last sample -- to the current positions; rows outside the group are zero.  A slot that holds no origin stored since the
+        last reset() is refused.  (x: see LIMIT above.)"""
+        if (slot is None) == (lag is None):
+            raise ValueError("displacement() takes a slot or a lag")
+        slot = self._schedule.slot_of_lag(lag) if slot is None else int(slot)
+        if slot not in self._schedule.live:
+            raise ValueError(f"slot {slot} holds no origin stored since the last reset()")
+        s = self.system
+        return self.integrator.engine.msd_displacement(s.pos, s.image, self._origins, slot, s.strain,
+                                                       group=self.integrator.group.members).cpu().numpy()

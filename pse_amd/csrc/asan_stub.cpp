@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -40,6 +40,7 @@ struct pse_exclusions : Topology { using Topology::Topology; };
 struct pse_typed_table : Topology { using Topology::Topology; };   // row_off: the REAL layout (pse_host_typed_table_layout), entries: the types
 struct pse_pair_hist : Topology { using Topology::Topology; };     // entries: the types (zeros where none were given)
 struct pse_structure_factor : Topology { using Topology::Topology; };   // row_off: the REAL plan (structure_factor_plan), entries: its permutation
+struct pse_msd : Topology { using Topology::Topology; int norigins = 0; unsigned long long stored = 0ull; };   // the slots' bookkeeping alone
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -190,6 +191,32 @@ int pse_structure_factor_destroy(pse_structure_factor *f) { return topology_dest
 int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *pos, const unsigned *, unsigned N, double *rho, double *sums) {
     pse_handle *h = f ? f->h : nullptr;   // (pos, rho and sums are device pointers and there is no device: nothing is read or written)
     return structure_factor_validate(f, h ? h->par.n_max : 0u, N, pos, rho, sums);
+}
+int pse_msd_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int norigins, pse_msd **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_msd_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_msd_create: null handle");
+    if (int rc = msd_create_validate(h->par.n_max, n, types_host, ntypes, norigins)) return rc;
+    pse_msd *m = new pse_msd(h, 0, 0);
+    m->norigins = norigins;
+    return topology_adopt(m, 0, out);
+}
+int pse_msd_destroy(pse_msd *m) { return topology_destroy(m); }
+// (pos, image, sums and out are device pointers and there is no device: nothing is read or written; a store marks its slot)
+int pse_msd_store(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *, unsigned N, double strain) {
+    if (int rc = msd_slot_validate("pse_msd_store", m, m ? m->norigins : 0, m ? m->h->par.n_max : 0u, slot, N, pos, image, strain)) return rc;
+    m->stored |= 1ull << slot;
+    return 0;
+}
+int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *, unsigned N, double strain,
+                         pse_double4 *out) {
+    if (int rc = msd_slot_validate("pse_msd_displacement", m, m ? m->norigins : 0, m ? m->h->par.n_max : 0u, slot, N, pos, image, strain)) return rc;
+    return msd_displacement_validate(m->stored, slot, out);
+}
+int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image, const unsigned *, unsigned N, double strain, int npairs,
+                       const int *slots_host, const int *rows_host, int nrows, double *sums) {
+    return msd_accumulate_validate(m, m ? m->norigins : 0, m ? m->stored : 0ull, m ? m->h->par.n_max : 0u, N, pos, image, strain, npairs,
+                                   slots_host, rows_host, nrows, sums);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -458,6 +458,19 @@ struct pse_structure_factor : Topology {
         for (void *p : ptrs) if (p) (void)hipFree(p);
     }
 };
+// Displacement origins (include/pse_amd.h): n = particles with a type, count = norigins slots, ntypes; the planes of the unwrapped
+// positions and the workspace of the partial sums.  `stored`: bit s = slot s holds positions (host bookkeeping).  The arrays of
+// Topology stay null.
+struct pse_msd : Topology {
+    unsigned char *types = nullptr;         // n: the type of caller-order particle t
+    double *planes = nullptr;               // norigins x 3 x n_max
+    double *part = nullptr;                 // msd_workspace(n_max, ntypes): rows for 64 listed pairs
+    unsigned long long stored = 0ull;
+    ~pse_msd() override {
+        void *ptrs[] = {types, planes, part};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
+};
 
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
@@ -2953,6 +2966,72 @@ extern "C" int pse_structure_factor_accumulate(pse_structure_factor *f, const ps
     HIPCHK(hipSetDevice(h->device));
     const StructureFactor sf{f->types, f->n, f->ntypes, f->segs, f->nseg, f->nlong, f->perm, f->uoff, f->nu, (int)f->count, f->rows, f->span};
     launch_structure_factor((const double4 *)pos, group, (int)N, h->dbox, sf, rho, sums, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Displacement moments (include/pse_amd.h): the types, the slots of unwrapped positions and the workspace on the device, and the
+// three passes.  Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
+extern "C" int pse_msd_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int norigins, pse_msd **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_msd_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_msd_create: null handle");
+    TRY(msd_create_validate((unsigned)h->n_max, n, types_host, ntypes, norigins));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
+    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
+    pse_msd *m = new pse_msd();
+    m->h = h; m->n = n; m->count = (unsigned)norigins; m->ntypes = ntypes;
+    const size_t planes = (size_t)norigins * 3 * (size_t)h->n_max * sizeof(double);
+    const size_t work = msd_workspace((unsigned)h->n_max, ntypes) * sizeof(double);
+    hipError_t e = hipMalloc((void **)&m->types, n);
+    if (e == hipSuccess) e = hipMemcpy(m->types, types.data(), n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&m->planes, planes);
+    if (e == hipSuccess) e = hipMemset(m->planes, 0, planes);
+    if (e == hipSuccess) e = hipMalloc((void **)&m->part, work);
+    if (e != hipSuccess) {
+        delete m;
+        return fail(PSE_ERR_HIP, "pse_msd_create: %u types, %d origins of %zu bytes and a workspace of %zu bytes on the device failed: %s", n,
+                    norigins, planes / (size_t)norigins, work, hipGetErrorString(e));
+    }
+    h->topologies.push_back(m);
+    *out = m;
+    return 0;
+}
+extern "C" int pse_msd_destroy(pse_msd *m) { return topology_destroy(m); }
+static MsdOrigins msd_origins(const pse_msd *m) { return MsdOrigins{m->types, m->n, m->ntypes, m->planes, (size_t)m->h->n_max, m->part}; }
+extern "C" int pse_msd_store(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain) {
+    pse_handle *h = m ? m->h : nullptr;
+    TRY(msd_slot_validate("pse_msd_store", m, m ? (int)m->count : 0, h ? (unsigned)h->n_max : 0u, slot, N, pos, image, strain));
+    HIPCHK(hipSetDevice(h->device));
+    launch_msd_store((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
+                     msd_origins(m), slot, nullptr, h->stream);
+    HIPCHK(hipGetLastError());
+    m->stored |= 1ull << slot;
+    return 0;
+}
+extern "C" int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N,
+                                    double strain, pse_double4 *out) {
+    pse_handle *h = m ? m->h : nullptr;
+    TRY(msd_slot_validate("pse_msd_displacement", m, m ? (int)m->count : 0, h ? (unsigned)h->n_max : 0u, slot, N, pos, image, strain));
+    TRY(msd_displacement_validate(m->stored, slot, out));
+    HIPCHK(hipSetDevice(h->device));
+    launch_msd_store((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
+                     msd_origins(m), slot, (double4 *)out, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
+                                  int npairs, const int *slots_host, const int *rows_host, int nrows, double *sums) {
+    pse_handle *h = m ? m->h : nullptr;
+    TRY(msd_accumulate_validate(m, m ? (int)m->count : 0, m ? m->stored : 0ull, h ? (unsigned)h->n_max : 0u, N, pos, image, strain, npairs,
+                                slots_host, rows_host, nrows, sums));
+    HIPCHK(hipSetDevice(h->device));
+    MsdPairs pairs{};
+    pairs.npairs = npairs;
+    for (int q = 0; q < npairs; ++q) { pairs.slot[q] = (unsigned char)slots_host[q]; pairs.row[q] = rows_host[q]; }
+    launch_msd_accumulate((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
+                          msd_origins(m), pairs, sums, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -71,5 +71,17 @@ int structure_factor_validate(const void *f, unsigned n_max, unsigned N, const v
 // eight ints per segment: m0x, m0y, m0z, len, dx, dy, dz, first (the position of m0 among the distinct modes); the segments of more
 // than SF_SHORT modes come first, the short ones behind them, each class in the canonical order.
 void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> &perm, std::vector<unsigned> &uoff, std::vector<int> &segs);
+// the argument checks of pse_msd_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them (types
+// may be null: one type), with the handle's n_max
+int msd_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, int norigins);
+// the argument checks that pse_msd_store and pse_msd_displacement (`who`) share: the object (norigins its own, n_max its handle's), the
+// slot, N, pos, image, strain
+int msd_slot_validate(const char *who, const void *m, int norigins, unsigned n_max, int slot, unsigned N, const void *pos, const void *image,
+                      double strain);
+// what pse_msd_displacement checks behind them: the slot was stored (stored: bit s = slot s holds positions), out
+int msd_displacement_validate(unsigned long long stored, int slot, const void *out);
+// the argument checks of pse_msd_accumulate
+int msd_accumulate_validate(const void *m, int norigins, unsigned long long stored, unsigned n_max, unsigned N, const void *pos,
+                            const void *image, double strain, int npairs, const int *slots, const int *rows, int nrows, const void *sums);
 
 }  // namespace pse

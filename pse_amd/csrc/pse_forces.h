@@ -82,6 +82,31 @@ int sf_span(unsigned n_max, int ntypes, int nk);
 size_t sf_workspace(unsigned n_max, int ntypes, int nk);
 void launch_structure_factor(const double4 *pos, const unsigned *group, int N, DBox box, const StructureFactor &sf, double *rho, double *sums,
                              hipStream_t s);
+// displacement moments (k_msd_store, k_msd_partial, k_msd_finish; pse_msd_create): the device arrays of one object.  types: n bytes as
+// in PairTypedTables (a caller index >= n acts as type 0); planes: norigins slots of three planes (x, y, z) of n_max doubles each,
+// plane c of slot s at planes + (3 s + c) n_max, indexed by the caller-order particle index: a lane's loads are 8 bytes and, with an
+// identity group, consecutive; part: the workspace, one row of MSD_MOMENTS doubles per (wave of 256 particles, listed pair, type).
+// Lx, Ly, Lz: the box lengths, sLy = strain Ly (formed on the host).  A caller index >= n_max is skipped (nothing read, nothing written).
+struct MsdOrigins {
+    const unsigned char *types;
+    unsigned n;
+    int ntypes;
+    double *planes;
+    size_t n_max;
+    double *part;
+};
+// the pairs of one pse_msd_accumulate, by value in the kernel arguments: slot[q] the origin, row[q] the row of sums
+struct MsdPairs {
+    int npairs;
+    unsigned char slot[MSD_MAX_ORIGINS];
+    int row[MSD_MAX_ORIGINS];
+};
+size_t msd_workspace(unsigned n_max, int ntypes);   // doubles: rows for MSD_MAX_ORIGINS listed pairs, whatever the number of slots
+// out == null: r_u of the group members into `slot`; out != null: out[t] = (d.xyz, |d|^2) against `slot`, nothing stored
+void launch_msd_store(const double4 *pos, const int3 *image, const unsigned *group, int N, double Lx, double Ly, double Lz, double sLy,
+                      const MsdOrigins &mo, int slot, double4 *out, hipStream_t s);
+void launch_msd_accumulate(const double4 *pos, const int3 *image, const unsigned *group, int N, double Lx, double Ly, double Lz, double sLy,
+                           const MsdOrigins &mo, const MsdPairs &pairs, double *sums, hipStream_t s);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
 // entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
 // eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does

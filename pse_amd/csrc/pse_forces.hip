@@ -597,6 +597,193 @@ void launch_structure_factor(const double4 *pos, const unsigned *group, int N, D
                        sf.nk, sf.perm, sf.uoff, rho, sums);
 }
 
+// Displacement moments (pse_msd_store, pse_msd_accumulate, pse_msd_displacement): the unwrapped position of a particle is
+// r_u = (fma(iy, sLy, fma(ix, Lx, x)), fma(iy, Ly, y), fma(iz, Lz, z)), sLy = strain Ly from the host: two roundings in x_u, one in y_u
+// and z_u.  An object keeps slots of r_u as three planes of n_max doubles, indexed by the caller-order particle index.
+// k_msd_store: one lane per group member; OUT = false writes r_u into the planes of a slot, OUT = true reads them and writes
+// (d, |d|^2) to the caller's row.
+// k_msd_partial: a WAVE owns MSD_SPAN = 256 consecutive group members, four per lane (member = base + 64 p + lane: every load of a
+// plane is 8 bytes per lane and, with an identity group, 512 contiguous bytes per wave); the waves of a workgroup share nothing: no
+// LDS, no barrier.  A lane reads pos, image and type of its four particles ONCE, forms r_u once and walks the listed slots: twelve
+// 8-byte loads, the four displacements, and per type PRESENT in the wave (one ballot per type, before the loop) the ten moments of
+// the lane's particles of that type, added in the order p = 0..3 -- ten doubles, never a table of types x moments.  The wave then
+// adds them up with msd_wave_rows: a halving tree instead of ten butterflies -- at the level of lane bit b a lane keeps half of
+// its values, sends the other half to the lane across that bit and adds what it receives, 10 -> 5 -> 3 -> 2 -> 1 values over bits
+// 0..3 (11 exchanges), then two butterfly levels over bits 4 and 5: 13 exchanges of a double where ten butterflies take 60 (the
+// exchanges go through the LDS crossbar, which the first form of this kernel -- one particle per lane, ten butterflies, the four waves
+// added through LDS behind a barrier per slot -- was bound by: 1.48 ms for 64 origins at N = 10^6, docs/HISTORY.md).  Lane l < 16 ends
+// with the wave's sum of moment 5 b0 + 3 b1 + 2 b2 + b3 (b_i the bits of l; the ten lanes for which that is a moment) and writes it to
+// row (wave, pair, type) of the workspace; a type that is absent from the wave gets zeros.  Every row is written whole: the finish
+// reads no stale word.  A member past N carries the type 255, which no ballot matches, and reads nothing.
+// k_msd_finish: one workgroup of MSD_FIN threads per listed pair; a thread owns one of the ntypes x 10 columns and one of the
+// MSD_FIN / columns strips; a strip adds the rows b = strip, strip + nstrip, ... in ascending order, four in flight, the strips
+// are added in strip order through LDS, and the first strip adds the total to the caller's sums.  No floating-point atomics: every sum
+// has a fixed order, equal inputs give equal bits.  Two pairs never name the same row of sums (the validator refuses that), so the
+// workgroups of the finish write disjoint rows.
+// The pass is a stream over N (45 + 24 npairs) bytes.  Measured: docs/HISTORY.md.
+constexpr int MSD_PER_LANE = 4;                 // particles of one lane of k_msd_partial
+constexpr int MSD_SPAN = 64 * MSD_PER_LANE;     // particles of one wave: one row of the workspace per (wave, pair, type)
+constexpr int MSD_FIN = 1024;   // threads of a workgroup of k_msd_finish
+__device__ __forceinline__ void msd_unwrap(const double4 p, const int3 im, double Lx, double Ly, double Lz, double sLy, double &xu, double &yu,
+                                           double &zu) {
+    xu = fma((double)im.y, sLy, fma((double)im.x, Lx, p.x));
+    yu = fma((double)im.y, Ly, p.y);
+    zu = fma((double)im.z, Lz, p.z);
+}
+template <bool OUT>
+__global__ void __launch_bounds__(TPB)
+k_msd_store(const double4 *__restrict__ pos, const int3 *__restrict__ image, const unsigned *__restrict__ group, int N, double Lx, double Ly,
+            double Lz, double sLy, double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, size_t n_max,
+            double4 *__restrict__ out) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    const unsigned idx = group ? group[i] : (unsigned)i;
+    if (idx >= n_max) return;
+    double xu, yu, zu;
+    msd_unwrap(pos[idx], image[idx], Lx, Ly, Lz, sLy, xu, yu, zu);
+    if (OUT) {
+        const double dx = xu - px[idx], dy = yu - py[idx], dz = zu - pz[idx];
+        out[idx] = make_double4(dx, dy, dz, (dx * dx + dy * dy) + dz * dz);
+    } else {
+        px[idx] = xu; py[idx] = yu; pz[idx] = zu;
+    }
+}
+// One level of the halving tree: of v[0 .. N) the lane keeps the lower half if `up` is false, the upper half (padded with +0.0) if it
+// is true, sends the other half across `mask` and adds what the lane there sends: v[0 .. (N + 1)/2) on return.
+template <int N>
+__device__ __forceinline__ void msd_halve(double (&v)[MSD_MOMENTS], bool up, int mask) {
+    constexpr int H = (N + 1) / 2;
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const double lo = v[j], hi = j + H < N ? v[j + H] : 0.0;
+        v[j] = (up ? hi : lo) + __shfl_xor(up ? lo : hi, mask, 64);
+    }
+}
+// The sums over the wave of the ten values of every lane: on return lane l < 16 holds in v[0] the sum of value msd_lane_moment(l), if
+// that is below MSD_MOMENTS (ten of the sixteen lanes).  Fixed order: equal inputs give equal bits.
+__device__ __forceinline__ void msd_wave_rows(double (&v)[MSD_MOMENTS], int lane) {
+    static_assert(MSD_MOMENTS == 10, "the tree halves 10 -> 5 -> 3 -> 2 -> 1");
+    msd_halve<10>(v, lane & 1, 1);
+    msd_halve<5>(v, lane & 2, 2);
+    msd_halve<3>(v, lane & 4, 4);
+    msd_halve<2>(v, lane & 8, 8);
+    v[0] += __shfl_xor(v[0], 16, 64);
+    v[0] += __shfl_xor(v[0], 32, 64);
+}
+__device__ __forceinline__ int msd_lane_moment(int lane) {   // (>= MSD_MOMENTS: the lane holds a sum of padding)
+    const int b0 = lane & 1, b1 = (lane >> 1) & 1, b2 = (lane >> 2) & 1, b3 = (lane >> 3) & 1;
+    const int low = 2 * b2 + b3;   // position among the (at most) three values kept at bit 1
+    return low < (b1 ? 2 : 3) ? 5 * b0 + 3 * b1 + low : MSD_MOMENTS;
+}
+__global__ void __launch_bounds__(TPB)
+k_msd_partial(const double4 *__restrict__ pos, const int3 *__restrict__ image, const unsigned *__restrict__ group, int N,
+              const unsigned char *__restrict__ types, unsigned ntyped, int ntypes, double Lx, double Ly, double Lz, double sLy,
+              const double *__restrict__ planes, size_t n_max, MsdPairs pairs, double *__restrict__ part /* [waves][npairs][ntypes][10] */) {
+    const int lane = threadIdx.x & 63;
+    const long wave = (long)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (wave * MSD_SPAN >= N) return;   // (wave-uniform; the waves share nothing)
+    unsigned idx[MSD_PER_LANE];
+    int ty[MSD_PER_LANE];
+    double xu[MSD_PER_LANE], yu[MSD_PER_LANE], zu[MSD_PER_LANE];
+#pragma unroll
+    for (int p = 0; p < MSD_PER_LANE; ++p) {
+        const long i = wave * MSD_SPAN + p * 64 + lane;
+        idx[p] = 0u; ty[p] = 255; xu[p] = yu[p] = zu[p] = 0.0;
+        if (i < N) {
+            idx[p] = group ? group[i] : (unsigned)i;
+            if (idx[p] < n_max) {
+                ty[p] = idx[p] < ntyped ? (int)types[idx[p]] : 0;
+                msd_unwrap(pos[idx[p]], image[idx[p]], Lx, Ly, Lz, sLy, xu[p], yu[p], zu[p]);
+            }
+        }
+    }
+    unsigned present = 0u;   // (wave-uniform)
+    for (int a = 0; a < ntypes; ++a) {
+        bool mine = false;
+#pragma unroll
+        for (int p = 0; p < MSD_PER_LANE; ++p) mine |= ty[p] == a;
+        if (__ballot(mine) != 0ull) present |= 1u << a;
+    }
+    const int c = msd_lane_moment(lane);
+    const bool writer = lane < 16 && c < MSD_MOMENTS;
+    for (int q = 0; q < pairs.npairs; ++q) {
+        const double *__restrict__ px = planes + (size_t)pairs.slot[q] * 3 * n_max;
+        double dx[MSD_PER_LANE], dy[MSD_PER_LANE], dz[MSD_PER_LANE];
+#pragma unroll
+        for (int p = 0; p < MSD_PER_LANE; ++p) {
+            dx[p] = dy[p] = dz[p] = 0.0;
+            if (ty[p] != 255) { dx[p] = xu[p] - px[idx[p]]; dy[p] = yu[p] - px[n_max + idx[p]]; dz[p] = zu[p] - px[2 * n_max + idx[p]]; }
+        }
+        double *__restrict__ row = part + ((size_t)wave * pairs.npairs + q) * ntypes * MSD_MOMENTS;
+        for (int a = 0; a < ntypes; ++a, row += MSD_MOMENTS) {
+            if (!(present & (1u << a))) {   // (wave-uniform: a scalar branch)
+                if (lane < MSD_MOMENTS) row[lane] = 0.0;
+                continue;
+            }
+            double v[MSD_MOMENTS];
+#pragma unroll
+            for (int k = 0; k < MSD_MOMENTS; ++k) v[k] = 0.0;
+#pragma unroll
+            for (int p = 0; p < MSD_PER_LANE; ++p) {
+                if (ty[p] != a) continue;
+                const double xx = dx[p] * dx[p], yy = dy[p] * dy[p], zz = dz[p] * dz[p];
+                const double r2 = (xx + yy) + zz;
+                v[0] += dx[p]; v[1] += dy[p]; v[2] += dz[p];
+                v[3] += xx; v[4] += yy; v[5] += zz;
+                v[6] += dx[p] * dy[p]; v[7] += dx[p] * dz[p]; v[8] += dy[p] * dz[p];
+                v[9] += r2 * r2;
+            }
+            msd_wave_rows(v, lane);
+            if (writer) row[c] = v[0];
+        }
+    }
+}
+__global__ void __launch_bounds__(MSD_FIN)
+k_msd_finish(const double *__restrict__ part, int nblk, int ntypes, MsdPairs pairs, double *__restrict__ sums) {
+    __shared__ double sh[MSD_FIN];
+    const int ncol = ntypes * MSD_MOMENTS, nstrip = MSD_FIN / ncol;
+    const int q = blockIdx.x, strip = threadIdx.x / ncol, col = threadIdx.x - strip * ncol;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (strip < nstrip) {
+        const size_t stride = (size_t)pairs.npairs * ncol;
+        const double *__restrict__ p = part + (size_t)q * ncol + col;
+        int b = strip;
+        for (; b + 3 * nstrip < nblk; b += 4 * nstrip) {
+            const double v0 = p[(size_t)b * stride], v1 = p[(size_t)(b + nstrip) * stride], v2 = p[(size_t)(b + 2 * nstrip) * stride],
+                         v3 = p[(size_t)(b + 3 * nstrip) * stride];
+            s0 += v0; s1 += v1; s2 += v2; s3 += v3;
+        }
+        for (; b < nblk; b += nstrip) s0 += p[(size_t)b * stride];
+    }
+    sh[threadIdx.x] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (strip != 0) return;   // (behind the only barrier)
+    double t = 0.0;
+    for (int r = 0; r < nstrip; ++r) t += sh[r * ncol + col];
+    sums[(size_t)pairs.row[q] * ncol + col] += t;
+}
+// (a call lists up to MSD_MAX_ORIGINS pairs whatever the number of slots -- a slot may be named for several rows -- and the rows of
+// the workspace are per listed pair: sized for the most pairs, never for norigins)
+size_t msd_workspace(unsigned n_max, int ntypes) {
+    return (size_t)nblocks((long)n_max, MSD_SPAN) * MSD_MAX_ORIGINS * ntypes * MSD_MOMENTS;
+}
+void launch_msd_store(const double4 *pos, const int3 *image, const unsigned *group, int N, double Lx, double Ly, double Lz, double sLy,
+                      const MsdOrigins &mo, int slot, double4 *out, hipStream_t s) {
+    double *px = mo.planes + (size_t)slot * 3 * mo.n_max, *py = px + mo.n_max, *pz = py + mo.n_max;
+    if (out)
+        hipLaunchKernelGGL(k_msd_store<true>, dim3(nblocks(N, TPB)), dim3(TPB), 0, s, pos, image, group, N, Lx, Ly, Lz, sLy, px, py, pz, mo.n_max, out);
+    else
+        hipLaunchKernelGGL(k_msd_store<false>, dim3(nblocks(N, TPB)), dim3(TPB), 0, s, pos, image, group, N, Lx, Ly, Lz, sLy, px, py, pz, mo.n_max, out);
+}
+void launch_msd_accumulate(const double4 *pos, const int3 *image, const unsigned *group, int N, double Lx, double Ly, double Lz, double sLy,
+                           const MsdOrigins &mo, const MsdPairs &pairs, double *sums, hipStream_t s) {
+    static_assert(MSD_FIN >= PAIR_TYPED_MAX_TYPES * MSD_MOMENTS, "a workgroup of k_msd_finish holds at least one strip");
+    const int nblk = nblocks(N, MSD_SPAN);   // rows of the workspace per (pair, type): one per wave; npairs <= MSD_MAX_ORIGINS, N <= n_max (validated)
+    hipLaunchKernelGGL(k_msd_partial, dim3(nblocks(nblk, TPB / 64)), dim3(TPB), 0, s, pos, image, group, N, mo.types, mo.n, mo.ntypes, Lx, Ly, Lz, sLy, mo.planes,
+                       mo.n_max, pairs, mo.part);
+    hipLaunchKernelGGL(k_msd_finish, dim3(pairs.npairs), dim3(MSD_FIN), 0, s, mo.part, nblk, mo.ntypes, pairs, sums);
+}
+
 // Bonded forces (HOOMD's bond.harmonic and bond.fene; no reference counterpart: the reference leaves forces to HOOMD).  One thread
 // per particle of the CALLER-order arrays walks its row of the bond object -- entries (partner, type), one 8-byte load each, sorted by
 // (partner, type) on the host -- and gathers each partner's position with one double4 load.  With d = r_i - r_j (minimum image),

@@ -16,6 +16,8 @@ constexpr int SF_MAX_INDEX = 4096;     // |mx|, |my|, |mz| of a structure-factor
 constexpr int SF_MAX_MODES = 32768;    // modes of one structure-factor object (PSE_SF_MAX_MODES)
 constexpr int SF_RUN = 8;              // modes of one segment: a lane of k_sf_partial keeps their sums in registers, seeded exactly, 7 steps
 constexpr int SF_SHORT = 2;            // a segment of at most this many modes is walked by the short form of the kernel (k_sf_partial<SF_SHORT>)
+constexpr int MSD_MAX_ORIGINS = 64;   // slots of one displacement object, and pairs (slot, row) of one pse_msd_accumulate (PSE_MSD_MAX_ORIGINS)
+constexpr int MSD_MOMENTS = 10;       // dx dy dz, dx^2 dy^2 dz^2 dxdy dxdz dydz, |d|^4 (PSE_MSD_MOMENTS)
 constexpr int PAIR_TYPED_MAX_TYPES = 8;      // particle types of a typed pair table (pse_typed_table_create): at most 36 pair types
 constexpr int PAIR_TYPED_MAX_ENTRIES = 3584; // entries of all its tables together: 56 KB of LDS, next to 1.4 KB of static LDS, inside 64 KB
 constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS

@@ -318,6 +318,63 @@ int structure_factor_validate(const void *f, unsigned n_max, unsigned N, const v
     return 0;
 }
 
+int msd_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, int norigins) {
+    const char *who = "pse_msd_create";
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (norigins < 1 || norigins > MSD_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: norigins = %d outside [1, %d]", who, norigins, MSD_MAX_ORIGINS);
+    if (types)
+        for (unsigned i = 0; i < n; ++i)
+            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    return 0;
+}
+
+int msd_slot_validate(const char *who, const void *m, int norigins, unsigned n_max, int slot, unsigned N, const void *pos, const void *image,
+                      double strain) {
+    if (!m) return fail(PSE_ERR_INVALID, "%s: null displacement object", who);
+    if (slot < 0 || slot >= norigins) return fail(PSE_ERR_INVALID, "%s: slot = %d outside [0, norigins = %d)", who, slot, norigins);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!image) return fail(PSE_ERR_INVALID, "%s: null image", who);
+    if (!std::isfinite(strain)) return fail(PSE_ERR_INVALID, "%s: strain = %g is not finite", who, strain);
+    return 0;
+}
+
+int msd_displacement_validate(unsigned long long stored, int slot, const void *out) {
+    const char *who = "pse_msd_displacement";
+    if (!((stored >> slot) & 1ull)) return fail(PSE_ERR_INVALID, "%s: slot %d was never stored", who, slot);
+    if (!out) return fail(PSE_ERR_INVALID, "%s: null out", who);
+    if (((uintptr_t)out & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: out = %p is not 8-byte aligned (doubles)", who, out);
+    return 0;
+}
+
+int msd_accumulate_validate(const void *m, int norigins, unsigned long long stored, unsigned n_max, unsigned N, const void *pos,
+                            const void *image, double strain, int npairs, const int *slots, const int *rows, int nrows, const void *sums) {
+    const char *who = "pse_msd_accumulate";
+    if (!m) return fail(PSE_ERR_INVALID, "%s: null displacement object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!image) return fail(PSE_ERR_INVALID, "%s: null image", who);
+    if (!std::isfinite(strain)) return fail(PSE_ERR_INVALID, "%s: strain = %g is not finite", who, strain);
+    if (npairs < 1 || npairs > MSD_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: npairs = %d outside [1, %d]", who, npairs, MSD_MAX_ORIGINS);
+    if (!slots) return fail(PSE_ERR_INVALID, "%s: null slots_host", who);
+    if (!rows) return fail(PSE_ERR_INVALID, "%s: null rows_host", who);
+    if (nrows < 1) return fail(PSE_ERR_INVALID, "%s: nrows = %d, need at least one row", who, nrows);
+    for (int q = 0; q < npairs; ++q)
+        if (slots[q] < 0 || slots[q] >= norigins)
+            return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d outside [0, norigins = %d)", who, q, slots[q], norigins);
+    for (int q = 0; q < npairs; ++q)
+        if (!((stored >> slots[q]) & 1ull)) return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d, which was never stored", who, q, slots[q]);
+    for (int q = 0; q < npairs; ++q)
+        if (rows[q] < 0 || rows[q] >= nrows) return fail(PSE_ERR_INVALID, "%s: pair %d names the row %d outside [0, nrows = %d)", who, q, rows[q], nrows);
+    for (int q = 0; q < npairs; ++q)
+        for (int p = 0; p < q; ++p)
+            if (rows[p] == rows[q]) return fail(PSE_ERR_INVALID, "%s: pairs %d and %d both name the row %d", who, p, q, rows[q]);
+    if (!sums) return fail(PSE_ERR_INVALID, "%s: null sums", who);
+    if (((uintptr_t)sums & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sums = %p is not 8-byte aligned (doubles)", who, sums);
+    return 0;
+}
+
 void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> &perm, std::vector<unsigned> &uoff, std::vector<int> &segs) {
     perm.resize(nk);
     for (unsigned q = 0; q < nk; ++q) perm[q] = q;

@@ -25,6 +25,8 @@ class Trajectory:
 
 
 def load(filename):
-    """Frames back as a dict of arrays; unwrapped positions = position + image * box lengths (+ xy tilt for y images)."""
+    """Frames back as a dict of arrays.  Unwrapped positions: pse_amd.analyze.unwrap(position, image, box, strain) with the ACCUMULATED
+    strain of the frame (System.strain: the box's xy plus the Lees-Edwards flips so far; it is not recorded here).  position + image *
+    box lengths with the frame's own xy for the y images jumps by image.y * Lx at every flip."""
     with np.load(filename) as z:
         return {k: z[k] for k in z.files}

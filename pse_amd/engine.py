@@ -428,6 +428,63 @@ class StructureFactorModes(_DeviceObject):
         self._create(engine, "pse_structure_factor_create", self.n, _vp(types), self.ntypes, self.nk, _vp(self.modes))
 
 
+MSD_MAX_ORIGINS = 64   # pse_msd_create: slots of one object, and pairs (slot, row) of one pse_msd_accumulate
+MSD_MOMENTS = 10       # dx dy dz, dx^2 dy^2 dz^2 dxdy dxdz dydz, |d|^4
+
+
+def _msd_arguments(types, ntypes, norigins):
+    """The arguments of a displacement object, checked before the device is touched: (types uint32 (n,) or None, ntypes, norigins)."""
+    norigins = int(norigins)
+    if not 1 <= norigins <= MSD_MAX_ORIGINS:
+        raise ValueError(f"norigins = {norigins} outside [1, {MSD_MAX_ORIGINS}]")
+    types, ntypes, _, _, _ = _pair_hist_arguments(types, ntypes, 1, 0.0, 1.0)
+    return types, ntypes, norigins
+
+
+def _msd_pairs(slots, rows, norigins, nrows):
+    """The (slot, row) lists of one pse_msd_accumulate as two int32 arrays, checked before the device is touched."""
+    import numpy as np
+    slots, rows = np.asarray(slots), np.asarray(rows)
+    if slots.ndim != 1 or rows.shape != slots.shape:
+        raise ValueError("slots and rows must be 1-D integer sequences of one length")
+    if not 1 <= slots.shape[0] <= MSD_MAX_ORIGINS:
+        raise ValueError(f"{slots.shape[0]} pairs outside [1, {MSD_MAX_ORIGINS}]")
+    if not np.issubdtype(slots.dtype, np.integer) or not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError("slots and rows must be 1-D integer sequences of one length")
+    if slots.min() < 0 or slots.max() >= norigins:
+        raise ValueError(f"slots holds a slot outside [0, {norigins})")
+    if rows.min() < 0 or rows.max() >= nrows:
+        raise ValueError(f"rows holds a row outside [0, {nrows})")
+    if len(set(rows.tolist())) != rows.shape[0]:
+        raise ValueError("rows names a row twice")
+    return np.ascontiguousarray(slots, dtype=np.int32), np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def _finite(x, name):
+    x = float(x)
+    if not math.isfinite(x):
+        raise ValueError(f"{name} = {x} is not finite")
+    return x
+
+
+class DisplacementOrigins(_DeviceObject):
+    """Owner of a pse_msd object: one type per particle and `norigins` slots of unwrapped positions on the device.  `types`: (n,)
+    integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts as type 0.  Pass it as
+    `origins` to Engine.msd_store, msd_accumulate and msd_displacement."""
+
+    DESTROY = "pse_msd_destroy"
+
+    def __init__(self, engine, types, ntypes, norigins, n=None):
+        types, self.ntypes, self.norigins = _msd_arguments(types, ntypes, norigins)
+        if types is None:
+            self.n = _rows(engine, n)
+        else:
+            self.n = int(types.shape[0] if n is None else n)
+            if not 0 <= self.n <= types.shape[0]:
+                raise ValueError("n outside [0, len(types)]")
+        self._create(engine, "pse_msd_create", self.n, _vp(types), self.ntypes, self.norigins)
+
+
 class _ForcePasses:
     """The force providers of the C-ABI on one handle, for whoever holds one: an Engine, which owns its handle, and the
     StokesEngine of an integrator, whose handle the C++ Stokes object owns.  Needs `_lib`, `_h` (the handle; raises where there is
@@ -558,6 +615,63 @@ class _ForcePasses:
             raise ValueError("rho and sums are both None: nothing to compute")
         _lib.check(self._lib.pse_structure_factor_accumulate(sf._handle(self), _ptr(pos), _ptr(group), n, _ptr(rho), _ptr(sums)))
         return rho, sums
+
+    def msd_origins(self, types, ntypes, norigins, n=None):
+        """Displacement origins on the device (pse_msd_create; see include/pse_amd.h): `types` (n,) the type of every caller-order
+        particle, below `ntypes` <= 8, or None: one type; `norigins` <= 64 slots of n_max unwrapped positions, zeroed; `n`: how many of
+        `types` to use (default: all; without types: n_max).  Returns a DisplacementOrigins with ntypes, norigins and close()."""
+        return DisplacementOrigins(self, types, ntypes, norigins, n)
+
+    @staticmethod
+    def _msd_common(pos, image, group):
+        import torch
+        _chk4(pos, "pos"); _chk_group(group)
+        _chk_arr(image, "image", 3, torch.int32, pos.shape[0])
+        return pos.shape[0] if group is None else group.shape[0]
+
+    def msd_store(self, pos, image, origins, slot, strain, group=None):
+        """The unwrapped positions x + ix Lx + iy strain Ly, y + iy Ly, z + iz Lz of the group into slot `slot` of `origins`
+        (pse_msd_store), in the engine's current box lengths.  `strain`: the accumulated tilt (System.strain), NOT the box's xy.
+        With it the unwrapped x survives a flip, but a y image gained AFTER a flip shifts it by flips Ly (include/pse_amd.h, LIMIT):
+        the moments with x are right for a sheared run only while no particle gains a y image after a flip; y and z always are.
+        Queue-only."""
+        n = self._msd_common(pos, image, group)
+        slot = int(slot)
+        if not 0 <= slot < origins.norigins:
+            raise ValueError(f"slot = {slot} outside [0, {origins.norigins})")
+        _lib.check(self._lib.pse_msd_store(origins._handle(self), slot, _ptr(pos), _ptr(image), _ptr(group), n, _finite(strain, "strain")))
+
+    def msd_accumulate(self, pos, image, origins, strain, slots, rows, sums, group=None):
+        """One sample of the displacement moments (pse_msd_accumulate): for every pair (slots[q], rows[q]) and every type a,
+        sums[rows[q], a, :] += the ten moments dx dy dz, dx^2 dy^2 dz^2 dxdy dxdz dydz, |d|^4 of d = r_u(now) - r_u(slot) summed over
+        the group members of type a.  `sums`: a contiguous (nrows, ntypes, 10) float64 CUDA tensor, ADDED to; at most 64 pairs, every
+        slot stored before, no row twice; the group must be the one the slots were stored with.  Queue-only: nothing is read back,
+        no atomics, equal inputs give equal bits.  Returns sums."""
+        import torch
+        n = self._msd_common(pos, image, group)
+        if not (isinstance(sums, torch.Tensor) and sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and sums.dim() == 3
+                and sums.shape[0] >= 1 and tuple(sums.shape[1:]) == (origins.ntypes, MSD_MOMENTS)):
+            raise ValueError(f"sums must be a contiguous (nrows, {origins.ntypes}, {MSD_MOMENTS}) float64 CUDA tensor")
+        slots, rows = _msd_pairs(slots, rows, origins.norigins, int(sums.shape[0]))
+        _lib.check(self._lib.pse_msd_accumulate(origins._handle(self), _ptr(pos), _ptr(image), _ptr(group), n, _finite(strain, "strain"),
+                                                int(slots.shape[0]), _vp(slots), _vp(rows), int(sums.shape[0]), _ptr(sums)))
+        return sums
+
+    def msd_displacement(self, pos, image, origins, slot, strain, out=None, group=None):
+        """The displacement of every group member against slot `slot` (pse_msd_displacement): out[t] = (dx, dy, dz, |d|^2), a
+        contiguous (N, 4) float64 CUDA tensor in the caller's order (default: a new one of zeros); rows outside the group are not
+        touched.  Queue-only.  Returns out."""
+        import torch
+        n = self._msd_common(pos, image, group)
+        slot = int(slot)
+        if not 0 <= slot < origins.norigins:
+            raise ValueError(f"slot = {slot} outside [0, {origins.norigins})")
+        if out is None:
+            out = torch.zeros_like(pos)
+        _chk4(out, "out", pos.shape[0])
+        _lib.check(self._lib.pse_msd_displacement(origins._handle(self), slot, _ptr(pos), _ptr(image), _ptr(group), n,
+                                                  _finite(strain, "strain"), _ptr(out)))
+        return out
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)

@@ -7,6 +7,12 @@ import numpy as np
 from . import context
 
 
+def flips_between(old_xy, new_xy):
+    """The whole lattice vectors a change of the tilt from old_xy to new_xy took off it: 0 for a continuous change, 1 for a flip from
+    +0.5 to -0.5."""
+    return int(round(old_xy - new_xy))
+
+
 class Group:
     """hoomd.group.all(): the index array handed to the integrator as d_group_members (PSEv1/Stokes.cc:461)."""
 
@@ -38,7 +44,13 @@ class System:
         self.forces = []          # force providers (pse_amd.forces): fill net_force before the integrators run
         self.analyzers = []       # e.g. pse_amd.dump.Trajectory
         self.box_tilt_variant = None    # a variant.shear_variant: Lees-Edwards box deformation
+        self.tilt_flips = 0       # whole lattice vectors that Lees-Edwards flips have taken off the tilt so far
         context.current = self
+
+    @property
+    def strain(self):
+        """The accumulated tilt: the box's xy plus the flips so far.  What unwrapped positions need in place of xy (analyze.unwrap)."""
+        return self.box[3] + self.tilt_flips
 
     @classmethod
     def create_lattice_sc(cls, a, n, dt=1e-3):
@@ -69,7 +81,8 @@ class System:
 
     def _set_tilt(self, xy):
         # changing the tilt re-labels images: keep every particle inside the new primary cell
-        Lx, Ly, Lz, _ = self.box
+        Lx, Ly, Lz, old = self.box
+        self.tilt_flips += flips_between(old, float(xy))
         self.box = (Lx, Ly, Lz, float(xy))
         import torch
         f = torch.floor((self.pos[:, 0] - xy * self.pos[:, 1]) / Lx + 0.5)
