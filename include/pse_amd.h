@@ -421,6 +421,46 @@ int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image
 int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
                          pse_double4 *out /* DEVICE, caller order: d.xyz, |d|^2 in w; rows outside the group untouched */);
 
+/* ---- cluster analysis: the connected components of a distance criterion (no reference counterpart) ----
+ * A pse_clusters object fixes the types of the particles and the link distances: types_host, ntypes <= 8 and the pair types
+ * p(a, b) exactly as for pse_pair_hist_create (NULL: one type; a caller index >= n acts as type 0); rlink_host holds one link
+ * distance per pair type, npt = ntypes (ntypes + 1)/2 of them in that order: 0 switches a pair type off, every other entry must be
+ * finite, > 0 and <= rcut (the cell list is built for the hydrodynamic cutoff), and at least one must be on.
+ * pse_clusters_label: two of the N group members are LINKED when their minimum-image distance has 0 < r^2 < rlink[p]^2 and the pair
+ * is not in ex; a cluster is a connected component of the links.  All outputs are DEVICE arrays, each may be NULL but not all:
+ *   label[t]  (unsigned, by CALLER index) the smallest caller index in t's cluster: a member of it, independent of the sort and of
+ *             the order of the launch; entries of indices outside the group are left alone
+ *   size[t]   (unsigned, by caller index) the number of members of t's cluster
+ *   stats     four unsigned 64-bit words, 8-byte aligned, OVERWRITTEN: the number of clusters, the size of the largest, the sum of
+ *             s^2 over the clusters, N
+ *   hist      nhist >= 1 unsigned 64-bit words, 8-byte aligned, ADDED to: every cluster of size s adds 1 to hist[min(s, nhist) - 1]
+ *             (the last word counts every cluster of nhist members or more); samples accumulate on the device
+ * Queue-only wherever pse_pair_hist_accumulate is: the sort, the type mirror and a fixed sequence of five launches (a union-find over
+ * the sorted rows), nothing is read back, no lane waits for another, only integers are summed: equal inputs give equal bits and a
+ * permuted particle order gives the same partition.  The loops of the union-find are proven to end; each nevertheless
+ * carries a trip cap of N, and a lane that reaches it sets a bit of the object's sticky status word: that call then writes label = ~0u
+ * and size = 0 everywhere.  pse_clusters_status waits for the stream and returns the word (0: every call so far was complete); once it
+ * has returned a non-zero word, pse_clusters_label refuses.  Until the host has read the word, later calls are still queued and,
+ * the word being sticky on the device, write ~0u labels too: a caller that meets a ~0u label asks pse_clusters_status.
+ * Not computed: whether a cluster is connected to its own periodic image (percolation); per-cluster geometry (centre of mass,
+ * gyration tensor); links longer than the real-space cutoff.  A slab rank (n_slabs >= 2) orders only its own cells: pse_clusters_label refuses
+ * it; teams and owned-particle steps have no cluster entry point.
+ * The object belongs to its handle as a pse_pair_hist does (pse_destroy frees it; pse_clusters_destroy waits for the stream).
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_clusters_create, in this order: a null out
+ * or h, n == 0 or n > n_max, ntypes outside [1, 8], a null rlink_host, an entry that is not finite, negative or > rcut, no entry on, a
+ * type >= ntypes (*out is null after a refusal).  pse_clusters_label, in this order: a null g, N == 0 or N > n_max, a
+ * null pos, all four outputs null, stats or hist not 8-byte aligned, hist with nhist == 0, an ex created on another handle than g, a
+ * slab rank, a status word already known to be non-zero.  pse_clusters_status: a null g or status. */
+typedef struct pse_clusters pse_clusters;
+int pse_clusters_create(pse_handle *h, unsigned n, const unsigned *types_host /* n, or NULL: one type */, int ntypes,
+                        const double *rlink_host /* npt */, pse_clusters **out);
+int pse_clusters_destroy(pse_clusters *g);
+int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *label /* DEVICE, may be NULL */,
+                       unsigned *size /* DEVICE, may be NULL */, unsigned long long *stats /* DEVICE, 4, may be NULL */,
+                       unsigned long long *hist /* DEVICE, nhist, ADDED to, may be NULL */, unsigned nhist,
+                       const pse_exclusions *ex /* may be NULL */);
+int pse_clusters_status(pse_clusters *g, unsigned *status /* HOST */);
+
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,

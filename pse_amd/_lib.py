@@ -143,6 +143,10 @@ SYMBOLS = {
     "pse_msd_store": (_i, [_vp, _i, _vp, _vp, _vp, _u, _d]),
     "pse_msd_accumulate": (_i, [_vp, _vp, _vp, _vp, _u, _d, _i, _vp, _vp, _i, _vp]),
     "pse_msd_displacement": (_i, [_vp, _i, _vp, _vp, _vp, _u, _d, _vp]),
+    "pse_clusters_create": (_i, [_vp, _u, _vp, _i, _vp, _vp]),
+    "pse_clusters_destroy": (_i, [_vp]),
+    "pse_clusters_label": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _vp, _u, _vp]),
+    "pse_clusters_status": (_i, [_vp, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

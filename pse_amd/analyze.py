@@ -5,10 +5,12 @@ half of how structure is reported: the densities rho_a(k) on the reciprocal latt
 on the device (pse_structure_factor_accumulate), and their products S_ab(k) -- at any k the box admits, far below 2 pi / rcut, and
 resolved in direction.  MSD is the dynamic counterpart: the engine keeps up to 64 time origins of unwrapped positions
 (pse_msd_store) and one streaming pass per sample sums the first, second and fourth moments of the displacement per type and per
-origin (pse_msd_accumulate): the drift, the mean-squared displacement tensor and the non-Gaussian parameter over many time origins."""
+origin (pse_msd_accumulate): the drift, the mean-squared displacement tensor and the non-Gaussian parameter over many time origins.
+Clusters says which particles hang together: the connected components of a distance criterion, labelled on the device by a union-find
+over the sorted rows (pse_clusters_label), with the number of clusters, the largest one and the size distribution n(s) per sample."""
 import math
 
-from .engine import (MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, DisplacementOrigins, PairHistogram, StructureFactorModes, _msd_arguments,
+from .engine import (MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, ClusterLinks, DisplacementOrigins, PairHistogram, StructureFactorModes, _cluster_arguments, _msd_arguments,
                      _pair_hist_arguments, _structure_factor_arguments, pair_type_index)
 from .forces import _excl_list
 
@@ -572,3 +574,146 @@ class MSD:
         s = self.system
         return self.integrator.engine.msd_displacement(s.pos, s.image, self._origins, slot, s.strain,
                                                        group=self.integrator.group.members).cpu().numpy()
+
+
+def size_distribution_of(hist, samples):
+    """n(s), s = 1 .. len(hist): the mean number of clusters of s members per sample, from the accumulated counts; the last entry
+    holds every cluster of len(hist) members or more.  NumPy only."""
+    import numpy as np
+    if samples < 1:
+        raise ValueError("no samples yet")
+    return np.asarray(hist, dtype=np.float64) / float(samples)
+
+
+def averages_of(rows):
+    """From the per-sample rows (clusters, largest, sum of s^2, N), one per sample: the number-average size sum N / sum clusters,
+    the weight-average size sum s^2 / sum N -- the size of the cluster a randomly chosen particle is in -- and the mean over the
+    samples of largest / N.  Returns (number_average, weight_average, largest_fraction).  NumPy only."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+    if rows.shape[0] < 1:
+        raise ValueError("no samples yet")
+    return (float(rows[:, 3].sum() / rows[:, 0].sum()), float(rows[:, 2].sum() / rows[:, 3].sum()), float((rows[:, 1] / rows[:, 3]).mean()))
+
+
+def _cluster_analyzer_arguments(rlink, types, type_names, period, nhist, capacity):
+    """What Clusters checks before it touches the device.  A dict `rlink` may name its types by `type_names`.  Returns (types uint32
+    or None, ntypes, rlink (npt,), names or None, period, nhist or None, capacity)."""
+    types, ntypes, names, period = _typed_arguments(types, type_names, period)
+    if isinstance(rlink, dict):
+        coded = {}
+        for key, r in rlink.items():
+            if not (isinstance(key, tuple) and len(key) == 2):
+                raise ValueError(f"rlink key {key!r}: need a pair (a, b) of types")
+            coded.setdefault(tuple(sorted(_type_codes(list(key), names))), []).append(r)
+        if any(len(v) > 1 for v in coded.values()):
+            raise ValueError("rlink names a pair of types twice")
+        rlink = {k: v[0] for k, v in coded.items()}
+    types, ntypes, rlink = _cluster_arguments(types, ntypes, rlink)
+    if nhist is not None and int(nhist) < 1:
+        raise ValueError("nhist must be positive")
+    if int(capacity) < 1:
+        raise ValueError("capacity must be positive")
+    return types, ntypes, rlink, names, period, None if nhist is None else int(nhist), int(capacity)
+
+
+class Clusters:
+    """Which particles hang together: every `period` steps the members of the integrator's group are labelled by the connected
+    component of the links 0 < r < rlink (pse_clusters_label; a union-find on the device over the cell list the step uses anyway).
+    `rlink`: a scalar, a dict {(a, b): r} over pairs of types (names with `type_names=`; a missing pair never links) or one entry per
+    pair of types; none may exceed the hydrodynamic real-space cutoff.  `types`, `type_names`, `exclusions`: as for RDF.
+    Each sample writes its row (clusters, largest, sum of s^2, N) into a device ring of `capacity` rows -- once full, the oldest rows
+    are replaced -- and adds its clusters to the size counts, `nhist` words (default: the number of particles; the last holds every
+    larger cluster).  Sampling only queues work; the readers are the only places that wait for the device.
+    Not measured: percolation (a cluster connected to its own periodic image) and per-cluster geometry.
+
+    labels(), sizes() -- the last sample, by particle index (-1 / 0 outside the group);  table() -- (samples kept, 5): step, clusters,
+    largest, sum s^2, N;  size_distribution() -- mean n(s) per sample;  number_average(), weight_average(), largest_fraction() -- over
+    the samples kept;  members(label);  samples;  reset()."""
+
+    COLUMNS = ("timestep", "clusters", "largest", "sum_s2", "N")
+
+    def __init__(self, integrator, rlink, types=None, type_names=None, exclusions=None, period=1, nhist=None, capacity=1024):
+        import numpy as np
+        import torch
+        types, self.ntypes, self.rlink, self.type_names, self.period, nhist, self.capacity = _cluster_analyzer_arguments(
+            rlink, types, type_names, period, nhist, capacity)   # (raises before the device is touched)
+        system = integrator.system
+        if types is not None and types.shape[0] != system.n:
+            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
+        self.integrator, self.system = integrator, system
+        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
+        self.nhist = system.n if nhist is None else nhist
+        self._excl = _excl_list(integrator, exclusions)
+        self._links = ClusterLinks(integrator.engine, types, self.ntypes, self.rlink, system.n)
+        dev = system.pos.device
+        self._label = torch.full((system.n,), -1, dtype=torch.int32, device=dev)
+        self._size = torch.zeros(system.n, dtype=torch.int32, device=dev)
+        self._rows = torch.zeros((self.capacity, 4), dtype=torch.int64, device=dev)
+        self._hist = torch.zeros(self.nhist, dtype=torch.int64, device=dev)
+        self._steps = [None] * self.capacity
+        self.samples = 0
+        system.analyzers.append(self)
+
+    def analyze(self, timestep):
+        if timestep % self.period:
+            return
+        q = self.samples % self.capacity
+        self.integrator.engine.cluster_label(self.system.pos, self._links, label=self._label, size=self._size, stats=self._rows[q],
+                                             hist=self._hist, group=self.integrator.group.members, exclusions=self._excl)
+        self._steps[q] = int(timestep)
+        self.samples += 1
+
+    def reset(self):
+        self._rows.zero_(); self._hist.zero_()
+        self._label.fill_(-1); self._size.zero_()
+        self._steps = [None] * self.capacity
+        self.samples = 0
+
+    def status(self):
+        """The give-up word of the device object (0: every sample was labelled completely; see include/pse_amd.h)."""
+        return self._links.status()
+
+    def _sampled(self):
+        if self.samples < 1:
+            raise ValueError("no samples yet")
+
+    def labels(self):
+        """(n,) int64: the smallest particle index of every particle's cluster in the last sample; -1 outside the group."""
+        self._sampled()
+        return self._label.cpu().numpy().astype("int64")
+
+    def sizes(self):
+        """(n,) int64: the number of members of every particle's cluster in the last sample; 0 outside the group."""
+        self._sampled()
+        return self._size.cpu().numpy().astype("int64")
+
+    def members(self, label):
+        """The particle indices of the cluster whose label is `label` (the smallest index among them), ascending."""
+        import numpy as np
+        return np.nonzero(self.labels() == int(label))[0]
+
+    def table(self):
+        """(samples kept, 5) int64, oldest first: timestep, clusters, largest, sum of s^2, N (one copy from the device)."""
+        import numpy as np
+        n = min(self.samples, self.capacity)
+        dev = self._rows.cpu().numpy()
+        out = np.zeros((n, 5), dtype=np.int64)
+        for r in range(n):
+            q = (self.samples - n + r) % self.capacity
+            out[r, 0], out[r, 1:] = self._steps[q], dev[q]
+        return out
+
+    def size_distribution(self):
+        """n(s) for s = 1 .. nhist: the mean number of clusters of s members per sample since the last reset(); its sum is the mean
+        number of clusters.  The last entry counts every cluster of nhist members or more."""
+        return size_distribution_of(self._hist.cpu().numpy(), self.samples)
+
+    def number_average(self):
+        return averages_of(self.table()[:, 1:])[0]
+
+    def weight_average(self):
+        return averages_of(self.table()[:, 1:])[1]
+
+    def largest_fraction(self):
+        return averages_of(self.table()[:, 1:])[2]

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -41,6 +41,7 @@ struct pse_typed_table : Topology { using Topology::Topology; };   // row_off: t
 struct pse_pair_hist : Topology { using Topology::Topology; };     // entries: the types (zeros where none were given)
 struct pse_structure_factor : Topology { using Topology::Topology; };   // row_off: the REAL plan (structure_factor_plan), entries: its permutation
 struct pse_msd : Topology { using Topology::Topology; int norigins = 0; unsigned long long stored = 0ull; };   // the slots' bookkeeping alone
+struct pse_clusters : Topology { using Topology::Topology; };      // entries: the types (zeros where none were given); the status word is always 0
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -217,6 +218,28 @@ int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image
                        const int *slots_host, const int *rows_host, int nrows, double *sums) {
     return msd_accumulate_validate(m, m ? m->norigins : 0, m ? m->stored : 0ull, m ? m->h->par.n_max : 0u, N, pos, image, strain, npairs,
                                    slots_host, rows_host, nrows, sums);
+}
+int pse_clusters_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const double *rlink_host, pse_clusters **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_clusters_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_clusters_create: null handle");
+    if (int rc = clusters_create_validate(h->d.rcut, h->par.n_max, n, types_host, ntypes, rlink_host)) return rc;
+    pse_clusters *g = new pse_clusters(h, 0, (size_t)n);
+    if (types_host) std::copy(types_host, types_host + n, g->entries.begin());
+    return topology_adopt(g, 0, out);
+}
+int pse_clusters_destroy(pse_clusters *g) { return topology_destroy(g); }
+int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *, unsigned N, unsigned *label, unsigned *size,
+                       unsigned long long *stats, unsigned long long *hist, unsigned nhist, const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;   // (the arrays are device pointers and there is no device: nothing is read or written)
+    return clusters_label_validate(g, h, h ? h->par.n_max : 0u, h ? h->par.n_slabs : 1, 0u, N, pos, label, size, stats, hist, nhist, ex,
+                                   ex ? ex->h : nullptr);
+}
+int pse_clusters_status(pse_clusters *g, unsigned *status) {
+    if (!g) return fail(PSE_ERR_INVALID, "pse_clusters_status: null cluster object");
+    if (!status) return fail(PSE_ERR_INVALID, "pse_clusters_status: null status");
+    *status = 0u;   // (nothing ever ran)
+    return 0;
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -444,6 +444,21 @@ struct pse_pair_hist : Topology {
         for (void *p : ptrs) if (p) (void)hipFree(p);
     }
 };
+// Cluster links (include/pse_amd.h): n = particles with a type, ntypes, the squared link distances and the union-find workspace of
+// k_cluster_link (three unsigned arrays of n_max and the sticky status word).  known_status: the last word pse_clusters_status read.
+// The arrays of Topology stay null.
+struct pse_clusters : Topology {
+    unsigned char *types = nullptr;         // n: the type of caller-order particle t
+    unsigned char *type_s = nullptr;        // n_max: the types in sorted order, written by every call (k_type_mirror)
+    double *rlink2 = nullptr;               // npt: rlink^2, 0 = off
+    unsigned *work = nullptr;               // parent, mintag, csize (n_max each), then the status word
+    double rl2_all = 0.0;
+    unsigned known_status = 0u;
+    ~pse_clusters() override {
+        void *ptrs[] = {types, type_s, rlink2, work};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
+};
 // A static structure factor (include/pse_amd.h): n = particles with a type, count = nk modes, ntypes; the plan of the modes
 // (structure_factor_plan) and the workspace of the partial sums.  The arrays of Topology stay null.
 struct pse_structure_factor : Topology {
@@ -3033,6 +3048,65 @@ extern "C" int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_
     launch_msd_accumulate((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
                           msd_origins(m), pairs, sums, h->stream);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Cluster analysis (include/pse_amd.h): the types and the link distances on the device, and the pass.  Queue-only: the sort, the type
+// mirror and the four kernels of the union-find; nothing is read back.
+extern "C" int pse_clusters_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const double *rlink_host,
+                                   pse_clusters **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_clusters_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_clusters_create: null handle");
+    TRY(clusters_create_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, rlink_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
+    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
+    const int npt = ntypes * (ntypes + 1) / 2;
+    std::vector<double> rl2((size_t)npt);
+    pse_clusters *g = new pse_clusters();
+    g->h = h; g->n = n; g->count = (unsigned)npt; g->ntypes = ntypes;
+    for (int p = 0; p < npt; ++p) { rl2[p] = rlink_host[p] * rlink_host[p]; g->rl2_all = std::max(g->rl2_all, rl2[p]); }
+    const size_t nwork = 3 * (size_t)h->n_max + 1;
+    hipError_t e = hipMalloc((void **)&g->types, n);
+    if (e == hipSuccess) e = hipMemcpy(g->types, types.data(), n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&g->type_s, (size_t)h->n_max);
+    if (e == hipSuccess) e = hipMalloc((void **)&g->rlink2, (size_t)npt * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(g->rlink2, rl2.data(), (size_t)npt * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&g->work, nwork * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(g->work, 0, nwork * sizeof(unsigned));
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memset may return early)
+    if (e != hipSuccess) {
+        delete g;
+        return fail(PSE_ERR_HIP, "pse_clusters_create: %u types and a workspace of %zu words on the device failed: %s", n, nwork, hipGetErrorString(e));
+    }
+    h->topologies.push_back(g);
+    *out = g;
+    return 0;
+}
+extern "C" int pse_clusters_destroy(pse_clusters *g) { return topology_destroy(g); }
+extern "C" int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *label, unsigned *size,
+                                  unsigned long long *stats, unsigned long long *hist, unsigned nhist, const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;
+    TRY(clusters_label_validate(g, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, g ? g->known_status : 0u, N, pos, label, size, stats, hist,
+                                nhist, ex, ex ? ex->h : nullptr));
+    HIPCHK(hipSetDevice(h->device));
+    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
+    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
+    const size_t nm = (size_t)h->n_max;
+    const ClusterLinks cl{g->types, g->type_s, g->n, g->ntypes, g->rlink2, g->rl2_all, g->work, g->work + nm, g->work + 2 * nm, g->work + 3 * nm};
+    launch_clusters(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, cl, label, size, stats, hist, nhist, h->stream, ex ? &er : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int pse_clusters_status(pse_clusters *g, unsigned *status) {
+    if (!g) return fail(PSE_ERR_INVALID, "pse_clusters_status: null cluster object");
+    if (!status) return fail(PSE_ERR_INVALID, "pse_clusters_status: null status");
+    pse_handle *h = g->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(&g->known_status, g->work + 3 * (size_t)h->n_max, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *status = g->known_status;
     return 0;
 }
 

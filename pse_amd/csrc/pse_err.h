@@ -83,5 +83,13 @@ int msd_displacement_validate(unsigned long long stored, int slot, const void *o
 // the argument checks of pse_msd_accumulate
 int msd_accumulate_validate(const void *m, int norigins, unsigned long long stored, unsigned n_max, unsigned N, const void *pos,
                             const void *image, double strain, int npairs, const int *slots, const int *rows, int nrows, const void *sums);
+// the argument checks of pse_clusters_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them
+// (types may be null: one type), with the handle's rcut and n_max
+int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rlink);
+// the argument checks of pse_clusters_label: the object (g_handle: the handle it was created on, n_max and n_slabs that handle's;
+// known_status: the last word pse_clusters_status returned), N, pos, the outputs, an exclusion object of the same handle, the slab rank
+int clusters_label_validate(const void *g, const void *g_handle, unsigned n_max, int n_slabs, unsigned known_status, unsigned N, const void *pos,
+                            const void *label, const void *size, const void *stats, const void *hist, unsigned nhist, const void *ex,
+                            const void *ex_handle);
 
 }  // namespace pse

@@ -107,6 +107,23 @@ void launch_msd_store(const double4 *pos, const int3 *image, const unsigned *gro
                       const MsdOrigins &mo, int slot, double4 *out, hipStream_t s);
 void launch_msd_accumulate(const double4 *pos, const int3 *image, const unsigned *group, int N, double Lx, double Ly, double Lz, double sLy,
                            const MsdOrigins &mo, const MsdPairs &pairs, double *sums, hipStream_t s);
+// cluster analysis (pse_clusters_label): the device arrays and the link distances of one object.  types, type_s: as in PairHist.
+// rlink2: npt squares of the link distances (0: off), rl2_all the largest; parent, mintag, csize: n_max unsigned words each, the
+// union-find over the sorted rows, rewritten by every call; status: the object's sticky word (a trip cap was reached).  Two sorted rows
+// are linked when 0 < r^2 < rlink2[p] and the pair is not in `ex`; label and size are written by caller index (tag_s), stats (four
+// words) is overwritten, hist (nhist words) is added to with integer atomics; each may be null.
+struct ClusterLinks {
+    const unsigned char *types;
+    unsigned char *type_s;
+    unsigned n;
+    int ntypes;
+    const double *rlink2;
+    double rl2_all;
+    unsigned *parent, *mintag, *csize, *status;
+};
+void launch_clusters(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const ClusterLinks &cl,
+                     unsigned *label, unsigned *size, unsigned long long *stats, unsigned long long *hist, unsigned nhist, hipStream_t s,
+                     const PairExclusions *ex = nullptr);
 // bonded forces (k_bond_forces): one row of (partner, type) entries per particle of the caller-order arrays, row i =
 // entries[row_off[i] .. row_off[i + 1]), sorted (pse_host_bond_rows); par = ntypes <= BOND_MAX_TYPES parameter sets.  out8 != null: the
 // eight observables through `rows` (pair_virial_rows(n) doubles) as above; out8 == null: forces only.  A FENE bond at r >= r0 does

@@ -1,5 +1,5 @@
-// Kernels of the force providers (pse_forces.h): pair repulsion, tabulated and typed pair tables with exclusions and the pair-distance
-// histogram on the engine's cell list, the static structure factor on the caller-order positions, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
+// Kernels of the force providers (pse_forces.h): pair repulsion, tabulated and typed pair tables with exclusions, the pair-distance
+// histogram and the cluster analysis on the engine's cell list, the static structure factor on the caller-order positions, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
 // they leave in net_force.  gfx950, wave64, fp64.
 #include "pse_forces.h"
 
@@ -429,6 +429,200 @@ void launch_pair_hist(const double4 *pos_s, const unsigned *tag_s, int N, const 
         hipLaunchKernelGGL((k_pair_hist<decltype(excl)::value>), dim3(nb), dim3(TPB), lds, s, pos_s, tag_s, ph.type_s, N, cell_off, box,
                            nc, ph.ntypes, ph.nbins, ncount, ph.rmin, ph.rmax * ph.rmax, scale, counts, er);
     });
+}
+
+// Cluster analysis (pse_clusters_label): the connected components of the graph whose edges are the pairs with 0 < r^2 < rlink[p]^2,
+// p the pair type, that are not excluded.  A lock-free union-find over the SORTED ROWS -- neighbours in space are neighbours in memory
+// there -- in five launches behind the sort: k_type_mirror, k_cluster_init, k_cluster_link, k_cluster_flatten, k_cluster_write.
+// parent[x] <= x always: a row is its own root until ONE compare-and-swap hooks it under a smaller row, and nothing else ever writes
+// parent[x] while x is a root (path halving points a row that is NOT a root at a smaller row of its own tree: the inequality stays,
+// trees only ever merge, and every walk still ends at the one root of the tree).  Hence
+//   find(x) follows strictly decreasing rows: at most N loads;
+//   unite(i, j) finds both roots, hooks the LARGER under the smaller with atomicCAS(parent + hi, hi, lo), and where the CAS fails --
+//     another lane hooked hi first -- continues from the value it returned, which is below hi: the rows it tries to hook decrease
+//     strictly, so it fails fewer than N times (and over all lanes at most N - 1 hooks ever succeed).
+// No lane ever waits for another.  Every loop nevertheless carries a trip cap of N; a lane that reaches it ORs a bit into the object's
+// status word and leaves, and k_cluster_write then writes ~0u labels and zero sizes.
+// parent is read with relaxed agent-scope atomic loads (global_load_dword sc1): a plain load may be kept in a register or served from
+// this CU's L1.  Nothing depends on how FRESH a load is: an old value of parent[x] is x itself, which the lane takes for a root; the
+// CAS, which is decided where the word lives, then fails and returns the truth.  A successful CAS needs hi to be a root, not lo: a root
+// hooked under ANY smaller row of the other tree is a valid union.
+// The partition and the smallest caller index of a component do not depend on the order in which the hooks happen, and everything
+// summed is an integer: equal inputs give equal outputs, and a permuted particle order gives the same labels.
+// Path halving in k_cluster_link (cluster_find<true>) was measured against the plain walk at N = 10^6 (docs/HISTORY.md): one cluster of
+// 10^6 rows 1.70 ms against 2.44, below the threshold 0.59 against 0.57 and 0.86 against 0.80; kept.  k_cluster_flatten walks without it
+// and shortens every path to one hop.
+constexpr unsigned CLUSTER_CAP_FIND = 1u, CLUSTER_CAP_UNITE = 2u;   // bits of the status word
+__device__ __forceinline__ unsigned cluster_parent(const unsigned *parent, unsigned x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The root of x's tree, or ~0u behind the trip cap (never reached: x, parent[x], ... decrease strictly and x < cap = N).
+// HALVE: path halving -- a row that is not a root is pointed at its grandparent on the way (a relaxed store: parent[x] stays a row
+// of x's own tree below x, whichever of two racing stores lands last and however old the values they were made from; the CAS of
+// cluster_unite only ever succeeds on a root, and a row that has stopped being a root never becomes one again).
+template <bool HALVE>
+__device__ __forceinline__ unsigned cluster_find(unsigned *parent, unsigned x, unsigned cap, unsigned *status) {
+    for (unsigned trip = 0; trip < cap; ++trip) {
+        const unsigned p = cluster_parent(parent, x);
+        if (p == x) return x;
+        if (HALVE) {
+            const unsigned gp = cluster_parent(parent, p);
+            if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            x = gp;
+        } else {
+            x = p;
+        }
+    }
+    atomicOr(status, CLUSTER_CAP_FIND);
+    return ~0u;
+}
+__device__ __forceinline__ void cluster_unite(unsigned *parent, unsigned a, unsigned b, unsigned cap, unsigned *status) {
+    for (unsigned trip = 0; trip < cap; ++trip) {
+        a = cluster_find<true>(parent, a, cap, status);
+        b = cluster_find<true>(parent, b, cap, status);
+        if (a == b || a == ~0u || b == ~0u) return;
+        const unsigned hi = max(a, b), lo = min(a, b);
+        const unsigned seen = atomicCAS(parent + hi, hi, lo);
+        if (seen == hi) return;
+        a = seen; b = lo;   // hi was hooked by another lane, under seen < hi
+    }
+    atomicOr(status, CLUSTER_CAP_UNITE);
+}
+__global__ void __launch_bounds__(TPB)
+k_cluster_init(int N, unsigned *__restrict__ parent, unsigned *__restrict__ mintag, unsigned *__restrict__ csize,
+               unsigned long long *__restrict__ stats /* may be null */) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i < N) { parent[i] = (unsigned)i; mintag[i] = ~0u; csize[i] = 0u; }
+    if (stats && i < 4) stats[i] = 0ull;
+}
+// One thread per sorted row i, the rows j > i of its 27 cells -- every unordered pair once, the walk of k_pair_hist written out the
+// same way.  rl2[p] = rlink[p]^2 (0: off) of at most 36 pair types staged in LDS; per pair the wave-uniform prefilter
+// r^2 < max_p rl2 and r^2 > 0 first, behind it the partner's type byte, the pair type's own rl2 and, with EXCL, the lookup of
+// k_pair_table_typed.  A linked pair calls cluster_unite(i, j).  No lane leaves before the barrier.
+template <bool EXCL>
+__global__ void __launch_bounds__(TPB)
+k_cluster_link(const double4 *__restrict__ pos_s, const unsigned *__restrict__ tag_s, const unsigned char *__restrict__ type_s, int N,
+               const int *__restrict__ cell_off, DBox box, DCells nc, int ntypes, const double *__restrict__ rlink2 /* npt */, double rl2_all,
+               unsigned *parent, unsigned *status, ExclRows ex) {
+    __shared__ double rl2[PAIR_TYPED_MAX_PAIR_TYPES];
+    if ((int)threadIdx.x < ntypes * (ntypes + 1) / 2) rl2[threadIdx.x] = rlink2[threadIdx.x];
+    __syncthreads();
+    const int i = xcd_block(blockIdx.x, gridDim.x) * TPB + threadIdx.x;
+    if (i < N) {
+        const double4 pi = pos_s[i];
+        double fx, fy, fz;
+        frac_coords(box, pi.x, pi.y, pi.z, fx, fy, fz);
+        const int cx = cell_coord(fx, nc.nx), cy = cell_coord(fy, nc.ny), cz = cell_coord(fz, nc.nz);
+        const int ti = type_s[i];
+        unsigned eb = 0u, ee = 0u;
+        if (EXCL) excl_row(ex, tag_s[i], eb, ee);
+        for_each_run(nc, cell_off, cx, cy, cz, [&](int jb, int je, unsigned) {
+            for (int j = max(jb, i + 1); j < je; ++j) {
+                const double4 pj = pos_s[j];
+                double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                min_image(box, dx, dy, dz);
+                const double r2 = dx * dx + dy * dy + dz * dz;
+                if (r2 < rl2_all && r2 > 0.0) {
+                    const int tj = type_s[j];
+                    const int lo = min(ti, tj), hi = max(ti, tj);
+                    const int p = lo * ntypes - ((lo * (lo - 1)) >> 1) + (hi - lo);
+                    if (r2 < rl2[p] && !(EXCL && eb < ee && excl_has(ex.ent, eb, ee, tag_s[j])))
+                        cluster_unite(parent, (unsigned)i, (unsigned)j, (unsigned)N, status);
+                }
+            }
+        });
+    }
+}
+// Every row learns its root and stores it back (one hop from now on); the root collects the smallest caller index and the number of
+// members with integer atomics.  A store of a root into parent[i] while another lane walks through i hands that lane an ancestor of i,
+// as the old value was.  The rows of a wave are neighbours in space and, in a large cluster, share their root: the lanes whose root
+// is that of the wave's first lane reduce among themselves (a butterfly minimum, a ballot count) and ONE of them adds for all; the
+// others add for themselves.  (One atomic per row put 2 x 10^6 atomics on two words when the system is one cluster: 11.5 ms of a
+// 13.7 ms call at N = 10^6, docs/HISTORY.md.)  No lane leaves before the butterfly.
+__global__ void __launch_bounds__(TPB)
+k_cluster_flatten(const unsigned *__restrict__ tag_s, int N, unsigned *parent, unsigned *__restrict__ mintag, unsigned *__restrict__ csize,
+                  unsigned *status) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    unsigned root = ~0u, tag = ~0u;   // (~0u: a lane past the last row, or one that gave up)
+    if (i < N) {
+        root = cluster_find<false>(parent, (unsigned)i, (unsigned)N, status);   // (no halving here: k_cluster_write needs parent[i] = root)
+        if (root != ~0u) {
+            __hip_atomic_store(parent + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tag = tag_s[i];
+        }
+    }
+    const unsigned lead = __shfl(root, 0, 64);
+    const bool with_lead = root != ~0u && root == lead;
+    const unsigned long long group = __ballot(with_lead);
+    unsigned least = with_lead ? tag : ~0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) least = min(least, (unsigned)__shfl_xor((int)least, o, 64));
+    if (with_lead) {
+        if ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)group) - 1)) {
+            atomicMin(mintag + root, least);
+            atomicAdd(csize + root, (unsigned)__popcll(group));
+        }
+    } else if (root != ~0u) {
+        atomicMin(mintag + root, tag);
+        atomicAdd(csize + root, 1u);
+    }
+}
+// label and size by caller index; a row that is its own root adds its cluster to stats (clusters, largest, sum s^2, N) and to
+// hist[min(s, nhist) - 1].  The workgroup first sums in LDS -- four 64-bit words and the first CLUSTER_LDS_BINS bins, where the small
+// clusters of a dilute system all land -- and adds what is not zero to the caller's words behind ONE barrier; a cluster beyond those
+// bins adds to its word directly.  A non-zero status word: ~0u labels, zero sizes, stats left at the zeros of k_cluster_init, hist untouched.
+constexpr int CLUSTER_LDS_BINS = 64;
+__global__ void __launch_bounds__(TPB)
+k_cluster_write(const unsigned *__restrict__ tag_s, int N, const unsigned *__restrict__ parent, const unsigned *__restrict__ mintag,
+                const unsigned *__restrict__ csize, const unsigned *__restrict__ status, unsigned *__restrict__ label,
+                unsigned *__restrict__ size, unsigned long long *__restrict__ stats, unsigned long long *__restrict__ hist, unsigned nhist) {
+    __shared__ unsigned long long st[4];
+    __shared__ unsigned hb[CLUSTER_LDS_BINS];
+    if (threadIdx.x < 4) st[threadIdx.x] = 0ull;
+    if (threadIdx.x < CLUSTER_LDS_BINS) hb[threadIdx.x] = 0u;
+    __syncthreads();
+    const bool gave_up = *status != 0u;
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i < N) {
+        const unsigned root = parent[i], t = tag_s[i];
+        if (label) label[t] = gave_up ? ~0u : mintag[root];
+        if (size) size[t] = gave_up ? 0u : csize[root];
+        if (!gave_up && root == (unsigned)i) {
+            const unsigned long long sz = csize[i];
+            if (stats) {
+                atomicAdd(st + 0, 1ull);
+                atomicMax(st + 1, sz);
+                atomicAdd(st + 2, sz * sz);
+                atomicAdd(st + 3, sz);
+            }
+            if (hist) {
+                const unsigned long long b = min(sz, (unsigned long long)nhist) - 1ull;
+                if (b < (unsigned long long)CLUSTER_LDS_BINS) atomicAdd(hb + (unsigned)b, 1u);
+                else atomicAdd(hist + b, 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    if (stats && threadIdx.x < 4 && st[threadIdx.x]) {
+        if (threadIdx.x == 1) atomicMax(stats + 1, st[1]);
+        else atomicAdd(stats + threadIdx.x, st[threadIdx.x]);
+    }
+    if (hist && threadIdx.x < CLUSTER_LDS_BINS && threadIdx.x < nhist && hb[threadIdx.x]) atomicAdd(hist + threadIdx.x, (unsigned long long)hb[threadIdx.x]);
+}
+void launch_clusters(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc, const ClusterLinks &cl,
+                     unsigned *label, unsigned *size, unsigned long long *stats, unsigned long long *hist, unsigned nhist, hipStream_t s,
+                     const PairExclusions *ex) {
+    static_assert(PAIR_TYPED_MAX_PAIR_TYPES <= TPB, "one lane stages one link distance");
+    const int nb = nblocks(N, TPB);
+    hipLaunchKernelGGL(k_type_mirror, dim3(nb), dim3(TPB), 0, s, tag_s, N, cl.types, cl.n, cl.type_s);
+    hipLaunchKernelGGL(k_cluster_init, dim3(nb), dim3(TPB), 0, s, N, cl.parent, cl.mintag, cl.csize, stats);
+    launch_with_excl(ex, [&](auto excl, ExclRows er) {
+        hipLaunchKernelGGL((k_cluster_link<decltype(excl)::value>), dim3(nb), dim3(TPB), 0, s, pos_s, tag_s, cl.type_s, N, cell_off, box, nc,
+                           cl.ntypes, cl.rlink2, cl.rl2_all, cl.parent, cl.status, er);
+    });
+    hipLaunchKernelGGL(k_cluster_flatten, dim3(nb), dim3(TPB), 0, s, tag_s, N, cl.parent, cl.mintag, cl.csize, cl.status);
+    hipLaunchKernelGGL(k_cluster_write, dim3(nb), dim3(TPB), 0, s, tag_s, N, cl.parent, cl.mintag, cl.csize, cl.status, label, size, stats,
+                       hist, nhist);
 }
 
 // Static structure factor (pse_structure_factor_accumulate): rho_a(m) = sum_{j of type a} exp(-2 pi i m.s_j) over a list of integer

@@ -375,6 +375,49 @@ int msd_accumulate_validate(const void *m, int norigins, unsigned long long stor
     return 0;
 }
 
+int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rlink) {
+    const char *who = "pse_clusters_create";
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (!rlink) return fail(PSE_ERR_INVALID, "%s: null rlink_host", who);
+    const int npt = ntypes * (ntypes + 1) / 2;
+    bool on = false;
+    for (int p = 0; p < npt; ++p) {
+        if (!std::isfinite(rlink[p])) return fail(PSE_ERR_INVALID, "%s: pair type %d has rlink = %g, which is not finite", who, p, rlink[p]);
+        if (rlink[p] < 0.0) return fail(PSE_ERR_INVALID, "%s: pair type %d has rlink = %g, which is negative (0 switches a pair type off)", who, p, rlink[p]);
+        if (rlink[p] > rcut)
+            return fail(PSE_ERR_INVALID, "%s: pair type %d has rlink = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic cutoff", who,
+                        p, rlink[p], rcut);
+        on = on || rlink[p] > 0.0;
+    }
+    if (!on) return fail(PSE_ERR_INVALID, "%s: every pair type is off (rlink = 0): nothing could be linked", who);
+    if (types)
+        for (unsigned i = 0; i < n; ++i)
+            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    return 0;
+}
+
+int clusters_label_validate(const void *g, const void *g_handle, unsigned n_max, int n_slabs, unsigned known_status, unsigned N, const void *pos,
+                            const void *label, const void *size, const void *stats, const void *hist, unsigned nhist, const void *ex,
+                            const void *ex_handle) {
+    const char *who = "pse_clusters_label";
+    if (!g) return fail(PSE_ERR_INVALID, "%s: null cluster object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!label && !size && !stats && !hist) return fail(PSE_ERR_INVALID, "%s: label, size, stats and hist are all null: nothing to write", who);
+    if (((uintptr_t)stats & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: stats is not 8-byte aligned (64-bit words)", who);
+    if (((uintptr_t)hist & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: hist is not 8-byte aligned (64-bit words)", who);
+    if (hist && nhist == 0) return fail(PSE_ERR_INVALID, "%s: hist given with nhist = 0, need at least one word", who);
+    if (ex) if (int rc = pair_excl_validate(who, ex, ex_handle, g_handle)) return rc;
+    if (n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "%s: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the clusters would be partial", who,
+                    n_slabs);
+    if (known_status)
+        return fail(PSE_ERR_INVALID, "%s: an earlier call gave up (status word 0x%x, pse_clusters_status): its labels were not complete", who,
+                    known_status);
+    return 0;
+}
+
 void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> &perm, std::vector<unsigned> &uoff, std::vector<int> &segs) {
     perm.resize(nk);
     for (unsigned q = 0; q < nk; ++q) perm[q] = q;

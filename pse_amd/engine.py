@@ -485,6 +485,71 @@ class DisplacementOrigins(_DeviceObject):
         self._create(engine, "pse_msd_create", self.n, _vp(types), self.ntypes, self.norigins)
 
 
+def _cluster_arguments(types, ntypes, rlink):
+    """The arguments of a ClusterLinks, checked before the device is touched: (types uint32 (n,) or None, ntypes, rlink float64 (npt,)).
+    `rlink`: a scalar (every pair type), a dict {(a, b): r} in either key order with a missing pair off, or npt entries in the
+    order of pair_type_index; 0 switches a pair type off, at least one must be on."""
+    import numpy as np
+    ntypes = int(ntypes)
+    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
+        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    npt = ntypes * (ntypes + 1) // 2
+    if isinstance(rlink, dict):
+        out = np.zeros(npt)
+        seen = set()
+        for key, r in rlink.items():
+            if not (isinstance(key, tuple) and len(key) == 2 and all(isinstance(v, (int, np.integer)) and 0 <= v < ntypes for v in key)):
+                raise ValueError(f"rlink key {key!r}: need a pair (a, b) of types in [0, {ntypes})")
+            p = pair_type_index(int(key[0]), int(key[1]), ntypes)
+            if p in seen:
+                raise ValueError(f"rlink names the pair of types {tuple(sorted(key))} twice")
+            seen.add(p)
+            out[p] = float(r)
+    elif np.ndim(rlink) == 0:
+        out = np.full(npt, float(rlink))
+    else:
+        out = np.array(rlink, dtype=np.float64)
+        if out.shape != (npt,):
+            raise ValueError(f"rlink must be a scalar, a dict or {npt} entries, one per pair of types")
+    if not np.isfinite(out).all() or (out < 0.0).any():
+        raise ValueError("rlink must be finite and not negative (0 switches a pair type off)")
+    if not (out > 0.0).any():
+        raise ValueError("every pair type is off: rlink needs a positive entry")
+    if types is not None:
+        types = np.asarray(types)
+        if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
+            raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
+        if types.max() >= ntypes:
+            raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
+        types = np.ascontiguousarray(types, dtype=np.uint32)
+    return types, ntypes, np.ascontiguousarray(out)
+
+
+class ClusterLinks(_DeviceObject):
+    """Owner of a pse_clusters object: one type per particle and one link distance per pair of types (see _cluster_arguments for
+    `rlink`).  `types`: (n,) integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts
+    as type 0.  Pass it as `links` to Engine.cluster_label."""
+
+    DESTROY = "pse_clusters_destroy"
+
+    def __init__(self, engine, types, ntypes, rlink, n=None):
+        types, self.ntypes, self.rlink = _cluster_arguments(types, ntypes, rlink)
+        self.npt = self.ntypes * (self.ntypes + 1) // 2
+        if types is None:
+            self.n = _rows(engine, n)
+        else:
+            self.n = int(types.shape[0] if n is None else n)
+            if not 0 <= self.n <= types.shape[0]:
+                raise ValueError("n outside [0, len(types)]")
+        self._create(engine, "pse_clusters_create", self.n, _vp(types), self.ntypes, _vp(self.rlink))
+
+    def status(self):
+        """The object's sticky give-up word (pse_clusters_status: waits for the stream).  0: every labelling so far was complete."""
+        word = ctypes.c_uint(0)
+        _lib.check(self._lib.pse_clusters_status(self._handle(), ctypes.byref(word)))
+        return int(word.value)
+
+
 class _ForcePasses:
     """The force providers of the C-ABI on one handle, for whoever holds one: an Engine, which owns its handle, and the
     StokesEngine of an integrator, whose handle the C++ Stokes object owns.  Needs `_lib`, `_h` (the handle; raises where there is
@@ -672,6 +737,48 @@ class _ForcePasses:
         _lib.check(self._lib.pse_msd_displacement(origins._handle(self), slot, _ptr(pos), _ptr(image), _ptr(group), n,
                                                   _finite(strain, "strain"), _ptr(out)))
         return out
+
+    def clusters(self, types, ntypes, rlink, n=None):
+        """The link criterion of a cluster analysis on the device (pse_clusters_create; see include/pse_amd.h): `types` (n,) the type
+        of every caller-order particle, below `ntypes` <= 8, or None: one type; `rlink`: a scalar, a dict {(a, b): r} (a missing pair
+        is off) or npt entries, each 0 (off) or in (0, rcut]; `n`: how many of `types` to use (default: all; without types: n_max).
+        Returns a ClusterLinks: the `links` of cluster_label."""
+        return ClusterLinks(self, types, ntypes, rlink, n)
+
+    def cluster_label(self, pos, links, label=None, size=None, stats=None, hist=None, group=None, exclusions=None):
+        """The connected components of the links among the group members (pse_clusters_label): two particles are linked when
+        0 < r < rlink of their pair of types and the pair is not in `exclusions`.  All outputs are CUDA tensors, any may be None, not all:
+        `label`, `size`: contiguous 1-D int32 or int64 tensors of at least pos.shape[0] entries, by caller index -- the smallest
+        caller index of the particle's cluster and its number of members; entries outside the group are left alone;
+        `stats`: contiguous (4,) int64, OVERWRITTEN with the number of clusters, the largest size, the sum of s^2 and N;
+        `hist`: contiguous 1-D int64, ADDED to: a cluster of size s adds 1 to hist[min(s, len(hist)) - 1].
+        Queue-only: nothing is read back (an int64 label or size goes through an int32 copy on the device); integers only, so the
+        result does not depend on the order of the particles.  Returns (label, size, stats, hist)."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        for t, name in ((label, "label"), (size, "size")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.int32, torch.int64) and t.dim() == 1
+                                      and t.is_contiguous() and t.shape[0] >= pos.shape[0]):
+                raise ValueError(f"{name} must be a contiguous 1-D int32 or int64 CUDA tensor of at least {pos.shape[0]} entries")
+        if stats is not None and not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int64
+                                      and stats.is_contiguous() and tuple(stats.shape) == (4,)):
+            raise ValueError("stats must be a contiguous (4,) int64 CUDA tensor")
+        if hist is not None and not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous()
+                                     and hist.dim() == 1 and hist.shape[0] >= 1):
+            raise ValueError("hist must be a contiguous 1-D int64 CUDA tensor of at least one entry")
+        if label is None and size is None and stats is None and hist is None:
+            raise ValueError("label, size, stats and hist are all None: nothing to compute")
+        obj = links._handle(self)
+        ex = None if exclusions is None else exclusions._handle(self)
+        narrow = [None if t is None or t.dtype == torch.int32 else t.to(torch.int32) for t in (label, size)]   # (keeps the entries outside the group)
+        l32, s32 = [t if w is None else w for t, w in zip((label, size), narrow)]
+        _lib.check(self._lib.pse_clusters_label(obj, _ptr(pos), _ptr(group), n, _ptr(l32), _ptr(s32), _ptr(stats), _ptr(hist),
+                                                0 if hist is None else int(hist.shape[0]), ex))
+        for t, w in zip((label, size), narrow):
+            if w is not None:
+                t.copy_(w)
+        return label, size, stats, hist
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
