@@ -601,6 +601,18 @@ int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out);
  * pse_debug_copy_grid, so the spread can be compared node by node and not only through the gather */
 int pse_debug_spread(pse_handle *h, const pse_double4 *pos, const pse_double4 *force, const unsigned int *group_members,
                      unsigned int N);
+/* sort + gather only (gpu_stokes_Contract_kernel, PSEv1/Mobility.cu:325-477), the twin of pse_debug_spread: the three velocity grids
+ * are taken from grid_host (HOST array of 3*nx_local*Ny*Nz doubles in the layout pse_debug_copy_grid returns) and gathered at the
+ * particles; vel_out (DEVICE, rows in the caller's order like pse_mobility's vel, .w kept) = h^3 sum_nodes w u_grid, so the gather can
+ * be checked against any grid -- a single nonzero node gives one weight -- and not only behind spread and transforms.  No slab
+ * ranks. */
+int pse_debug_gather(pse_handle *h, const pse_double4 *pos, const double *grid_host, const unsigned int *group_members,
+                     unsigned int N, pse_double4 *vel_out);
+/* which far-field kernels a call with N particles launches on this handle, by the host functions that decide the launches:
+ * out6 = {spread by blocks (k_spread_tiles; 0: k_spread_atomic), its TZ (8 | 16), its NW (1 | 4), gather by bins (k_gather_bins;
+ * 0: k_gather), its BZ (1 | 2), SHEAR instantiations (xy != 0)}; TZ, NW, BZ are 0 where the generic kernel runs.  Lets a test
+ * assert the instantiation it was written for (PSE_SPREAD_TZ, PSE_SPREAD_NW, PSE_GATHER_BZ are read per handle in pse_create). */
+int pse_debug_far_path(pse_handle *h, unsigned int N, int *out6);
 /* the k-space operator of n grid nodes (i, j, k) (host array of 3 n ints, 0 <= k < Nz: any node of the reference's full C2C
  * grid) exactly as the scaling kernels evaluate it, for the current box: out_host[5 t ..] = kx, ky, kz, w sinc^2,
  * sqrt(w) sinc -- what gpu_stokes_SetGridk_kernel tabulates (PSEv1/Helper.cu:285-332: index folding, sheared ky, scale

@@ -3228,6 +3228,32 @@ extern "C" int pse_debug_spread(pse_handle *h, const pse_double4 *pos, const pse
     return 0;
 }
 
+extern "C" int pse_debug_gather(pse_handle *h, const pse_double4 *pos, const double *grid_host, const unsigned *group, unsigned N,
+                                pse_double4 *vel_out) {
+    TRY(check_n(h, N));
+    if (!pos || !grid_host || !vel_out) return fail(PSE_ERR_INVALID, "null array");
+    if (h->n_slabs > 1) return fail(PSE_ERR_INVALID, "this handle is a slab rank: drive it through a pse_team");
+    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N));   // (no vector: the records' force words are not read by the gather)
+    const DGrid &G = h->G;
+    const size_t nr = (size_t)(G.nxl + G.hl + G.nhalo) * G.Ny * G.Nz, plane = (size_t)G.Ny * G.Nz;
+    HIPCHK(launch_far_records(h->pos_s, h->f_s, (int)N, G, h->dbox, h->sw, h->stream));
+    for (int c = 0; c < 3; ++c)   // the layout pse_debug_copy_grid returns (a single GPU stores no halo planes: hl = nhalo = 0)
+        HIPCHK(hipMemcpyAsync(h->rgrid + c * nr + plane * G.hl, grid_host + (size_t)c * plane * G.nxl, plane * G.nxl * sizeof(double),
+                              hipMemcpyHostToDevice, h->stream));
+    HIPCHK(launch_gather(h->pos_s, h->sw, (int)N, h->rgrid, h->rgrid + nr, h->rgrid + 2 * nr, G, h->dbox, h->uw_s, h->stream));
+    launch_scatter_sum(h->uw_s, nullptr, nullptr, h->tag_s, (int)N, (double4 *)vel_out, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int pse_debug_far_path(pse_handle *h, unsigned N, int *out6) {
+    TRY(check_n(h, N));
+    if (!out6) return fail(PSE_ERR_INVALID, "null array");
+    far_path(h->G, h->sw, (int)N, h->dbox.xy, out6);
+    return 0;
+}
+
 extern "C" int pse_debug_copy_grid(pse_handle *h, int stage, double *host_out) {
     if (!h || !host_out) return fail(PSE_ERR_INVALID, "bad argument");
     (void)stage;

@@ -402,11 +402,47 @@ static int spread_tz(const DGrid &G, int force) {
     const long blocks16 = (long)((G.nxl + 7) / 8) * ((G.Ny + 7) / 8) * ((G.Nz + 15) / 16);
     return G.Nz >= 64 && blocks16 >= 2048 ? 16 : 8;
 }
+constexpr int SPREAD_NW = 4;   // waves per block on small grids
+// waves that share a block of the spread (TZ = 16 blocks and supports above 8 always have one)
+static int spread_nw(const DGrid &G, int tz, int nw_env) {
+    const long blocks8 = (long)((G.nxl + 7) / 8) * ((G.Ny + 7) / 8) * ((G.Nz + 7) / 8);
+    return tz == 8 && G.P <= 8 && (nw_env ? nw_env > 1 : blocks8 < 1024) ? SPREAD_NW : 1;   // fewer blocks than SIMDs
+}
 
 bool farfield_fast_path(const DGrid &G) {
     // the block kernels resolve a support to its nearest image of the block (needs N >= 2 max(block, support) per axis)
     const int need = 2 * std::max(8, G.P);
     return G.P >= 4 && G.P <= FAR_PMAX && G.Nx >= need && G.Ny >= need && G.Nz >= need;
+}
+static bool spread_fast(const DGrid &G, const SpreadWork &w) { return farfield_fast_path(G) && w.rec_t; }
+static bool gather_fast(const DGrid &G, const SpreadWork &w) { return farfield_fast_path(G) && w.rec_t && !(G.Nz & 1); }
+// the x bins a rank gathers: all of them, or (a slab rank) those that hold the origins of the particles of its own planes,
+// [x0 - hl - 1, x0 + nxl)
+static void gather_x_bins(const DGrid &G, int &bx0, int &nbx_l) {
+    const int nbx = bins_of(G.Nx);
+    bx0 = 0; nbx_l = nbx;
+    if (G.nxl < G.Nx) {
+        const int olo = ((G.x0 - G.hl - 1) % G.Nx + G.Nx) % G.Nx, ohi = (G.x0 + G.nxl - 1) % G.Nx;
+        bx0 = olo / BIN;
+        nbx_l = std::min(nbx, ((ohi / BIN - bx0) % nbx + nbx) % nbx + 1);
+    }
+}
+// bins per workgroup along z: two where a bin holds fewer than ~20 particles on average (PSE_GATHER_BZ=1|2 overrides); the
+// two-bin kernel exists for supports up to 7
+static int gather_bz(const DGrid &G, const SpreadWork &w, int N, int nbx_l) {
+    const double per_bin = (double)N / ((double)(w.rows_local ? nbx_l : bins_of(G.Nx)) * bins_of(G.Ny) * bins_of(G.Nz));
+    return (G.P <= 7 && G.Nz >= 32 && (w.force_bz ? w.force_bz == 2 : per_bin < 20.0)) ? 2 : 1;
+}
+// what launch_spread and launch_gather would launch for N particles: {spread by blocks, TZ, NW, gather by bins, BZ, SHEAR instantiations}
+// (0 where the generic kernel runs)
+void far_path(const DGrid &G, const SpreadWork &w, int N, double xy, int out[6]) {
+    const bool sf = spread_fast(G, w), gf = gather_fast(G, w);
+    const int tz = sf ? spread_tz(G, w.force_tz) : 0;
+    int bx0, nbx_l;
+    gather_x_bins(G, bx0, nbx_l);
+    out[0] = sf; out[1] = tz; out[2] = sf ? spread_nw(G, tz, w.force_nw) : 0;
+    out[3] = gf; out[4] = gf ? gather_bz(G, w, N, nbx_l) : 0;
+    out[5] = (sf || gf) && xy != 0.0 ? 1 : 0;   // (gauss_consts: gc.s = xy)
 }
 bool spread_needs_zero(const DGrid &G) { return !farfield_fast_path(G); }
 size_t farfield_bins(const DGrid &G) { return (size_t)bins_of(G.Nx) * bins_of(G.Ny) * bins_of(G.Nz); }
@@ -420,19 +456,18 @@ static void launch_spread_pt(const FarRec *rec, FarBins fb, double *gx, double *
     if (gc.s != 0.0) hipLaunchKernelGGL((k_spread_tiles<P, TZ, true, NW>), g, b, 0, s, rec, fb, gx, gy, gz, G, gc, dz, dy);
     else hipLaunchKernelGGL((k_spread_tiles<P, TZ, false, NW>), g, b, 0, s, rec, fb, gx, gy, gz, G, gc, dz, dy);
 }
-constexpr int SPREAD_NW = 4;   // waves per block on small grids
 template <int P>
 static void launch_spread_p(const FarRec *rec, FarBins fb, double *gx, double *gy, double *gz, const DGrid &G, const GaussConsts &gc,
                             int force_tz, int nw_env, hipStream_t s) {
-    const long blocks8 = (long)((G.nxl + 7) / 8) * ((G.Ny + 7) / 8) * ((G.Nz + 7) / 8);
-    if (spread_tz(G, force_tz) == 16) launch_spread_pt<P, 16, 1>(rec, fb, gx, gy, gz, G, gc, s);
-    else if (P <= 8 && (nw_env ? nw_env > 1 : blocks8 < 1024)) launch_spread_pt<P, 8, SPREAD_NW>(rec, fb, gx, gy, gz, G, gc, s);   // fewer blocks than SIMDs
+    const int tz = spread_tz(G, force_tz), nw = spread_nw(G, tz, nw_env);
+    if (tz == 16) launch_spread_pt<P, 16, 1>(rec, fb, gx, gy, gz, G, gc, s);
+    else if (P <= 8 && nw > 1) launch_spread_pt<P, 8, SPREAD_NW>(rec, fb, gx, gy, gz, G, gc, s);
     else launch_spread_pt<P, 8, 1>(rec, fb, gx, gy, gz, G, gc, s);
 }
 
 hipError_t launch_spread(const double4 *pos_s, const double4 *f_s, int N, double *gx, double *gy, double *gz, DGrid G,
                          DBox box, SpreadWork w, hipStream_t s) {
-    if (!farfield_fast_path(G) || !w.rec_t) {
+    if (!spread_fast(G, w)) {
         hipLaunchKernelGGL(k_spread_atomic, dim3(nblocks(N, 4)), dim3(256), 0, s, pos_s, f_s, N, gx, gy, gz, G, box, w.need, w.cell_off);
         return hipGetLastError();
     }
@@ -688,25 +723,18 @@ static void launch_gather_p(const FarRec *rec, FarBins fb, int bx0, int nbx_l, c
 
 hipError_t launch_gather(const double4 *pos_s, SpreadWork w, int N, const double *gx, const double *gy, const double *gz, DGrid G,
                          DBox box, double4 *u_s, hipStream_t s) {
-    if (!farfield_fast_path(G) || !w.rec_t || (G.Nz & 1)) {
+    if (!gather_fast(G, w)) {
         hipLaunchKernelGGL(k_gather, dim3(nblocks(N, 4)), dim3(256), 0, s, pos_s, N, gx, gy, gz, G, box, u_s, w.need, w.cell_off);
         return hipGetLastError();
     }
     FarBins fb = w.fb;
     fb.nbx = bins_of(G.Nx); fb.nby = bins_of(G.Ny); fb.nbz = bins_of(G.Nz);
-    int bx0 = 0, nbx_l = fb.nbx;
-    if (G.nxl < G.Nx) {
-        // a slab rank gathers the particles of its own planes (zeros elsewhere): their origins lie in [x0 - hl - 1, x0 + nxl)
+    int bx0, nbx_l;
+    gather_x_bins(G, bx0, nbx_l);
+    if (G.nxl < G.Nx)   // a slab rank gathers the particles of its own planes (zeros elsewhere)
         if (hipError_t e = hipMemsetAsync(u_s, 0, (size_t)N * sizeof(double4), s); e != hipSuccess) return e;
-        const int olo = ((G.x0 - G.hl - 1) % G.Nx + G.Nx) % G.Nx, ohi = (G.x0 + G.nxl - 1) % G.Nx;
-        bx0 = olo / BIN;
-        nbx_l = std::min(fb.nbx, ((ohi / BIN - bx0) % fb.nbx + fb.nbx) % fb.nbx + 1);
-    }
     const GaussConsts gc = gauss_consts(G, box.xy);
-    // bins per workgroup along z: two where a bin holds fewer than ~20 particles on average (PSE_GATHER_BZ=1|2 overrides)
-    const int bz_env = w.force_bz;
-    const double per_bin = (double)N / ((double)(w.rows_local ? nbx_l : fb.nbx) * fb.nby * fb.nbz);
-    const int bz = (G.Nz >= 32 && (bz_env ? bz_env == 2 : per_bin < 20.0)) ? 2 : 1;
+    const int bz = gather_bz(G, w, N, nbx_l);
     switch (G.P) {
 #define PSE_GATHER_CASE(PV) case PV: launch_gather_p<PV>(w.rec_t, fb, bx0, nbx_l, gx, gy, gz, G, gc, u_s, s, bz); break;
         PSE_GATHER_CASE(4) PSE_GATHER_CASE(5) PSE_GATHER_CASE(6) PSE_GATHER_CASE(7) PSE_GATHER_CASE(8) PSE_GATHER_CASE(9)

@@ -262,6 +262,9 @@ void launch_xfft_scale(double2 *X, double2 *Y, double2 *Z, DGrid G, DBox box, Sc
 hipError_t launch_gather(const double4 *pos_s, SpreadWork w, int N, const double *gx, const double *gy, const double *gz, DGrid G,
                    DBox box, double4 *u_s, hipStream_t s);
 
+// which kernels launch_spread / launch_gather would launch for N particles (pse_debug_far_path): decided by the functions the launchers call
+void far_path(const DGrid &G, const SpreadWork &w, int N, double xy, int out[6]);
+
 // ---- slab decomposition helpers
 void launch_slab_pack(double2 *cgrid, double2 *buf, int nxl, int Ny, int Nzh, int nyl, int unpack, hipStream_t s);
 void launch_add_inplace(double *a, const double *b, size_t n, hipStream_t s);

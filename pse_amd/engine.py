@@ -1007,6 +1007,29 @@ class Engine(_ForcePasses):
         _lib.check(self._lib.pse_debug_spread(self._h, _ptr(pos), _ptr(force), _ptr(group), n))
         return self.debug_grid()
 
+    def debug_gather(self, pos, grid, group=None):
+        """The gather alone: (N, 4) velocities (caller order) that the three host grids `grid` (3, Nx, Ny, Nz) give at the particles."""
+        import numpy as np
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        i = self.info()
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        if grid.shape != (3, i["Nx"] // max(1, self.params.n_slabs), i["Ny"], i["Nz"]):
+            raise ValueError(f"grid must have the shape of debug_grid(), not {grid.shape}")
+        vel = torch.zeros_like(pos)
+        _lib.check(self._lib.pse_debug_gather(self._h, _ptr(pos), grid.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _ptr(group), n,
+                                              _ptr(vel)))
+        return vel
+
+    FAR_PATH_FIELDS = ("spread_fast", "TZ", "NW", "gather_fast", "BZ", "shear")
+
+    def far_path(self, n):
+        """Which far-field kernels a call with n particles launches (pse_debug_far_path): dict of FAR_PATH_FIELDS."""
+        out = (ctypes.c_int * 6)()
+        _lib.check(self._lib.pse_debug_far_path(self._h, int(n), out))
+        return dict(zip(self.FAR_PATH_FIELDS, out))
+
     def debug_kvector(self, ijk):
         """(n, 5): kx, ky, kz, w sinc^2, sqrt(w) sinc of the grid nodes ijk (n, 3) as the k-space kernels evaluate them."""
         import numpy as np
