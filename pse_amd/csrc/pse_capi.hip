@@ -5,7 +5,8 @@
 // Differences from the reference driver that are deliberate: all workspaces are allocated once
 // in pse_create (the reference cudaMalloc/cudaFree's ~109 N Scalar4 every step); Lanczos scalars stay on the
 // device and the host is consulted only at convergence checks; wave vectors are computed inside the scaling
-// kernel; failures are returned, never exit()ed.
+// kernel; failures are returned, never exit()ed.  The device objects (bonds ... cluster links) and the entry points of their passes
+// are in pse_objects.hip; the handle, which both units see, is in pse_handle.h.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <rocfft/rocfft.h>
@@ -30,198 +31,17 @@
 #include "pse_host.h"
 #include "pse_kernels.h"
 #include "pse_forces.h"
-#include "pse_local.h"
+#include "pse_handle.h"
 
 using namespace pse;
 
-#define HIPCHK(x)                                                                                      \
-    do {                                                                                               \
-        hipError_t e_ = (x);                                                                           \
-        if (e_ != hipSuccess) return fail(PSE_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 #define FFTCHK(x)                                                                                      \
     do {                                                                                               \
         rocfft_status s_ = (x);                                                                        \
         if (s_ != rocfft_status_success) return fail(PSE_ERR_FFT, "%s failed: rocfft status %d (%s:%d)", #x, (int)s_, __FILE__, __LINE__); \
     } while (0)
 
-#define TRY(x)              \
-    do {                    \
-        int r_ = (x);       \
-        if (r_) return r_;  \
-    } while (0)
-
 constexpr int M_MAX = 100;   // Lanczos basis cap (PSEv1/Brownian.cu:397)
-constexpr int PH_COUNT_ = 13;   // timed phases (enum PH_* below)
-
-struct Phase {
-    hipEvent_t a = nullptr, b = nullptr;
-};
-struct Topology;
-
-struct pse_handle {
-    pse_params par;
-    Derived d;
-    Box box;
-    DBox dbox;
-    DGrid G;
-    DCells nc;
-    double cell_gamma;  // tilt bound the cell grid was sized for
-    int device = 0;
-    hipStream_t stream = nullptr;    // main chain: sort, near field, Lanczos, update (caller-visible ordering)
-    hipStream_t wstream = nullptr;   // wave-space chain; == stream unless the two chains overlap (single GPU)
-    hipStream_t side = nullptr;      // non-blocking stream behind wstream (an in-process team shares one among its members)
-    hipStream_t side_owned = nullptr;
-    int *bounds_host = nullptr;      // pinned: slab row boundaries on their way back from the device
-    hipEvent_t ev_bounds = nullptr;
-    bool bounds_pending = false;
-    // developer switches, read from the environment ONCE, in pse_create (nothing on the call path consults the environment)
-    struct Tuning {
-        int cell_bz = 6;          // PSE_CELL_BZ: height of the z blocks of the cell storage order (0: plain x, y, z order)
-        double skin = 0.4;        // PSE_SKIN: r_buff of the neighbour list kept across calls (0: off)
-        int overlap = 1;          // PSE_OVERLAP: 1 (default since round 6) two chains for every call, 0 only for kT = 0, -1 never
-        bool no_xfuse = false;    // PSE_NO_XFUSE: rocFFT for the x pass
-        int own_y_pow2 = 1;       // PSE_OWN_Y_POW2=0: rocFFT's 2-D transforms at Ny = 256 instead of its 1-D z pass + k_yfft_regs (A/B)
-        int own_y = 1;            // PSE_OWN_Y=0: rocFFT's 2-D (y, z) transforms also where the own y pass applies
-        int own_z = 1;            // PSE_OWN_Z=0: rocFFT's 1-D z transforms also where k_zfft_rows applies (A/B)
-        int yslab_regs = 1;       // PSE_YSLAB_REGS=0: a slab rank's y pass at Ny = 256, 512 by k_fft_cols instead of k_yfft_regs (A/B)
-        int yfft_kb = 4;          // PSE_YFFT_KB: kz columns per workgroup of the own y pass (2, 4, 8)
-        int wave_mode = 0;        // PSE_WAVE_MODE: 0 automatic, 1 slab, 2 replicated
-        int spread_tz = 0, spread_nw = 0;   // PSE_SPREAD_TZ, PSE_SPREAD_NW
-        int gather_bz = 0;        // PSE_GATHER_BZ=1|2: bins along z per gather workgroup (0: by the particles per bin)
-        int xmix_runtime = 0;     // PSE_XMIX=1: runtime radix plan of the mixed x pass also where a compile-time plan exists
-        int xfft_small_wide = 0;  // PSE_XFFT_SMALL_KB=8: the eight-column x pass also on small grids
-        bool verbose = false;     // PSE_VERBOSE
-        bool team_sstep = true;      // PSE_TEAM_SSTEP=0: teams run one Lanczos iteration per exchange (default: two, see lanczos_team)
-        int team_sched[3] = {1, 2, 3};   // PSE_TEAM_SCHED=a,b,c: far-field exchange k of a team step is issued before Lanczos exchange sched[k]
-        int vq = 1;                  // PSE_VQ=0: the pair-list mat-vec gathers the neighbours' rows as doubles (two gathers per pair) (A/B)
-        int place_trials = 10;       // PSE_PLACE_TRIALS=K: the two grids are allocated up to K times and the pair the x + inverse y + z passes run fastest on is kept (0, 1: off)
-        int lz_extra = 2;            // PSE_LANCZOS_EXTRA: iterations a queue-only Brownian call queues beyond the starting count (gated on the device-side decision)
-        int lz_op = PSE_LANCZOS_RECORDS16;   // PSE_LANCZOS_OP=fp64: the handle starts with the fp64 Lanczos operator (pse_set_lanczos_operator)
-    } tun;
-    DCells bidx_nc = {0, 0, 0};      // cell grid the boundary-cell indices on the device belong to
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool overlap_all = false;   // fork also for Brownian steps (PSE_OVERLAP=1)
-    bool side_on = false;       // this call runs the wave chain on the side stream
-    hipEvent_t ev_scal = nullptr;   // the Lanczos scalars have reached the pinned host buffer
-    int n_max = 0, n_pad = 0;
-    // sorted particle state
-    unsigned *keys = nullptr, *keys_s = nullptr, *vals = nullptr, *perm = nullptr, *tag_s = nullptr;
-    void *sort_tmp = nullptr;
-    int *cell_cnt = nullptr;
-    size_t sort_tmp_bytes = 0;
-    int *cell_off = nullptr;
-    double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
-    std::vector<Topology *> topologies;   // the bond, angle and dihedral objects created on this handle and still alive (pse_destroy frees them)
-    int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
-    size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
-    SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
-    NbList nb = {};              // nb.c64 = nb64 while the fp64 Lanczos operator is selected, else null
-    double4 *nb64 = nullptr;     // the fp64 plane of the pair list (allocated when the mode is first selected)
-    int lz_op = PSE_LANCZOS_RECORDS16;
-    bool nb_valid = false;   // the pair list matches the current sorted positions
-    bool lz_last_queued = false;   // the most recent Brownian call took its Lanczos decision on the device (pse_get_info then reads the host mirror)
-    // neighbour list kept across steps (HOOMD's NeighborList with r_buff and a distance check every step, PSEv1/integrate.py:60,79)
-    double skin = 0.0;           // r_buff; 0: cell walk every step
-    double skin_max = 0.0;       // what the cell grid and the list capacity were sized for
-    VerletList vl = {};
-    double4 *pos_build = nullptr;   // sorted positions at the build
-    int *flags_host = nullptr;      // pinned copy of vl.flags
-    bool vl_valid = false;       // the list on the device belongs to the current order (perm) and box
-    bool vl_use = false;         // this call runs on the kept list (no sort, no cell walk)
-    bool vl_pending = false;     // this call's first cell pass writes the list
-    int vl_N = 0; const unsigned *vl_group = nullptr; Box vl_box = {};
-    bool nc_wide = false;        // the cell grid in use is the one sized for rcut + skin_max
-    unsigned long long nlist_builds = 0, nlist_reuses = 0;
-    // A list that is never reused costs a wider cell grid and its own writes at every build: after two builds in a row whose
-    // list failed its first distance check (particles diffuse more than r_buff / 2 per call) the list is suspended for a while
-    // -- builds then run exactly as with r_buff = 0 -- and tried again, with the pause doubling while it keeps failing.
-    // Kept per kind of call -- [1]: integrating steps (pse_step), [0]: evaluations (pse_mobility, pse_brownian_velocity, ...): a
-    // time-stepping loop that outruns the skin must not switch the list off for evaluations repeated at fixed positions.
-    int vl_reused_since_build = 0, vl_misses[2] = {0, 0}, vl_suspend_left[2] = {0, 0}, vl_suspend_len[2] = {32, 32};
-    int vl_kind = 0;             // kind of the call being prepared
-    bool pv_is_f = false;        // the vector half of pv mirrors f_s (as the permute wrote it)
-    bool w_is_mpsi = false;  // w_s already holds M_real psi_s (delivered by the pass that built the pair list)
-    bool sums0_done = false; // ... and scal[LZ_TMP ..] the sums psi.psi, psi.M psi of Lanczos iteration 0
-    CombineSink sink = {};   // where the final Lanczos combination of this call sends its rows (velocity() sets it; off: ub_s)
-    bool tail_done = false;  // ... and it did: the sum of the three contributions has reached its destination
-    bool async_mode = false; // pse_set_async: deterministic evaluations queue their work and return -- no flag read-back, capturable
-    bool gated = false;      // this call decides between the kept list and a rebuild ON THE DEVICE: both chains are queued (gate_word)
-    int *gate_word = nullptr;   // (cnt_block): flags[0] | flags[1] of this call, read by the kernels of both chains
-    size_t n_cells_alloc = 0;
-    float4 *posf_s = nullptr;   // single-precision copy of pos_s (cutoff pre-filter of the near field)
-    double2 *pv = nullptr;      // [N][3] packed (position, force) records gathered by the drain of the near-field passes
-    double4 *pos_s = nullptr, *f_s = nullptr, *uw_s = nullptr, *ur_s = nullptr, *ub_s = nullptr, *psi_s = nullptr, *w_s = nullptr;
-    // real-space table
-    double *coef = nullptr;
-    int n_intervals = 0;
-    // grids
-    double *rgrid = nullptr;     // [3][nxl][Ny][Nz]
-    double2 *cgrid = nullptr;    // [3][nxl][Ny][Nzh]
-    rocfft_plan plan_fwd = nullptr, plan_inv = nullptr;      // single GPU: 3-D real transforms, batch 3
-    rocfft_plan plan_x_fwd = nullptr, plan_x_inv = nullptr;  // slab mode: 1-D complex transforms along x (strided, in place)
-    rocfft_execution_info info_fwd = nullptr, info_inv = nullptr;
-    // slab decomposition (n_slabs > 1): x planes [x0, x0+nxl) of the real grid, y rows [y0, y0+nyl) of the transposed spectrum
-    int n_slabs = 1, slab_rank = 0, nyl = 0, y0 = 0;
-    double2 *sendbuf = nullptr, *recvbuf = nullptr;          // [3][n_slabs][nxl][nyl][Nzh] each
-    int *d_bidx = nullptr, *d_bounds = nullptr;              // slab mode: cell indices / row offsets of the cell-slab boundaries
-    std::vector<int> row_lo, first_end, last_begin;          // per rank: own rows [row_lo[r], row_lo[r+1]), first / last cell layer
-    std::vector<int> first2_end, last2_begin;                // ... and its first / last TWO cell layers (two-step Lanczos of a team)
-    double4 *w2_s = nullptr, *u_s = nullptr;                 // two-step Lanczos: w2 = M M v_j, u = M v_{j-1}
-    double *sums_all = nullptr;                              // [n_slabs][LZ_NGRAM]: every rank's partial Lanczos sums (they travel with the ghost rows)
-    double4 *utot_s = nullptr;                               // slab mode: summed velocity of the own rows, all-gathered
-    bool xfuse = false;                                      // power-of-two Nx: fused x pass (k_xfft_scale)
-    bool own_y = false;                                      // y transforms by k_fft_cols, rocFFT does the z transforms only
-    bool own_y_slab = false;                                 // ... on a slab rank, with the all-to-all block layout as its output / input
-    int lz_extra = -1;           // pse_set_lanczos_extra: gated iterations a queue-only call queues beyond its starting count (-1: PSE_LANCZOS_EXTRA)
-    void *vq = nullptr;          // [n] 16-byte mirror of the newest Lanczos vector (single GPU; k_lz_update writes it, the pair-list mat-vec gathers from it)
-    int place_tried = 0; float place_ms_first = 0, place_ms_kept = 0;   // place_grids: pairs tried, the probe's time on the first and on the kept one
-    bool own_z = false;                                      // z transforms by k_zfft_rows (Nz = 256, 512): rocFFT is then off the path
-    double2 *twiddle_z = nullptr, *twiddle_z_owned = nullptr;   // [Nz] exp(-2 pi i m / Nz)
-    double2 *twiddle_y = nullptr;                            // [Ny] exp(-2 pi i m / Ny) (== twiddle when Ny == Nx)
-    double2 *twiddle_y_owned = nullptr;
-    int grid_slabs = 1;   // slabs the far-field grid is cut into: n_slabs, or 1 when every rank keeps the whole grid
-    double2 *twiddle = nullptr;                              // [Nx] exp(-2 pi i m / Nx)
-    void *fft_work = nullptr;
-    size_t fft_work_bytes = 0;
-    // Lanczos
-    double4 *V = nullptr;        // [M_MAX + 1][n_max]
-    double *scal = nullptr, *partials = nullptr;
-    double *sc_host = nullptr;   // pinned host copy of scal, mapped: the Lanczos kernels write alpha, beta, the norm there as well
-    double *sc_host_dev = nullptr;   // its device address
-    int *bounds_host_dev = nullptr;  // device address of bounds_host (mapped pinned): k_pick writes the row boundaries straight to the host
-    int npart_cap = 0;
-    // owned-particle rank (pse_params.local_rows; pse_local.h): geometry, capacities and the buffers of the step's first exchange
-    struct LocalPlan {
-        bool on = false;
-        LocalGeom g{};
-        int rows_cap = 0;                    // c_own + 2 c_g
-        double *send[2] = {nullptr, nullptr}, *recv[2] = {nullptr, nullptr};   // [left, right] messages: LOCAL_HDR + LOCAL_REC * c_x doubles
-        size_t msg = 0;                      // doubles per message
-        double4 *stage_w1 = nullptr, *stage_w2 = nullptr;   // the last layers of w1, w2 on their way to the right neighbour (c_g rows each)
-        double4 *porig_s = nullptr; double *mass_s = nullptr; int3 *image_s = nullptr;
-        LocalRows *rows = nullptr;           // device
-        int *counters = nullptr;             // (inside cnt_block: zeroed with the cell counts)
-        int *layer_cnt = nullptr;            // (likewise) kept particles per x layer of the cell grid: LOCAL_MAX_LAYERS ints
-        size_t zero_ints = 0;                // ints of cnt_block a step starts from zero
-        bool zeroed = false;                 // the last step's k_local_finish has cleared them (else: a memset in front of the step)
-        int *err = nullptr, *err_host = nullptr;   // error word: device, and a pinned word the status call copies it to
-        // pse_team_redistribute_local (allocated at its first call): records out / in (c_own each), the destination of every particle,
-        // the ranks' count rows [G][row] (row = G counts, the rank's capacity, its particle count; an even number of ints), send offsets + fill counters
-        double *rd_send = nullptr, *rd_recv = nullptr;
-        int *rd_rows = nullptr, *rd_off = nullptr, *rd_host = nullptr;
-    } loc;
-    LzState *lz_state = nullptr;     // the device-side Lanczos decision of queue-only Brownian calls (pse_set_async)
-    unsigned long long lz_seq = 0;   // calls that queued one (the decision kernel stamps the host mirror with it)
-    const uint32_t *ts_off = nullptr;   // pse_set_timestep_offset: the noise of a Brownian call is drawn at timestep + *ts_off
-    // bookkeeping
-    pse_info info;
-    bool timing = false;
-    Phase ph[PH_COUNT_];
-    unsigned long long bytes = 0;
-    int sorted_N = 0;
-    bool matvec_timed = false;
-};
 
 static std::once_flag g_fft_once;
 
@@ -400,98 +220,11 @@ static int collect_times(pse_handle *h, unsigned mask) {
     return 0;
 }
 
-// A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
-// and, for bonds, the counter of overstretched FENE bonds.  Owned by its handle; the destructor frees the device arrays.
-struct Topology {
-    pse_handle *h = nullptr;
-    unsigned n = 0, count = 0;              // particles; bonds, angles or dihedrals
-    int ntypes = 0;
-    void *row_off = nullptr;                // n + 1 (bonds: unsigned, angles: int)
-    void *entries = nullptr;                // bonds: 2 count x uint2 (partner, type); angles: 3 count x uint4 (i, j, k, type), j the vertex, i < k;
-                                            // dihedrals: 4 count x uint4 (i, j, k, l), i < l, then 4 count x unsigned types
-    void *par = nullptr;                    // ntypes x BondParam, AngleParam or DihedralParam
-    unsigned long long *over = nullptr;     // bonds: FENE bonds seen at r >= r0 since creation
-    virtual ~Topology() {
-        void *ptrs[] = {row_off, entries, par, over};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-    }
-};
-struct pse_bonds : Topology {};
-struct pse_angles : Topology {};
-struct pse_dihedrals : Topology {};
-struct pse_exclusions : Topology {};   // row_off: unsigned, entries: the partners, one unsigned each (pse_host_exclusion_rows); no parameters
-// A typed pair table (include/pse_amd.h): n = particles with a type, count = entries of all tables; `par` holds the two 16-byte words per
-// pair type that k_pair_table_typed stages.  The other arrays are its own: row_off and entries stay null.
-struct pse_typed_table : Topology {
-    unsigned char *types = nullptr;         // n: the type of caller-order particle t
-    unsigned char *type_s = nullptr;        // n_max: the types in sorted order, written by every call (k_type_mirror)
-    double *tables = nullptr;               // count x (V, F)
-    double rmax2_all = 0.0;                 // the largest rmax^2 of the pair types that are on
-    ~pse_typed_table() override {
-        void *ptrs[] = {types, type_s, tables};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-    }
-};
-// A pair-distance histogram (include/pse_amd.h): n = particles with a type, ntypes, and the bins; types and type_s as in pse_typed_table.
-// The arrays of Topology stay null.
-struct pse_pair_hist : Topology {
-    unsigned char *types = nullptr;         // n: the type of caller-order particle t
-    unsigned char *type_s = nullptr;        // n_max: the types in sorted order, written by every call (k_type_mirror)
-    int nbins = 0;
-    double rmin = 0.0, rmax = 0.0;
-    ~pse_pair_hist() override {
-        void *ptrs[] = {types, type_s};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-    }
-};
-// Cluster links (include/pse_amd.h): n = particles with a type, ntypes, the squared link distances and the union-find workspace of
-// k_cluster_link (three unsigned arrays of n_max and the sticky status word).  known_status: the last word pse_clusters_status read.
-// The arrays of Topology stay null.
-struct pse_clusters : Topology {
-    unsigned char *types = nullptr;         // n: the type of caller-order particle t
-    unsigned char *type_s = nullptr;        // n_max: the types in sorted order, written by every call (k_type_mirror)
-    double *rlink2 = nullptr;               // npt: rlink^2, 0 = off
-    unsigned *work = nullptr;               // parent, mintag, csize (n_max each), then the status word
-    double rl2_all = 0.0;
-    unsigned known_status = 0u;
-    ~pse_clusters() override {
-        void *ptrs[] = {types, type_s, rlink2, work};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-    }
-};
-// A static structure factor (include/pse_amd.h): n = particles with a type, count = nk modes, ntypes; the plan of the modes
-// (structure_factor_plan) and the workspace of the partial sums.  The arrays of Topology stay null.
-struct pse_structure_factor : Topology {
-    unsigned char *types = nullptr;         // n: the type of caller-order particle t
-    int4 *segs = nullptr;                   // 2 nseg: the segments of the canonical order
-    unsigned *perm = nullptr;               // nk: the caller's indices in the canonical order
-    unsigned *uoff = nullptr;               // nu + 1: where the u-th distinct mode begins in perm
-    double2 *rows = nullptr;                // sf_workspace(n_max, ntypes, nk)
-    int nseg = 0, nlong = 0, nu = 0, span = 0;
-    ~pse_structure_factor() override {
-        void *ptrs[] = {types, segs, perm, uoff, rows};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-    }
-};
-// Displacement origins (include/pse_amd.h): n = particles with a type, count = norigins slots, ntypes; the planes of the unwrapped
-// positions and the workspace of the partial sums.  `stored`: bit s = slot s holds positions (host bookkeeping).  The arrays of
-// Topology stay null.
-struct pse_msd : Topology {
-    unsigned char *types = nullptr;         // n: the type of caller-order particle t
-    double *planes = nullptr;               // norigins x 3 x n_max
-    double *part = nullptr;                 // msd_workspace(n_max, ntypes): rows for 64 listed pairs
-    unsigned long long stored = 0ull;
-    ~pse_msd() override {
-        void *ptrs[] = {types, planes, part};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
-    }
-};
-
 extern "C" int pse_destroy(pse_handle *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    for (Topology *t : h->topologies) delete t;
+    for (DeviceObject *t : h->topologies) delete t;
     h->topologies.clear();
     if (h->plan_fwd) rocfft_plan_destroy(h->plan_fwd);
     if (h->plan_inv) rocfft_plan_destroy(h->plan_inv);
@@ -1425,9 +1158,8 @@ static CellRanges slab_need(const pse_handle *h) {
 // step, Stokes.cc:433): the particles are gathered into the order of the last sort, every one is compared with where it
 // was at the build, and one flag comes back to the host.  Kept: perm, the neighbour list; rebuilt as before: the far-field
 // records, the per-step (f, h) pair list.
-struct PrepExtra { bool psi; unsigned timestep; };   // psi: the pass also draws the particle noise of this step into psi_s
-static int prepare(pse_handle *h, const double4 *pos, const double4 *vec, const unsigned *group, int N, bool defer_bounds = false,
-                   bool need_cells = false, PrepExtra px = PrepExtra{false, 0}, bool with_real = true) {
+int prepare(pse_handle *h, const double4 *pos, const double4 *vec, const unsigned *group, int N, bool defer_bounds = false,
+            bool need_cells = false, PrepExtra px = PrepExtra{false, 0}, bool with_real = true) {
     TRY(ts(h, PH_SORT));
     const FarBinArgs far = far_bin_args(h->G, h->sw);
     double4 *psi_out = px.psi ? h->psi_s : nullptr;
@@ -2624,489 +2356,6 @@ extern "C" int pse_sqrt_mreal(pse_handle *h, const pse_double4 *pos, const pse_d
     TRY(lanczos(T, (int)N, tol, 1.0, lanczos_m));
     launch_scatter_sum(h->ub_s, nullptr, nullptr, h->tag_s, (int)N, (double4 *)out, h->stream);
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// pse_pair_repulsion and pse_pair_repulsion_virial (include/pse_amd.h): the force pass, and the same pass with the pair observables of
-// the repulsion -- energy, virial and pair count in eight device doubles.  Queue-only: nothing is read back, out8 is written by the stream.
-// The rows of an exclusion object as the launches take them.
-static PairExclusions excl_rows(const pse_exclusions *ex) {
-    return PairExclusions{(const unsigned *)ex->row_off, (const unsigned *)ex->entries, ex->n};
-}
-// `excl`: the name of the entry point that takes an exclusion object `ex`, checked behind the plain pass's own arguments; null: a plain pass.
-static int pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, double k, double sigma,
-                          int accumulate, bool virial, double *out8, const char *excl = nullptr, const pse_exclusions *ex = nullptr) {
-    if (!h) return fail(PSE_ERR_INVALID, "null handle");
-    TRY(pair_repulsion_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, virial, out8, sigma));
-    if (excl) TRY(pair_excl_validate(excl, ex, ex ? ex->h : nullptr, h));
-    HIPCHK(hipSetDevice(h->device));
-    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
-    launch_pair_repulsion(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->pv_rows, out8,
-                          h->stream, ex ? &er : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-extern "C" int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                                  double k, double sigma, int accumulate) {
-    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, false, nullptr);
-}
-extern "C" int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                                         double k, double sigma, int accumulate, double *out8) {
-    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, true, out8);
-}
-extern "C" int pse_pair_repulsion_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                                       double k, double sigma, int accumulate, double *out8, const pse_exclusions *ex) {
-    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, out8 != nullptr, out8, "pse_pair_repulsion_excl", ex);
-}
-
-// Tabulated pair potential on the same cell list (include/pse_amd.h), with or without the eight observables.  Queue-only wherever
-// pse_pair_repulsion is; the table is read by the stream.
-static int pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, const double *table,
-                      int width, double rmin, double rmax, int accumulate, double *out8, const char *excl, const pse_exclusions *ex) {
-    if (!h) return fail(PSE_ERR_INVALID, "null handle");
-    TRY(pair_table_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, table, width, rmin, rmax, out8));
-    if (excl) TRY(pair_excl_validate(excl, ex, ex ? ex->h : nullptr, h));
-    HIPCHK(hipSetDevice(h->device));
-    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
-    launch_pair_table(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, table, width, rmin, rmax, accumulate, (double4 *)force,
-                      h->pv_rows, out8, h->stream, ex ? &er : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                              const double *table, int width, double rmin, double rmax, int accumulate, double *out8) {
-    return pair_table(h, pos, force, group, N, table, width, rmin, rmax, accumulate, out8, nullptr, nullptr);
-}
-extern "C" int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                                   const double *table, int width, double rmin, double rmax, int accumulate, double *out8,
-                                   const pse_exclusions *ex) {
-    return pair_table(h, pos, force, group, N, table, width, rmin, rmax, accumulate, out8, "pse_pair_table_excl", ex);
-}
-
-// ---- bonded forces and angle forces (include/pse_amd.h) ------------------------------------------------------------------------
-// The device copy of a topology: the host rows `off` and `ent`, the par_bytes of the ntypes parameter sets and, with `counter`, a
-// zeroed counter.  `what` is "bonds", "angles", "dihedrals" or "exclusions".
-template <class T>
-static int topology_create(pse_handle *h, const char *what, unsigned n, unsigned count, int ntypes, const std::vector<int> &off,
-                           const std::vector<unsigned> &ent, const void *par, size_t par_bytes, bool counter, T **out) {
-    T *t = new T();
-    t->h = h; t->n = n; t->count = count; t->ntypes = ntypes;
-    auto put = [](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes);
-        if (e != hipSuccess) return e;
-        return src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
-    };
-    hipError_t e = put(&t->row_off, off.data(), off.size() * sizeof(int));
-    if (e == hipSuccess) e = put(&t->entries, ent.data(), ent.size() * sizeof(unsigned));
-    if (e == hipSuccess && par_bytes) e = put(&t->par, par, par_bytes);   // (pair exclusions have no parameters)
-    if (e == hipSuccess && counter) e = put((void **)&t->over, nullptr, sizeof(unsigned long long));
-    if (e == hipSuccess && counter) e = hipDeviceSynchronize();   // (the memset is the one call above that may return early)
-    if (e != hipSuccess) {
-        delete t;
-        return fail(PSE_ERR_HIP, "pse_%s_create: copying %u %s to the device failed: %s", what, count, what, hipGetErrorString(e));
-    }
-    h->topologies.push_back(t);
-    *out = t;
-    return 0;
-}
-static int topology_destroy(Topology *t) {
-    if (!t) return 0;
-    pse_handle *h = t->h;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
-    h->topologies.erase(std::remove(h->topologies.begin(), h->topologies.end(), t), h->topologies.end());
-    delete t;
-    return 0;
-}
-
-extern "C" int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
-                                const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_bonds_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_bonds_create: null handle");
-    TRY(bonds_validate((unsigned)h->n_max, n, nbonds, pairs_host, types_host, ntypes, kind_host, k_host, r0_host));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<int> off((size_t)n + 1);
-    std::vector<unsigned> ent((size_t)nbonds * 4);
-    TRY(pse_host_bond_rows(n, nbonds, pairs_host, types_host, off.data(), ent.data()));
-    std::vector<BondParam> par((size_t)ntypes);
-    for (int t = 0; t < ntypes; ++t)
-        par[t] = BondParam{k_host[t], r0_host[t], r0_host[t] > 0.0 ? 1.0 / (r0_host[t] * r0_host[t]) : 0.0, (double)kind_host[t]};
-    return topology_create(h, "bonds", n, nbonds, ntypes, off, ent, par.data(), par.size() * sizeof(BondParam), true, out);
-}
-extern "C" int pse_bonds_destroy(pse_bonds *b) { return topology_destroy(b); }
-
-// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
-extern "C" int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
-    if (!b) return fail(PSE_ERR_INVALID, "pse_bond_forces: null bond object");
-    if (!pos) return fail(PSE_ERR_INVALID, "pse_bond_forces: null pos");
-    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_bond_forces: force and out8 are both null: nothing to compute");
-    pse_handle *h = b->h;
-    HIPCHK(hipSetDevice(h->device));
-    launch_bond_forces((const double4 *)pos, (int)b->n, (const unsigned *)b->row_off, (const uint2 *)b->entries, (const BondParam *)b->par,
-                       b->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, b->over, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) {
-    if (!b || !count) return fail(PSE_ERR_INVALID, "pse_bonds_overstretched: null argument");
-    pse_handle *h = b->h;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(count, b->over, sizeof *count, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, const unsigned *triples_host, const unsigned *types_host,
-                                 int ntypes, const int *kind_host, const double *k_host, const double *theta0_host, pse_angles **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_angles_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_angles_create: null handle");
-    TRY(angles_validate((unsigned)h->n_max, n, nangles, triples_host, types_host, ntypes, kind_host, k_host, theta0_host));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<int> off((size_t)n + 1);
-    std::vector<unsigned> ent((size_t)nangles * 12);
-    TRY(pse_host_angle_rows(n, nangles, triples_host, types_host, off.data(), ent.data()));
-    std::vector<AngleParam> par((size_t)ntypes);
-    for (int t = 0; t < ntypes; ++t) par[t] = AngleParam{k_host[t], theta0_host[t], std::cos(theta0_host[t]), (double)kind_host[t]};
-    return topology_create(h, "angles", n, nangles, ntypes, off, ent, par.data(), par.size() * sizeof(AngleParam), false, out);
-}
-extern "C" int pse_angles_destroy(pse_angles *a) { return topology_destroy(a); }
-
-// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
-extern "C" int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
-    if (!a) return fail(PSE_ERR_INVALID, "pse_angle_forces: null angle object");
-    if (!pos) return fail(PSE_ERR_INVALID, "pse_angle_forces: null pos");
-    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_angle_forces: force and out8 are both null: nothing to compute");
-    pse_handle *h = a->h;
-    HIPCHK(hipSetDevice(h->device));
-    launch_angle_forces((const double4 *)pos, (int)a->n, (const int *)a->row_off, (const uint4 *)a->entries, (const AngleParam *)a->par,
-                        a->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int pse_dihedrals_create(pse_handle *h, unsigned n, unsigned ndihedrals, const unsigned *quads_host, const unsigned *types_host,
-                                    int ntypes, const int *kind_host, const double *params_host, pse_dihedrals **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_dihedrals_create: null handle");
-    TRY(dihedrals_validate((unsigned)h->n_max, n, ndihedrals, quads_host, types_host, ntypes, kind_host, params_host));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<int> off((size_t)n + 1);
-    std::vector<unsigned> ent((size_t)ndihedrals * 20);
-    TRY(pse_host_dihedral_rows(n, ndihedrals, quads_host, types_host, off.data(), ent.data()));
-    std::vector<DihedralParam> par((size_t)ntypes);
-    for (int t = 0; t < ntypes; ++t) {
-        const double *p = params_host + 4 * (size_t)t;
-        // (d = +-1: the products with it are exact; mult >= 1 marks the harmonic kind, 0 the OPLS kind)
-        if (kind_host[t] == PSE_DIHEDRAL_HARMONIC) par[t] = DihedralParam{0.5 * p[0], p[1] * std::cos(p[3]), p[1] * std::sin(p[3]), 0.0, p[2], 0.0};
-        else par[t] = DihedralParam{p[0], p[1], p[2], p[3], 0.0, 0.0};
-    }
-    return topology_create(h, "dihedrals", n, ndihedrals, ntypes, off, ent, par.data(), par.size() * sizeof(DihedralParam), false, out);
-}
-extern "C" int pse_dihedrals_destroy(pse_dihedrals *d) { return topology_destroy(d); }
-
-// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
-extern "C" int pse_dihedral_forces(pse_dihedrals *d, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
-    if (!d) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null dihedral object");
-    if (!pos) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null pos");
-    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: force and out8 are both null: nothing to compute");
-    pse_handle *h = d->h;
-    HIPCHK(hipSetDevice(h->device));
-    launch_dihedral_forces((const double4 *)pos, (int)d->n, (const int *)d->row_off, (const uint4 *)d->entries,
-                           (const unsigned *)d->entries + 16 * (size_t)d->count, (const DihedralParam *)d->par, d->ntypes, h->dbox, accumulate,
-                           (double4 *)force, h->pv_rows, out8, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Pair exclusions (include/pse_amd.h): the rows of pse_host_exclusion_rows on the device, read by the _excl pair passes.
-extern "C" int pse_exclusions_create(pse_handle *h, unsigned n, unsigned npairs, const unsigned *pairs_host, pse_exclusions **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_exclusions_create: null handle");
-    TRY(exclusions_validate((unsigned)h->n_max, n, npairs, pairs_host));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<int> off((size_t)n + 1);
-    std::vector<unsigned> ent((size_t)npairs * 2);
-    TRY(pse_host_exclusion_rows(n, npairs, pairs_host, off.data(), ent.data()));
-    ent.resize((size_t)(unsigned)off[n]);   // duplicates are gone
-    return topology_create(h, "exclusions", n, (unsigned)off[n] / 2, 0, off, ent, nullptr, 0, false, out);
-}
-extern "C" int pse_exclusions_destroy(pse_exclusions *ex) { return topology_destroy(ex); }
-
-// Typed pair tables (include/pse_amd.h): the types, the concatenated tables and the per-pair-type words on the device, and the pass.
-extern "C" int pse_typed_table_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const int *width_host,
-                                      const double *rmin_host, const double *rmax_host, const double *tables_host, pse_typed_table **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_typed_table_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_typed_table_create: null handle");
-    TRY(typed_table_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, width_host, rmin_host, rmax_host, tables_host));
-    HIPCHK(hipSetDevice(h->device));
-    const int npt = ntypes * (ntypes + 1) / 2;
-    std::vector<int> base(npt);
-    std::vector<double> scale(npt), rmax2(npt);
-    int total = 0;
-    TRY(pse_host_typed_table_layout(ntypes, width_host, rmin_host, rmax_host, base.data(), scale.data(), rmax2.data(), &total));
-    std::vector<double> par((size_t)4 * npt);   // (rmin, rmax2), (scale, {base, width - 2}): an off pair type is all zeros
-    double rmax2_all = 0.0;
-    for (int p = 0; p < npt; ++p) {
-        if (width_host[p] == 0) continue;
-        const long long bw = (long long)(unsigned)base[p] | ((long long)(width_host[p] - 2) << 32);
-        par[4 * p] = rmin_host[p]; par[4 * p + 1] = rmax2[p]; par[4 * p + 2] = scale[p];
-        memcpy(&par[4 * p + 3], &bw, sizeof bw);
-        rmax2_all = std::max(rmax2_all, rmax2[p]);
-    }
-    std::vector<unsigned char> types(n);
-    for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
-    pse_typed_table *t = new pse_typed_table();
-    t->h = h; t->n = n; t->count = (unsigned)total; t->ntypes = ntypes; t->rmax2_all = rmax2_all;
-    hipError_t e = hipMalloc((void **)&t->types, n);
-    if (e == hipSuccess) e = hipMemcpy(t->types, types.data(), n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->type_s, (size_t)h->n_max);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->tables, (size_t)total * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(t->tables, tables_host, (size_t)total * 2 * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&t->par, par.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(t->par, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        delete t;
-        return fail(PSE_ERR_HIP, "pse_typed_table_create: copying %d table entries and %u types to the device failed: %s", total, n,
-                    hipGetErrorString(e));
-    }
-    h->topologies.push_back(t);
-    *out = t;
-    return 0;
-}
-extern "C" int pse_typed_table_destroy(pse_typed_table *t) { return topology_destroy(t); }
-extern "C" int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
-                                    int accumulate, double *out8, const pse_exclusions *ex) {
-    pse_handle *h = t ? t->h : nullptr;
-    TRY(pair_typed_validate(t, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, N, pos, force, out8, ex, ex ? ex->h : nullptr));
-    HIPCHK(hipSetDevice(h->device));
-    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
-    const PairTypedTables tt{t->types, t->type_s, t->tables, (const double *)t->par, t->n, t->ntypes, (int)t->count, t->rmax2_all};
-    launch_pair_table_typed(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, tt, accumulate, (double4 *)force, h->pv_rows, out8,
-                            h->stream, ex ? &er : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Pair-distance histograms (include/pse_amd.h): the types on the device, and the pass.  Queue-only: the sort, the type mirror, the
-// pass; nothing is read back, the counters are added to by the stream.
-extern "C" int pse_pair_hist_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int nbins, double rmin, double rmax,
-                                    pse_pair_hist **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_pair_hist_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_pair_hist_create: null handle");
-    TRY(pair_hist_create_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, n, types_host, ntypes, nbins, rmin, rmax));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
-    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
-    pse_pair_hist *g = new pse_pair_hist();
-    g->h = h; g->n = n; g->count = (unsigned)(ntypes * (ntypes + 1) / 2 * nbins); g->ntypes = ntypes;
-    g->nbins = nbins; g->rmin = rmin; g->rmax = rmax;
-    hipError_t e = hipMalloc((void **)&g->types, n);
-    if (e == hipSuccess) e = hipMemcpy(g->types, types.data(), n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->type_s, (size_t)h->n_max);
-    if (e != hipSuccess) {
-        delete g;
-        return fail(PSE_ERR_HIP, "pse_pair_hist_create: copying %u types to the device failed: %s", n, hipGetErrorString(e));
-    }
-    h->topologies.push_back(g);
-    *out = g;
-    return 0;
-}
-extern "C" int pse_pair_hist_destroy(pse_pair_hist *g) { return topology_destroy(g); }
-extern "C" int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned long long *counts,
-                                        const pse_exclusions *ex) {
-    pse_handle *h = g ? g->h : nullptr;
-    TRY(pair_hist_validate(g, h, h ? (unsigned)h->n_max : 0u, N, pos, counts, ex, ex ? ex->h : nullptr));
-    HIPCHK(hipSetDevice(h->device));
-    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
-    const PairHist ph{g->types, g->type_s, g->n, g->ntypes, g->nbins, g->rmin, g->rmax};
-    launch_pair_hist(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, ph, counts, h->stream, ex ? &er : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Static structure factors (include/pse_amd.h): the types, the plan of the modes and the workspace on the device, and the pass.
-// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
-extern "C" int pse_structure_factor_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, unsigned nk, const int *modes_host,
-                                           pse_structure_factor **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_structure_factor_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_structure_factor_create: null handle");
-    TRY(structure_factor_create_validate((unsigned)h->n_max, n, types_host, ntypes, nk, modes_host));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
-    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
-    std::vector<unsigned> perm, uoff;
-    std::vector<int> segs;
-    structure_factor_plan(nk, modes_host, perm, uoff, segs);
-    pse_structure_factor *f = new pse_structure_factor();
-    f->h = h; f->n = n; f->count = nk; f->ntypes = ntypes;
-    f->nseg = (int)(segs.size() / 8);
-    for (size_t g = 0; g < segs.size(); g += 8) f->nlong += segs[g + 3] > SF_SHORT;
-    f->nu = (int)uoff.size() - 1; f->span = sf_span((unsigned)h->n_max, ntypes, (int)nk);
-    const size_t work = sf_workspace((unsigned)h->n_max, ntypes, (int)nk) * sizeof(double2);
-    hipError_t e = hipMalloc((void **)&f->types, n);
-    if (e == hipSuccess) e = hipMemcpy(f->types, types.data(), n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->segs, segs.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(f->segs, segs.data(), segs.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->perm, (size_t)nk * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemcpy(f->perm, perm.data(), (size_t)nk * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->uoff, uoff.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemcpy(f->uoff, uoff.data(), uoff.size() * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->rows, work);
-    if (e != hipSuccess) {
-        delete f;
-        return fail(PSE_ERR_HIP, "pse_structure_factor_create: %u types, %u modes and a workspace of %zu bytes on the device failed: %s", n, nk,
-                    work, hipGetErrorString(e));
-    }
-    h->topologies.push_back(f);
-    *out = f;
-    return 0;
-}
-extern "C" int pse_structure_factor_destroy(pse_structure_factor *f) { return topology_destroy(f); }
-extern "C" int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *pos, const unsigned *group, unsigned N, double *rho,
-                                               double *sums) {
-    pse_handle *h = f ? f->h : nullptr;
-    TRY(structure_factor_validate(f, h ? (unsigned)h->n_max : 0u, N, pos, rho, sums));
-    HIPCHK(hipSetDevice(h->device));
-    const StructureFactor sf{f->types, f->n, f->ntypes, f->segs, f->nseg, f->nlong, f->perm, f->uoff, f->nu, (int)f->count, f->rows, f->span};
-    launch_structure_factor((const double4 *)pos, group, (int)N, h->dbox, sf, rho, sums, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Displacement moments (include/pse_amd.h): the types, the slots of unwrapped positions and the workspace on the device, and the
-// three passes.  Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
-extern "C" int pse_msd_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int norigins, pse_msd **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_msd_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_msd_create: null handle");
-    TRY(msd_create_validate((unsigned)h->n_max, n, types_host, ntypes, norigins));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
-    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
-    pse_msd *m = new pse_msd();
-    m->h = h; m->n = n; m->count = (unsigned)norigins; m->ntypes = ntypes;
-    const size_t planes = (size_t)norigins * 3 * (size_t)h->n_max * sizeof(double);
-    const size_t work = msd_workspace((unsigned)h->n_max, ntypes) * sizeof(double);
-    hipError_t e = hipMalloc((void **)&m->types, n);
-    if (e == hipSuccess) e = hipMemcpy(m->types, types.data(), n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->planes, planes);
-    if (e == hipSuccess) e = hipMemset(m->planes, 0, planes);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->part, work);
-    if (e != hipSuccess) {
-        delete m;
-        return fail(PSE_ERR_HIP, "pse_msd_create: %u types, %d origins of %zu bytes and a workspace of %zu bytes on the device failed: %s", n,
-                    norigins, planes / (size_t)norigins, work, hipGetErrorString(e));
-    }
-    h->topologies.push_back(m);
-    *out = m;
-    return 0;
-}
-extern "C" int pse_msd_destroy(pse_msd *m) { return topology_destroy(m); }
-static MsdOrigins msd_origins(const pse_msd *m) { return MsdOrigins{m->types, m->n, m->ntypes, m->planes, (size_t)m->h->n_max, m->part}; }
-extern "C" int pse_msd_store(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain) {
-    pse_handle *h = m ? m->h : nullptr;
-    TRY(msd_slot_validate("pse_msd_store", m, m ? (int)m->count : 0, h ? (unsigned)h->n_max : 0u, slot, N, pos, image, strain));
-    HIPCHK(hipSetDevice(h->device));
-    launch_msd_store((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
-                     msd_origins(m), slot, nullptr, h->stream);
-    HIPCHK(hipGetLastError());
-    m->stored |= 1ull << slot;
-    return 0;
-}
-extern "C" int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N,
-                                    double strain, pse_double4 *out) {
-    pse_handle *h = m ? m->h : nullptr;
-    TRY(msd_slot_validate("pse_msd_displacement", m, m ? (int)m->count : 0, h ? (unsigned)h->n_max : 0u, slot, N, pos, image, strain));
-    TRY(msd_displacement_validate(m->stored, slot, out));
-    HIPCHK(hipSetDevice(h->device));
-    launch_msd_store((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
-                     msd_origins(m), slot, (double4 *)out, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-extern "C" int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
-                                  int npairs, const int *slots_host, const int *rows_host, int nrows, double *sums) {
-    pse_handle *h = m ? m->h : nullptr;
-    TRY(msd_accumulate_validate(m, m ? (int)m->count : 0, m ? m->stored : 0ull, h ? (unsigned)h->n_max : 0u, N, pos, image, strain, npairs,
-                                slots_host, rows_host, nrows, sums));
-    HIPCHK(hipSetDevice(h->device));
-    MsdPairs pairs{};
-    pairs.npairs = npairs;
-    for (int q = 0; q < npairs; ++q) { pairs.slot[q] = (unsigned char)slots_host[q]; pairs.row[q] = rows_host[q]; }
-    launch_msd_accumulate((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
-                          msd_origins(m), pairs, sums, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Cluster analysis (include/pse_amd.h): the types and the link distances on the device, and the pass.  Queue-only: the sort, the type
-// mirror and the four kernels of the union-find; nothing is read back.
-extern "C" int pse_clusters_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const double *rlink_host,
-                                   pse_clusters **out) {
-    if (!out) return fail(PSE_ERR_INVALID, "pse_clusters_create: null out");
-    *out = nullptr;
-    if (!h) return fail(PSE_ERR_INVALID, "pse_clusters_create: null handle");
-    TRY(clusters_create_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, rlink_host));
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<unsigned char> types(n, (unsigned char)0);   // (types_host == null: one type)
-    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
-    const int npt = ntypes * (ntypes + 1) / 2;
-    std::vector<double> rl2((size_t)npt);
-    pse_clusters *g = new pse_clusters();
-    g->h = h; g->n = n; g->count = (unsigned)npt; g->ntypes = ntypes;
-    for (int p = 0; p < npt; ++p) { rl2[p] = rlink_host[p] * rlink_host[p]; g->rl2_all = std::max(g->rl2_all, rl2[p]); }
-    const size_t nwork = 3 * (size_t)h->n_max + 1;
-    hipError_t e = hipMalloc((void **)&g->types, n);
-    if (e == hipSuccess) e = hipMemcpy(g->types, types.data(), n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->type_s, (size_t)h->n_max);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->rlink2, (size_t)npt * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(g->rlink2, rl2.data(), (size_t)npt * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->work, nwork * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(g->work, 0, nwork * sizeof(unsigned));
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memset may return early)
-    if (e != hipSuccess) {
-        delete g;
-        return fail(PSE_ERR_HIP, "pse_clusters_create: %u types and a workspace of %zu words on the device failed: %s", n, nwork, hipGetErrorString(e));
-    }
-    h->topologies.push_back(g);
-    *out = g;
-    return 0;
-}
-extern "C" int pse_clusters_destroy(pse_clusters *g) { return topology_destroy(g); }
-extern "C" int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *label, unsigned *size,
-                                  unsigned long long *stats, unsigned long long *hist, unsigned nhist, const pse_exclusions *ex) {
-    pse_handle *h = g ? g->h : nullptr;
-    TRY(clusters_label_validate(g, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, g ? g->known_status : 0u, N, pos, label, size, stats, hist,
-                                nhist, ex, ex ? ex->h : nullptr));
-    HIPCHK(hipSetDevice(h->device));
-    TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true));
-    const PairExclusions er = ex ? excl_rows(ex) : PairExclusions{};
-    const size_t nm = (size_t)h->n_max;
-    const ClusterLinks cl{g->types, g->type_s, g->n, g->ntypes, g->rlink2, g->rl2_all, g->work, g->work + nm, g->work + 2 * nm, g->work + 3 * nm};
-    launch_clusters(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, cl, label, size, stats, hist, nhist, h->stream, ex ? &er : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-extern "C" int pse_clusters_status(pse_clusters *g, unsigned *status) {
-    if (!g) return fail(PSE_ERR_INVALID, "pse_clusters_status: null cluster object");
-    if (!status) return fail(PSE_ERR_INVALID, "pse_clusters_status: null status");
-    pse_handle *h = g->h;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(&g->known_status, g->work + 3 * (size_t)h->n_max, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *status = g->known_status;
     return 0;
 }
 

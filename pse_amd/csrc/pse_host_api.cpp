@@ -189,6 +189,22 @@ int pair_excl_validate(const char *who, const void *ex, const void *ex_handle, c
     return 0;
 }
 
+// What the create validators of the typed objects (typed tables, histograms, structure factors, displacement origins, clusters) share,
+// under the name `who` of the entry point: n and, with `with_ntypes`, ntypes ...
+static int sizes_in_range(const char *who, unsigned n_max, unsigned n, int ntypes, bool with_ntypes = true) {
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (with_ntypes && (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES))
+        return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    return 0;
+}
+// ... and the type of every particle (types null: one type, nothing to check)
+static int types_in_range(const char *who, unsigned n, const unsigned *types, int ntypes) {
+    if (types)
+        for (unsigned i = 0; i < n; ++i)
+            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    return 0;
+}
+
 // What pse_host_typed_table_layout computes and refuses, under the name `who` of the entry point that asks.
 static int typed_layout(const char *who, int ntypes, const int *width, const double *rmin, const double *rmax, int *base, double *scale,
                         double *rmax2, int *total) {
@@ -227,11 +243,10 @@ int typed_table_validate(double rcut, unsigned n_max, unsigned n, const unsigned
     const char *who = "pse_typed_table_create";
     if (!types) return fail(PSE_ERR_INVALID, "%s: null types_host", who);
     if (!tables) return fail(PSE_ERR_INVALID, "%s: null tables_host", who);
-    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (int rc = sizes_in_range(who, n_max, n, ntypes, false)) return rc;   // (ntypes: behind the null arrays, in typed_layout)
     int total = 0;
     if (int rc = typed_layout(who, ntypes, width, rmin, rmax, nullptr, nullptr, nullptr, &total)) return rc;
-    for (unsigned i = 0; i < n; ++i)
-        if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    if (int rc = types_in_range(who, n, types, ntypes)) return rc;
     for (int p = 0; p < ntypes * (ntypes + 1) / 2; ++p)
         if (width[p] != 0 && rmax[p] > rcut)
             return fail(PSE_ERR_INVALID, "%s: pair type %d: table range rmax = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic "
@@ -257,8 +272,7 @@ int pair_typed_validate(const void *t, const void *t_handle, unsigned n_max, int
 int pair_hist_create_validate(double rcut, unsigned n_max, int n_slabs, unsigned n, const unsigned *types, int ntypes, int nbins, double rmin,
                               double rmax) {
     const char *who = "pse_pair_hist_create";
-    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
-    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (int rc = sizes_in_range(who, n_max, n, ntypes)) return rc;
     if (nbins < 1) return fail(PSE_ERR_INVALID, "%s: nbins = %d, need at least one bin", who, nbins);
     const long long npt = ntypes * (ntypes + 1) / 2;
     if (npt * nbins > PAIR_HIST_MAX_COUNTERS)
@@ -273,9 +287,7 @@ int pair_hist_create_validate(double rcut, unsigned n_max, int n_slabs, unsigned
     if (n_slabs > 1)
         return fail(PSE_ERR_INVALID, "%s: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the counts would be partial", who,
                     n_slabs);
-    if (types)
-        for (unsigned i = 0; i < n; ++i)
-            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    if (int rc = types_in_range(who, n, types, ntypes)) return rc;
     return 0;
 }
 
@@ -293,17 +305,14 @@ int pair_hist_validate(const void *g, const void *g_handle, unsigned n_max, unsi
 
 int structure_factor_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes) {
     const char *who = "pse_structure_factor_create";
-    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
-    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (int rc = sizes_in_range(who, n_max, n, ntypes)) return rc;
     if (nk == 0 || nk > (unsigned)SF_MAX_MODES) return fail(PSE_ERR_INVALID, "%s: nk = %u outside [1, %d]", who, nk, SF_MAX_MODES);
     if (!modes) return fail(PSE_ERR_INVALID, "%s: null modes_host", who);
     for (unsigned q = 0; q < nk; ++q)
         for (int c = 0; c < 3; ++c)
             if (modes[3 * (size_t)q + c] > SF_MAX_INDEX || modes[3 * (size_t)q + c] < -SF_MAX_INDEX)
                 return fail(PSE_ERR_INVALID, "%s: mode %u has the index m%c = %d beyond +-%d", who, q, "xyz"[c], modes[3 * (size_t)q + c], SF_MAX_INDEX);
-    if (types)
-        for (unsigned i = 0; i < n; ++i)
-            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    if (int rc = types_in_range(who, n, types, ntypes)) return rc;
     return 0;
 }
 
@@ -320,12 +329,9 @@ int structure_factor_validate(const void *f, unsigned n_max, unsigned N, const v
 
 int msd_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, int norigins) {
     const char *who = "pse_msd_create";
-    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
-    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (int rc = sizes_in_range(who, n_max, n, ntypes)) return rc;
     if (norigins < 1 || norigins > MSD_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: norigins = %d outside [1, %d]", who, norigins, MSD_MAX_ORIGINS);
-    if (types)
-        for (unsigned i = 0; i < n; ++i)
-            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    if (int rc = types_in_range(who, n, types, ntypes)) return rc;
     return 0;
 }
 
@@ -377,8 +383,7 @@ int msd_accumulate_validate(const void *m, int norigins, unsigned long long stor
 
 int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rlink) {
     const char *who = "pse_clusters_create";
-    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
-    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (int rc = sizes_in_range(who, n_max, n, ntypes)) return rc;
     if (!rlink) return fail(PSE_ERR_INVALID, "%s: null rlink_host", who);
     const int npt = ntypes * (ntypes + 1) / 2;
     bool on = false;
@@ -391,9 +396,7 @@ int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsi
         on = on || rlink[p] > 0.0;
     }
     if (!on) return fail(PSE_ERR_INVALID, "%s: every pair type is off (rlink = 0): nothing could be linked", who);
-    if (types)
-        for (unsigned i = 0; i < n; ++i)
-            if (types[i] >= (unsigned)ntypes) return fail(PSE_ERR_INVALID, "%s: particle %u has type %u >= ntypes = %d", who, i, types[i], ntypes);
+    if (int rc = types_in_range(who, n, types, ntypes)) return rc;
     return 0;
 }
 

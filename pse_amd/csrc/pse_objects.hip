@@ -1,0 +1,479 @@
+// The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
+// typed table, histogram, clusters), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors and displacement
+// moments.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, the objects own their arrays through DeviceObject
+// (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "pse_handle.h"
+#include "pse_forces.h"
+
+// A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
+// and, for bonds, the counter of overstretched FENE bonds.
+struct Topology : DeviceObject {
+    unsigned n = 0, count = 0;              // particles; bonds, angles or dihedrals
+    int ntypes = 0;
+    int *row_off = nullptr;                 // n + 1 (bonds and exclusions read them as unsigned, angles and dihedrals as int)
+    unsigned *entries = nullptr;            // bonds: 2 count x uint2 (partner, type); angles: 3 count x uint4 (i, j, k, type), j the vertex, i < k;
+                                            // dihedrals: 4 count x uint4 (i, j, k, l), i < l, then 4 count x unsigned types
+    void *par = nullptr;                    // ntypes x BondParam, AngleParam or DihedralParam
+    unsigned long long *over = nullptr;     // bonds: FENE bonds seen at r >= r0 since creation
+};
+struct pse_bonds : Topology {};
+struct pse_angles : Topology {};
+struct pse_dihedrals : Topology {};
+struct pse_exclusions : Topology {};   // entries: the partners, one unsigned each (pse_host_exclusion_rows); no parameters
+// The other objects hold the struct that their launches take (pse_forces.h, which documents the arrays), filled once at creation, and
+// the host-only words that the entry points keep about them.
+struct pse_typed_table : DeviceObject { PairTypedTables tt{}; };
+struct pse_pair_hist : DeviceObject { PairHist ph{}; };
+struct pse_clusters : DeviceObject {
+    ClusterLinks cl{};
+    unsigned known_status = 0u;             // the last word pse_clusters_status read
+};
+struct pse_structure_factor : DeviceObject { StructureFactor sf{}; };
+struct pse_msd : DeviceObject {
+    MsdOrigins mo{};
+    int norigins = 0;
+    unsigned long long stored = 0ull;       // bit s = slot s holds positions
+};
+
+// ---- what every pse_*_create shares (`who`: its name) --------------------------------------------------------------------------------
+// In front of the validator: a null `out` and a null handle, refused in that order.
+template <class T>
+static int create_begin(const char *who, pse_handle *h, T **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "%s: null out", who);
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "%s: null handle", who);
+    return 0;
+}
+// Behind the put()s of the new object `t`, `e` what the last of them returned (the first failure, if there was one): the object goes
+// again, with whatever it had placed, or it is adopted by the handle and handed out.
+template <class T>
+static int create_end(const char *who, pse_handle *h, T *t, hipError_t e, T **out) {
+    // a hipMemset may return before the memory is zero, and it ran on the null stream, which a non-blocking h->stream (pse_set_stream)
+    // does not wait for: the object's first pass must not overtake it
+    if (e == hipSuccess && t->zeroed) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        const size_t bytes = t->bytes;
+        delete t;
+        return fail(PSE_ERR_HIP, "%s: placing %zu bytes on the device failed: %s", who, bytes, hipGetErrorString(e));
+    }
+    h->topologies.push_back(t);
+    *out = t;
+    return 0;
+}
+// The types of n particles as the device holds them, one byte each; types_host null: one type.
+static std::vector<unsigned char> type_bytes(const unsigned *types_host, unsigned n) {
+    std::vector<unsigned char> types(n, (unsigned char)0);
+    if (types_host) for (unsigned i = 0; i < n; ++i) types[i] = (unsigned char)types_host[i];
+    return types;
+}
+static int object_destroy(DeviceObject *t) {
+    if (!t) return 0;
+    pse_handle *h = t->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));   // a queued pass may still read the rows
+    h->topologies.erase(std::remove(h->topologies.begin(), h->topologies.end(), t), h->topologies.end());
+    delete t;
+    return 0;
+}
+
+// What the five passes over the cell list share behind their validators: the device, the sort with the cell list, and the rows of an
+// optional exclusion object as the launches take them (rows == null: a plain pass).
+struct CellPass {
+    PairExclusions er{};
+    const PairExclusions *rows = nullptr;
+    int begin(pse_handle *h, const pse_double4 *pos, const unsigned *group, unsigned N, const pse_exclusions *ex) {
+        HIPCHK(hipSetDevice(h->device));
+        TRY(prepare(h, (const double4 *)pos, nullptr, group, (int)N, false, true, PrepExtra{false, 0}, true));
+        if (ex) { er = PairExclusions{(const unsigned *)ex->row_off, ex->entries, ex->n}; rows = &er; }
+        return 0;
+    }
+};
+
+// pse_pair_repulsion and pse_pair_repulsion_virial (include/pse_amd.h): the force pass, and the same pass with the pair observables of
+// the repulsion -- energy, virial and pair count in eight device doubles.  Queue-only: nothing is read back, out8 is written by the stream.
+// `excl`: the name of the entry point that takes an exclusion object `ex`, checked behind the plain pass's own arguments; null: a plain pass.
+static int pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, double k, double sigma,
+                          int accumulate, bool virial, double *out8, const char *excl = nullptr, const pse_exclusions *ex = nullptr) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    TRY(pair_repulsion_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, virial, out8, sigma));
+    if (excl) TRY(pair_excl_validate(excl, ex, ex ? ex->h : nullptr, h));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    launch_pair_repulsion(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, k, sigma, accumulate, (double4 *)force, h->pv_rows, out8,
+                          h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int pse_pair_repulsion(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                  double k, double sigma, int accumulate) {
+    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, false, nullptr);
+}
+extern "C" int pse_pair_repulsion_virial(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                         double k, double sigma, int accumulate, double *out8) {
+    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, true, out8);
+}
+extern "C" int pse_pair_repulsion_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                       double k, double sigma, int accumulate, double *out8, const pse_exclusions *ex) {
+    return pair_repulsion(h, pos, force, group, N, k, sigma, accumulate, out8 != nullptr, out8, "pse_pair_repulsion_excl", ex);
+}
+
+// Tabulated pair potential on the same cell list (include/pse_amd.h), with or without the eight observables.  Queue-only wherever
+// pse_pair_repulsion is; the table is read by the stream.
+static int pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N, const double *table,
+                      int width, double rmin, double rmax, int accumulate, double *out8, const char *excl, const pse_exclusions *ex) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    TRY(pair_table_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, N, pos, force, table, width, rmin, rmax, out8));
+    if (excl) TRY(pair_excl_validate(excl, ex, ex ? ex->h : nullptr, h));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    launch_pair_table(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, table, width, rmin, rmax, accumulate, (double4 *)force,
+                      h->pv_rows, out8, h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int pse_pair_table(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                              const double *table, int width, double rmin, double rmax, int accumulate, double *out8) {
+    return pair_table(h, pos, force, group, N, table, width, rmin, rmax, accumulate, out8, nullptr, nullptr);
+}
+extern "C" int pse_pair_table_excl(pse_handle *h, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                   const double *table, int width, double rmin, double rmax, int accumulate, double *out8,
+                                   const pse_exclusions *ex) {
+    return pair_table(h, pos, force, group, N, table, width, rmin, rmax, accumulate, out8, "pse_pair_table_excl", ex);
+}
+
+// ---- bonded forces, angle forces, dihedral forces and pair exclusions (include/pse_amd.h) ------------------------------------------
+// The device copy of a topology: the host rows `off` and `ent`, the ntypes parameter sets `par` (none: pair exclusions) and, with
+// `counter`, a zeroed counter.
+template <class T, class Param>
+static int topology_create(const char *who, pse_handle *h, unsigned n, unsigned count, const std::vector<int> &off,
+                           const std::vector<unsigned> &ent, const std::vector<Param> &par, bool counter, T **out) {
+    T *t = new T();
+    t->h = h; t->n = n; t->count = count; t->ntypes = (int)par.size();
+    Param *dpar = nullptr;
+    hipError_t e = t->put(&t->row_off, off.data(), off.size());
+    e = t->put(&t->entries, ent.data(), ent.size());
+    if (!par.empty()) e = t->put(&dpar, par.data(), par.size());
+    if (counter) e = t->put(&t->over, nullptr, 1, true);
+    t->par = dpar;
+    return create_end(who, h, t, e, out);
+}
+
+extern "C" int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
+                                const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {
+    TRY(create_begin("pse_bonds_create", h, out));
+    TRY(bonds_validate((unsigned)h->n_max, n, nbonds, pairs_host, types_host, ntypes, kind_host, k_host, r0_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)nbonds * 4);
+    TRY(pse_host_bond_rows(n, nbonds, pairs_host, types_host, off.data(), ent.data()));
+    std::vector<BondParam> par((size_t)ntypes);
+    for (int t = 0; t < ntypes; ++t)
+        par[t] = BondParam{k_host[t], r0_host[t], r0_host[t] > 0.0 ? 1.0 / (r0_host[t] * r0_host[t]) : 0.0, (double)kind_host[t]};
+    return topology_create("pse_bonds_create", h, n, nbonds, off, ent, par, true, out);
+}
+extern "C" int pse_bonds_destroy(pse_bonds *b) { return object_destroy(b); }
+
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_bond_forces(pse_bonds *b, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
+    if (!b) return fail(PSE_ERR_INVALID, "pse_bond_forces: null bond object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_bond_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_bond_forces: force and out8 are both null: nothing to compute");
+    pse_handle *h = b->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_bond_forces((const double4 *)pos, (int)b->n, (const unsigned *)b->row_off, (const uint2 *)b->entries, (const BondParam *)b->par,
+                       b->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, b->over, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pse_bonds_overstretched(pse_bonds *b, unsigned long long *count) {
+    if (!b || !count) return fail(PSE_ERR_INVALID, "pse_bonds_overstretched: null argument");
+    pse_handle *h = b->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(count, b->over, sizeof *count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int pse_angles_create(pse_handle *h, unsigned n, unsigned nangles, const unsigned *triples_host, const unsigned *types_host,
+                                 int ntypes, const int *kind_host, const double *k_host, const double *theta0_host, pse_angles **out) {
+    TRY(create_begin("pse_angles_create", h, out));
+    TRY(angles_validate((unsigned)h->n_max, n, nangles, triples_host, types_host, ntypes, kind_host, k_host, theta0_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)nangles * 12);
+    TRY(pse_host_angle_rows(n, nangles, triples_host, types_host, off.data(), ent.data()));
+    std::vector<AngleParam> par((size_t)ntypes);
+    for (int t = 0; t < ntypes; ++t) par[t] = AngleParam{k_host[t], theta0_host[t], std::cos(theta0_host[t]), (double)kind_host[t]};
+    return topology_create("pse_angles_create", h, n, nangles, off, ent, par, false, out);
+}
+extern "C" int pse_angles_destroy(pse_angles *a) { return object_destroy(a); }
+
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_angle_forces(pse_angles *a, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
+    if (!a) return fail(PSE_ERR_INVALID, "pse_angle_forces: null angle object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_angle_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_angle_forces: force and out8 are both null: nothing to compute");
+    pse_handle *h = a->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_angle_forces((const double4 *)pos, (int)a->n, a->row_off, (const uint4 *)a->entries, (const AngleParam *)a->par,
+                        a->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pse_dihedrals_create(pse_handle *h, unsigned n, unsigned ndihedrals, const unsigned *quads_host, const unsigned *types_host,
+                                    int ntypes, const int *kind_host, const double *params_host, pse_dihedrals **out) {
+    TRY(create_begin("pse_dihedrals_create", h, out));
+    TRY(dihedrals_validate((unsigned)h->n_max, n, ndihedrals, quads_host, types_host, ntypes, kind_host, params_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)ndihedrals * 20);
+    TRY(pse_host_dihedral_rows(n, ndihedrals, quads_host, types_host, off.data(), ent.data()));
+    std::vector<DihedralParam> par((size_t)ntypes);
+    for (int t = 0; t < ntypes; ++t) {
+        const double *p = params_host + 4 * (size_t)t;
+        // (d = +-1: the products with it are exact; mult >= 1 marks the harmonic kind, 0 the OPLS kind)
+        if (kind_host[t] == PSE_DIHEDRAL_HARMONIC) par[t] = DihedralParam{0.5 * p[0], p[1] * std::cos(p[3]), p[1] * std::sin(p[3]), 0.0, p[2], 0.0};
+        else par[t] = DihedralParam{p[0], p[1], p[2], p[3], 0.0, 0.0};
+    }
+    return topology_create("pse_dihedrals_create", h, n, ndihedrals, off, ent, par, false, out);
+}
+extern "C" int pse_dihedrals_destroy(pse_dihedrals *d) { return object_destroy(d); }
+
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_dihedral_forces(pse_dihedrals *d, const pse_double4 *pos, pse_double4 *force, int accumulate, double *out8) {
+    if (!d) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null dihedral object");
+    if (!pos) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: null pos");
+    if (!force && !out8) return fail(PSE_ERR_INVALID, "pse_dihedral_forces: force and out8 are both null: nothing to compute");
+    pse_handle *h = d->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_dihedral_forces((const double4 *)pos, (int)d->n, d->row_off, (const uint4 *)d->entries, d->entries + 16 * (size_t)d->count,
+                           (const DihedralParam *)d->par, d->ntypes, h->dbox, accumulate, (double4 *)force, h->pv_rows, out8, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Pair exclusions (include/pse_amd.h): the rows of pse_host_exclusion_rows on the device, read by the _excl pair passes.
+extern "C" int pse_exclusions_create(pse_handle *h, unsigned n, unsigned npairs, const unsigned *pairs_host, pse_exclusions **out) {
+    TRY(create_begin("pse_exclusions_create", h, out));
+    TRY(exclusions_validate((unsigned)h->n_max, n, npairs, pairs_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<int> off((size_t)n + 1);
+    std::vector<unsigned> ent((size_t)npairs * 2);
+    TRY(pse_host_exclusion_rows(n, npairs, pairs_host, off.data(), ent.data()));
+    ent.resize((size_t)(unsigned)off[n]);   // duplicates are gone
+    return topology_create("pse_exclusions_create", h, n, (unsigned)off[n] / 2, off, ent, std::vector<char>(), false, out);
+}
+extern "C" int pse_exclusions_destroy(pse_exclusions *ex) { return object_destroy(ex); }
+
+// Typed pair tables (include/pse_amd.h): the types, the concatenated tables and the per-pair-type words on the device, and the pass.
+extern "C" int pse_typed_table_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const int *width_host,
+                                      const double *rmin_host, const double *rmax_host, const double *tables_host, pse_typed_table **out) {
+    const char *who = "pse_typed_table_create";
+    TRY(create_begin(who, h, out));
+    TRY(typed_table_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, width_host, rmin_host, rmax_host, tables_host));
+    HIPCHK(hipSetDevice(h->device));
+    const int npt = ntypes * (ntypes + 1) / 2;
+    std::vector<int> base(npt);
+    std::vector<double> scale(npt), rmax2(npt);
+    int total = 0;
+    TRY(pse_host_typed_table_layout(ntypes, width_host, rmin_host, rmax_host, base.data(), scale.data(), rmax2.data(), &total));
+    pse_typed_table *t = new pse_typed_table();
+    t->h = h;
+    PairTypedTables &tt = t->tt;
+    tt.n = n; tt.ntypes = ntypes; tt.total = total;
+    std::vector<double> par((size_t)4 * npt);   // (rmin, rmax2), (scale, {base, width - 2}): an off pair type is all zeros
+    for (int p = 0; p < npt; ++p) {
+        if (width_host[p] == 0) continue;
+        const long long bw = (long long)(unsigned)base[p] | ((long long)(width_host[p] - 2) << 32);
+        par[4 * p] = rmin_host[p]; par[4 * p + 1] = rmax2[p]; par[4 * p + 2] = scale[p];
+        memcpy(&par[4 * p + 3], &bw, sizeof bw);
+        tt.rmax2_all = std::max(tt.rmax2_all, rmax2[p]);
+    }
+    hipError_t e = t->put(&tt.types, type_bytes(types_host, n).data(), n);
+    e = t->put(&tt.type_s, nullptr, (size_t)h->n_max);
+    e = t->put(&tt.tables, tables_host, (size_t)total * 2);
+    e = t->put(&tt.par, par.data(), par.size());
+    return create_end(who, h, t, e, out);
+}
+extern "C" int pse_typed_table_destroy(pse_typed_table *t) { return object_destroy(t); }
+extern "C" int pse_pair_table_typed(pse_typed_table *t, const pse_double4 *pos, pse_double4 *force, const unsigned *group, unsigned N,
+                                    int accumulate, double *out8, const pse_exclusions *ex) {
+    pse_handle *h = t ? t->h : nullptr;
+    TRY(pair_typed_validate(t, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, N, pos, force, out8, ex, ex ? ex->h : nullptr));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    launch_pair_table_typed(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, t->tt, accumulate, (double4 *)force, h->pv_rows, out8,
+                            h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Pair-distance histograms (include/pse_amd.h): the types on the device, and the pass.  Queue-only: the sort, the type mirror, the
+// pass; nothing is read back, the counters are added to by the stream.
+extern "C" int pse_pair_hist_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int nbins, double rmin, double rmax,
+                                    pse_pair_hist **out) {
+    const char *who = "pse_pair_hist_create";
+    TRY(create_begin(who, h, out));
+    TRY(pair_hist_create_validate(h->d.rcut, (unsigned)h->n_max, h->n_slabs, n, types_host, ntypes, nbins, rmin, rmax));
+    HIPCHK(hipSetDevice(h->device));
+    pse_pair_hist *g = new pse_pair_hist();
+    g->h = h;
+    g->ph.n = n; g->ph.ntypes = ntypes; g->ph.nbins = nbins; g->ph.rmin = rmin; g->ph.rmax = rmax;
+    hipError_t e = g->put(&g->ph.types, type_bytes(types_host, n).data(), n);
+    e = g->put(&g->ph.type_s, nullptr, (size_t)h->n_max);
+    return create_end(who, h, g, e, out);
+}
+extern "C" int pse_pair_hist_destroy(pse_pair_hist *g) { return object_destroy(g); }
+extern "C" int pse_pair_hist_accumulate(pse_pair_hist *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned long long *counts,
+                                        const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;
+    TRY(pair_hist_validate(g, h, h ? (unsigned)h->n_max : 0u, N, pos, counts, ex, ex ? ex->h : nullptr));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    launch_pair_hist(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, g->ph, counts, h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Static structure factors (include/pse_amd.h): the types, the plan of the modes and the workspace on the device, and the pass.
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
+extern "C" int pse_structure_factor_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, unsigned nk, const int *modes_host,
+                                           pse_structure_factor **out) {
+    const char *who = "pse_structure_factor_create";
+    TRY(create_begin(who, h, out));
+    TRY(structure_factor_create_validate((unsigned)h->n_max, n, types_host, ntypes, nk, modes_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<unsigned> perm, uoff;
+    std::vector<int> segs;
+    structure_factor_plan(nk, modes_host, perm, uoff, segs);
+    pse_structure_factor *f = new pse_structure_factor();
+    f->h = h;
+    StructureFactor &sf = f->sf;
+    sf.n = n; sf.ntypes = ntypes; sf.nk = (int)nk;
+    sf.nseg = (int)(segs.size() / 8);
+    for (size_t g = 0; g < segs.size(); g += 8) sf.nlong += segs[g + 3] > SF_SHORT;
+    sf.nu = (int)uoff.size() - 1; sf.span = sf_span((unsigned)h->n_max, ntypes, (int)nk);
+    hipError_t e = f->put(&sf.types, type_bytes(types_host, n).data(), n);
+    e = f->put(&sf.segs, (const int4 *)segs.data(), segs.size() / 4);
+    e = f->put(&sf.perm, perm.data(), perm.size());
+    e = f->put(&sf.uoff, uoff.data(), uoff.size());
+    e = f->put(&sf.rows, nullptr, sf_workspace((unsigned)h->n_max, ntypes, (int)nk));
+    return create_end(who, h, f, e, out);
+}
+extern "C" int pse_structure_factor_destroy(pse_structure_factor *f) { return object_destroy(f); }
+extern "C" int pse_structure_factor_accumulate(pse_structure_factor *f, const pse_double4 *pos, const unsigned *group, unsigned N, double *rho,
+                                               double *sums) {
+    pse_handle *h = f ? f->h : nullptr;
+    TRY(structure_factor_validate(f, h ? (unsigned)h->n_max : 0u, N, pos, rho, sums));
+    HIPCHK(hipSetDevice(h->device));
+    launch_structure_factor((const double4 *)pos, group, (int)N, h->dbox, f->sf, rho, sums, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Displacement moments (include/pse_amd.h): the types, the slots of unwrapped positions and the workspace on the device, and the
+// three passes.  Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
+extern "C" int pse_msd_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, int norigins, pse_msd **out) {
+    const char *who = "pse_msd_create";
+    TRY(create_begin(who, h, out));
+    TRY(msd_create_validate((unsigned)h->n_max, n, types_host, ntypes, norigins));
+    HIPCHK(hipSetDevice(h->device));
+    pse_msd *m = new pse_msd();
+    m->h = h;
+    m->norigins = norigins;
+    m->mo.n = n; m->mo.ntypes = ntypes; m->mo.n_max = (size_t)h->n_max;
+    hipError_t e = m->put(&m->mo.types, type_bytes(types_host, n).data(), n);
+    e = m->put(&m->mo.planes, nullptr, (size_t)norigins * 3 * m->mo.n_max, true);
+    e = m->put(&m->mo.part, nullptr, msd_workspace((unsigned)h->n_max, ntypes));
+    return create_end(who, h, m, e, out);
+}
+extern "C" int pse_msd_destroy(pse_msd *m) { return object_destroy(m); }
+extern "C" int pse_msd_store(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain) {
+    pse_handle *h = m ? m->h : nullptr;
+    TRY(msd_slot_validate("pse_msd_store", m, m ? m->norigins : 0, h ? (unsigned)h->n_max : 0u, slot, N, pos, image, strain));
+    HIPCHK(hipSetDevice(h->device));
+    launch_msd_store((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
+                     m->mo, slot, nullptr, h->stream);
+    HIPCHK(hipGetLastError());
+    m->stored |= 1ull << slot;
+    return 0;
+}
+extern "C" int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N,
+                                    double strain, pse_double4 *out) {
+    pse_handle *h = m ? m->h : nullptr;
+    TRY(msd_slot_validate("pse_msd_displacement", m, m ? m->norigins : 0, h ? (unsigned)h->n_max : 0u, slot, N, pos, image, strain));
+    TRY(msd_displacement_validate(m->stored, slot, out));
+    HIPCHK(hipSetDevice(h->device));
+    launch_msd_store((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
+                     m->mo, slot, (double4 *)out, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
+                                  int npairs, const int *slots_host, const int *rows_host, int nrows, double *sums) {
+    pse_handle *h = m ? m->h : nullptr;
+    TRY(msd_accumulate_validate(m, m ? m->norigins : 0, m ? m->stored : 0ull, h ? (unsigned)h->n_max : 0u, N, pos, image, strain, npairs,
+                                slots_host, rows_host, nrows, sums));
+    HIPCHK(hipSetDevice(h->device));
+    MsdPairs pairs{};
+    pairs.npairs = npairs;
+    for (int q = 0; q < npairs; ++q) { pairs.slot[q] = (unsigned char)slots_host[q]; pairs.row[q] = rows_host[q]; }
+    launch_msd_accumulate((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
+                          m->mo, pairs, sums, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Cluster analysis (include/pse_amd.h): the types and the link distances on the device, and the pass.  Queue-only: the sort, the type
+// mirror and the four kernels of the union-find; nothing is read back.
+extern "C" int pse_clusters_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const double *rlink_host,
+                                   pse_clusters **out) {
+    const char *who = "pse_clusters_create";
+    TRY(create_begin(who, h, out));
+    TRY(clusters_create_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, rlink_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> rl2((size_t)(ntypes * (ntypes + 1) / 2));
+    pse_clusters *g = new pse_clusters();
+    g->h = h;
+    ClusterLinks &cl = g->cl;
+    cl.n = n; cl.ntypes = ntypes;
+    for (size_t p = 0; p < rl2.size(); ++p) { rl2[p] = rlink_host[p] * rlink_host[p]; cl.rl2_all = std::max(cl.rl2_all, rl2[p]); }
+    const size_t nm = (size_t)h->n_max;
+    hipError_t e = g->put(&cl.types, type_bytes(types_host, n).data(), n);
+    e = g->put(&cl.type_s, nullptr, nm);
+    e = g->put(&cl.rlink2, rl2.data(), rl2.size());
+    e = g->put(&cl.parent, nullptr, 3 * nm + 1, true);   // one array: parent, mintag, csize (n_max each), then the status word
+    if (e == hipSuccess) { cl.mintag = cl.parent + nm; cl.csize = cl.parent + 2 * nm; cl.status = cl.parent + 3 * nm; }
+    return create_end(who, h, g, e, out);
+}
+extern "C" int pse_clusters_destroy(pse_clusters *g) { return object_destroy(g); }
+extern "C" int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *label, unsigned *size,
+                                  unsigned long long *stats, unsigned long long *hist, unsigned nhist, const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;
+    TRY(clusters_label_validate(g, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, g ? g->known_status : 0u, N, pos, label, size, stats, hist,
+                                nhist, ex, ex ? ex->h : nullptr));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    launch_clusters(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, g->cl, label, size, stats, hist, nhist, h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int pse_clusters_status(pse_clusters *g, unsigned *status) {
+    if (!g) return fail(PSE_ERR_INVALID, "pse_clusters_status: null cluster object");
+    if (!status) return fail(PSE_ERR_INVALID, "pse_clusters_status: null status");
+    pse_handle *h = g->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(&g->known_status, g->cl.status, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *status = g->known_status;
+    return 0;
+}

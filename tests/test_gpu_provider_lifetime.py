@@ -1,6 +1,7 @@
 """GPU tests of what the force providers (pse_amd.forces) owe to the engine they are made on (integrate.PSEv1.engine, the ctypes
 binding on the handle of the C++ Stokes object): a provider dies with the handle that setParams() replaces and says so, a collected
-provider frees its device object and leaves the others alone, and an empty group is treated as the C++ layer treated it.
+provider frees its device object and leaves the others alone, and an empty group is treated as the C++ layer treated it.  The same
+two promises for the analysis objects of an Engine (exclusions, histogram, structure factor, displacement origins, cluster links).
 
 64 particles, four chains of 16 beads (tests/bond_ref.py chains) in the cubic box of the provider tests.  Everything compared here is
 the output of the same kernels on the same arguments, so equal means bit for bit: np.array_equal."""
@@ -144,3 +145,91 @@ def test_a_collected_provider_frees_its_object_and_leaves_the_rest(case, restore
     s.run(2)                                                       # ... and the integrator steps with what is left
     moved = s.pos.cpu().numpy()[:, :3]
     assert np.isfinite(moved).all() and np.abs(moved - case["pos"]).max() > 0.0
+
+
+# -- the analysis objects of an Engine ----------------------------------------------------------------------------------------------
+
+ANALYSIS = ("exclusions", "histogram", "structure_factor", "origins", "links")   # in the order they are made
+
+
+def make(eng, case, name):
+    from pse_amd import analyze
+    types = np.array(case["types"])
+    return {"exclusions": lambda: eng.exclusions(np.array(case["pairs"])),
+            "histogram": lambda: eng.pair_histogram(types, 2, 8, 0.0, RMAX),
+            "structure_factor": lambda: eng.structure_factor(types, 2, analyze.axis_modes(2)),
+            "origins": lambda: eng.msd_origins(types, 2, 2),
+            "links": lambda: eng.clusters(types, 2, 1.8)}[name]()
+
+
+def run_pass(eng, case, objs, name):
+    """The pass of objs[name] into fresh output tensors, read back: a tuple of arrays.  The exclusions act in a repulsion pass of their
+    own (and in the histogram's, where both are alive)."""
+    import torch
+    n = NCHAINS * BEADS
+
+    def to4(a):
+        o = np.zeros((n, 4)); o[:, :3] = a
+        return torch.tensor(o, dtype=torch.float64, device="cuda")
+
+    pos, obj = to4(case["pos"]), objs[name]
+    if name == "exclusions":
+        out = (eng.pair_repulsion(pos, torch.zeros_like(pos), 40.0, sigma=2.5, exclusions=obj),)
+    elif name == "histogram":
+        out = (eng.pair_hist_accumulate(pos, obj, torch.zeros((3, 8), dtype=torch.int64, device="cuda"), exclusions=objs.get("exclusions")),)
+    elif name == "structure_factor":
+        out = eng.structure_factor_accumulate(pos, obj, rho=torch.zeros((2, 6, 2), dtype=torch.float64, device="cuda"),
+                                              sums=torch.zeros((3, 6), dtype=torch.float64, device="cuda"))
+    elif name == "origins":
+        image = torch.zeros((n, 3), dtype=torch.int32, device="cuda")
+        shift = 0.125 * ((np.arange(3 * n).reshape(n, 3) % 5) - 2.0)
+        eng.msd_store(pos, image, obj, 0, 0.0)
+        eng.msd_store(to4(case["pos"] + shift), image, obj, 1, 0.0)
+        out = (eng.msd_accumulate(to4(case["pos"] - shift), image, obj, 0.0, [0, 1], [1, 0], torch.zeros((2, 2, 10), dtype=torch.float64, device="cuda")),
+               eng.msd_displacement(pos, image, obj, 1, 0.0))
+    else:
+        out = eng.cluster_label(pos, obj, label=torch.zeros(n, dtype=torch.int32, device="cuda"), size=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                                stats=torch.zeros(4, dtype=torch.int64, device="cuda"), hist=torch.zeros(n, dtype=torch.int64, device="cuda"))
+        assert obj.status() == 0
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def same(a, b):
+    return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_a_collected_analysis_object_frees_its_arrays_and_leaves_the_rest(case):
+    import pse_amd
+    eng = pse_amd.Engine(NCHAINS * BEADS, BOX, xi=0.5, error=1e-3, seed=3)
+    objs = {name: make(eng, case, name) for name in ANALYSIS}
+    first = {name: run_pass(eng, case, objs, name) for name in ANALYSIS}
+    assert first["exclusions"][0].any() and first["histogram"][0].sum() > 0 and np.abs(first["structure_factor"][0]).max() > 0.0
+    assert first["origins"][0].any() and first["links"][2][0] < NCHAINS * BEADS               # something was linked
+    dropped = (ANALYSIS[1], ANALYSIS[-1])
+    with _Unraisable() as quiet:
+        for name in dropped:
+            del objs[name]
+        gc.collect()                                               # pse_pair_hist_destroy and pse_clusters_destroy run here
+    assert quiet.seen == []
+    for name in objs:
+        assert same(run_pass(eng, case, objs, name), first[name]), name
+    for name in dropped:
+        objs[name] = make(eng, case, name)
+        assert same(run_pass(eng, case, objs, name), first[name]), name
+    eng.close()
+
+
+def test_the_analysis_objects_go_with_the_engine(case):
+    import pse_amd
+    eng = pse_amd.Engine(NCHAINS * BEADS, BOX, xi=0.5, error=1e-3, seed=3)
+    objs = {name: make(eng, case, name) for name in ANALYSIS}
+    eng.close()                                                    # pse_destroy freed the five device objects
+    for name in ANALYSIS:
+        with pytest.raises(ValueError, match="went with the engine"):
+            run_pass(eng, case, {name: objs[name]}, name)
+    with pytest.raises(ValueError, match="went with the engine"):
+        objs["links"].status()
+    with _Unraisable() as quiet:                                   # nothing is freed twice, nothing complains
+        del objs
+        gc.collect()
+    assert quiet.seen == []
