@@ -613,6 +613,21 @@ int pse_debug_gather(pse_handle *h, const pse_double4 *pos, const double *grid_h
  * 0: k_gather), its BZ (1 | 2), SHEAR instantiations (xy != 0)}; TZ, NW, BZ are 0 where the generic kernel runs.  Lets a test
  * assert the instantiation it was written for (PSE_SPREAD_TZ, PSE_SPREAD_NW, PSE_GATHER_BZ are read per handle in pse_create). */
 int pse_debug_far_path(pse_handle *h, unsigned int N, int *out6);
+/* the wave-space stage of a step from grid to grid, by the code a step runs (the transforms of part 0, parts 1 and 2 of the chain): the
+ * three real grids are taken from grid_in_host (HOST, 3*Nx*Ny*Nz doubles in the layout pse_debug_copy_grid returns; NULL: zeros),
+ * transformed forward (z, y, x), multiplied by the k-space operator -- with xi / eta in place of the handle's own where > 0; eta = 1
+ * switches the exponential of the operator off, so that no mode is damped out of sight -- plus the k-space noise of (kT, dt, timestep)
+ * if noise != 0, transformed back and copied to grid_out_host (HOST, same layout).  poison != 0: before the input is copied in, every
+ * byte of the real grids and of the spectra is set to 0xFF (NaN doubles: the pad columns of the spectrum rows included), so that a
+ * kernel that lets pad or stale data into a live mode turns the output into NaN.  Every tuning switch acts as on a step.  No slab ranks. */
+int pse_debug_wave_grid(pse_handle *h, const double *grid_in_host, double xi, double eta, int noise, double kT, double dt,
+                        unsigned int timestep, int poison, double *grid_out_host);
+/* which transform kernels this handle runs, by the functions the launchers switch on: out8 = {xfuse, own_y, own_z,
+ * x kernel (0: rocFFT + k_scale, 1: k_xfft_scale in LDS, 2: k_xfft_scale_cols in registers, 3 / 4: k_xfft_scale_mixed with a
+ * compile-time / runtime plan), its kz columns per workgroup,
+ * y kernel (0: rocFFT, 1 / 2: k_fft_cols with a compile-time / runtime plan, 3: k_yfft_regs), its kz columns per workgroup,
+ * z kernel (0: rocFFT, 1: k_zfft_rows, 2: k_zfft_rows_g)}.  The PSE_* switches are read per handle in pse_create. */
+int pse_debug_fft_path(pse_handle *h, int *out8);
 /* the k-space operator of n grid nodes (i, j, k) (host array of 3 n ints, 0 <= k < Nz: any node of the reference's full C2C
  * grid) exactly as the scaling kernels evaluate it, for the current box: out_host[5 t ..] = kx, ky, kz, w sinc^2,
  * sqrt(w) sinc -- what gpu_stokes_SetGridk_kernel tabulates (PSEv1/Helper.cu:285-332: index folding, sheared ky, scale

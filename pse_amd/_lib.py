@@ -165,6 +165,8 @@ SYMBOLS = {
     "pse_debug_spread": (_i, [_vp, _vp, _vp, _vp, _u]),
     "pse_debug_gather": (_i, [_vp, _vp, _dp, _vp, _u, _vp]),
     "pse_debug_far_path": (_i, [_vp, _u, _ip]),
+    "pse_debug_wave_grid": (_i, [_vp, _dp, _d, _d, _i, _d, _d, _u, _i, _dp]),
+    "pse_debug_fft_path": (_i, [_vp, _ip]),
     "pse_debug_kvector": (_i, [_vp, _i, _ip, _dp]),
     "pse_debug_grid_placement": (_i, [_vp, _ip, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "pse_debug_vq_roundtrip": (_i, [_i, _dp, _dp]),

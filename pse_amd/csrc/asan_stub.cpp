@@ -312,6 +312,8 @@ int pse_debug_copy_grid(pse_handle *, int, double *) { return no_device("pse_deb
 int pse_debug_spread(pse_handle *, const pse_double4 *, const pse_double4 *, const unsigned int *, unsigned int) { return no_device("pse_debug_spread"); }
 int pse_debug_gather(pse_handle *, const pse_double4 *, const double *, const unsigned int *, unsigned int, pse_double4 *) { return no_device("pse_debug_gather"); }
 int pse_debug_far_path(pse_handle *, unsigned int, int *) { return no_device("pse_debug_far_path"); }
+int pse_debug_wave_grid(pse_handle *, const double *, double, double, int, double, double, unsigned int, int, double *) { return no_device("pse_debug_wave_grid"); }
+int pse_debug_fft_path(pse_handle *, int *) { return no_device("pse_debug_fft_path"); }
 int pse_debug_kvector(pse_handle *, int, const int *, double *) { return no_device("pse_debug_kvector"); }
 int pse_debug_grid_placement(pse_handle *, int *, float *, float *) { return no_device("pse_debug_grid_placement"); }
 int pse_debug_vq_roundtrip(int, const double *, double *) { return no_device("pse_debug_vq_roundtrip"); }

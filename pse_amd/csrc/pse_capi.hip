@@ -75,7 +75,7 @@ static void *vq_of(const pse_handle *h) { return h->nb.c64 ? nullptr : h->vq; }
 // against 3.98 - 4.05 on the next five: docs/HISTORY.md).  A planner's answer: with the first pair in place, allocate more
 // pairs (all alive at once, so that they ARE elsewhere), time the x pass + the inverse y + z passes on each, keep the fastest and free the rest.
 // Only for grids large enough to matter, only while the device has room for all the candidates; results do not depend on the choice.
-static ScaleArgs scale_args(pse_handle *h, bool noise, double kT, double dt, unsigned timestep);
+static ScaleArgs scale_args(pse_handle *h, bool noise, double kT, double dt, unsigned timestep, double xi = 0.0, double eta = 0.0);
 static int place_grids(pse_handle *h, size_t nr, size_t ncx) {
     const DGrid &G = h->G;
     const size_t bytes_r = 3 * nr * sizeof(double), bytes_c = 3 * ncx * sizeof(double2);
@@ -1271,10 +1271,11 @@ int prepare(pse_handle *h, const double4 *pos, const double4 *vec, const unsigne
     return 0;
 }
 
-static ScaleArgs scale_args(pse_handle *h, bool noise, double kT, double dt, unsigned timestep) {
+// xi, eta > 0: the operator with these in place of the handle's own (pse_debug_wave_grid; a step never passes them)
+static ScaleArgs scale_args(pse_handle *h, bool noise, double kT, double dt, unsigned timestep, double xi, double eta) {
     ScaleArgs a;
     const DGrid &G = h->G;
-    a.xi = h->d.xi; a.eta = h->d.eta; a.noise = noise ? 1 : 0;
+    a.xi = xi > 0.0 ? xi : h->d.xi; a.eta = eta > 0.0 ? eta : h->d.eta; a.noise = noise ? 1 : 0;
     a.noise_fac = noise ? std::sqrt(2.0 * kT / dt / (G.hx * G.hy * G.hz)) : 0.0;   // PSEv1/Brownian.cu:197
     a.seed = h->par.seed; a.timestep = timestep; a.ts_off = h->ts_off;
     a.transposed = h->grid_slabs > 1 ? 1 : 0; a.y0 = h->y0; a.nyl = h->grid_slabs > 1 ? h->nyl : G.Ny;
@@ -1289,7 +1290,33 @@ static ScaleArgs scale_args(pse_handle *h, bool noise, double kT, double dt, uns
 //   part 2  (unpack +) 2-D inverse transforms                        exchange 2  plane halo of the gather
 //   part 3  gather
 // A single GPU, or a team that keeps the whole grid on every rank, has no exchanges: the parts simply follow one another.
-struct WaveArgs { int N; bool noise; double kT, dt; unsigned timestep; };
+struct WaveArgs { int N; bool noise; double kT, dt; unsigned timestep; double xi = 0.0, eta = 0.0; /* > 0: operator overrides (debug) */ };
+// the forward transforms of part 0 (+ a slab rank's pack): real grids -> half spectra, z and y (single GPU with rocFFT's 3-D plan: x too)
+static int wave_forward_transforms(pse_handle *h, int GS) {
+    const DGrid &G = h->G;
+    const size_t nr = (size_t)(G.nxl + G.hl + G.nhalo) * G.Ny * G.Nz, ncx = (size_t)G.nxl * G.Ny * G.Nzp;
+    TRY(tsw(h, PH_FFTF));
+    double *zr[3]; double2 *zs[3];   // the rows of the own planes of each component
+    for (int c = 0; c < 3; ++c) { zr[c] = h->rgrid + c * nr + (size_t)G.hl * G.Ny * G.Nz; zs[c] = h->cgrid + c * ncx; }
+    if (GS == 1) {
+        if (h->own_z) launch_zfft(zr, zs, G.Nx * G.Ny, G.Nz, G.Nzp, false, h->twiddle_z, h->wstream);
+        else {
+            void *in[1] = {h->rgrid}, *out[1] = {h->cgrid};
+            FFTCHK(rocfft_execute(h->plan_fwd, in, out, h->info_fwd));
+        }
+        if (h->own_y) launch_yfft(h->cgrid, G, false, h->twiddle_y, h->wstream, h->tun.yfft_kb);
+    } else {
+        if (h->own_z) launch_zfft(zr, zs, G.nxl * G.Ny, G.Nz, G.Nzp, false, h->twiddle_z, h->wstream);
+        else for (int c = 0; c < 3; ++c) {   // 2-D (y,z) transforms of the local planes, one component at a time
+            void *in[1] = {h->rgrid + c * nr + (size_t)G.hl * G.Ny * G.Nz}, *out[1] = {h->cgrid + c * ncx};
+            FFTCHK(rocfft_execute(h->plan_fwd, in, out, h->info_fwd));
+        }
+        if (h->own_y_slab) launch_yfft_slab(h->cgrid, h->sendbuf, G, h->nyl, false, h->twiddle_y, h->wstream, h->tun.yslab_regs > 0);
+        else launch_slab_pack(h->cgrid, h->sendbuf, G.nxl, G.Ny, G.Nzp, h->nyl, 0, h->wstream);
+    }
+    TRY(tew(h, PH_FFTF));
+    return 0;
+}
 static int wave_compute(pse_team &T, const WaveArgs &a, int part) {
     const int GS = T.m[0]->grid_slabs;   // 1: every rank transforms the whole grid (single GPU, or a team that replicates it)
     for (pse_handle *h : act(T)) {
@@ -1304,30 +1331,11 @@ static int wave_compute(pse_team &T, const WaveArgs &a, int part) {
             if (spread_needs_zero(G)) HIPCHK(hipMemsetAsync(h->rgrid, 0, 3 * nr * sizeof(double), h->wstream));
             HIPCHK(launch_spread(h->pos_s, h->f_s, a.N, gx, gy, gz, G, h->dbox, h->sw, h->wstream));
             TRY(tew(h, PH_SPREAD));
-            TRY(tsw(h, PH_FFTF));
-            double *zr[3]; double2 *zs[3];   // the rows of the own planes of each component
-            for (int c = 0; c < 3; ++c) { zr[c] = h->rgrid + c * nr + (size_t)G.hl * G.Ny * G.Nz; zs[c] = h->cgrid + c * ncx; }
-            if (GS == 1) {
-                if (h->own_z) launch_zfft(zr, zs, G.Nx * G.Ny, G.Nz, G.Nzp, false, h->twiddle_z, h->wstream);
-                else {
-                    void *in[1] = {h->rgrid}, *out[1] = {h->cgrid};
-                    FFTCHK(rocfft_execute(h->plan_fwd, in, out, h->info_fwd));
-                }
-                if (h->own_y) launch_yfft(h->cgrid, G, false, h->twiddle_y, h->wstream, h->tun.yfft_kb);
-            } else {
-                if (h->own_z) launch_zfft(zr, zs, G.nxl * G.Ny, G.Nz, G.Nzp, false, h->twiddle_z, h->wstream);
-                else for (int c = 0; c < 3; ++c) {   // 2-D (y,z) transforms of the local planes, one component at a time
-                    void *in[1] = {h->rgrid + c * nr + (size_t)G.hl * G.Ny * G.Nz}, *out[1] = {h->cgrid + c * ncx};
-                    FFTCHK(rocfft_execute(h->plan_fwd, in, out, h->info_fwd));
-                }
-                if (h->own_y_slab) launch_yfft_slab(h->cgrid, h->sendbuf, G, h->nyl, false, h->twiddle_y, h->wstream, h->tun.yslab_regs > 0);
-                else launch_slab_pack(h->cgrid, h->sendbuf, G.nxl, G.Ny, G.Nzp, h->nyl, 0, h->wstream);
-            }
-            TRY(tew(h, PH_FFTF));
+            TRY(wave_forward_transforms(h, GS));
         } else if (part == 1) {
             double2 *sp = GS == 1 ? h->cgrid : h->recvbuf;   // [3][Nx][nyl][Nzh] after the transpose
             TRY(tsw(h, PH_SCALE));
-            const ScaleArgs sa = scale_args(h, a.noise, a.kT, a.dt, a.timestep);
+            const ScaleArgs sa = scale_args(h, a.noise, a.kT, a.dt, a.timestep, a.xi, a.eta);
             if (h->xfuse) {
                 launch_xfft_scale(sp, sp + ncx, sp + 2 * ncx, G, h->dbox, sa, h->twiddle, h->wstream);
             } else {
@@ -2500,6 +2508,52 @@ extern "C" int pse_debug_far_path(pse_handle *h, unsigned N, int *out6) {
     TRY(check_n(h, N));
     if (!out6) return fail(PSE_ERR_INVALID, "null array");
     far_path(h->G, h->sw, (int)N, h->dbox.xy, out6);
+    return 0;
+}
+
+// The wave-space stage of a step from grid to grid: parts 0 (its transforms), 1 and 2 of wave_compute as a step queues them.
+extern "C" int pse_debug_wave_grid(pse_handle *h, const double *grid_in_host, double xi, double eta, int noise, double kT, double dt,
+                                   unsigned timestep, int poison, double *grid_out_host) {
+    if (!h) return fail(PSE_ERR_INVALID, "null handle");
+    if (!grid_out_host) return fail(PSE_ERR_INVALID, "null array");
+    if (noise && !(kT >= 0.0)) return fail(PSE_ERR_INVALID, "kT must be non-negative");
+    if (noise && !(dt > 0.0)) return fail(PSE_ERR_INVALID, "dt must be positive");
+    pse_team T;
+    TRY(team_of_one(h, T));   // (refuses a slab rank)
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));   // whatever an earlier call left queued on either lane
+    if (h->side) HIPCHK(hipStreamSynchronize(h->side));
+    const DGrid &G = h->G;
+    const size_t plane = (size_t)G.Ny * G.Nz, nr = plane * (G.nxl + G.hl + G.nhalo), ncx = (size_t)G.nxl * G.Ny * G.Nzp;
+    if (poison) {   // NaN in every double of both grids: the pad columns of the spectrum rows included
+        HIPCHK(hipMemsetAsync(h->rgrid, 0xFF, 3 * nr * sizeof(double), h->wstream));
+        HIPCHK(hipMemsetAsync(h->cgrid, 0xFF, 3 * ncx * sizeof(double2), h->wstream));
+    }
+    for (int c = 0; c < 3; ++c) {   // the layout pse_debug_copy_grid returns
+        double *dst = h->rgrid + c * nr + plane * G.hl;
+        if (grid_in_host) HIPCHK(hipMemcpyAsync(dst, grid_in_host + (size_t)c * plane * G.nxl, plane * G.nxl * sizeof(double), hipMemcpyHostToDevice, h->wstream));
+        else HIPCHK(hipMemsetAsync(dst, 0, plane * G.nxl * sizeof(double), h->wstream));
+    }
+    WaveArgs a{0, noise != 0, kT, dt, timestep};
+    a.xi = xi; a.eta = eta;
+    TRY(wave_forward_transforms(h, 1));
+    TRY(wave_compute(T, a, 1));
+    TRY(wave_compute(T, a, 2));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->wstream));
+    for (int c = 0; c < 3; ++c)
+        HIPCHK(hipMemcpy(grid_out_host + (size_t)c * plane * G.nxl, h->rgrid + c * nr + plane * G.hl, plane * G.nxl * sizeof(double),
+                         hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int pse_debug_fft_path(pse_handle *h, int *out8) {
+    if (!h || !out8) return fail(PSE_ERR_INVALID, "pse_debug_fft_path: null argument");
+    const FftChoice none{FFT_ROCFFT, 0};
+    const FftChoice x = h->xfuse ? xfft_choice(h->G, scale_args(h, false, 0.0, 1.0, 0)) : none;
+    const FftChoice y = h->own_y ? yfft_choice(h->G, h->tun.yfft_kb) : none;   // (a slab rank's y pass, launch_yfft_slab, is not reported)
+    const int out[8] = {h->xfuse, h->own_y, h->own_z, x.kernel, x.kb, y.kernel, y.kb, h->own_z ? zfft_choice(h->G.Nz) : FFT_ROCFFT};
+    std::copy(out, out + 8, out8);
     return 0;
 }
 

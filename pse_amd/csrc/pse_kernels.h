@@ -265,6 +265,18 @@ hipError_t launch_gather(const double4 *pos_s, SpreadWork w, int N, const double
 // which kernels launch_spread / launch_gather would launch for N particles (pse_debug_far_path): decided by the functions the launchers call
 void far_path(const DGrid &G, const SpreadWork &w, int N, double xy, int out[6]);
 
+// Which kernel family a transform launcher takes, and its kz columns per workgroup (pse_debug_fft_path).  launch_xfft_scale, launch_yfft
+// and launch_zfft switch on what these return, so the report cannot name another kernel than the one launched.  FFT_ROCFFT is never
+// returned: it is what the handle reports for an axis whose launcher is not called (xfuse / own_y / own_z off).
+enum { FFT_ROCFFT = 0,
+       XFFT_LDS = 1, XFFT_REGS = 2, XFFT_MIXED_CT = 3, XFFT_MIXED_RT = 4,      // k_xfft_scale, k_xfft_scale_cols, k_xfft_scale_mixed with a compile-time / runtime plan
+       YFFT_COLS_CT = 1, YFFT_COLS_RT = 2, YFFT_REGS = 3,                     // k_fft_cols with a compile-time / runtime plan, k_yfft_regs
+       ZFFT_ROWS = 1, ZFFT_ROWS_G = 2 };                                      // k_zfft_rows (256, 512), k_zfft_rows_g (pse_zfft.hip)
+struct FftChoice { int kernel, kb; };
+FftChoice xfft_choice(const DGrid &G, const ScaleArgs &a);
+FftChoice yfft_choice(const DGrid &G, int kb);
+int zfft_choice(int Nz);
+
 // ---- slab decomposition helpers
 void launch_slab_pack(double2 *cgrid, double2 *buf, int nxl, int Ny, int Nzh, int nyl, int unpack, hipStream_t s);
 void launch_add_inplace(double *a, const double *b, size_t n, hipStream_t s);

@@ -1944,19 +1944,31 @@ static bool yfft_slab_regs(double2 *cgrid, double2 *blocks, DGrid G, int nyl, bo
 }
 bool zfft_supported(int Nz);
 // all three components: [3 Nx] planes of [Ny][Nzp]; tw[m] = exp(-2 pi i m / Ny)
+// the kernel launch_yfft takes (also what pse_debug_fft_path reports): the register pass at 256 and, with the own z pass, at 512; k_fft_cols
+// with kb = 2, 4 or 8 columns otherwise, by a compile-time plan where one exists (four columns, the sizes of the x pass)
+FftChoice yfft_choice(const DGrid &G, int kb) {
+    if (G.Ny == 256) return {YFFT_REGS, 8};   // (four columns: +3 %)
+    if (G.Ny == 512 && yfft_regs_supported(G.Ny, G.Nz, zfft_supported(G.Nz))) return {YFFT_REGS, 4};
+    if (kb == 8 || kb == 2) return {YFFT_COLS_RT, kb};
+    if (kb == 4 && (G.Ny == 360 || G.Ny == 270 || G.Ny == 375 || G.Ny == 500)) return {YFFT_COLS_CT, 4};
+    return {YFFT_COLS_RT, 4};
+}
 void launch_yfft(double2 *spectra, DGrid G, bool inverse, const double2 *tw, hipStream_t s, int kb) {
     FftPlanX pl;
     plan_x(G.Ny, pl);
     const int nplanes = 3 * G.nxl;
     const size_t ps = (size_t)G.Ny * G.Nzp;
-    if (G.Ny == 256) { launch_yfft_regs<256, 8, 8, 8, 44, 5, 359>(spectra, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s); return; }   // (four columns: +3 %)
-    if (G.Ny == 512 && yfft_regs_supported(G.Ny, G.Nz, zfft_supported(G.Nz))) { launch_yfft_regs<512, 8, 8, 4, 72, 9, 578>(spectra, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s); return; }
-    if (kb == 8) launch_fft_cols<8, 256>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
-    else if (kb == 2) launch_fft_cols<2, 256>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
-    else if (kb == 4 && G.Ny == 360) launch_fft_cols<4, 256, CtPlan<360, 9, 8, 5>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);   // compile-time plans, as in the x pass
-    else if (kb == 4 && G.Ny == 270) launch_fft_cols<4, 256, CtPlan<270, 9, 5, 3, 2>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
-    else if (kb == 4 && G.Ny == 375) launch_fft_cols<4, 256, CtPlan<375, 5, 5, 5, 3>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
-    else if (kb == 4 && G.Ny == 500) launch_fft_cols<4, 256, CtPlan<500, 5, 5, 5, 4>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+    const FftChoice c = yfft_choice(G, kb);
+    if (c.kernel == YFFT_REGS) {
+        if (G.Ny == 256) launch_yfft_regs<256, 8, 8, 8, 44, 5, 359>(spectra, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+        else launch_yfft_regs<512, 8, 8, 4, 72, 9, 578>(spectra, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+    } else if (c.kernel == YFFT_COLS_CT) {   // compile-time plans, as in the x pass
+        if (G.Ny == 360) launch_fft_cols<4, 256, CtPlan<360, 9, 8, 5>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+        else if (G.Ny == 270) launch_fft_cols<4, 256, CtPlan<270, 9, 5, 3, 2>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+        else if (G.Ny == 375) launch_fft_cols<4, 256, CtPlan<375, 5, 5, 5, 3>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+        else launch_fft_cols<4, 256, CtPlan<500, 5, 5, 5, 4>>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+    } else if (c.kb == 8) launch_fft_cols<8, 256>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
+    else if (c.kb == 2) launch_fft_cols<2, 256>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
     else launch_fft_cols<4, 256>(spectra, pl, tw, nplanes, G.Nzh, G.Nzp, ps, inverse, s);
 }
 
@@ -2085,8 +2097,9 @@ constexpr int ZFFT_RPW = 8;
 bool zfft_g_supported(int Nz);   // pse_zfft.hip: NC = R0 x R1 x R2 (360, 270, 180, ...)
 void launch_zfft_g(double *const real[3], double2 *const spec[3], int rows, int Nz, int Nzp, bool inverse, const double2 *tw, hipStream_t s);
 bool zfft_supported(int Nz) { return Nz == 256 || Nz == 512 || zfft_g_supported(Nz); }
+int zfft_choice(int Nz) { return Nz == 256 || Nz == 512 ? ZFFT_ROWS : ZFFT_ROWS_G; }
 void launch_zfft(double *const real[3], double2 *const spec[3], int rows, int Nz, int Nzp, bool inverse, const double2 *tw, hipStream_t s) {
-    if (Nz != 256 && Nz != 512) { launch_zfft_g(real, spec, rows, Nz, Nzp, inverse, tw, s); return; }
+    if (zfft_choice(Nz) == ZFFT_ROWS_G) { launch_zfft_g(real, spec, rows, Nz, Nzp, inverse, tw, s); return; }
     ZRows zr{};
     for (int c = 0; c < 3; ++c) { zr.real[c] = real[c]; zr.spec[c] = spec[c]; }
     zr.rows = rows; zr.Nz = Nz; zr.Nzp = Nzp;
@@ -2118,47 +2131,68 @@ static void launch_xfft_t(double2 *X, double2 *Y, double2 *Z, DGrid G, DBox box,
     hipLaunchKernelGGL((k_xfft_scale<LOGN, KB, NTH>), dim3(rows * nkb), dim3(NTH), lds, s, X, Y, Z, G, box, a, tw);
 }
 
-void launch_xfft_scale(double2 *X, double2 *Y, double2 *Z, DGrid G, DBox box, ScaleArgs a, const double2 *tw, hipStream_t s) {
-    // (k_xfft_scale_cols addresses a component with 32-bit byte offsets: 512 x 512 x 264 complex numbers, the largest grid, are 1.1 GB)
+// the kernel launch_xfft_scale takes (also what pse_debug_fft_path reports)
+FftChoice xfft_choice(const DGrid &G, const ScaleArgs &a) {
     if (G.Nx & (G.Nx - 1)) {   // not a power of two: mixed-radix passes; 4 kz columns per workgroup while two buffers fit
-        FftPlanX pl;
-        plan_x(G.Nx, pl);
         // (one kz column per workgroup, 128 or 256 threads: 1.34 / 1.35 ms at 360^3 against 1.34 with two columns and 256 threads; two
         // columns with 128 / 192 threads: 1.90 / 1.52 ms -- the pass is bound by instruction issue, not occupancy; variants removed)
         if (!a.runtime_plan) {   // compile-time plans for the sizes of the reference's rule at the BASELINE configurations (PSE_XMIX=1: runtime plan)
             switch (G.Nx) {
-                case 360:   // 0.80 ms at 360^3 (10 x 6 x 6, no spills at two waves per SIMD; three waves: 66 spilled, 0.97); the passes in LDS: 1.05
-                    launch_xfft_cols<360, 10, 6, 4, 2, false, 54, 9, 538>(X, Y, Z, G, box, a, tw, s);
-                    return;
-                case 270: launch_xfft_mixed<2, 256, CtPlan<270, 9, 5, 3, 2>>(X, Y, Z, G, box, a, tw, pl, s); return;
-                case 375: launch_xfft_mixed<2, 256, CtPlan<375, 5, 5, 5, 3>>(X, Y, Z, G, box, a, tw, pl, s); return;
-                case 500: launch_xfft_mixed<2, 256, CtPlan<500, 5, 5, 5, 4>>(X, Y, Z, G, box, a, tw, pl, s); return;
-                case 180: launch_xfft_mixed<4, 256, CtPlan<180, 9, 5, 4>>(X, Y, Z, G, box, a, tw, pl, s); return;
+                case 360: return {XFFT_REGS, 4};   // 0.80 ms at 360^3 (10 x 6 x 6, no spills at two waves per SIMD; three waves: 66 spilled, 0.97); the passes in LDS: 1.05
+                case 270: case 375: case 500: return {XFFT_MIXED_CT, 2};
+                case 180: return {XFFT_MIXED_CT, 4};
                 default: break;
             }
         }
-        if (G.Nx <= 200) launch_xfft_mixed<4, 256>(X, Y, Z, G, box, a, tw, pl, s);
-        else launch_xfft_mixed<2, 256>(X, Y, Z, G, box, a, tw, pl, s);   // four columns, 512 threads, one workgroup per CU: 1.61 against 1.38 ms at 360^3
-        return;
+        return {XFFT_MIXED_RT, G.Nx <= 200 ? 4 : 2};   // four columns, 512 threads, one workgroup per CU: 1.61 against 1.38 ms at 360^3
     }
     // small grids (BASELINE config 2: 64^3): with eight kz columns per workgroup the launch is a single, partly filled wave of
     // workgroups and its duration is one workgroup's latency chain (34 us at 64^3); two columns per workgroup give four times as
     // many, shorter chains (the 32-byte pieces of a line are fetched by neighbouring workgroups of one XCD)
     const int rows_ = a.transposed ? a.nyl : G.Ny;
-    if (G.Nx <= 128 && (long)rows_ * ((G.Nzh + 7) / 8) < 1024 && !a.wide_small) {
-        switch (G.Nx) {
-            case 16: launch_xfft_t<4, 2, 64>(X, Y, Z, G, box, a, tw, s); return;
-            case 32: launch_xfft_t<5, 2, 64>(X, Y, Z, G, box, a, tw, s); return;
-            case 64: launch_xfft_t<6, 2, 128>(X, Y, Z, G, box, a, tw, s); return;
-            case 128: launch_xfft_t<7, 2, 256>(X, Y, Z, G, box, a, tw, s); return;
-            default: break;
+    if (G.Nx <= 128) return {XFFT_LDS, (long)rows_ * ((G.Nzh + 7) / 8) < 1024 && !a.wide_small ? 2 : 8};   // 8 kz columns per workgroup = 128-byte pieces; LDS = 3*KB*(N+1)*16 B
+    return {XFFT_REGS, G.Nx == 256 ? 8 : 4};
+}
+
+void launch_xfft_scale(double2 *X, double2 *Y, double2 *Z, DGrid G, DBox box, ScaleArgs a, const double2 *tw, hipStream_t s) {
+    // (k_xfft_scale_cols addresses a component with 32-bit byte offsets: 512 x 512 x 264 complex numbers, the largest grid, are 1.1 GB)
+    const FftChoice c = xfft_choice(G, a);
+    if (c.kernel == XFFT_MIXED_CT || c.kernel == XFFT_MIXED_RT) {
+        FftPlanX pl;
+        plan_x(G.Nx, pl);
+        if (c.kernel == XFFT_MIXED_RT) {
+            if (c.kb == 4) launch_xfft_mixed<4, 256>(X, Y, Z, G, box, a, tw, pl, s);
+            else launch_xfft_mixed<2, 256>(X, Y, Z, G, box, a, tw, pl, s);
+            return;
         }
+        switch (G.Nx) {
+            case 270: launch_xfft_mixed<2, 256, CtPlan<270, 9, 5, 3, 2>>(X, Y, Z, G, box, a, tw, pl, s); break;
+            case 375: launch_xfft_mixed<2, 256, CtPlan<375, 5, 5, 5, 3>>(X, Y, Z, G, box, a, tw, pl, s); break;
+            case 500: launch_xfft_mixed<2, 256, CtPlan<500, 5, 5, 5, 4>>(X, Y, Z, G, box, a, tw, pl, s); break;
+            default: launch_xfft_mixed<4, 256, CtPlan<180, 9, 5, 4>>(X, Y, Z, G, box, a, tw, pl, s); break;   // 180
+        }
+        return;
     }
-    switch (G.Nx) {   // 8 kz columns per workgroup = 128-byte pieces; LDS = 3*KB*(N+1)*16 B
-        case 16: launch_xfft_t<4, 8, 256>(X, Y, Z, G, box, a, tw, s); break;
-        case 32: launch_xfft_t<5, 8, 256>(X, Y, Z, G, box, a, tw, s); break;
-        case 64: launch_xfft_t<6, 8, 256>(X, Y, Z, G, box, a, tw, s); break;
-        case 128: launch_xfft_t<7, 8, 512>(X, Y, Z, G, box, a, tw, s); break;
+    if (c.kernel == XFFT_LDS) {
+        if (c.kb == 2) {
+            switch (G.Nx) {
+                case 16: launch_xfft_t<4, 2, 64>(X, Y, Z, G, box, a, tw, s); break;
+                case 32: launch_xfft_t<5, 2, 64>(X, Y, Z, G, box, a, tw, s); break;
+                case 64: launch_xfft_t<6, 2, 128>(X, Y, Z, G, box, a, tw, s); break;
+                default: launch_xfft_t<7, 2, 256>(X, Y, Z, G, box, a, tw, s); break;   // 128
+            }
+            return;
+        }
+        switch (G.Nx) {
+            case 16: launch_xfft_t<4, 8, 256>(X, Y, Z, G, box, a, tw, s); break;
+            case 32: launch_xfft_t<5, 8, 256>(X, Y, Z, G, box, a, tw, s); break;
+            case 64: launch_xfft_t<6, 8, 256>(X, Y, Z, G, box, a, tw, s); break;
+            default: launch_xfft_t<7, 8, 512>(X, Y, Z, G, box, a, tw, s); break;   // 128
+        }
+        return;
+    }
+    switch (G.Nx) {   // the register passes
+        case 360: launch_xfft_cols<360, 10, 6, 4, 2, false, 54, 9, 538>(X, Y, Z, G, box, a, tw, s); break;
         // 64-byte pieces (four kz): 3.87 TB/s at 256 x 512 x 512; 32-byte pieces (two kz, three workgroups per CU) 2.73; 128-byte pieces with
         // all three components in LDS (eight kz, one workgroup per CU) 2.71
         case 256:

@@ -1030,6 +1030,39 @@ class Engine(_ForcePasses):
         _lib.check(self._lib.pse_debug_far_path(self._h, int(n), out))
         return dict(zip(self.FAR_PATH_FIELDS, out))
 
+    FFT_PATH_FIELDS = ("xfuse", "own_y", "own_z", "x", "x_kb", "y", "y_kb", "z")
+    FFT_X_KERNELS = ("rocfft+k_scale", "k_xfft_scale", "k_xfft_scale_cols", "k_xfft_scale_mixed/ct", "k_xfft_scale_mixed/rt")
+    FFT_Y_KERNELS = ("rocfft", "k_fft_cols/ct", "k_fft_cols/rt", "k_yfft_regs")
+    FFT_Z_KERNELS = ("rocfft", "k_zfft_rows", "k_zfft_rows_g")
+
+    def fft_path(self):
+        """Which transform kernels this engine runs (pse_debug_fft_path): dict of FFT_PATH_FIELDS, the kernels by name (FFT_*_KERNELS),
+        x_kb / y_kb the kz columns per workgroup (0 where rocFFT serves the axis)."""
+        out = (ctypes.c_int * 8)()
+        _lib.check(self._lib.pse_debug_fft_path(self._h, out))
+        d = dict(zip(self.FFT_PATH_FIELDS, out))
+        d["x"] = self.FFT_X_KERNELS[d["x"]]; d["y"] = self.FFT_Y_KERNELS[d["y"]]; d["z"] = self.FFT_Z_KERNELS[d["z"]]
+        return d
+
+    def debug_wave_grid(self, grid=None, xi=0.0, eta=0.0, noise=False, kT=0.0, dt=1.0, timestep=0, poison=True):
+        """The wave-space stage alone, grid to grid (pse_debug_wave_grid): the host grids `grid` (3, Nx, Ny, Nz; None: zeros) through the
+        forward transforms, the k-space operator (xi, eta > 0 replace the engine's own; + the k-space noise if `noise`) and the inverse
+        transforms, as a step runs them; returns the (3, Nx, Ny, Nz) host array.  poison: both device grids are filled with NaN first."""
+        import numpy as np
+        i = self.info()
+        shape = (3, i["Nx"] // max(1, self.params.n_slabs), i["Ny"], i["Nz"])
+        dp = ctypes.POINTER(ctypes.c_double)
+        src = None
+        if grid is not None:
+            grid = np.ascontiguousarray(grid, dtype=np.float64)
+            if grid.shape != shape:
+                raise ValueError(f"grid must have the shape of debug_grid(), not {grid.shape}")
+            src = grid.ctypes.data_as(dp)
+        out = np.zeros(shape)
+        _lib.check(self._lib.pse_debug_wave_grid(self._h, src, float(xi), float(eta), int(bool(noise)), float(kT), float(dt), int(timestep),
+                                                 int(bool(poison)), out.ctypes.data_as(dp)))
+        return out
+
     def debug_kvector(self, ijk):
         """(n, 5): kx, ky, kz, w sinc^2, sqrt(w) sinc of the grid nodes ijk (n, 3) as the k-space kernels evaluate them."""
         import numpy as np

@@ -25,6 +25,13 @@ def _params(L, n_max=64, **kw):
     return p
 
 
+def _lib_info(lib, h):
+    from pse_amd._lib import pse_info
+    info = pse_info()
+    assert lib.pse_get_info(h, ctypes.byref(info)) == 0
+    return info
+
+
 def test_misuse_is_reported_not_fatal():
     import torch
     from pse_amd import _lib
@@ -85,12 +92,26 @@ def test_misuse_is_reported_not_fatal():
     assert lib.pse_eval_realspace(h, r.ctypes.data_as(dp), 1, f.ctypes.data_as(dp), g.ctypes.data_as(dp)) == INVALID and "table range" in msg()
     ijk = np.array([0, 0, 10 ** 6], dtype=np.int32); out = np.zeros(5)
     assert lib.pse_debug_kvector(h, 1, ijk.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), out.ctypes.data_as(dp)) == INVALID and "outside" in msg()
+    # the wave-space stage from grid to grid: null output, noise without a time step; a good call leaves the handle usable (below)
+    Ng = 3 * int(np.prod([getattr(_lib_info(lib, h), k) for k in ("Nx", "Ny", "Nz")]))
+    gin, gout = np.zeros(Ng), np.zeros(Ng)
+    assert lib.pse_debug_wave_grid(h, gin.ctypes.data_as(dp), 0.0, 0.0, 0, 0.0, 1.0, 0, 1, None) == INVALID and "null array" in msg()
+    assert lib.pse_debug_wave_grid(None, gin.ctypes.data_as(dp), 0.0, 0.0, 0, 0.0, 1.0, 0, 1, gout.ctypes.data_as(dp)) == INVALID and "null handle" in msg()
+    assert lib.pse_debug_wave_grid(h, None, 0.0, 0.0, 1, 1.0, 0.0, 0, 1, gout.ctypes.data_as(dp)) == INVALID and "dt" in msg()
+    assert lib.pse_debug_wave_grid(h, None, 0.0, 0.0, 1, 1.0, -1e-3, 0, 1, gout.ctypes.data_as(dp)) == INVALID and "dt" in msg()
+    assert lib.pse_debug_wave_grid(h, None, 0.0, 0.0, 1, -1.0, 1e-3, 0, 1, gout.ctypes.data_as(dp)) == INVALID and "kT" in msg()
+    assert lib.pse_debug_wave_grid(h, gin.ctypes.data_as(dp), 0.0, 0.0, 0, 0.0, 0.0, 0, 1, gout.ctypes.data_as(dp)) == 0, msg()   # (dt is the noise's)
+    assert (gout == 0.0).all()
+    path = (ctypes.c_int * 8)()
+    assert lib.pse_debug_fft_path(h, None) == INVALID and lib.pse_debug_fft_path(None, path) == INVALID and "null" in msg()
+    assert lib.pse_debug_fft_path(h, path) == 0
     info = _lib.pse_info()
     assert lib.pse_get_info(h, None) == INVALID and lib.pse_get_info(None, ctypes.byref(info)) == INVALID
     # a slab rank refuses to be driven alone
     rc, hs = create(_params(40.0, n_max=n, n_slabs=2, slab_rank=0, Nx=48, Ny=48, Nz=48))
     if rc == 0:
         assert lib.pse_mobility(hs, P(dpos), P(dF), P(vel), None, n, 3) == INVALID and "pse_team" in msg()
+        assert lib.pse_debug_wave_grid(hs, None, 0.0, 0.0, 0, 0.0, 1.0, 0, 1, gout.ctypes.data_as(dp)) == INVALID and "pse_team" in msg()
         assert lib.pse_destroy(hs) == 0
     # ... and after all of that the handle still gives the same answer
     vel.zero_()

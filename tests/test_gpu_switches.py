@@ -1,7 +1,7 @@
 """Every developer switch the README names runs the parity cases of the code it selects, in a child process with the switch set
 (the environment is read once per handle, in pse_create): no kernel family lives in the library without a test.
-The cases are the ones of tests/test_gpu_parity.py, tests/test_gpu_slabs.py and tests/test_gpu_local.py that exercise the sizes
-the switch matters at."""
+The cases are the ones of tests/test_gpu_parity.py, tests/test_gpu_wave_grid.py, tests/test_gpu_slabs.py and tests/test_gpu_local.py
+that exercise the sizes the switch matters at."""
 import os
 import subprocess
 import sys
@@ -11,17 +11,18 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-X = "far_field_passes_at_the_switch_sizes"
+X = "far_field_passes_at_the_switch_sizes or wave_grid_at_the_switch_sizes"    # end to end, and the wave-space stage grid to grid at every mode
+FFT = ["test_gpu_parity.py", "test_gpu_wave_grid.py"]
 CASES = [
     # (environment, files, -k expression)
-    ({"PSE_OWN_Y": "0"}, ["test_gpu_parity.py"], X),                       # rocFFT's 2-D (y, z) plans everywhere
-    ({"PSE_OWN_Y_POW2": "0"}, ["test_gpu_parity.py"], X),                  # ... at Ny = 256 / 512 only
-    ({"PSE_OWN_Z": "0"}, ["test_gpu_parity.py"], X),                       # rocFFT's 1-D z transforms under the own y pass
-    ({"PSE_XMIX": "1"}, ["test_gpu_parity.py"], X),                        # runtime radix plans where compile-time ones exist
-    ({"PSE_NO_XFUSE": "1"}, ["test_gpu_parity.py"], X + " or wave_matches_port"),   # rocFFT 3-D + k_scale
-    ({"PSE_XFFT_SMALL_KB": "8"}, ["test_gpu_parity.py"], X),               # eight-column x pass on small grids
-    ({"PSE_YFFT_KB": "2"}, ["test_gpu_parity.py"], X),
-    ({"PSE_YFFT_KB": "8"}, ["test_gpu_parity.py"], X),
+    ({"PSE_OWN_Y": "0"}, FFT, X),                       # rocFFT's 2-D (y, z) plans everywhere
+    ({"PSE_OWN_Y_POW2": "0"}, FFT, X),                  # ... at Ny = 256 / 512 only
+    ({"PSE_OWN_Z": "0"}, FFT, X),                       # rocFFT's 1-D z transforms under the own y pass
+    ({"PSE_XMIX": "1"}, FFT, X),                        # runtime radix plans where compile-time ones exist
+    ({"PSE_NO_XFUSE": "1"}, FFT, X + " or wave_matches_port"),   # rocFFT 3-D + k_scale
+    ({"PSE_XFFT_SMALL_KB": "8"}, FFT, X),               # eight-column x pass on small grids
+    ({"PSE_YFFT_KB": "2"}, FFT, X),
+    ({"PSE_YFFT_KB": "8"}, FFT, X),
     ({"PSE_OVERLAP": "0"}, ["test_gpu_parity.py"], "brownian_velocity_matches_port or step_integrates or wave_matches_port"),   # Brownian steps on one stream (the default of rounds 1-5)
     ({"PSE_OVERLAP": "-1"}, ["test_gpu_parity.py"], "brownian_velocity_matches_port or total_mobility"),
     ({"PSE_GATHER_BZ": "1"}, ["test_gpu_parity.py"], "wave_matches_port or both_halves"),
