@@ -461,6 +461,70 @@ int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *
                        const pse_exclusions *ex /* may be NULL */);
 int pse_clusters_status(pse_clusters *g, unsigned *status /* HOST */);
 
+/* ---- bond-orientational order: the Steinhardt q_l per particle, the neighbour-averaged q-bar_l and solid-like bonds (no reference counterpart) ----
+ * A pse_bond_order object fixes the types of the particles, the neighbour distances and the degrees: types_host, ntypes <= 8 and the
+ * pair types p(a, b) exactly as for pse_pair_hist_create (NULL: one type; a caller index >= n acts as type 0); rnb_host holds one
+ * neighbour distance per pair type under the rules of rlink in pse_clusters_create: 0 switches a pair type off, every other entry
+ * must be finite, > 0 and <= rcut, and at least one must be on; degrees_host holds nl distinct even degrees from {2, 4, ..., 12},
+ * 1 <= nl <= PSE_BOND_ORDER_MAX_DEGREES (odd degrees vanish on centrosymmetric shells).
+ * Two of the N group members i, j are NEIGHBOURS when their minimum-image distance has 0 < r^2 < rnb[p]^2 and the pair is not in ex;
+ * the relation is symmetric.  For particle i with nb(i) neighbours and unit vectors d_ij = (r_j - r_i)/r, minimum image:
+ *   c_lm(i)   = (1/nb) sum_j C_lm(d_ij), m = -l..l, C_lm = sqrt(4 pi/(2l + 1)) Y_lm the semi-normalised harmonics with the
+ *               Condon-Shortley phase; only m = 0..l is formed, c_l,-m = (-1)^m conj c_lm; nb = 0 gives c_lm = 0
+ *   q_l(i)    = sqrt(|c_l0|^2 + 2 sum_{m>0} |c_lm|^2), the usual sqrt(4 pi/(2l + 1) sum_m |q_lm|^2)
+ *   qbar_l(i) from cbar_lm(i) = (c_lm(i) + sum_{j in nb(i)} c_lm(j)) / (nb(i) + 1) with the same norm (Lechner and Dellago)
+ *   s_ij      = Re sum_m c_Lm(i) conj c_Lm(j) / (q_L(i) q_L(j)) for ONE designated degree L = degrees[solid_degree], defined as 0 when
+ *               either q_L is 0; n_conn(i) is the number of neighbours with s_ij > threshold, and i is SOLID-LIKE when
+ *               n_conn(i) >= min_conn (ten Wolde, Ruiz-Montero and Frenkel)
+ * pse_bond_order_compute writes, all DEVICE arrays, each may be NULL but not all:
+ *   nnb[t]            (unsigned, by CALLER index) nb(t)
+ *   q[t nl + d]       (double, by caller index) q_l of degree d of the object;  qbar[t nl + d] likewise
+ *   nconn[t]          (unsigned, by caller index) n_conn(t); not written when solid_degree < 0
+ *   stats             2 ntypes unsigned 64-bit words, 8-byte aligned, OVERWRITTEN: stats[2a] the number of group members of type a,
+ *                     stats[2a + 1] the number of those that are solid-like (0 when solid_degree < 0)
+ * Rows of indices outside the group are left alone.
+ * The harmonics are evaluated without an angle: C_lm = T_l^m(z) (x + i y)^m with the polynomial T_l^m = sqrt((l - m)!/(l + m)!)
+ * P_l^m(z)/sin^m(theta) from the three-term recurrence upward in l and (x + i y)^m by repeated multiplication: no trigonometric call,
+ * nothing singular at the poles.  DESIGN.md derives the error bound of c_lm, q_l and qbar_l from the order of the operations.
+ * Queue-only wherever pse_pair_hist_accumulate is: the sort, the type mirror, one launch per degree (pass 1: c_lm and q_l) and one
+ * more per degree that needs qbar or the solid bonds (pass 2, which gathers the neighbours' rows of c_lm); nothing is read back and
+ * there are no floating-point atomics: every per-particle sum runs in the walk order of the stable-sorted rows, so equal inputs give
+ * equal bits; stats is summed with integer atomics.  A permuted particle order changes the order of the sums: equal to rounding.
+ * A slab rank (n_slabs >= 2) orders only its own cells: pse_bond_order_compute refuses it; teams and owned-particle steps have no
+ * bond-order entry point.  Not computed: the third-order invariants w_l; neighbours by anything but a distance.
+ * pse_bond_order_histogram bins one column of a caller-order array of nl columns (q or qbar of a compute, say) per type: the group
+ * member t of type a with lo <= v < hi, v = values[t nl + column], adds 1 to counts[a nbins + b], b = min((int)((v - lo) nbins /
+ * (hi - lo)), nbins - 1); other values, NaN included, are not counted.  counts (ntypes x nbins, ntypes nbins <= 8192) is ADDED to with
+ * integer atomics: exact, samples accumulate on the device.  It needs neither the sort nor the cell list and works on any handle.
+ * The object belongs to its handle as a pse_pair_hist does (pse_destroy frees it, pse_bond_order_destroy after that is a caller error;
+ * pse_bond_order_destroy waits for the stream).  It holds the type mirror, the q_l of the sorted rows and the c_lm workspace: n_max
+ * rows of sum_l (l + 1) complex doubles.  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_bond_order_create, in this order: a null
+ * out or h, n == 0 or n > n_max, ntypes outside [1, 8], a null rnb_host, an entry that is not finite, negative or > rcut, no entry on,
+ * a type >= ntypes, nl outside [1, 4], a null degrees_host, a degree that is not even or outside [2, 12], a degree listed twice (*out
+ * is null after a refusal).  pse_bond_order_compute, in this order: a null b, N == 0 or N > n_max, a null pos, all five outputs null,
+ * solid_degree outside [-1, nl), with solid_degree >= 0 a threshold that is not finite or outside [-1, 1], stats not 8-byte aligned,
+ * an ex created on another handle than b, a slab rank.  pse_bond_order_histogram, in this order: a null b, N == 0 or N > n_max, a
+ * null values, column outside [0, nl), nbins < 1, ntypes nbins > 8192, lo or hi not finite, hi <= lo, a null counts or one that is not
+ * 8-byte aligned. */
+#define PSE_BOND_ORDER_MAX_DEGREES 4
+#define PSE_BOND_ORDER_MAX_L       12
+typedef struct pse_bond_order pse_bond_order;
+int pse_bond_order_create(pse_handle *h, unsigned n, const unsigned *types_host /* n, or NULL: one type */, int ntypes,
+                          const double *rnb_host /* npt */, int nl, const int *degrees_host /* nl */, pse_bond_order **out);
+int pse_bond_order_destroy(pse_bond_order *b);
+int pse_bond_order_compute(pse_bond_order *b, const pse_double4 *pos, const unsigned *group, unsigned N,
+                           unsigned *nnb   /* DEVICE, by caller index, may be NULL */,
+                           double   *q     /* DEVICE, caller index x nl, may be NULL */,
+                           double   *qbar  /* DEVICE, caller index x nl, may be NULL */,
+                           int solid_degree /* index into the degrees, or -1: no solid-bond pass */, double threshold, unsigned min_conn,
+                           unsigned *nconn /* DEVICE, by caller index, may be NULL */,
+                           unsigned long long *stats /* DEVICE, ntypes x 2, 8-byte aligned, OVERWRITTEN, may be NULL */,
+                           const pse_exclusions *ex /* may be NULL */);
+int pse_bond_order_histogram(pse_bond_order *b, const double *values /* DEVICE, caller index x nl, e.g. q or qbar */, int column,
+                             const unsigned *group, unsigned N, int nbins, double lo, double hi,
+                             unsigned long long *counts /* DEVICE, ntypes x nbins, 8-byte aligned, ADDED to */);
+
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,

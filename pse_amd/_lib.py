@@ -147,6 +147,10 @@ SYMBOLS = {
     "pse_clusters_destroy": (_i, [_vp]),
     "pse_clusters_label": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _vp, _u, _vp]),
     "pse_clusters_status": (_i, [_vp, _vp]),
+    "pse_bond_order_create": (_i, [_vp, _u, _vp, _i, _vp, _i, _vp, _vp]),
+    "pse_bond_order_destroy": (_i, [_vp]),
+    "pse_bond_order_compute": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _i, _d, _u, _vp, _vp, _vp]),
+    "pse_bond_order_histogram": (_i, [_vp, _vp, _i, _vp, _u, _i, _d, _d, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

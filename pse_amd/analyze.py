@@ -7,10 +7,13 @@ resolved in direction.  MSD is the dynamic counterpart: the engine keeps up to 6
 (pse_msd_store) and one streaming pass per sample sums the first, second and fourth moments of the displacement per type and per
 origin (pse_msd_accumulate): the drift, the mean-squared displacement tensor and the non-Gaussian parameter over many time origins.
 Clusters says which particles hang together: the connected components of a distance criterion, labelled on the device by a union-find
-over the sorted rows (pse_clusters_label), with the number of clusters, the largest one and the size distribution n(s) per sample."""
+over the sorted rows (pse_clusters_label), with the number of clusters, the largest one and the size distribution n(s) per sample.
+BondOrder says whether a neighbourhood is ordered: the Steinhardt q_l, the neighbour-averaged q-bar_l and the solid-like bonds of
+every particle (pse_bond_order_compute: spherical harmonics up to degree 12 summed over the neighbours on the cell list), with their
+per-type distributions and the solid-like fraction per sample."""
 import math
 
-from .engine import (MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, ClusterLinks, DisplacementOrigins, PairHistogram, StructureFactorModes, _cluster_arguments, _msd_arguments,
+from .engine import (BOND_ORDER_MAX_COUNTERS, MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, BondOrderShells, ClusterLinks, _bond_order_arguments, DisplacementOrigins, PairHistogram, StructureFactorModes, _cluster_arguments, _msd_arguments,
                      _pair_hist_arguments, _structure_factor_arguments, pair_type_index)
 from .forces import _excl_list
 
@@ -717,3 +720,199 @@ class Clusters:
 
     def largest_fraction(self):
         return averages_of(self.table()[:, 1:])[2]
+
+
+# The upper edge of the bins of q_l and q-bar_l in BondOrder.  pse_bond_order_histogram counts lo <= v < hi, and both are at most 1
+# exactly but 1 up to rounding for a particle with one neighbour -- above it as often as below, by less than 1e-9 (the error bound of
+# DESIGN.md): with hi = 1 those particles would be dropped.  The bins are therefore [b, b + 1) BOND_ORDER_HI / nbins.
+BOND_ORDER_HI = 1.0 + 2.0 ** -26
+
+
+def histogram_mean(counts, lo=0.0, hi=BOND_ORDER_HI):
+    """The mean of the binned values from their counts: sum_b counts[b] centre_b / sum_b counts[b], centre_b the middle of bin b of
+    the uniform bins on [lo, hi) (default: the bins of BondOrder) -- exact to half a bin width.  NumPy only."""
+    import numpy as np
+    counts = np.asarray(counts, dtype=np.float64).ravel()
+    if counts.sum() <= 0:
+        raise ValueError("no samples yet")
+    edges = bin_edges(len(counts), lo, hi)
+    return float((counts * 0.5 * (edges[:-1] + edges[1:])).sum() / counts.sum())
+
+
+def solid_fraction_of(rows, a=None):
+    """From the per-sample rows (members, solid-like) per type, shape (samples, ntypes, 2): the solid-like members of type `a` (None:
+    of all types) over all samples divided by the members.  NumPy only."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.float64)
+    rows = rows.reshape(-1, rows.shape[-2] if rows.ndim >= 2 else 1, 2)
+    if rows.shape[0] < 1:
+        raise ValueError("no samples yet")
+    sel = rows if a is None else rows[:, int(a):int(a) + 1]
+    if sel[..., 0].sum() <= 0:
+        raise ValueError("no members of that type")
+    return float(sel[..., 1].sum() / sel[..., 0].sum())
+
+
+def _bond_order_analyzer_arguments(rnb, degrees, types, type_names, period, solid, nbins, capacity):
+    """What BondOrder checks before it touches the device.  A dict `rnb` may name its types by `type_names`.  Returns (types uint32 or
+    None, ntypes, rnb (npt,), degrees int32, names or None, period, solid or None, nbins, capacity)."""
+    types, ntypes, names, period = _typed_arguments(types, type_names, period)
+    if isinstance(rnb, dict):
+        coded = {}
+        for key, r in rnb.items():
+            if not (isinstance(key, tuple) and len(key) == 2):
+                raise ValueError(f"rnb key {key!r}: need a pair (a, b) of types")
+            coded.setdefault(tuple(sorted(_type_codes(list(key), names))), []).append(r)
+        if any(len(v) > 1 for v in coded.values()):
+            raise ValueError("rnb names a pair of types twice")
+        rnb = {k: v[0] for k, v in coded.items()}
+    types, ntypes, rnb, degrees = _bond_order_arguments(types, ntypes, rnb, degrees)
+    if solid is not None:
+        if not (isinstance(solid, (tuple, list)) and len(solid) == 3):
+            raise ValueError("solid must be None or (degree, threshold, min_conn)")
+        degree, threshold, min_conn = int(solid[0]), float(solid[1]), int(solid[2])
+        if degree not in degrees.tolist():
+            raise ValueError(f"solid names the degree {degree}, which is not among the degrees {tuple(degrees.tolist())}")
+        if not (math.isfinite(threshold) and -1.0 <= threshold <= 1.0):
+            raise ValueError(f"solid threshold = {threshold} outside [-1, 1]")
+        if min_conn < 0:
+            raise ValueError("solid min_conn must not be negative")
+        solid = (degree, threshold, min_conn)
+    if int(nbins) < 1 or ntypes * int(nbins) > BOND_ORDER_MAX_COUNTERS:
+        raise ValueError(f"nbins = {nbins}: need at least one bin and at most {BOND_ORDER_MAX_COUNTERS} counters over the {ntypes} types")
+    if int(capacity) < 1:
+        raise ValueError("capacity must be positive")
+    return types, ntypes, rnb, degrees, names, period, solid, int(nbins), int(capacity)
+
+
+class BondOrder:
+    """Whether the neighbourhoods are ordered: every `period` steps the Steinhardt bond-orientational order parameters q_l of the
+    members of the integrator's group, their neighbour-averaged form q-bar_l (Lechner and Dellago) and, with `solid=(degree, threshold,
+    min_conn)`, e.g. (6, 0.7, 7), the solid-like bonds of ten Wolde, Ruiz-Montero and Frenkel (pse_bond_order_compute: two passes over
+    the cell list the step uses anyway).  Neighbours are the particles within `rnb`: a scalar, a dict {(a, b): r} over pairs of types
+    (names with `type_names=`; a missing pair is never a neighbour) or one entry per pair of types, none beyond the hydrodynamic
+    real-space cutoff.  `degrees`: 1 to 4 distinct even l from 2 to 12.  `types`, `type_names`, `exclusions`: as for RDF.
+    Each sample adds q_l and q-bar_l of every degree to per-type histograms of `nbins` uniform bins on [0, BOND_ORDER_HI) on the device --
+    the upper edge 1 + 2^-26, so that a q of 1 with its rounding (one neighbour) lands in the last bin: every member is counted -- and writes its
+    row (members, solid-like per type) into a device ring of `capacity` rows -- once full, the oldest rows are replaced.  Sampling
+    only queues work; the readers are the only places that wait for the device.
+    solid_like() is a boolean mask by particle index: Group(system, numpy.nonzero(mask)[0]) of it is the group an analyze.Clusters on
+    a second integrator view would label to find the largest crystalline nucleus (the coupling itself is left to the caller).
+
+    q(l), qbar(l), neighbors(), connections(), solid_like() -- the last sample, by particle index (0 outside the group);
+    histogram(l, a=None, averaged=False) -- the accumulated counts;  mean(l, a=None, averaged=False) -- from them;  table() --
+    (samples kept, 1 + 2 ntypes): timestep, then members and solid-like per type;  solid_fraction(a=None);  samples;  reset()."""
+
+    def __init__(self, integrator, rnb, degrees=(4, 6), types=None, type_names=None, exclusions=None, period=1, solid=None, nbins=100,
+                 capacity=1024):
+        import numpy as np
+        import torch
+        types, self.ntypes, self.rnb, self.degrees, self.type_names, self.period, self.solid, self.nbins, self.capacity = \
+            _bond_order_analyzer_arguments(rnb, degrees, types, type_names, period, solid, nbins, capacity)   # (raises before the device is touched)
+        system = integrator.system
+        if types is not None and types.shape[0] != system.n:
+            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
+        self.integrator, self.system = integrator, system
+        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
+        self.nl = int(self.degrees.shape[0])
+        self._excl = _excl_list(integrator, exclusions)
+        self._shells = BondOrderShells(integrator.engine, types, self.ntypes, self.rnb, self.degrees, system.n)
+        dev = system.pos.device
+        self._nnb = torch.zeros(system.n, dtype=torch.int32, device=dev)
+        self._nconn = torch.zeros(system.n, dtype=torch.int32, device=dev)
+        self._q = torch.zeros((system.n, self.nl), dtype=torch.float64, device=dev)
+        self._qbar = torch.zeros((system.n, self.nl), dtype=torch.float64, device=dev)
+        self._rows = torch.zeros((self.capacity, self.ntypes, 2), dtype=torch.int64, device=dev)
+        self._hist = torch.zeros((2, self.nl, self.ntypes, self.nbins), dtype=torch.int64, device=dev)   # [q | q-bar][degree][type][bin]
+        self._steps = [None] * self.capacity
+        self.samples = 0
+        system.analyzers.append(self)
+
+    def analyze(self, timestep):
+        if timestep % self.period:
+            return
+        eng, members = self.integrator.engine, self.integrator.group.members
+        r = self.samples % self.capacity
+        eng.bond_order(self.system.pos, self._shells, nnb=self._nnb, q=self._q, qbar=self._qbar, solid=self.solid,
+                       nconn=None if self.solid is None else self._nconn, stats=self._rows[r], group=members, exclusions=self._excl)
+        for which, values in enumerate((self._q, self._qbar)):
+            for d, l in enumerate(self.degrees.tolist()):
+                eng.bond_order_histogram(values, self._shells, l, self._hist[which, d], 0.0, BOND_ORDER_HI, group=members)
+        self._steps[r] = int(timestep)
+        self.samples += 1
+
+    def reset(self):
+        for t in (self._rows, self._hist, self._nnb, self._nconn, self._q, self._qbar):
+            t.zero_()
+        self._steps = [None] * self.capacity
+        self.samples = 0
+
+    def _sampled(self):
+        if self.samples < 1:
+            raise ValueError("no samples yet")
+
+    def q(self, l):
+        """(n,) float64: q_l of every particle in the last sample; 0 outside the group."""
+        self._sampled()
+        return self._q[:, self._shells.column(l)].cpu().numpy()
+
+    def qbar(self, l):
+        """(n,) float64: the neighbour-averaged q-bar_l of every particle in the last sample; 0 outside the group."""
+        self._sampled()
+        return self._qbar[:, self._shells.column(l)].cpu().numpy()
+
+    def neighbors(self):
+        """(n,) int64: the number of neighbours of every particle in the last sample; 0 outside the group."""
+        self._sampled()
+        return self._nnb.cpu().numpy().astype("int64")
+
+    def _solid(self):
+        self._sampled()
+        if self.solid is None:
+            raise ValueError("this BondOrder has no solid-bond pass: give solid=(degree, threshold, min_conn)")
+
+    def connections(self):
+        """(n,) int64: the number of solid-like bonds of every particle in the last sample; 0 outside the group."""
+        self._solid()
+        return self._nconn.cpu().numpy().astype("int64")
+
+    def solid_like(self):
+        """(n,) bool: the group members with at least min_conn solid-like bonds in the last sample -- the particles to hand, as a
+        Group, to an analyze.Clusters that is to find the crystalline nuclei."""
+        import numpy as np
+        conn = self.connections()
+        members = self.integrator.group.members   # (None: every particle)
+        if members is None:
+            return conn >= self.solid[2]
+        mask = np.zeros(self.system.n, dtype=bool)
+        members = members.cpu().numpy().astype("int64")
+        mask[members] = conn[members] >= self.solid[2]
+        return mask
+
+    def histogram(self, l, a=None, averaged=False):
+        """(nbins,) int64: the counts of q_l (averaged=True: of q-bar_l) in the bins on [0, BOND_ORDER_HI) over all samples since the last reset(), of type `a`
+        (an index or a name; None: of all types)."""
+        self._sampled()
+        h = self._hist[1 if averaged else 0, self._shells.column(l)].cpu().numpy()
+        return h.sum(axis=0) if a is None else h[_type_codes([a], self.type_names)[0]]
+
+    def mean(self, l, a=None, averaged=False):
+        """The mean of q_l (averaged=True: of q-bar_l) over all samples, from the histogram: exact to half a bin width."""
+        return histogram_mean(self.histogram(l, a, averaged))
+
+    def table(self):
+        """(samples kept, 1 + 2 ntypes) int64, oldest first: timestep, then for every type its members and its solid-like members (one
+        copy from the device)."""
+        import numpy as np
+        n = min(self.samples, self.capacity)
+        dev = self._rows.cpu().numpy().reshape(self.capacity, 2 * self.ntypes)
+        out = np.zeros((n, 1 + 2 * self.ntypes), dtype=np.int64)
+        for r in range(n):
+            k = (self.samples - n + r) % self.capacity
+            out[r, 0], out[r, 1:] = self._steps[k], dev[k]
+        return out
+
+    def solid_fraction(self, a=None):
+        """The solid-like members of type `a` (None: all) over the samples kept, divided by the members."""
+        self._solid()
+        return solid_fraction_of(self.table()[:, 1:].reshape(-1, self.ntypes, 2), None if a is None else _type_codes([a], self.type_names)[0])

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -42,6 +42,7 @@ struct pse_pair_hist : Topology { using Topology::Topology; };     // entries: t
 struct pse_structure_factor : Topology { using Topology::Topology; };   // row_off: the REAL plan (structure_factor_plan), entries: its permutation
 struct pse_msd : Topology { using Topology::Topology; int norigins = 0; unsigned long long stored = 0ull; };   // the slots' bookkeeping alone
 struct pse_clusters : Topology { using Topology::Topology; };      // entries: the types (zeros where none were given); the status word is always 0
+struct pse_bond_order : Topology { using Topology::Topology; int ntypes = 1; };   // entries: the types; row_off: the degrees
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -240,6 +241,31 @@ int pse_clusters_status(pse_clusters *g, unsigned *status) {
     if (!status) return fail(PSE_ERR_INVALID, "pse_clusters_status: null status");
     *status = 0u;   // (nothing ever ran)
     return 0;
+}
+int pse_bond_order_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const double *rnb_host, int nl, const int *degrees_host,
+                          pse_bond_order **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_bond_order_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_bond_order_create: null handle");
+    if (int rc = bond_order_create_validate(h->d.rcut, h->par.n_max, n, types_host, ntypes, rnb_host, nl, degrees_host)) return rc;
+    pse_bond_order *b = new pse_bond_order(h, (size_t)nl, (size_t)n);
+    b->ntypes = ntypes;
+    std::copy(degrees_host, degrees_host + nl, b->row_off.begin());
+    if (types_host) std::copy(types_host, types_host + n, b->entries.begin());
+    return topology_adopt(b, 0, out);
+}
+int pse_bond_order_destroy(pse_bond_order *b) { return topology_destroy(b); }
+// (the arrays are device pointers and there is no device: nothing is read or written)
+int pse_bond_order_compute(pse_bond_order *b, const pse_double4 *pos, const unsigned *, unsigned N, unsigned *nnb, double *q, double *qbar,
+                           int solid_degree, double threshold, unsigned, unsigned *nconn, unsigned long long *stats, const pse_exclusions *ex) {
+    pse_handle *h = b ? b->h : nullptr;
+    return bond_order_compute_validate(b, h, b ? (int)b->row_off.size() : 0, h ? h->par.n_max : 0u, h ? h->par.n_slabs : 1, N, pos, nnb, q, qbar,
+                                       solid_degree, threshold, nconn, stats, ex, ex ? ex->h : nullptr);
+}
+int pse_bond_order_histogram(pse_bond_order *b, const double *values, int column, const unsigned *, unsigned N, int nbins, double lo, double hi,
+                             unsigned long long *counts) {
+    return bond_order_histogram_validate(b, b ? (int)b->row_off.size() : 0, b ? b->ntypes : 1, b ? b->h->par.n_max : 0u, values, column, N, nbins,
+                                         lo, hi, counts);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -91,5 +91,17 @@ int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsi
 int clusters_label_validate(const void *g, const void *g_handle, unsigned n_max, int n_slabs, unsigned known_status, unsigned N, const void *pos,
                             const void *label, const void *size, const void *stats, const void *hist, unsigned nhist, const void *ex,
                             const void *ex_handle);
+// the argument checks of pse_bond_order_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them
+// (types may be null: one type), with the handle's rcut and n_max
+int bond_order_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rnb, int nl,
+                               const int *degrees);
+// the argument checks of pse_bond_order_compute: the object (b_handle: the handle it was created on, n_max and n_slabs that handle's,
+// nl its number of degrees), N, pos, the outputs, the solid degree and its threshold, an exclusion object of the same handle, the slab rank
+int bond_order_compute_validate(const void *b, const void *b_handle, int nl, unsigned n_max, int n_slabs, unsigned N, const void *pos,
+                                const void *nnb, const void *q, const void *qbar, int solid_degree, double threshold, const void *nconn,
+                                const void *stats, const void *ex, const void *ex_handle);
+// the argument checks of pse_bond_order_histogram: the object (nl and ntypes its own, n_max its handle's), N, values, the column, the bins, counts
+int bond_order_histogram_validate(const void *b, int nl, int ntypes, unsigned n_max, const void *values, int column, unsigned N, int nbins,
+                                  double lo, double hi, const void *counts);
 
 }  // namespace pse

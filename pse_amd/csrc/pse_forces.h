@@ -44,6 +44,8 @@ struct PairTypedTables {
     int ntypes, total;
     double rmax2_all;
 };
+// the type mirror of the typed cell-list passes (k_type_mirror): type_s[i] = types[tag_s[i]], 0 for a tag >= n
+void launch_type_mirror(const unsigned *tag_s, int N, const unsigned char *types, unsigned n, unsigned char *type_s, hipStream_t s);
 void launch_pair_table_typed(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
                              const PairTypedTables &tt, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
                              const PairExclusions *ex = nullptr);

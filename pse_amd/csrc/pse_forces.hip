@@ -2,6 +2,7 @@
 // histogram and the cluster analysis on the engine's cell list, the static structure factor on the caller-order positions, bonds, angles and dihedrals on the caller-order arrays.  They stand beside the path: the step consumes the forces
 // they leave in net_force.  gfx950, wave64, fp64.
 #include "pse_forces.h"
+#include "pse_excl.h"
 
 #include <type_traits>
 
@@ -52,41 +53,6 @@ __device__ __forceinline__ void obs_rows_store(double (&o)[PV_NOBS], int blk, do
 __device__ __forceinline__ void stage_type_params(pt_entry *dst, const void *__restrict__ par, int ntypes, int words = 2) {
     if ((int)threadIdx.x < words * ntypes) dst[threadIdx.x] = ((const pt_entry *)par)[threadIdx.x];
     __syncthreads();
-}
-
-// Pair exclusions of the two cell-list passes below (HOOMD's nlist.reset_exclusions): ExclRows is the device copy of the rows of
-// pse_host_exclusion_rows -- a CSR over the first n CALLER-order particle indices, row t the partners excluded from t, sorted
-// ascending, without duplicates, every pair in both rows.  The rows are indexed by tags (tag_s), never by sorted-order rows.
-struct ExclRows {
-    const unsigned *__restrict__ off;   // n + 1
-    const unsigned *__restrict__ ent;   // off[n] partners
-    unsigned n;
-};
-constexpr unsigned EXCL_LINEAR = 8;   // rows (or what the bisection leaves of one) up to this length are compared in one batch of loads
-// The row bounds [eb, ee) of the particle with tag t: a tag >= n has no exclusions and reads nothing.
-__device__ __forceinline__ void excl_row(const ExclRows &ex, unsigned t, unsigned &eb, unsigned &ee) {
-    eb = ee = 0u;
-    if (t < ex.n) { eb = ex.off[t]; ee = ex.off[t + 1]; }
-}
-// Is tag tj in the sorted row [eb, ee), eb < ee?  Called for a pair that has passed the distance test, a few per particle, and only
-// by a lane whose row is not empty (the caller tests eb < ee before it loads tag_s[j]).  Search: rows are typically the 2-6 partners
-// of a chain's 1-2, 1-3 and 1-4 neighbours, so a row of at most EXCL_LINEAR = 8 entries is compared whole: eight 4-byte loads along
-// the row, indices past the end clamped to the last entry, issued back to back and waited for once -- one or two cache lines, ONE
-// memory latency behind the load of tag_s[j].  (A scan in ascending order with an early exit at the first entry >= tj makes fewer
-// loads but waits for each before it decides on the next: three to four latencies in a row per pair, measured 1.40x the plain table
-// pass on six-entry rows against 1.28x for this form, docs/HISTORY.md.)  A longer row (a hub, a cross-linker) uses the sorted
-// order: it is bisected until at most 8 candidates are left, log2(len / 8) dependent loads, and the same batch finishes -- a row of
-// 500 costs 6 loads and a batch instead of 500 loads.  The lanes of a wave diverge here; the pass is bound by the position gathers.
-__device__ __forceinline__ bool excl_has(const unsigned *__restrict__ ent, unsigned eb, unsigned ee, unsigned tj) {
-    while (ee - eb > EXCL_LINEAR) {   // tj, if present, stays in [eb, ee)
-        const unsigned mid = eb + ((ee - eb) >> 1);
-        if (ent[mid] <= tj) eb = mid; else ee = mid;
-    }
-    const unsigned last = ee - 1u;
-    bool hit = false;
-#pragma unroll
-    for (unsigned q = 0; q < EXCL_LINEAR; ++q) hit |= ent[min(eb + q, last)] == tj;
-    return hit;
 }
 
 // Soft repulsion F_i = sum_j k (sigma - r) (r_i - r_j)/r over pairs closer than sigma, from the engine's own cell list.  One thread
@@ -164,12 +130,6 @@ static void launch_with_obs(int nb, double *rows, double *out8, hipStream_t s, L
     } else {
         launch(std::false_type{}, (double *)nullptr);
     }
-}
-// The exclusion flag of a launch as a std::bool_constant, as launch_with_obs hands over OBS: `launch` is instantiated for both.
-template <class L>
-static void launch_with_excl(const PairExclusions *ex, L &&launch) {
-    if (ex) launch(std::true_type{}, ExclRows{ex->row_off, ex->entries, ex->n});
-    else launch(std::false_type{}, ExclRows{nullptr, nullptr, 0u});
 }
 void launch_pair_repulsion(const double4 *pos_s, const unsigned *tag_s, int N, const int *cell_off, DBox box, DCells nc,
                            double k, double sigma, int accumulate, double4 *force, double *rows, double *out8, hipStream_t s,
@@ -284,6 +244,9 @@ k_type_mirror(const unsigned *__restrict__ tag_s, int N, const unsigned char *__
         const unsigned t = tag_s[i];
         type_s[i] = t < n ? types[t] : (unsigned char)0;   // never past n
     }
+}
+void launch_type_mirror(const unsigned *tag_s, int N, const unsigned char *types, unsigned n, unsigned char *type_s, hipStream_t s) {
+    hipLaunchKernelGGL(k_type_mirror, dim3(nblocks(N, TPB)), dim3(TPB), 0, s, tag_s, N, types, n, type_s);
 }
 template <bool OBS, bool EXCL>
 __global__ void __launch_bounds__(TPB)

@@ -421,6 +421,72 @@ int clusters_label_validate(const void *g, const void *g_handle, unsigned n_max,
     return 0;
 }
 
+int bond_order_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rnb, int nl,
+                               const int *degrees) {
+    const char *who = "pse_bond_order_create";
+    if (int rc = sizes_in_range(who, n_max, n, ntypes)) return rc;
+    if (!rnb) return fail(PSE_ERR_INVALID, "%s: null rnb_host", who);
+    const int npt = ntypes * (ntypes + 1) / 2;
+    bool on = false;
+    for (int p = 0; p < npt; ++p) {
+        if (!std::isfinite(rnb[p])) return fail(PSE_ERR_INVALID, "%s: pair type %d has rnb = %g, which is not finite", who, p, rnb[p]);
+        if (rnb[p] < 0.0) return fail(PSE_ERR_INVALID, "%s: pair type %d has rnb = %g, which is negative (0 switches a pair type off)", who, p, rnb[p]);
+        if (rnb[p] > rcut)
+            return fail(PSE_ERR_INVALID, "%s: pair type %d has rnb = %.4f beyond rcut = %.4f: the cell list is built for the hydrodynamic cutoff", who,
+                        p, rnb[p], rcut);
+        on = on || rnb[p] > 0.0;
+    }
+    if (!on) return fail(PSE_ERR_INVALID, "%s: every pair type is off (rnb = 0): nobody would have a neighbour", who);
+    if (int rc = types_in_range(who, n, types, ntypes)) return rc;
+    if (nl < 1 || nl > BOND_ORDER_MAX_DEGREES) return fail(PSE_ERR_INVALID, "%s: nl = %d outside [1, %d]", who, nl, BOND_ORDER_MAX_DEGREES);
+    if (!degrees) return fail(PSE_ERR_INVALID, "%s: null degrees_host", who);
+    for (int d = 0; d < nl; ++d)
+        if (degrees[d] < 2 || degrees[d] > BOND_ORDER_MAX_L || (degrees[d] & 1))
+            return fail(PSE_ERR_INVALID, "%s: degree %d = %d is not one of the even degrees 2..%d", who, d, degrees[d], BOND_ORDER_MAX_L);
+    for (int d = 0; d < nl; ++d)
+        for (int e = 0; e < d; ++e)
+            if (degrees[e] == degrees[d]) return fail(PSE_ERR_INVALID, "%s: the degree %d is listed twice (degrees %d and %d)", who, degrees[d], e, d);
+    return 0;
+}
+
+int bond_order_compute_validate(const void *b, const void *b_handle, int nl, unsigned n_max, int n_slabs, unsigned N, const void *pos,
+                                const void *nnb, const void *q, const void *qbar, int solid_degree, double threshold, const void *nconn,
+                                const void *stats, const void *ex, const void *ex_handle) {
+    const char *who = "pse_bond_order_compute";
+    if (!b) return fail(PSE_ERR_INVALID, "%s: null bond-order object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!nnb && !q && !qbar && !nconn && !stats) return fail(PSE_ERR_INVALID, "%s: nnb, q, qbar, nconn and stats are all null: nothing to write", who);
+    if (solid_degree < -1 || solid_degree >= nl)
+        return fail(PSE_ERR_INVALID, "%s: solid_degree = %d outside [-1, nl = %d): an index into the degrees, or -1", who, solid_degree, nl);
+    if (solid_degree >= 0 && !(std::isfinite(threshold) && threshold >= -1.0 && threshold <= 1.0))
+        return fail(PSE_ERR_INVALID, "%s: threshold = %g outside [-1, 1] (s_ij is a normalised scalar product)", who, threshold);
+    if (((uintptr_t)stats & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: stats is not 8-byte aligned (64-bit words)", who);
+    if (ex) if (int rc = pair_excl_validate(who, ex, ex_handle, b_handle)) return rc;
+    if (n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "%s: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the neighbours would be partial", who,
+                    n_slabs);
+    return 0;
+}
+
+int bond_order_histogram_validate(const void *b, int nl, int ntypes, unsigned n_max, const void *values, int column, unsigned N, int nbins,
+                                  double lo, double hi, const void *counts) {
+    const char *who = "pse_bond_order_histogram";
+    if (!b) return fail(PSE_ERR_INVALID, "%s: null bond-order object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!values) return fail(PSE_ERR_INVALID, "%s: null values", who);
+    if (column < 0 || column >= nl) return fail(PSE_ERR_INVALID, "%s: column = %d outside [0, nl = %d)", who, column, nl);
+    if (nbins < 1) return fail(PSE_ERR_INVALID, "%s: nbins = %d, need at least one bin", who, nbins);
+    if ((long long)ntypes * nbins > BOND_ORDER_MAX_COUNTERS)
+        return fail(PSE_ERR_INVALID, "%s: %d types x %d bins = %lld counters, more than %d (the counters are kept in 32 KB of LDS)", who, ntypes, nbins,
+                    (long long)ntypes * nbins, BOND_ORDER_MAX_COUNTERS);
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(PSE_ERR_INVALID, "%s: lo = %g, hi = %g must be finite", who, lo, hi);
+    if (!(hi > lo)) return fail(PSE_ERR_INVALID, "%s: hi = %g must exceed lo = %g", who, hi, lo);
+    if (!counts) return fail(PSE_ERR_INVALID, "%s: null counts", who);
+    if (((uintptr_t)counts & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: counts is not 8-byte aligned (64-bit counters)", who);
+    return 0;
+}
+
 void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> &perm, std::vector<unsigned> &uoff, std::vector<int> &segs) {
     perm.resize(nk);
     for (unsigned q = 0; q < nk; ++q) perm[q] = q;

@@ -1,5 +1,5 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
-// typed table, histogram, clusters), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors and displacement
+// typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors and displacement
 // moments.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 
 #include "pse_handle.h"
 #include "pse_forces.h"
+#include "pse_order.h"
 
 // A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
 // and, for bonds, the counter of overstretched FENE bonds.
@@ -35,6 +36,7 @@ struct pse_clusters : DeviceObject {
     ClusterLinks cl{};
     unsigned known_status = 0u;             // the last word pse_clusters_status read
 };
+struct pse_bond_order : DeviceObject { BondOrder bo{}; };
 struct pse_structure_factor : DeviceObject { StructureFactor sf{}; };
 struct pse_msd : DeviceObject {
     MsdOrigins mo{};
@@ -83,7 +85,7 @@ static int object_destroy(DeviceObject *t) {
     return 0;
 }
 
-// What the five passes over the cell list share behind their validators: the device, the sort with the cell list, and the rows of an
+// What the six passes over the cell list share behind their validators: the device, the sort with the cell list, and the rows of an
 // optional exclusion object as the launches take them (rows == null: a plain pass).
 struct CellPass {
     PairExclusions er{};
@@ -475,5 +477,54 @@ extern "C" int pse_clusters_status(pse_clusters *g, unsigned *status) {
     HIPCHK(hipMemcpyAsync(&g->known_status, g->cl.status, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *status = g->known_status;
+    return 0;
+}
+
+// Bond-orientational order (include/pse_amd.h): the types, the neighbour distances and the workspace of the c_lm rows on the device,
+// and the two passes.  Queue-only: the sort, the type mirror, one launch per degree and pass; nothing is read back.
+extern "C" int pse_bond_order_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, const double *rnb_host, int nl,
+                                     const int *degrees_host, pse_bond_order **out) {
+    const char *who = "pse_bond_order_create";
+    TRY(create_begin(who, h, out));
+    TRY(bond_order_create_validate(h->d.rcut, (unsigned)h->n_max, n, types_host, ntypes, rnb_host, nl, degrees_host));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> rn2((size_t)(ntypes * (ntypes + 1) / 2));
+    pse_bond_order *b = new pse_bond_order();
+    b->h = h;
+    BondOrder &bo = b->bo;
+    bo.n = n; bo.ntypes = ntypes; bo.nl = nl;
+    for (size_t p = 0; p < rn2.size(); ++p) { rn2[p] = rnb_host[p] * rnb_host[p]; bo.r2_all = std::max(bo.r2_all, rn2[p]); }
+    for (int d = 0; d < nl; ++d) { bo.degree[d] = degrees_host[d]; bo.off[d] = bo.stride; bo.stride += degrees_host[d] + 1; }
+    const size_t nm = (size_t)h->n_max;
+    hipError_t e = b->put(&bo.types, type_bytes(types_host, n).data(), n);
+    e = b->put(&bo.type_s, nullptr, nm);
+    e = b->put(&bo.rnb2, rn2.data(), rn2.size());
+    e = b->put(&bo.clm, nullptr, nm * (size_t)bo.stride);
+    e = b->put(&bo.ql_s, nullptr, nm * (size_t)nl);
+    return create_end(who, h, b, e, out);
+}
+extern "C" int pse_bond_order_destroy(pse_bond_order *b) { return object_destroy(b); }
+extern "C" int pse_bond_order_compute(pse_bond_order *b, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *nnb, double *q,
+                                      double *qbar, int solid_degree, double threshold, unsigned min_conn, unsigned *nconn,
+                                      unsigned long long *stats, const pse_exclusions *ex) {
+    pse_handle *h = b ? b->h : nullptr;
+    TRY(bond_order_compute_validate(b, h, b ? b->bo.nl : 0, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, N, pos, nnb, q, qbar, solid_degree,
+                                    threshold, nconn, stats, ex, ex ? ex->h : nullptr));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    launch_bond_order(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, b->bo, nnb, q, qbar, solid_degree, threshold, min_conn, nconn,
+                      stats, h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched.
+extern "C" int pse_bond_order_histogram(pse_bond_order *b, const double *values, int column, const unsigned *group, unsigned N, int nbins,
+                                        double lo, double hi, unsigned long long *counts) {
+    pse_handle *h = b ? b->h : nullptr;
+    TRY(bond_order_histogram_validate(b, b ? b->bo.nl : 0, b ? b->bo.ntypes : 1, h ? (unsigned)h->n_max : 0u, values, column, N, nbins, lo, hi,
+                                      counts));
+    HIPCHK(hipSetDevice(h->device));
+    launch_bond_order_hist(values, b->bo.nl, column, group, (int)N, (unsigned)h->n_max, b->bo, nbins, lo, hi, counts, h->stream);
+    HIPCHK(hipGetLastError());
     return 0;
 }

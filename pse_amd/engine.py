@@ -485,10 +485,10 @@ class DisplacementOrigins(_DeviceObject):
         self._create(engine, "pse_msd_create", self.n, _vp(types), self.ntypes, self.norigins)
 
 
-def _cluster_arguments(types, ntypes, rlink):
+def _cluster_arguments(types, ntypes, rlink, name="rlink"):
     """The arguments of a ClusterLinks, checked before the device is touched: (types uint32 (n,) or None, ntypes, rlink float64 (npt,)).
     `rlink`: a scalar (every pair type), a dict {(a, b): r} in either key order with a missing pair off, or npt entries in the
-    order of pair_type_index; 0 switches a pair type off, at least one must be on."""
+    order of pair_type_index; 0 switches a pair type off, at least one must be on.  `name`: what the messages call the distances."""
     import numpy as np
     ntypes = int(ntypes)
     if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
@@ -499,10 +499,10 @@ def _cluster_arguments(types, ntypes, rlink):
         seen = set()
         for key, r in rlink.items():
             if not (isinstance(key, tuple) and len(key) == 2 and all(isinstance(v, (int, np.integer)) and 0 <= v < ntypes for v in key)):
-                raise ValueError(f"rlink key {key!r}: need a pair (a, b) of types in [0, {ntypes})")
+                raise ValueError(f"{name} key {key!r}: need a pair (a, b) of types in [0, {ntypes})")
             p = pair_type_index(int(key[0]), int(key[1]), ntypes)
             if p in seen:
-                raise ValueError(f"rlink names the pair of types {tuple(sorted(key))} twice")
+                raise ValueError(f"{name} names the pair of types {tuple(sorted(key))} twice")
             seen.add(p)
             out[p] = float(r)
     elif np.ndim(rlink) == 0:
@@ -510,11 +510,11 @@ def _cluster_arguments(types, ntypes, rlink):
     else:
         out = np.array(rlink, dtype=np.float64)
         if out.shape != (npt,):
-            raise ValueError(f"rlink must be a scalar, a dict or {npt} entries, one per pair of types")
+            raise ValueError(f"{name} must be a scalar, a dict or {npt} entries, one per pair of types")
     if not np.isfinite(out).all() or (out < 0.0).any():
-        raise ValueError("rlink must be finite and not negative (0 switches a pair type off)")
+        raise ValueError(f"{name} must be finite and not negative (0 switches a pair type off)")
     if not (out > 0.0).any():
-        raise ValueError("every pair type is off: rlink needs a positive entry")
+        raise ValueError(f"every pair type is off: {name} needs a positive entry")
     if types is not None:
         types = np.asarray(types)
         if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
@@ -548,6 +548,54 @@ class ClusterLinks(_DeviceObject):
         word = ctypes.c_uint(0)
         _lib.check(self._lib.pse_clusters_status(self._handle(), ctypes.byref(word)))
         return int(word.value)
+
+
+BOND_ORDER_MAX_DEGREES = 4               # pse_bond_order_create: degrees of one object
+BOND_ORDER_DEGREES = (2, 4, 6, 8, 10, 12)  # ... and what they may be
+BOND_ORDER_MAX_COUNTERS = 8192           # pse_bond_order_histogram: types x bins
+
+
+def _bond_order_arguments(types, ntypes, rnb, degrees):
+    """The arguments of a BondOrderShells, checked before the device is touched: (types uint32 (n,) or None, ntypes, rnb float64
+    (npt,), degrees int32 (nl,)).  `rnb`: the three forms of _cluster_arguments' rlink; `degrees`: 1 to 4 distinct even integers from
+    2 to 12."""
+    import numpy as np
+    types, ntypes, rnb = _cluster_arguments(types, ntypes, rnb, "rnb")
+    deg = np.asarray(degrees)
+    if deg.ndim != 1 or not 1 <= deg.shape[0] <= BOND_ORDER_MAX_DEGREES or not np.issubdtype(deg.dtype, np.integer):
+        raise ValueError(f"degrees must be 1 to {BOND_ORDER_MAX_DEGREES} integers")
+    for l in deg.tolist():
+        if l not in BOND_ORDER_DEGREES:
+            raise ValueError(f"degree {l} is not one of the even degrees {BOND_ORDER_DEGREES}")
+    if len(set(deg.tolist())) != deg.shape[0]:
+        raise ValueError("degrees names a degree twice")
+    return types, ntypes, rnb, np.ascontiguousarray(deg, dtype=np.int32)
+
+
+class BondOrderShells(_DeviceObject):
+    """Owner of a pse_bond_order object: one type per particle, one neighbour distance per pair of types and the degrees l of the
+    Steinhardt parameters (see _bond_order_arguments).  `types`: (n,) integers below ntypes, the type of caller-order particle t, or
+    None: one type; a particle past them acts as type 0.  Pass it as `shells` to Engine.bond_order and Engine.bond_order_histogram."""
+
+    DESTROY = "pse_bond_order_destroy"
+
+    def __init__(self, engine, types, ntypes, rnb, degrees=(4, 6), n=None):
+        types, self.ntypes, self.rnb, self.degrees = _bond_order_arguments(types, ntypes, rnb, degrees)
+        self.npt, self.nl = self.ntypes * (self.ntypes + 1) // 2, int(self.degrees.shape[0])
+        if types is None:
+            self.n = _rows(engine, n)
+        else:
+            self.n = int(types.shape[0] if n is None else n)
+            if not 0 <= self.n <= types.shape[0]:
+                raise ValueError("n outside [0, len(types)]")
+        self._create(engine, "pse_bond_order_create", self.n, _vp(types), self.ntypes, _vp(self.rnb), self.nl, _vp(self.degrees))
+
+    def column(self, l):
+        """The column of degree `l` in q and qbar."""
+        cols = self.degrees.tolist()
+        if int(l) not in cols:
+            raise ValueError(f"degree {l} is not among the degrees {tuple(cols)} of this object")
+        return cols.index(int(l))
 
 
 class _ForcePasses:
@@ -779,6 +827,80 @@ class _ForcePasses:
             if w is not None:
                 t.copy_(w)
         return label, size, stats, hist
+
+    def bond_order_shells(self, types, ntypes, rnb, degrees=(4, 6), n=None):
+        """The neighbour criterion and the degrees of a bond-order analysis on the device (pse_bond_order_create; see
+        include/pse_amd.h): `types` (n,) the type of every caller-order particle, below `ntypes` <= 8, or None: one type; `rnb`: a
+        scalar, a dict {(a, b): r} (a missing pair is off) or npt entries, each 0 (off) or in (0, rcut]; `degrees`: 1 to 4 distinct
+        even l from 2 to 12; `n`: how many of `types` to use (default: all; without types: n_max).  Returns a BondOrderShells: the
+        `shells` of bond_order."""
+        return BondOrderShells(self, types, ntypes, rnb, degrees, n)
+
+    def bond_order(self, pos, shells, nnb=None, q=None, qbar=None, solid=None, nconn=None, stats=None, group=None, exclusions=None):
+        """The Steinhardt bond-orientational order of the group members (pse_bond_order_compute): two particles are neighbours when
+        0 < r < rnb of their pair of types and the pair is not in `exclusions`.  All outputs are CUDA tensors, any may be None, not all:
+        `nnb`, `nconn`: contiguous 1-D int32 tensors of at least pos.shape[0] entries, by caller index -- the number of neighbours
+        and the number of them connected by a solid-like bond; `q`, `qbar`: contiguous (>= pos.shape[0], nl) float64 -- q_l and the
+        neighbour-averaged q-bar_l, one column per degree of `shells`; entries outside the group are left alone;
+        `stats`: contiguous (ntypes, 2) int64, OVERWRITTEN with the members and the solid-like members of every type.
+        `solid`: None (no solid-bond pass: nconn is not written, the solid counts are 0) or (degree, threshold, min_conn): a bond is
+        solid-like when the normalised product s_ij of the two c_lm vectors of `degree` exceeds `threshold`, a particle with at least
+        `min_conn` of them.  Queue-only: nothing is read back, no floating-point atomics: equal inputs give equal bits.
+        Returns (nnb, q, qbar, nconn, stats)."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        for t, name in ((nnb, "nnb"), (nconn, "nconn")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1
+                                      and t.is_contiguous() and t.shape[0] >= pos.shape[0]):
+                raise ValueError(f"{name} must be a contiguous 1-D int32 CUDA tensor of at least {pos.shape[0]} entries")
+        for t, name in ((q, "q"), (qbar, "qbar")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2
+                                      and t.is_contiguous() and t.shape[0] >= pos.shape[0] and t.shape[1] == shells.nl):
+                raise ValueError(f"{name} must be a contiguous (N >= {pos.shape[0]}, {shells.nl}) float64 CUDA tensor")
+        if stats is not None and not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int64
+                                      and stats.is_contiguous() and tuple(stats.shape) == (shells.ntypes, 2)):
+            raise ValueError(f"stats must be a contiguous ({shells.ntypes}, 2) int64 CUDA tensor")
+        if nnb is None and q is None and qbar is None and nconn is None and stats is None:
+            raise ValueError("nnb, q, qbar, nconn and stats are all None: nothing to compute")
+        column, threshold, min_conn = -1, 0.0, 0
+        if solid is not None:
+            degree, threshold, min_conn = solid
+            column, threshold, min_conn = shells.column(degree), _finite(threshold, "threshold"), int(min_conn)
+            if not -1.0 <= threshold <= 1.0:
+                raise ValueError(f"threshold = {threshold} outside [-1, 1]")
+            if not 0 <= min_conn < 2 ** 32:
+                raise ValueError(f"min_conn = {min_conn} outside [0, 2^32)")
+        _lib.check(self._lib.pse_bond_order_compute(shells._handle(self), _ptr(pos), _ptr(group), n, _ptr(nnb), _ptr(q), _ptr(qbar), column,
+                                                    threshold, min_conn, _ptr(nconn), _ptr(stats),
+                                                    None if exclusions is None else exclusions._handle(self)))
+        return nnb, q, qbar, nconn, stats
+
+    def bond_order_histogram(self, values, shells, l, counts, lo=0.0, hi=1.0, group=None, n=None):
+        """One sample of the per-type distribution of a bond-order parameter (pse_bond_order_histogram): the group member t of type a
+        with lo <= v < hi, v = values[t, column of degree l], adds 1 to counts[a, b], b = min(int((v - lo) nbins / (hi - lo)),
+        nbins - 1).  `values`: a contiguous (N, nl) float64 CUDA tensor by caller index, q or qbar of bond_order; `counts`: a
+        contiguous (ntypes, nbins) int64 CUDA tensor, ADDED to; `n`: the number of group members without a group (default: the rows
+        of values).  Queue-only; integers only.  Returns counts."""
+        import torch
+        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float64 and values.dim() == 2
+                and values.is_contiguous() and values.shape[1] == shells.nl):
+            raise ValueError(f"values must be a contiguous (N, {shells.nl}) float64 CUDA tensor")
+        _chk_group(group)
+        if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()
+                and counts.dim() == 2 and counts.shape[0] == shells.ntypes and counts.shape[1] >= 1):
+            raise ValueError(f"counts must be a contiguous ({shells.ntypes}, nbins) int64 CUDA tensor")
+        if shells.ntypes * int(counts.shape[1]) > BOND_ORDER_MAX_COUNTERS:
+            raise ValueError(f"{shells.ntypes} types x {int(counts.shape[1])} bins, more than {BOND_ORDER_MAX_COUNTERS} counters")
+        lo, hi = _finite(lo, "lo"), _finite(hi, "hi")
+        if not hi > lo:
+            raise ValueError(f"hi = {hi} must exceed lo = {lo}")
+        members = (values.shape[0] if n is None else int(n)) if group is None else group.shape[0]
+        if group is None and members > values.shape[0]:
+            raise ValueError("n exceeds the rows of values")
+        _lib.check(self._lib.pse_bond_order_histogram(shells._handle(self), _ptr(values), shells.column(l), _ptr(group), members,
+                                                      int(counts.shape[1]), lo, hi, _ptr(counts)))
+        return counts
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
