@@ -11,16 +11,18 @@ over the sorted rows (pse_clusters_label), with the number of clusters, the larg
 BondOrder says whether a neighbourhood is ordered: the Steinhardt q_l, the neighbour-averaged q-bar_l and the solid-like bonds of
 every particle (pse_bond_order_compute: spherical harmonics up to degree 12 summed over the neighbours on the cell list), with their
 per-type distributions and the solid-like fraction per sample."""
+import contextlib
 import math
 
-from .engine import (BOND_ORDER_MAX_COUNTERS, MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, BondOrderShells, ClusterLinks, _bond_order_arguments, DisplacementOrigins, PairHistogram, StructureFactorModes, _cluster_arguments, _msd_arguments,
-                     _pair_hist_arguments, _structure_factor_arguments, pair_type_index)
+from .engine import (BOND_ORDER_MAX_COUNTERS, MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, BondOrderShells, ClusterLinks, DisplacementOrigins,
+                     PairHistogram, StructureFactorModes, _bond_order_arguments, _cluster_arguments, _msd_arguments, _ntypes_argument,
+                     _pair_hist_arguments, _structure_factor_arguments, _types_argument, pair_type_index)
 from .forces import _excl_list
 
 
-def _rdf_arguments(nbins, rmax, rmin, types, type_names, period):
-    """What RDF checks before it touches the device: `types` as integers -- a name is its position in `type_names` --, the number of
-    types, the bins and the period.  Returns (types uint32 or None, ntypes, nbins, rmin, rmax, names or None, period)."""
+def _typed_arguments(types, type_names, period):
+    """What every analyzer checks first, before it touches the device: `types` as integers -- a name is its position in `type_names`
+    --, the number of types and the period.  Returns (types uint32 or None, ntypes, names or None, period)."""
     names = None if type_names is None else list(type_names)
     if names is not None and (not names or len(set(names)) != len(names) or not all(isinstance(v, str) for v in names)):
         raise ValueError("type_names must be distinct strings")
@@ -36,13 +38,14 @@ def _rdf_arguments(nbins, rmax, rmin, types, type_names, period):
         if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
             raise ValueError("types must be a non-empty 1-D sequence of non-negative integers or names, one per particle")
         ntypes = max(int(types.max()) + 1, len(names or ()))
-    return _pair_hist_arguments(types, ntypes, nbins, rmin, rmax) + (names, int(period))
+    ntypes = _ntypes_argument(ntypes)
+    return _types_argument(types, ntypes), ntypes, names, int(period)
 
 
-def _typed_arguments(types, type_names, period):
-    """The part of _rdf_arguments that knows no bins: (types as an integer array or None, ntypes, names or None, period)."""
-    types, ntypes, _, _, _, names, period = _rdf_arguments(1, 1.0, 0.0, types, type_names, period)
-    return types, ntypes, names, period
+def _rdf_arguments(nbins, rmax, rmin, types, type_names, period):
+    """_typed_arguments and the bins of RDF.  Returns (types uint32 or None, ntypes, nbins, rmin, rmax, names or None, period)."""
+    types, ntypes, names, period = _typed_arguments(types, type_names, period)
+    return _pair_hist_arguments(types, ntypes, nbins, rmin, rmax) + (names, period)
 
 
 def _type_codes(values, names):
@@ -57,6 +60,87 @@ def _type_codes(values, names):
             v = names.index(v)
         out.append(v)
     return out
+
+
+def _pair_dict_codes(r, names, word):
+    """A dict {(a, b): r} over pairs of types, whose keys may name their types by `names`, with integer keys (a <= b); anything but a
+    dict comes back as it is.  `word`: what the messages call the distances."""
+    if not isinstance(r, dict):
+        return r
+    coded = {}
+    for key, v in r.items():
+        if not (isinstance(key, tuple) and len(key) == 2):
+            raise ValueError(f"{word} key {key!r}: need a pair (a, b) of types")
+        coded.setdefault(tuple(sorted(_type_codes(list(key), names))), []).append(v)
+    if any(len(v) > 1 for v in coded.values()):
+        raise ValueError(f"{word} names a pair of types twice")
+    return {k: v[0] for k, v in coded.items()}
+
+
+class _TypedAnalyzer:
+    """What the analyzers share: one type per particle of the system (`types`, `ntypes`, `type_names`), a `period`, a count of
+    `samples`, and their place in system.analyzers."""
+
+    @contextlib.contextmanager
+    def _attach(self, integrator, types):
+        """Around the rest of __init__: refuses `types` of another length than the system first, and registers the analyzer with
+        the system last -- only when the block, which makes the device object, has not raised.  Yields the system."""
+        import numpy as np
+        system = integrator.system
+        if types is not None and types.shape[0] != system.n:
+            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
+        self.integrator, self.system = integrator, system
+        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
+        yield system
+        system.analyzers.append(self)
+
+    def _due(self, timestep):
+        return timestep % self.period == 0
+
+    def _code(self, v):
+        v = _type_codes([v], self.type_names)[0]
+        if not 0 <= int(v) < self.ntypes:
+            raise ValueError(f"type {v} outside [0, {self.ntypes})")
+        return int(v)
+
+    def _type_counts(self):
+        """N_a among the members of the integrator's group."""
+        import numpy as np
+        m = self.integrator.group.members
+        t = self.types if m is None else self.types[m.cpu().numpy()]
+        return np.bincount(t, minlength=self.ntypes)
+
+    def _sampled(self):
+        if self.samples < 1:
+            raise ValueError("no samples yet")
+
+
+class _SampleRing:
+    """The ring of per-sample rows that Clusters and BondOrder keep: `_rows`, a device tensor of `capacity` rows that the sample
+    writes its slot of, and the timestep of every slot on the host.  Once full, the oldest rows are replaced."""
+
+    def _ring_reset(self):
+        self._steps = [None] * self.capacity
+        self.samples = 0
+
+    def _slot(self):
+        """Where this sample's row goes."""
+        return self.samples % self.capacity
+
+    def _record(self, slot, timestep):
+        self._steps[slot] = int(timestep)
+        self.samples += 1
+
+    def table(self):
+        """(samples kept, 1 + the words of a row) int64, oldest first: the timestep, then the sample's row (one copy from the device)."""
+        import numpy as np
+        n = min(self.samples, self.capacity)
+        dev = self._rows.cpu().numpy().reshape(self.capacity, -1)
+        out = np.zeros((n, 1 + dev.shape[1]), dtype=np.int64)
+        for r in range(n):
+            q = (self.samples - n + r) % self.capacity
+            out[r, 0], out[r, 1:] = self._steps[q], dev[q]
+        return out
 
 
 def bin_edges(nbins, rmin, rmax):
@@ -113,7 +197,7 @@ def coordination_of_counts(counts, samples, type_counts, a, b, edges, r):
     return (2.0 if a == b else 1.0) * pairs / float(type_counts[a])
 
 
-class RDF:
+class RDF(_TypedAnalyzer):
     """Radial distribution functions of a run: every `period` steps the distances of all pairs of the integrator's group below `rmax`
     are binned on the device (pse_pair_hist_accumulate), one row of `nbins` uniform bins on [rmin, rmax) per pair of types, into an
     int64 CUDA tensor of this object.  Sampling only queues work; the readers below are the only places that wait for the device.
@@ -125,25 +209,19 @@ class RDF:
     coordination(a, b, r);  samples;  reset()."""
 
     def __init__(self, integrator, nbins, rmax, rmin=0.0, types=None, type_names=None, exclusions=None, period=1):
-        import numpy as np
         import torch
         types, self.ntypes, self.nbins, self.rmin, self.rmax, self.type_names, self.period = _rdf_arguments(
             nbins, rmax, rmin, types, type_names, period)   # (raises before the device is touched)
-        system = integrator.system
-        if types is not None and types.shape[0] != system.n:
-            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
-        self.integrator, self.system = integrator, system
-        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
-        self._excl = _excl_list(integrator, exclusions)
-        self._hist = PairHistogram(integrator.engine, types, self.ntypes, self.nbins, self.rmin, self.rmax, system.n)
-        self.npt = self._hist.npt
-        self._counts = torch.zeros((self.npt, self.nbins), dtype=torch.int64, device=system.pos.device)
-        self.samples = 0
-        self._volume = 0.0      # the sum of the box volumes of the samples
-        system.analyzers.append(self)
+        with self._attach(integrator, types) as system:
+            self._excl = _excl_list(integrator, exclusions)
+            self._hist = PairHistogram(integrator.engine, types, self.ntypes, self.nbins, self.rmin, self.rmax, system.n)
+            self.npt = self._hist.npt
+            self._counts = torch.zeros((self.npt, self.nbins), dtype=torch.int64, device=system.pos.device)
+            self.samples = 0
+            self._volume = 0.0      # the sum of the box volumes of the samples
 
     def analyze(self, timestep):
-        if timestep % self.period:
+        if not self._due(timestep):
             return
         s = self.system
         self.integrator.engine.pair_hist_accumulate(s.pos, self._hist, self._counts, group=self.integrator.group.members,
@@ -154,19 +232,6 @@ class RDF:
     def reset(self):
         self._counts.zero_()
         self.samples, self._volume = 0, 0.0
-
-    def _code(self, v):
-        v = _type_codes([v], self.type_names)[0]
-        if not 0 <= int(v) < self.ntypes:
-            raise ValueError(f"type {v} outside [0, {self.ntypes})")
-        return int(v)
-
-    def _type_counts(self):
-        """N_a among the members of the integrator's group."""
-        import numpy as np
-        m = self.integrator.group.members
-        t = self.types if m is None else self.types[m.cpu().numpy()]
-        return np.bincount(t, minlength=self.ntypes)
 
     @property
     def counts(self):
@@ -188,8 +253,7 @@ class RDF:
         """g_ab at the bin centres, (nbins,); without arguments all pair types, (npt, nbins).  V is the mean volume of the samples."""
         if (a is None) != (b is None):
             raise ValueError("g() takes both types or neither")
-        if self.samples < 1:
-            raise ValueError("no samples yet")
+        self._sampled()
         g = g_of_counts(self.counts, self.samples, self._type_counts(), self.edges, self._volume / self.samples)
         return g if a is None else g[pair_type_index(self._code(a), self._code(b), self.ntypes)]
 
@@ -290,7 +354,7 @@ def _structure_factor_analyzer_arguments(modes, types, type_names, period):
     return types, ntypes, modes, names, period
 
 
-class StructureFactor:
+class StructureFactor(_TypedAnalyzer):
     """Static structure factors of a run: every `period` steps the densities rho_a(m) = sum_{j of type a} exp(-2 pi i m.s_j) of the
     integrator's group are summed on the device (pse_structure_factor_accumulate) for the integer modes `modes` (nk, 3) of the
     reciprocal lattice of the box AS IT IS at that step, and Re(rho_a conj rho_b) is added to a float64 CUDA tensor of this object,
@@ -305,23 +369,17 @@ class StructureFactor:
     of |k|: (centres, means, counts);  density() -- (ntypes, nk) complex, the rho of one fresh call on the current positions."""
 
     def __init__(self, integrator, modes, types=None, type_names=None, period=1):
-        import numpy as np
         import torch
         types, self.ntypes, self.modes, self.type_names, self.period = _structure_factor_analyzer_arguments(
             modes, types, type_names, period)   # (raises before the device is touched)
-        system = integrator.system
-        if types is not None and types.shape[0] != system.n:
-            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
-        self.integrator, self.system = integrator, system
-        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
-        self._sf = StructureFactorModes(integrator.engine, types, self.ntypes, self.modes, system.n)
-        self.npt, self.nk = self._sf.npt, self._sf.nk
-        self._sums = torch.zeros((self.npt, self.nk), dtype=torch.float64, device=system.pos.device)
-        self.samples, self.boxes = 0, []
-        system.analyzers.append(self)
+        with self._attach(integrator, types) as system:
+            self._sf = StructureFactorModes(integrator.engine, types, self.ntypes, self.modes, system.n)
+            self.npt, self.nk = self._sf.npt, self._sf.nk
+            self._sums = torch.zeros((self.npt, self.nk), dtype=torch.float64, device=system.pos.device)
+            self.samples, self.boxes = 0, []
 
     def analyze(self, timestep):
-        if timestep % self.period:
+        if not self._due(timestep):
             return
         s = self.system
         self.integrator.engine.structure_factor_accumulate(s.pos, self._sf, sums=self._sums, group=self.integrator.group.members)
@@ -331,9 +389,6 @@ class StructureFactor:
     def reset(self):
         self._sums.zero_()
         self.samples, self.boxes = 0, []
-
-    _code = RDF._code
-    _type_counts = RDF._type_counts
 
     @property
     def sums(self):
@@ -351,8 +406,7 @@ class StructureFactor:
         """S_ab per mode, (nk,); without arguments the total S."""
         if (a is None) != (b is None):
             raise ValueError("S() takes both types or neither")
-        if self.samples < 1:
-            raise ValueError("no samples yet")
+        self._sampled()
         if a is not None:
             a, b = self._code(a), self._code(b)
         return S_of_sums(self.sums, self.samples, self._type_counts(), a, b)
@@ -461,7 +515,7 @@ def moments_of_sums(sums, counts, type_counts, a=None):
     return np.divide(tot, den[:, None], out=np.full(tot.shape, np.nan), where=den[:, None] > 0.0)
 
 
-class MSD:
+class MSD(_TypedAnalyzer):
     """Displacement moments of a run over many time origins: every `period` steps (a sample) the displacements d of the integrator's
     group since each live origin are reduced on the device (pse_msd_accumulate) to ten sums per particle type and lag -- dx dy dz,
     dx^2 dy^2 dz^2 dxdy dxdz dydz, |d|^4 -- in a float64 CUDA tensor of this object, and every `origin_every` samples the unwrapped
@@ -482,23 +536,17 @@ class MSD:
     particle against the CURRENT positions: d and |d|^2;  reset().  a = None: all types together."""
 
     def __init__(self, integrator, nlags, origin_every=1, types=None, type_names=None, period=1):
-        import numpy as np
         import torch
         self._schedule, types, self.ntypes, self.type_names, self.period = _msd_analyzer_arguments(
             nlags, origin_every, types, type_names, period)   # (raises before the device is touched)
-        system = integrator.system
-        if types is not None and types.shape[0] != system.n:
-            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
-        self.integrator, self.system = integrator, system
-        self.nlags, self.origin_every, self.norigins = self._schedule.nlags, self._schedule.origin_every, self._schedule.norigins
-        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
-        self._origins = DisplacementOrigins(integrator.engine, types, self.ntypes, self.norigins, system.n)
-        self._sums = torch.zeros((self.nlags, self.ntypes, MSD_MOMENTS), dtype=torch.float64, device=system.pos.device)
-        self.flipped = False      # a sample was taken with tilt_flips != 0: the moments that contain x are not to be trusted
-        system.analyzers.append(self)
+        with self._attach(integrator, types) as system:
+            self.nlags, self.origin_every, self.norigins = self._schedule.nlags, self._schedule.origin_every, self._schedule.norigins
+            self._origins = DisplacementOrigins(integrator.engine, types, self.ntypes, self.norigins, system.n)
+            self._sums = torch.zeros((self.nlags, self.ntypes, MSD_MOMENTS), dtype=torch.float64, device=system.pos.device)
+            self.flipped = False      # a sample was taken with tilt_flips != 0: the moments that contain x are not to be trusted
 
     def analyze(self, timestep):
-        if timestep % self.period:
+        if not self._due(timestep):
             return
         s, e, g = self.system, self.integrator.engine, self.integrator.group.members
         self.flipped = self.flipped or s.tilt_flips != 0
@@ -517,9 +565,6 @@ class MSD:
             warnings.warn(f"{what} contains the unwrapped x, which is shifted by flips * Ly for every y image gained after a "
                           "Lees-Edwards flip (analyze.unwrap): samples were taken in a flipped box; use the yy, zz, yz entries of "
                           "msd_tensor()", RuntimeWarning, stacklevel=3)
-
-    _code = RDF._code
-    _type_counts = RDF._type_counts
 
     @property
     def samples(self):
@@ -603,16 +648,7 @@ def _cluster_analyzer_arguments(rlink, types, type_names, period, nhist, capacit
     """What Clusters checks before it touches the device.  A dict `rlink` may name its types by `type_names`.  Returns (types uint32
     or None, ntypes, rlink (npt,), names or None, period, nhist or None, capacity)."""
     types, ntypes, names, period = _typed_arguments(types, type_names, period)
-    if isinstance(rlink, dict):
-        coded = {}
-        for key, r in rlink.items():
-            if not (isinstance(key, tuple) and len(key) == 2):
-                raise ValueError(f"rlink key {key!r}: need a pair (a, b) of types")
-            coded.setdefault(tuple(sorted(_type_codes(list(key), names))), []).append(r)
-        if any(len(v) > 1 for v in coded.values()):
-            raise ValueError("rlink names a pair of types twice")
-        rlink = {k: v[0] for k, v in coded.items()}
-    types, ntypes, rlink = _cluster_arguments(types, ntypes, rlink)
+    types, ntypes, rlink = _cluster_arguments(types, ntypes, _pair_dict_codes(rlink, names, "rlink"))
     if nhist is not None and int(nhist) < 1:
         raise ValueError("nhist must be positive")
     if int(capacity) < 1:
@@ -620,7 +656,7 @@ def _cluster_analyzer_arguments(rlink, types, type_names, period, nhist, capacit
     return types, ntypes, rlink, names, period, None if nhist is None else int(nhist), int(capacity)
 
 
-class Clusters:
+class Clusters(_TypedAnalyzer, _SampleRing):
     """Which particles hang together: every `period` steps the members of the integrator's group are labelled by the connected
     component of the links 0 < r < rlink (pse_clusters_label; a union-find on the device over the cell list the step uses anyway).
     `rlink`: a scalar, a dict {(a, b): r} over pairs of types (names with `type_names=`; a missing pair never links) or one entry per
@@ -637,49 +673,36 @@ class Clusters:
     COLUMNS = ("timestep", "clusters", "largest", "sum_s2", "N")
 
     def __init__(self, integrator, rlink, types=None, type_names=None, exclusions=None, period=1, nhist=None, capacity=1024):
-        import numpy as np
         import torch
         types, self.ntypes, self.rlink, self.type_names, self.period, nhist, self.capacity = _cluster_analyzer_arguments(
             rlink, types, type_names, period, nhist, capacity)   # (raises before the device is touched)
-        system = integrator.system
-        if types is not None and types.shape[0] != system.n:
-            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
-        self.integrator, self.system = integrator, system
-        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
-        self.nhist = system.n if nhist is None else nhist
-        self._excl = _excl_list(integrator, exclusions)
-        self._links = ClusterLinks(integrator.engine, types, self.ntypes, self.rlink, system.n)
-        dev = system.pos.device
-        self._label = torch.full((system.n,), -1, dtype=torch.int32, device=dev)
-        self._size = torch.zeros(system.n, dtype=torch.int32, device=dev)
-        self._rows = torch.zeros((self.capacity, 4), dtype=torch.int64, device=dev)
-        self._hist = torch.zeros(self.nhist, dtype=torch.int64, device=dev)
-        self._steps = [None] * self.capacity
-        self.samples = 0
-        system.analyzers.append(self)
+        with self._attach(integrator, types) as system:
+            self.nhist = system.n if nhist is None else nhist
+            self._excl = _excl_list(integrator, exclusions)
+            self._links = ClusterLinks(integrator.engine, types, self.ntypes, self.rlink, system.n)
+            dev = system.pos.device
+            self._label = torch.full((system.n,), -1, dtype=torch.int32, device=dev)
+            self._size = torch.zeros(system.n, dtype=torch.int32, device=dev)
+            self._rows = torch.zeros((self.capacity, 4), dtype=torch.int64, device=dev)
+            self._hist = torch.zeros(self.nhist, dtype=torch.int64, device=dev)
+            self._ring_reset()
 
     def analyze(self, timestep):
-        if timestep % self.period:
+        if not self._due(timestep):
             return
-        q = self.samples % self.capacity
+        q = self._slot()
         self.integrator.engine.cluster_label(self.system.pos, self._links, label=self._label, size=self._size, stats=self._rows[q],
                                              hist=self._hist, group=self.integrator.group.members, exclusions=self._excl)
-        self._steps[q] = int(timestep)
-        self.samples += 1
+        self._record(q, timestep)
 
     def reset(self):
         self._rows.zero_(); self._hist.zero_()
         self._label.fill_(-1); self._size.zero_()
-        self._steps = [None] * self.capacity
-        self.samples = 0
+        self._ring_reset()
 
     def status(self):
         """The give-up word of the device object (0: every sample was labelled completely; see include/pse_amd.h)."""
         return self._links.status()
-
-    def _sampled(self):
-        if self.samples < 1:
-            raise ValueError("no samples yet")
 
     def labels(self):
         """(n,) int64: the smallest particle index of every particle's cluster in the last sample; -1 outside the group."""
@@ -695,17 +718,6 @@ class Clusters:
         """The particle indices of the cluster whose label is `label` (the smallest index among them), ascending."""
         import numpy as np
         return np.nonzero(self.labels() == int(label))[0]
-
-    def table(self):
-        """(samples kept, 5) int64, oldest first: timestep, clusters, largest, sum of s^2, N (one copy from the device)."""
-        import numpy as np
-        n = min(self.samples, self.capacity)
-        dev = self._rows.cpu().numpy()
-        out = np.zeros((n, 5), dtype=np.int64)
-        for r in range(n):
-            q = (self.samples - n + r) % self.capacity
-            out[r, 0], out[r, 1:] = self._steps[q], dev[q]
-        return out
 
     def size_distribution(self):
         """n(s) for s = 1 .. nhist: the mean number of clusters of s members per sample since the last reset(); its sum is the mean
@@ -757,16 +769,7 @@ def _bond_order_analyzer_arguments(rnb, degrees, types, type_names, period, soli
     """What BondOrder checks before it touches the device.  A dict `rnb` may name its types by `type_names`.  Returns (types uint32 or
     None, ntypes, rnb (npt,), degrees int32, names or None, period, solid or None, nbins, capacity)."""
     types, ntypes, names, period = _typed_arguments(types, type_names, period)
-    if isinstance(rnb, dict):
-        coded = {}
-        for key, r in rnb.items():
-            if not (isinstance(key, tuple) and len(key) == 2):
-                raise ValueError(f"rnb key {key!r}: need a pair (a, b) of types")
-            coded.setdefault(tuple(sorted(_type_codes(list(key), names))), []).append(r)
-        if any(len(v) > 1 for v in coded.values()):
-            raise ValueError("rnb names a pair of types twice")
-        rnb = {k: v[0] for k, v in coded.items()}
-    types, ntypes, rnb, degrees = _bond_order_arguments(types, ntypes, rnb, degrees)
+    types, ntypes, rnb, degrees = _bond_order_arguments(types, ntypes, _pair_dict_codes(rnb, names, "rnb"), degrees)
     if solid is not None:
         if not (isinstance(solid, (tuple, list)) and len(solid) == 3):
             raise ValueError("solid must be None or (degree, threshold, min_conn)")
@@ -785,7 +788,7 @@ def _bond_order_analyzer_arguments(rnb, degrees, types, type_names, period, soli
     return types, ntypes, rnb, degrees, names, period, solid, int(nbins), int(capacity)
 
 
-class BondOrder:
+class BondOrder(_TypedAnalyzer, _SampleRing):
     """Whether the neighbourhoods are ordered: every `period` steps the Steinhardt bond-orientational order parameters q_l of the
     members of the integrator's group, their neighbour-averaged form q-bar_l (Lechner and Dellago) and, with `solid=(degree, threshold,
     min_conn)`, e.g. (6, 0.7, 7), the solid-like bonds of ten Wolde, Ruiz-Montero and Frenkel (pse_bond_order_compute: two passes over
@@ -805,51 +808,38 @@ class BondOrder:
 
     def __init__(self, integrator, rnb, degrees=(4, 6), types=None, type_names=None, exclusions=None, period=1, solid=None, nbins=100,
                  capacity=1024):
-        import numpy as np
         import torch
         types, self.ntypes, self.rnb, self.degrees, self.type_names, self.period, self.solid, self.nbins, self.capacity = \
             _bond_order_analyzer_arguments(rnb, degrees, types, type_names, period, solid, nbins, capacity)   # (raises before the device is touched)
-        system = integrator.system
-        if types is not None and types.shape[0] != system.n:
-            raise ValueError(f"types has {types.shape[0]} entries, the system {system.n} particles")
-        self.integrator, self.system = integrator, system
-        self.types = np.zeros(system.n, dtype=np.uint32) if types is None else types
-        self.nl = int(self.degrees.shape[0])
-        self._excl = _excl_list(integrator, exclusions)
-        self._shells = BondOrderShells(integrator.engine, types, self.ntypes, self.rnb, self.degrees, system.n)
-        dev = system.pos.device
-        self._nnb = torch.zeros(system.n, dtype=torch.int32, device=dev)
-        self._nconn = torch.zeros(system.n, dtype=torch.int32, device=dev)
-        self._q = torch.zeros((system.n, self.nl), dtype=torch.float64, device=dev)
-        self._qbar = torch.zeros((system.n, self.nl), dtype=torch.float64, device=dev)
-        self._rows = torch.zeros((self.capacity, self.ntypes, 2), dtype=torch.int64, device=dev)
-        self._hist = torch.zeros((2, self.nl, self.ntypes, self.nbins), dtype=torch.int64, device=dev)   # [q | q-bar][degree][type][bin]
-        self._steps = [None] * self.capacity
-        self.samples = 0
-        system.analyzers.append(self)
+        with self._attach(integrator, types) as system:
+            self.nl = int(self.degrees.shape[0])
+            self._excl = _excl_list(integrator, exclusions)
+            self._shells = BondOrderShells(integrator.engine, types, self.ntypes, self.rnb, self.degrees, system.n)
+            dev = system.pos.device
+            self._nnb = torch.zeros(system.n, dtype=torch.int32, device=dev)
+            self._nconn = torch.zeros(system.n, dtype=torch.int32, device=dev)
+            self._q = torch.zeros((system.n, self.nl), dtype=torch.float64, device=dev)
+            self._qbar = torch.zeros((system.n, self.nl), dtype=torch.float64, device=dev)
+            self._rows = torch.zeros((self.capacity, self.ntypes, 2), dtype=torch.int64, device=dev)
+            self._hist = torch.zeros((2, self.nl, self.ntypes, self.nbins), dtype=torch.int64, device=dev)   # [q | q-bar][degree][type][bin]
+            self._ring_reset()
 
     def analyze(self, timestep):
-        if timestep % self.period:
+        if not self._due(timestep):
             return
         eng, members = self.integrator.engine, self.integrator.group.members
-        r = self.samples % self.capacity
+        r = self._slot()
         eng.bond_order(self.system.pos, self._shells, nnb=self._nnb, q=self._q, qbar=self._qbar, solid=self.solid,
                        nconn=None if self.solid is None else self._nconn, stats=self._rows[r], group=members, exclusions=self._excl)
         for which, values in enumerate((self._q, self._qbar)):
             for d, l in enumerate(self.degrees.tolist()):
                 eng.bond_order_histogram(values, self._shells, l, self._hist[which, d], 0.0, BOND_ORDER_HI, group=members)
-        self._steps[r] = int(timestep)
-        self.samples += 1
+        self._record(r, timestep)
 
     def reset(self):
         for t in (self._rows, self._hist, self._nnb, self._nconn, self._q, self._qbar):
             t.zero_()
-        self._steps = [None] * self.capacity
-        self.samples = 0
-
-    def _sampled(self):
-        if self.samples < 1:
-            raise ValueError("no samples yet")
+        self._ring_reset()
 
     def q(self, l):
         """(n,) float64: q_l of every particle in the last sample; 0 outside the group."""
@@ -899,18 +889,6 @@ class BondOrder:
     def mean(self, l, a=None, averaged=False):
         """The mean of q_l (averaged=True: of q-bar_l) over all samples, from the histogram: exact to half a bin width."""
         return histogram_mean(self.histogram(l, a, averaged))
-
-    def table(self):
-        """(samples kept, 1 + 2 ntypes) int64, oldest first: timestep, then for every type its members and its solid-like members (one
-        copy from the device)."""
-        import numpy as np
-        n = min(self.samples, self.capacity)
-        dev = self._rows.cpu().numpy().reshape(self.capacity, 2 * self.ntypes)
-        out = np.zeros((n, 1 + 2 * self.ntypes), dtype=np.int64)
-        for r in range(n):
-            k = (self.samples - n + r) % self.capacity
-            out[r, 0], out[r, 1:] = self._steps[k], dev[k]
-        return out
 
     def solid_fraction(self, a=None):
         """The solid-like members of type `a` (None: all) over the samples kept, divided by the members."""

@@ -1,4 +1,4 @@
-// Pair exclusions as the kernels of the cell-list passes read them (pse_forces.hip, pse_order.hip): the rows, the lookup and the
+// Pair exclusions as the kernels of the cell-list passes read them (pse_forces.hip, pse_analysis.hip, pse_order.hip): the rows, the lookup and the
 // launch helper that instantiates a kernel with and without them.
 #pragma once
 #include <type_traits>

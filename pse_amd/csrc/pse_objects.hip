@@ -1,6 +1,6 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
 // typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors and displacement
-// moments.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, the objects own their arrays through DeviceObject
+// moments.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h or pse_order.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 
 #include "pse_handle.h"
 #include "pse_forces.h"
+#include "pse_analysis.h"
 #include "pse_order.h"
 
 // A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
@@ -28,7 +29,7 @@ struct pse_bonds : Topology {};
 struct pse_angles : Topology {};
 struct pse_dihedrals : Topology {};
 struct pse_exclusions : Topology {};   // entries: the partners, one unsigned each (pse_host_exclusion_rows); no parameters
-// The other objects hold the struct that their launches take (pse_forces.h, which documents the arrays), filled once at creation, and
+// The other objects hold the struct that their launches take (pse_forces.h, pse_analysis.h and pse_order.h, which document the arrays), filled once at creation, and
 // the host-only words that the entry points keep about them.
 struct pse_typed_table : DeviceObject { PairTypedTables tt{}; };
 struct pse_pair_hist : DeviceObject { PairHist ph{}; };

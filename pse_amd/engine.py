@@ -14,10 +14,15 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _is_cuda(t, *dtypes):
+    """Is `t` a contiguous CUDA tensor of one of `dtypes`?  Every caller adds its own shape clause and its own message."""
+    import torch
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.is_contiguous()
+
+
 def _chk4(t, name, n=None):
     import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2
-            and t.shape[1] == 4 and t.is_contiguous()):
+    if not (_is_cuda(t, torch.float64) and t.dim() == 2 and t.shape[1] == 4):
         raise ValueError(f"{name} must be a contiguous (N,4) float64 CUDA tensor")
     if n is not None and t.shape[0] < n:
         raise ValueError(f"{name} has fewer than {n} rows")
@@ -27,15 +32,12 @@ def _chk_group(g, name="group"):
     import torch
     if g is None:
         return
-    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype in (torch.int32, torch.uint32) and g.dim() == 1
-            and g.is_contiguous()):
+    if not (_is_cuda(g, torch.int32, torch.uint32) and g.dim() == 1):
         raise ValueError(f"{name} must be a contiguous 1-D int32/uint32 CUDA tensor (the C-ABI reads unsigned int indices)")
 
 
 def _chk_arr(t, name, cols, dtype, n):
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == cols
-            and t.is_contiguous() and t.shape[0] >= n):
+    if not (_is_cuda(t, dtype) and t.dim() == 2 and t.shape[1] == cols and t.shape[0] >= n):
         raise ValueError(f"{name} must be a contiguous (N>={n},{cols}) {dtype} CUDA tensor")
 
 
@@ -77,8 +79,7 @@ def _chk_out8(out, pos):
     import torch
     if out is None:
         return torch.empty(8, dtype=torch.float64, device=pos.device)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.shape[0] == 8
-            and out.is_contiguous()):
+    if not (_is_cuda(out, torch.float64) and out.dim() == 1 and out.shape[0] == 8):
         raise ValueError("out must be a contiguous 8-element float64 CUDA tensor (a row of a larger one will do)")
     return out
 
@@ -261,6 +262,43 @@ def pair_type_index(a, b, ntypes):
     return a * ntypes - a * (a - 1) // 2 + (b - a)
 
 
+def _ntypes_argument(ntypes):
+    """The number of particle types of a typed object, checked."""
+    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
+        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    return ntypes
+
+
+def _types_argument(types, ntypes=None):
+    """The type array of a typed object, checked: None (one type) stays None, anything else must be a non-empty 1-D array of
+    integers in [0, ntypes) -- ntypes=None: of non-negative integers -- and comes back as a contiguous uint32 array."""
+    import numpy as np
+    if types is None:
+        return None
+    types = np.asarray(types)
+    if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
+        raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
+    if ntypes is not None and types.max() >= ntypes:
+        raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
+    return np.ascontiguousarray(types, dtype=np.uint32)
+
+
+class _TypedObject(_DeviceObject):
+    """What the owners of an object with one type per particle share: `ntypes`, the number of pair types `npt`, and the rule for the
+    rows `n` that the object covers -- `n` of the `types` (default: all of them), or without types `n` rows of the engine's arrays
+    (default: n_max).  Every such object is made by create(handle, n, types, ntypes, *args, &object)."""
+
+    def _create(self, engine, create, types, ntypes, n, *args):
+        self.ntypes, self.npt = ntypes, ntypes * (ntypes + 1) // 2
+        if types is None:
+            self.n = _rows(engine, n)
+        else:
+            self.n = int(types.shape[0] if n is None else n)
+            if not 0 <= self.n <= types.shape[0]:
+                raise ValueError("n outside [0, len(types)]")
+        super()._create(engine, create, self.n, _vp(types), ntypes, *args)
+
+
 def _typed_tables(tables, ntypes):
     """The `tables` dictionary {(a, b): (table, rmin, rmax)} of a typed pair table as the arrays of pse_typed_table_create: (widths
     int32 (npt,), rmin float64 (npt,), rmax float64 (npt,), entries float64 (sum of widths, 2)).  A key may name its types in either
@@ -268,8 +306,7 @@ def _typed_tables(tables, ntypes):
     import numpy as np
     if not isinstance(tables, dict) or not tables:
         raise ValueError("tables must be a non-empty dict {(a, b): (table, rmin, rmax)}")
-    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
-        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    _ntypes_argument(ntypes)
     npt = ntypes * (ntypes + 1) // 2
     width, rmin, rmax, parts = np.zeros(npt, dtype=np.int32), np.zeros(npt), np.zeros(npt), [None] * npt
     for key, value in tables.items():
@@ -300,14 +337,12 @@ def _typed_types(types, tables):
     """(uint32 types, ntypes): the type array of a typed pair table, checked; ntypes is one more than the largest type in `types`
     or in a key of `tables`."""
     import numpy as np
-    types = np.asarray(types)
-    if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
-        raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
+    types = _types_argument(np.asarray(types))   # (None is no type array here: it fails the check as the 0-D array it becomes)
     keys = [int(t) for key in tables for t in key] if isinstance(tables, dict) and all(isinstance(k, tuple) for k in tables) else []
-    return np.ascontiguousarray(types, dtype=np.uint32), max([int(types.max())] + keys) + 1
+    return types, max([int(types.max())] + keys) + 1
 
 
-class TypedTable(_DeviceObject):
+class TypedTable(_TypedObject):
     """Owner of a pse_typed_table object: one type per particle and one tabulated potential per pair of types (HOOMD's pair.table with
     a pair_coeff per type pair).  `types`: (n,) integers, the type of caller-order particle t; a particle past them acts as type 0.
     `tables`: {(a, b): (table, rmin, rmax)} with `table` a (width, 2) array of V and F at the nodes as for Engine.pair_table; either
@@ -328,10 +363,8 @@ class TypedTable(_DeviceObject):
         return self
 
     def _create_from(self, engine, types, ntypes, width, rmin, rmax, entries, n):
-        self.n, self.ntypes, self.count = int(types.shape[0] if n is None else n), ntypes, int(width.sum())
-        if not 0 <= self.n <= types.shape[0]:
-            raise ValueError("n outside [0, len(types)]")
-        self._create(engine, "pse_typed_table_create", self.n, _vp(types), ntypes, _vp(width), _vp(rmin), _vp(rmax), _vp(entries))
+        self.count = int(width.sum())
+        self._create(engine, "pse_typed_table_create", types, ntypes, n, _vp(width), _vp(rmin), _vp(rmax), _vp(entries))
 
 
 PAIR_HIST_MAX_COUNTERS = 8192   # pse_pair_hist_create: pair types x bins
@@ -342,8 +375,7 @@ def _pair_hist_arguments(types, ntypes, nbins, rmin, rmax):
     rmax).  `types`: None (one type) or a 1-D array of integers in [0, ntypes)."""
     import numpy as np
     ntypes, nbins, rmin, rmax = int(ntypes), int(nbins), float(rmin), float(rmax)
-    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
-        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    _ntypes_argument(ntypes)
     if nbins < 1:
         raise ValueError(f"nbins = {nbins}: need at least one bin")
     npt = ntypes * (ntypes + 1) // 2
@@ -351,17 +383,10 @@ def _pair_hist_arguments(types, ntypes, nbins, rmin, rmax):
         raise ValueError(f"{npt} pair types x {nbins} bins = {npt * nbins} counters, more than {PAIR_HIST_MAX_COUNTERS}")
     if not 0.0 <= rmin < rmax < float("inf"):
         raise ValueError("need 0 <= rmin < rmax, both finite")
-    if types is not None:
-        types = np.asarray(types)
-        if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
-            raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
-        if types.max() >= ntypes:
-            raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
-        types = np.ascontiguousarray(types, dtype=np.uint32)
-    return types, ntypes, nbins, rmin, rmax
+    return _types_argument(types, ntypes), ntypes, nbins, rmin, rmax
 
 
-class PairHistogram(_DeviceObject):
+class PairHistogram(_TypedObject):
     """Owner of a pse_pair_hist object: one type per particle and nbins uniform bins on [rmin, rmax) for every pair of types.
     `types`: (n,) integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts as type 0.
     Pass it as `hist` to Engine.pair_hist_accumulate."""
@@ -369,15 +394,8 @@ class PairHistogram(_DeviceObject):
     DESTROY = "pse_pair_hist_destroy"
 
     def __init__(self, engine, types, ntypes, nbins, rmin, rmax, n=None):
-        types, self.ntypes, self.nbins, self.rmin, self.rmax = _pair_hist_arguments(types, ntypes, nbins, rmin, rmax)
-        self.npt = self.ntypes * (self.ntypes + 1) // 2
-        if types is None:
-            self.n = _rows(engine, n)
-        else:
-            self.n = int(types.shape[0] if n is None else n)
-            if not 0 <= self.n <= types.shape[0]:
-                raise ValueError("n outside [0, len(types)]")
-        self._create(engine, "pse_pair_hist_create", self.n, _vp(types), self.ntypes, self.nbins, self.rmin, self.rmax)
+        types, ntypes, self.nbins, self.rmin, self.rmax = _pair_hist_arguments(types, ntypes, nbins, rmin, rmax)
+        self._create(engine, "pse_pair_hist_create", types, ntypes, n, self.nbins, self.rmin, self.rmax)
 
 
 SF_MAX_INDEX = 4096    # pse_structure_factor_create: |mx|, |my|, |mz|
@@ -390,8 +408,7 @@ def _structure_factor_arguments(types, ntypes, modes):
     +-SF_MAX_INDEX, at most SF_MAX_MODES of them."""
     import numpy as np
     ntypes = int(ntypes)
-    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
-        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    _ntypes_argument(ntypes)
     modes = np.asarray(modes)
     if modes.ndim != 2 or modes.shape[1] != 3 or modes.shape[0] == 0 or not np.issubdtype(modes.dtype, np.integer):
         raise ValueError("modes must be a non-empty integer (nk, 3) array of reciprocal-lattice indices (mx, my, mz)")
@@ -399,17 +416,10 @@ def _structure_factor_arguments(types, ntypes, modes):
         raise ValueError(f"{modes.shape[0]} modes, more than {SF_MAX_MODES}")
     if np.abs(modes).max() > SF_MAX_INDEX:
         raise ValueError(f"modes holds the index {int(np.abs(modes).max())} beyond +-{SF_MAX_INDEX}")
-    if types is not None:
-        types = np.asarray(types)
-        if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
-            raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
-        if types.max() >= ntypes:
-            raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
-        types = np.ascontiguousarray(types, dtype=np.uint32)
-    return types, ntypes, np.ascontiguousarray(modes, dtype=np.int32)
+    return _types_argument(types, ntypes), ntypes, np.ascontiguousarray(modes, dtype=np.int32)
 
 
-class StructureFactorModes(_DeviceObject):
+class StructureFactorModes(_TypedObject):
     """Owner of a pse_structure_factor object: one type per particle and a list of integer modes (mx, my, mz) of the box's reciprocal
     lattice.  `types`: (n,) integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts
     as type 0.  Pass it as `sf` to Engine.structure_factor_accumulate."""
@@ -417,15 +427,9 @@ class StructureFactorModes(_DeviceObject):
     DESTROY = "pse_structure_factor_destroy"
 
     def __init__(self, engine, types, ntypes, modes, n=None):
-        types, self.ntypes, self.modes = _structure_factor_arguments(types, ntypes, modes)
-        self.npt, self.nk = self.ntypes * (self.ntypes + 1) // 2, int(self.modes.shape[0])
-        if types is None:
-            self.n = _rows(engine, n)
-        else:
-            self.n = int(types.shape[0] if n is None else n)
-            if not 0 <= self.n <= types.shape[0]:
-                raise ValueError("n outside [0, len(types)]")
-        self._create(engine, "pse_structure_factor_create", self.n, _vp(types), self.ntypes, self.nk, _vp(self.modes))
+        types, ntypes, self.modes = _structure_factor_arguments(types, ntypes, modes)
+        self.nk = int(self.modes.shape[0])
+        self._create(engine, "pse_structure_factor_create", types, ntypes, n, self.nk, _vp(self.modes))
 
 
 MSD_MAX_ORIGINS = 64   # pse_msd_create: slots of one object, and pairs (slot, row) of one pse_msd_accumulate
@@ -437,8 +441,8 @@ def _msd_arguments(types, ntypes, norigins):
     norigins = int(norigins)
     if not 1 <= norigins <= MSD_MAX_ORIGINS:
         raise ValueError(f"norigins = {norigins} outside [1, {MSD_MAX_ORIGINS}]")
-    types, ntypes, _, _, _ = _pair_hist_arguments(types, ntypes, 1, 0.0, 1.0)
-    return types, ntypes, norigins
+    ntypes = _ntypes_argument(int(ntypes))
+    return _types_argument(types, ntypes), ntypes, norigins
 
 
 def _msd_pairs(slots, rows, norigins, nrows):
@@ -467,7 +471,7 @@ def _finite(x, name):
     return x
 
 
-class DisplacementOrigins(_DeviceObject):
+class DisplacementOrigins(_TypedObject):
     """Owner of a pse_msd object: one type per particle and `norigins` slots of unwrapped positions on the device.  `types`: (n,)
     integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts as type 0.  Pass it as
     `origins` to Engine.msd_store, msd_accumulate and msd_displacement."""
@@ -475,14 +479,8 @@ class DisplacementOrigins(_DeviceObject):
     DESTROY = "pse_msd_destroy"
 
     def __init__(self, engine, types, ntypes, norigins, n=None):
-        types, self.ntypes, self.norigins = _msd_arguments(types, ntypes, norigins)
-        if types is None:
-            self.n = _rows(engine, n)
-        else:
-            self.n = int(types.shape[0] if n is None else n)
-            if not 0 <= self.n <= types.shape[0]:
-                raise ValueError("n outside [0, len(types)]")
-        self._create(engine, "pse_msd_create", self.n, _vp(types), self.ntypes, self.norigins)
+        types, ntypes, self.norigins = _msd_arguments(types, ntypes, norigins)
+        self._create(engine, "pse_msd_create", types, ntypes, n, self.norigins)
 
 
 def _cluster_arguments(types, ntypes, rlink, name="rlink"):
@@ -491,8 +489,7 @@ def _cluster_arguments(types, ntypes, rlink, name="rlink"):
     order of pair_type_index; 0 switches a pair type off, at least one must be on.  `name`: what the messages call the distances."""
     import numpy as np
     ntypes = int(ntypes)
-    if not 1 <= ntypes <= PAIR_TYPED_MAX_TYPES:
-        raise ValueError(f"ntypes = {ntypes} outside [1, {PAIR_TYPED_MAX_TYPES}]")
+    _ntypes_argument(ntypes)
     npt = ntypes * (ntypes + 1) // 2
     if isinstance(rlink, dict):
         out = np.zeros(npt)
@@ -515,17 +512,10 @@ def _cluster_arguments(types, ntypes, rlink, name="rlink"):
         raise ValueError(f"{name} must be finite and not negative (0 switches a pair type off)")
     if not (out > 0.0).any():
         raise ValueError(f"every pair type is off: {name} needs a positive entry")
-    if types is not None:
-        types = np.asarray(types)
-        if types.ndim != 1 or types.shape[0] == 0 or not np.issubdtype(types.dtype, np.integer) or types.min() < 0:
-            raise ValueError("types must be a non-empty 1-D array of non-negative integers, one per particle")
-        if types.max() >= ntypes:
-            raise ValueError(f"types holds the type {int(types.max())} >= ntypes = {ntypes}")
-        types = np.ascontiguousarray(types, dtype=np.uint32)
-    return types, ntypes, np.ascontiguousarray(out)
+    return _types_argument(types, ntypes), ntypes, np.ascontiguousarray(out)
 
 
-class ClusterLinks(_DeviceObject):
+class ClusterLinks(_TypedObject):
     """Owner of a pse_clusters object: one type per particle and one link distance per pair of types (see _cluster_arguments for
     `rlink`).  `types`: (n,) integers below ntypes, the type of caller-order particle t, or None: one type; a particle past them acts
     as type 0.  Pass it as `links` to Engine.cluster_label."""
@@ -533,15 +523,8 @@ class ClusterLinks(_DeviceObject):
     DESTROY = "pse_clusters_destroy"
 
     def __init__(self, engine, types, ntypes, rlink, n=None):
-        types, self.ntypes, self.rlink = _cluster_arguments(types, ntypes, rlink)
-        self.npt = self.ntypes * (self.ntypes + 1) // 2
-        if types is None:
-            self.n = _rows(engine, n)
-        else:
-            self.n = int(types.shape[0] if n is None else n)
-            if not 0 <= self.n <= types.shape[0]:
-                raise ValueError("n outside [0, len(types)]")
-        self._create(engine, "pse_clusters_create", self.n, _vp(types), self.ntypes, _vp(self.rlink))
+        types, ntypes, self.rlink = _cluster_arguments(types, ntypes, rlink)
+        self._create(engine, "pse_clusters_create", types, ntypes, n, _vp(self.rlink))
 
     def status(self):
         """The object's sticky give-up word (pse_clusters_status: waits for the stream).  0: every labelling so far was complete."""
@@ -572,7 +555,7 @@ def _bond_order_arguments(types, ntypes, rnb, degrees):
     return types, ntypes, rnb, np.ascontiguousarray(deg, dtype=np.int32)
 
 
-class BondOrderShells(_DeviceObject):
+class BondOrderShells(_TypedObject):
     """Owner of a pse_bond_order object: one type per particle, one neighbour distance per pair of types and the degrees l of the
     Steinhardt parameters (see _bond_order_arguments).  `types`: (n,) integers below ntypes, the type of caller-order particle t, or
     None: one type; a particle past them acts as type 0.  Pass it as `shells` to Engine.bond_order and Engine.bond_order_histogram."""
@@ -580,15 +563,9 @@ class BondOrderShells(_DeviceObject):
     DESTROY = "pse_bond_order_destroy"
 
     def __init__(self, engine, types, ntypes, rnb, degrees=(4, 6), n=None):
-        types, self.ntypes, self.rnb, self.degrees = _bond_order_arguments(types, ntypes, rnb, degrees)
-        self.npt, self.nl = self.ntypes * (self.ntypes + 1) // 2, int(self.degrees.shape[0])
-        if types is None:
-            self.n = _rows(engine, n)
-        else:
-            self.n = int(types.shape[0] if n is None else n)
-            if not 0 <= self.n <= types.shape[0]:
-                raise ValueError("n outside [0, len(types)]")
-        self._create(engine, "pse_bond_order_create", self.n, _vp(types), self.ntypes, _vp(self.rnb), self.nl, _vp(self.degrees))
+        types, ntypes, self.rnb, self.degrees = _bond_order_arguments(types, ntypes, rnb, degrees)
+        self.nl = int(self.degrees.shape[0])
+        self._create(engine, "pse_bond_order_create", types, ntypes, n, _vp(self.rnb), self.nl, _vp(self.degrees))
 
     def column(self, l):
         """The column of degree `l` in q and qbar."""
@@ -649,8 +626,7 @@ class _ForcePasses:
         _chk4(pos, "pos"); _chk_group(group)
         if force is not None:
             _chk4(force, "force")
-        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and table.dim() == 2
-                and table.shape[1] == 2 and table.is_contiguous()):
+        if not (_is_cuda(table, torch.float64) and table.dim() == 2 and table.shape[1] == 2):
             raise ValueError("table must be a contiguous (width, 2) float64 CUDA tensor: V and F at the nodes")
         out = _chk_out8(out, pos) if observables else None
         if exclusions is not None:
@@ -696,8 +672,7 @@ class _ForcePasses:
         import torch
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
-        if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()
-                and tuple(counts.shape) == (hist.npt, hist.nbins)):
+        if not (_is_cuda(counts, torch.int64) and tuple(counts.shape) == (hist.npt, hist.nbins)):
             raise ValueError(f"counts must be a contiguous ({hist.npt}, {hist.nbins}) int64 CUDA tensor")
         _lib.check(self._lib.pse_pair_hist_accumulate(hist._handle(self), _ptr(pos), _ptr(group), n, _ptr(counts),
                                                       None if exclusions is None else exclusions._handle(self)))
@@ -721,8 +696,7 @@ class _ForcePasses:
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
         for t, name, shape in ((rho, "rho", (sf.ntypes, sf.nk, 2)), (sums, "sums", (sf.npt, sf.nk))):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-                                      and tuple(t.shape) == shape):
+            if t is not None and not (_is_cuda(t, torch.float64) and tuple(t.shape) == shape):
                 raise ValueError(f"{name} must be a contiguous {shape} float64 CUDA tensor")
         if rho is None and sums is None:
             raise ValueError("rho and sums are both None: nothing to compute")
@@ -762,8 +736,8 @@ class _ForcePasses:
         no atomics, equal inputs give equal bits.  Returns sums."""
         import torch
         n = self._msd_common(pos, image, group)
-        if not (isinstance(sums, torch.Tensor) and sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and sums.dim() == 3
-                and sums.shape[0] >= 1 and tuple(sums.shape[1:]) == (origins.ntypes, MSD_MOMENTS)):
+        if not (_is_cuda(sums, torch.float64) and sums.dim() == 3 and sums.shape[0] >= 1
+                and tuple(sums.shape[1:]) == (origins.ntypes, MSD_MOMENTS)):
             raise ValueError(f"sums must be a contiguous (nrows, {origins.ntypes}, {MSD_MOMENTS}) float64 CUDA tensor")
         slots, rows = _msd_pairs(slots, rows, origins.norigins, int(sums.shape[0]))
         _lib.check(self._lib.pse_msd_accumulate(origins._handle(self), _ptr(pos), _ptr(image), _ptr(group), n, _finite(strain, "strain"),
@@ -806,14 +780,11 @@ class _ForcePasses:
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
         for t, name in ((label, "label"), (size, "size")):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.int32, torch.int64) and t.dim() == 1
-                                      and t.is_contiguous() and t.shape[0] >= pos.shape[0]):
+            if t is not None and not (_is_cuda(t, torch.int32, torch.int64) and t.dim() == 1 and t.shape[0] >= pos.shape[0]):
                 raise ValueError(f"{name} must be a contiguous 1-D int32 or int64 CUDA tensor of at least {pos.shape[0]} entries")
-        if stats is not None and not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int64
-                                      and stats.is_contiguous() and tuple(stats.shape) == (4,)):
+        if stats is not None and not (_is_cuda(stats, torch.int64) and tuple(stats.shape) == (4,)):
             raise ValueError("stats must be a contiguous (4,) int64 CUDA tensor")
-        if hist is not None and not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous()
-                                     and hist.dim() == 1 and hist.shape[0] >= 1):
+        if hist is not None and not (_is_cuda(hist, torch.int64) and hist.dim() == 1 and hist.shape[0] >= 1):
             raise ValueError("hist must be a contiguous 1-D int64 CUDA tensor of at least one entry")
         if label is None and size is None and stats is None and hist is None:
             raise ValueError("label, size, stats and hist are all None: nothing to compute")
@@ -851,15 +822,13 @@ class _ForcePasses:
         n = pos.shape[0] if group is None else group.shape[0]
         _chk4(pos, "pos"); _chk_group(group)
         for t, name in ((nnb, "nnb"), (nconn, "nconn")):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1
-                                      and t.is_contiguous() and t.shape[0] >= pos.shape[0]):
+            if t is not None and not (_is_cuda(t, torch.int32) and t.dim() == 1 and t.shape[0] >= pos.shape[0]):
                 raise ValueError(f"{name} must be a contiguous 1-D int32 CUDA tensor of at least {pos.shape[0]} entries")
         for t, name in ((q, "q"), (qbar, "qbar")):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2
-                                      and t.is_contiguous() and t.shape[0] >= pos.shape[0] and t.shape[1] == shells.nl):
+            if t is not None and not (_is_cuda(t, torch.float64) and t.dim() == 2 and t.shape[0] >= pos.shape[0]
+                                      and t.shape[1] == shells.nl):
                 raise ValueError(f"{name} must be a contiguous (N >= {pos.shape[0]}, {shells.nl}) float64 CUDA tensor")
-        if stats is not None and not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int64
-                                      and stats.is_contiguous() and tuple(stats.shape) == (shells.ntypes, 2)):
+        if stats is not None and not (_is_cuda(stats, torch.int64) and tuple(stats.shape) == (shells.ntypes, 2)):
             raise ValueError(f"stats must be a contiguous ({shells.ntypes}, 2) int64 CUDA tensor")
         if nnb is None and q is None and qbar is None and nconn is None and stats is None:
             raise ValueError("nnb, q, qbar, nconn and stats are all None: nothing to compute")
@@ -883,12 +852,10 @@ class _ForcePasses:
         contiguous (ntypes, nbins) int64 CUDA tensor, ADDED to; `n`: the number of group members without a group (default: the rows
         of values).  Queue-only; integers only.  Returns counts."""
         import torch
-        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float64 and values.dim() == 2
-                and values.is_contiguous() and values.shape[1] == shells.nl):
+        if not (_is_cuda(values, torch.float64) and values.dim() == 2 and values.shape[1] == shells.nl):
             raise ValueError(f"values must be a contiguous (N, {shells.nl}) float64 CUDA tensor")
         _chk_group(group)
-        if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()
-                and counts.dim() == 2 and counts.shape[0] == shells.ntypes and counts.shape[1] >= 1):
+        if not (_is_cuda(counts, torch.int64) and counts.dim() == 2 and counts.shape[0] == shells.ntypes and counts.shape[1] >= 1):
             raise ValueError(f"counts must be a contiguous ({shells.ntypes}, nbins) int64 CUDA tensor")
         if shells.ntypes * int(counts.shape[1]) > BOND_ORDER_MAX_COUNTERS:
             raise ValueError(f"{shells.ntypes} types x {int(counts.shape[1])} bins, more than {BOND_ORDER_MAX_COUNTERS} counters")
