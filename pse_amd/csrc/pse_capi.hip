@@ -30,6 +30,9 @@
 #include "pse_err.h"
 #include "pse_host.h"
 #include "pse_kernels.h"
+#include "pse_farfield.h"
+#include "pse_fft.h"
+#include "pse_vectors.h"
 #include "pse_forces.h"
 #include "pse_handle.h"
 

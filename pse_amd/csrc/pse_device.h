@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #include "pse_host.h"
 
@@ -107,13 +108,51 @@ __device__ __forceinline__ void vq_unpack(vq4 w, double &x, double &y, double &z
     z = fma((double)hz, 4294967296.0, (double)w.z) * sc;
 }
 
-// ---- launch geometry and the wave reduction that the kernel files share ----------------------------------------------------------
+// ---- launch geometry, the launch with dynamic LDS and the reductions that the kernel files share ------------------------------
 constexpr int TPB = 256;   // threads per workgroup of the one-thread-per-row kernels: four waves
 static inline int nblocks(long n, int tpb) { return (int)((n + tpb - 1) / tpb); }
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+// sum over a 256-thread block; result valid in all threads
+__device__ __forceinline__ double block_sum(double v, double *sh /* >= 4 doubles */) {
+    v = wave_sum(v);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+// every block reduces the same partial array in the same order -> identical value everywhere
+__device__ __forceinline__ double reduce_partials(const double *partials, int n, double *sh) {
+    double v = 0.0;
+    for (int i = threadIdx.x; i < n; i += TPB) v += partials[i];
+    return block_sum(v, sh);
+}
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE: every launcher keeps, per device ordinal, the largest size it has
+// raised the attribute to (a process-wide flag would leave a second device, or a second thread's first launch, without it).  Racing
+// threads at worst set the same attribute twice.
+struct LdsAttr {
+    std::atomic<size_t> have[32];
+    bool need(size_t lds) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev < 0 || dev >= 32) return true;
+        if (have[dev].load(std::memory_order_relaxed) >= lds) return false;
+        have[dev].store(lds, std::memory_order_relaxed);
+        return true;
+    }
+};
+// launch of kernel K with `lds` bytes of dynamic LDS: raises K's limit on the current device when `lds` exceeds what it was raised to
+// before (one LdsAttr per kernel; a size the default already allows changes no launch), then launches.  Args come from the call, not
+// from K's parameter list: K gets none of its default arguments, so name every one
+template <auto K, class... Args>
+static void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    static LdsAttr attr;
+    if (attr.need(lds)) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(K, grid, block, lds, s, args...);
 }
 
 __device__ __forceinline__ int wrapi(int a, int n) { a %= n; return a < 0 ? a + n : a; }

@@ -1,4 +1,4 @@
-// Complex helpers and the small in-register DFTs (radix 2, 3, 4, 5, 6, 8, 9, 10) the FFT passes are built from (pse_kernels.hip: x and y
+// Complex helpers and the small in-register DFTs (radix 2, 3, 4, 5, 6, 8, 9, 10) the FFT passes are built from (pse_fft.hip: x and y
 // passes, the z pass at 256 / 512; pse_zfft.hip: the z pass at the other 2^a 3^b 5^c sizes).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -3,7 +3,7 @@
 // its support origin lies in.  Round 4: the ranking is done by the pass that already holds the sorted position -- the separate
 // k_support launch and the 48 bytes per particle it parked for k_far_records are gone (the records recompute the support).
 #pragma once
-#include "pse_kernels.h"
+#include "pse_farfield.h"
 
 namespace pse {
 

@@ -13,7 +13,7 @@
 //   ax[t] = exp(-c (u + hx t)^2)                       ay[t] = exp(-c ((Y0 + hy t)^2 + s^2 hy^2 t^2 + 2 u s hy t))
 //   az[t] = exp(-c (Z0 + hz t)^2)                      K[t][v] = exp(-2 c s hx hy t v)   (the same for every particle)
 // and each of ax, ay, az obeys E(t+1) = E(t) q r_t with r_t independent of the particle (GaussConsts).
-#include "pse_kernels.h"
+#include "pse_farfield.h"
 #include "pse_farbin.h"
 
 #include <hipcub/hipcub.hpp>

@@ -11,6 +11,8 @@
 #include "pse_err.h"
 #include "pse_host.h"
 #include "pse_kernels.h"
+#include "pse_farfield.h"
+#include "pse_vectors.h"
 #include "pse_local.h"
 
 using namespace pse;

@@ -1,4 +1,4 @@
-// Launch wrappers of the HIP kernels (defined in pse_kernels.hip).  All take the stream explicitly.
+// Launch wrappers of the cell sort, the gates, the gather into cell order, the near field and k_eval_fg (defined in pse_kernels.hip).  All take the stream explicitly.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -190,176 +190,6 @@ void launch_mreal_lanczos(const double4 *pos_s, const double4 *vec_s, double4 *w
                           const void *vec_q = nullptr,    // (sums == 1) the 16-byte mirror of vec_s (launch_lz_update's xq): the neighbours' rows in ONE gather per pair
                           bool no_reduce = false);        // the mat-vec kernel only: no reduction of its partial sums behind it
 int mreal_partials_needed(int rows);
-void launch_lz_reduce3(const double *partials, int npart, int cap, double *scal, hipStream_t s);
-
-// ---- far field (K2-K8) -----------------------------------------------------------------------------------
-// scratch of the fast far-field path (rebuilt every call): particles binned by the 8^3 block of nodes their support
-// origin lies in, and their records written in bin order
-struct FarBins {
-    int nbx, nby, nbz;          // bins per axis (set by the launchers from the grid)
-    int *cnt, *off;             // [nbins], [nbins + 1]
-    int *rank_s;                // [N] rank of a particle inside its bin (-1: not needed by this slab rank)
-    void *tmp; size_t tmp_bytes;   // scan scratch
-};
-size_t bin_scan_temp_bytes(size_t nbins);
-struct FarRec;                  // 64-byte bin-ordered particle record (pse_farfield.hip)
-struct SpreadWork {
-    FarBins fb;
-    FarRec *rec_t;              // [N] bin order: origin, sorted index (bit 31: owned by another slab rank), offset, prefac * force
-    int force_tz, force_nw;     // tuning switches of the handle (0: automatic): z depth of a spread block, waves per block
-    int force_bz;               // ... bins along z per gather workgroup (PSE_GATHER_BZ=1|2)
-    CellRanges need;            // a slab rank: rows outside hold no particle data (their support cannot reach the slab)
-    const int *cell_off;
-    int rows_local;             // 1: N counts the rows of ONE slab rank (owned-particle teams), not the particles of the suspension
-};
-// per-step constants of the separable Gaussian weights: step ratios r_t = exp(-c h^2 (2t+1)) (y with the (1 + xy^2) of the
-// sheared lattice), ln K = -2 c xy hx hy, the tilt
-constexpr int FAR_PMAX = 14;   // largest support of the block far field (error 1e-6 gives P = 13)
-struct GaussConsts { double rx[FAR_PMAX - 1], ry[FAR_PMAX - 1], rz[FAR_PMAX - 1], lnk, s; };
-size_t farfield_bins(const DGrid &G);
-// true if the caller must zero the grids first (atomic fallback: P outside 4..8 or a grid smaller than two tiles)
-bool spread_needs_zero(const DGrid &G);
-// The far field of a step: (1) the pass that gathers the particles into cell order (launch_permute) ranks every particle inside
-// its bin (FarBinArgs; the bin counts are zeroed by the caller before it); (2) launch_far_records: bin offsets + the 64-byte
-// records in bin order; (3) launch_spread; ... (4) launch_gather, which reads the same records.
-struct FarBinArgs { bool on; DGrid G; FarBins fb; };
-FarBinArgs far_bin_args(const DGrid &G, const SpreadWork &w);
-size_t far_bin_count(const DGrid &G);   // ints of fb.cnt to zero
-hipError_t launch_far_records(const double4 *pos_s, const double4 *f_s, int N, DGrid G, DBox box, SpreadWork w, hipStream_t s);
-hipError_t launch_spread(const double4 *pos_s, const double4 *f_s, int N, double *gx, double *gy, double *gz, DGrid G,
-                   DBox box, SpreadWork w, hipStream_t s);
-struct ScaleArgs {
-    double xi, eta;
-    int noise;               // add k-space Brownian noise (K6)
-    double noise_fac;        // sqrt(2 kT / (dt h^3))
-    uint32_t seed, timestep;
-    const uint32_t *ts_off;  // nullable: the noise is drawn at timestep + *ts_off, read on the device (pse_set_timestep_offset)
-    int transposed;          // layout [Nx][ny_local][Nzh] (slab mode, after the transpose) instead of [nx_local][Ny][Nzh]
-    int y0, nyl;             // slab of y rows in transposed layout
-    int runtime_plan;        // PSE_XMIX=1: the runtime radix plan also where a compile-time one exists (A/B)
-    int wide_small;          // PSE_XFFT_SMALL_KB=8: eight kz columns per workgroup also on small grids (A/B)
-};
-void launch_scale(double2 *X, double2 *Y, double2 *Z, DGrid G, DBox box, ScaleArgs a, hipStream_t s);
-// debug: kx, ky, kz, w sinc^2, sqrt(w) sinc of n nodes (i, j, k)
-void launch_debug_kop(const int *ijk, int n, DGrid G, DBox box, double xi, double eta, double *out, hipStream_t s);
-// fused forward-x FFT + scale + inverse-x FFT on [3][Nx][Ny][Nzh] (Nx a power of two, 16..512); tw[m] = exp(-2 pi i m/Nx)
-bool xfuse_supported(int Nx);
-// own in-place y transforms of the half spectra [3 nxl][Ny][Nzp] (Ny = 2^a 3^b 5^c, not a power of two); tw[m] = exp(-2 pi i m / Ny);
-// kb: consecutive kz per workgroup (2, 4 or 8)
-bool yfft_supported(int Ny);
-bool yfft_regs_supported(int Ny, int Nz, bool own_z = false);   // the register y pass (k_yfft_regs) instead of rocFFT's strided pass: 256 (Nz <= 256), and 256 / 512 with the own z pass
-// a slab rank's y transforms with the reordering of the all-to-all blocks folded in: forward reads the planes [3][nxl][Ny][Nzp] and writes
-// [3][G][nxl][nyl][Nzp]; inverse the other way round (any Ny = 2^a 3^b 5^c in 16..512: yfft_possible)
-bool yfft_possible(int Ny);
-void launch_yfft_slab(double2 *cgrid, double2 *blocks, DGrid G, int nyl, bool inverse, const double2 *tw, hipStream_t s,
-                      bool regs = true);   // regs: Ny = 256, 512 by the register pass (k_yfft_regs with the block map) instead of k_fft_cols
-void launch_yfft(double2 *spectra, DGrid G, bool inverse, const double2 *tw, hipStream_t s, int kb = 4);
-// own z pass (k_zfft_rows): `rows` real rows of Nz doubles per component <-> spectrum rows of Nzp complex numbers; tw[m] = exp(-2 pi i m / Nz)
-bool zfft_supported(int Nz);
-void launch_zfft(double *const real[3], double2 *const spec[3], int rows, int Nz, int Nzp, bool inverse, const double2 *tw, hipStream_t s);
-void launch_xfft_scale(double2 *X, double2 *Y, double2 *Z, DGrid G, DBox box, ScaleArgs a, const double2 *tw, hipStream_t s);
-// the fast path reads the records written by launch_spread of the same step
-hipError_t launch_gather(const double4 *pos_s, SpreadWork w, int N, const double *gx, const double *gy, const double *gz, DGrid G,
-                   DBox box, double4 *u_s, hipStream_t s);
-
-// which kernels launch_spread / launch_gather would launch for N particles (pse_debug_far_path): decided by the functions the launchers call
-void far_path(const DGrid &G, const SpreadWork &w, int N, double xy, int out[6]);
-
-// Which kernel family a transform launcher takes, and its kz columns per workgroup (pse_debug_fft_path).  launch_xfft_scale, launch_yfft
-// and launch_zfft switch on what these return, so the report cannot name another kernel than the one launched.  FFT_ROCFFT is never
-// returned: it is what the handle reports for an axis whose launcher is not called (xfuse / own_y / own_z off).
-enum { FFT_ROCFFT = 0,
-       XFFT_LDS = 1, XFFT_REGS = 2, XFFT_MIXED_CT = 3, XFFT_MIXED_RT = 4,      // k_xfft_scale, k_xfft_scale_cols, k_xfft_scale_mixed with a compile-time / runtime plan
-       YFFT_COLS_CT = 1, YFFT_COLS_RT = 2, YFFT_REGS = 3,                     // k_fft_cols with a compile-time / runtime plan, k_yfft_regs
-       ZFFT_ROWS = 1, ZFFT_ROWS_G = 2 };                                      // k_zfft_rows (256, 512), k_zfft_rows_g (pse_zfft.hip)
-struct FftChoice { int kernel, kb; };
-FftChoice xfft_choice(const DGrid &G, const ScaleArgs &a);
-FftChoice yfft_choice(const DGrid &G, int kb);
-int zfft_choice(int Nz);
-
-// ---- slab decomposition helpers
-void launch_slab_pack(double2 *cgrid, double2 *buf, int nxl, int Ny, int Nzh, int nyl, int unpack, hipStream_t s);
-void launch_add_inplace(double *a, const double *b, size_t n, hipStream_t s);
-// in-process teams: the device copies that stand for one exchange, as ONE launch (a message transport posts one group too)
-struct CopyList { int n; const double *src[40]; double *dst[40]; unsigned cnt[40]; };   // counts in doubles
-void launch_copy_list(const CopyList &l, hipStream_t s);
-
-// ---- vector kernels (K10-K14) ----------------------------------------------------------------------------
-void launch_psi(double4 *psi_s, const unsigned *tag_s, int N, uint32_t seed, uint32_t timestep, hipStream_t s,
-                CellRanges need = CellRanges{}, const int *cell_off = nullptr);
-// scal layout (device doubles): [0..127] alpha, [128..255] beta, [256] psi norm, [257] scratch
-constexpr int LZ_ALPHA = 0, LZ_BETA = 128, LZ_NORM = 256, LZ_TMP = 257, LZ_UU = 272, LZ_NSCAL = 400;   // TMP: 3 sums (one-step) or the LZ_NGRAM sums of a two-step block; UU[j] = |M v_{j-1}|^2 of the block that starts at j
-constexpr int LZ_NPART = 1024;  // partial-sum slots
-// out_s = scale * sum_q t[q] X[q], X[0] = x0, X[q] = V[q] (the UNNORMALISED Lanczos vectors: t carries the 1 / |x_q|)
-// rows [lo, hi)
-struct BasisCoef { double t[104]; };   // the m <= 100 coefficients of the final combination, passed by value
-// sink.on: the result is not stored in out_s but added to add_a + add_b (nullable) of the row and sent on: vel[tag].xyz (single GPU) or
-// rows[i] = (sum, tag) (a team's all-gathered array)
-struct CombineSink { bool on; const double4 *add_a, *add_b; const unsigned *tag_s; double4 *vel; double4 *rows; };
-void launch_basis_combine(const double4 *x0, const double4 *V, size_t stride, const BasisCoef &t, int m, const double *scal,
-                          double scale, int use_norm, double4 *out_s, int lo, int hi, hipStream_t s, CombineSink sink = CombineSink{},
-                          const struct LzState *st = nullptr);   // st: m and the coefficients come from the device-side decision
-// Lanczos iteration on the own rows [lo, hi) (see k_lz_update in pse_kernels.hip).  dots: sums of x.x, x.y, x.vprev ->
-// scal[LZ_TMP..+2] (y = null: x.x only), for mat-vecs that did not fuse them; [all-reduce by the caller when sharded];
-// update: alpha_j, beta_j -> scal, x_{j+1} -> xnext
-void launch_lz_dots(const double4 *x, const double4 *y, const double4 *vprev, int lo, int hi, double *partials, int cap,
-                    double *scal, hipStream_t s);
-// one block of the two-iterations-per-exchange Lanczos of a team (k_lz_block in pse_kernels.hip)
-struct LzBlockArgs {
-    const double4 *q, *p, *w1, *w2;   // p null for j = 0; w2 null: a single step (scalars alpha_j, beta_{j+1} only)
-    double4 *u;                       // in: M p (not read for j = 0); out: M v_{j+1} (two steps) or M v_j = w1 (one step)
-    double4 *v1, *v2;                 // V[j + 1], V[j + 2]
-    int j;
-};
-// sums_all / nranks (teams): [nranks][LZ_NGRAM] partial sums of all ranks, added in rank order by the kernel; nranks = 0: scal[LZ_TMP ..]
-// sch: the host's copy of the scalars (device pointer of mapped pinned memory, nullable): alpha, beta, the norm are written there too
-void launch_lz_block(const LzBlockArgs &a, bool full, double *scal, const int (*row_ranges)[2], int n_ranges, hipStream_t s,
-                     const double *sums_all = nullptr, int nranks = 0, double *sch = nullptr,
-                     const RowRanges *rg_dev = nullptr, int rows_cap = 0,   // owned-particle ranks: the ranges come from device memory (vectors_off: scalars only)
-                     bool vectors_off = false, const int *stop = nullptr);
-void launch_vq_roundtrip(const double *in, double *out, int n, hipStream_t s);   // debug: vq_unpack(vq_pack(row)) of n rows of three doubles
-void launch_lz_update(const double4 *xin, const double4 *y, const double4 *xprev, double4 *xnext, int j,
-                      double *scal, const int (*row_ranges)[2], int n_ranges, hipStream_t s,   // up to three disjoint row ranges in one launch
-                      const double *sums_all = nullptr, int nranks = 0, double *sch = nullptr, const int *stop = nullptr,
-                      void *xq = nullptr);   // nullable: [rows] 16-byte mirror of xnext (vq_pack, pse_device.h), written on the same rows
-// ---- the convergence decision of the Lanczos iteration ON THE DEVICE (queue-only Brownian calls: pse_set_async) ----------------
-// Replaces, for calls that may not wait for the host, what the host driver does between batches of iterations (the reference's
-// LAPACKE_spteqr + host loops, PSEv1/Brownian.cu:540-582, and its step-norm test, PSEv1/Brownian.cu:673-724): one workgroup solves
-// the tridiagonal eigenproblems of the sizes to be checked (one wavefront each, implicit QL as tridiag_eigen in pse_params.cpp),
-// walks m upward exactly as the host does and, once the step norm is below the tolerance, closes the gate `done` that every later
-// kernel of the iteration reads, and leaves the coefficients of the final combination for k_basis_combine.
-struct LzState {
-    int done;            // the iteration has ended: m_final and coef are valid; later iteration kernels leave at once
-    int m_final;
-    int checked;         // t_prev holds T^{1/2} e_1 of this size (0: nothing yet)
-    int status;          // 0 converged, 1 the queued iterations ran out first (result from the last size checked), 2 non-finite coefficient / eigen-solve failure
-    double stepnorm;
-    double t_prev[104];
-    double coef[104];    // coefficients of the basis vectors in the final combination (t divided by the norms the basis carries)
-};
-struct LzDecide {
-    int m_lo, m_hi;      // sizes to check, at most two (m_lo = m_hi - 1 or m_hi)
-    int done_iters;      // iterations whose alpha exists; one-step driver: beta[done_iters] does not exist yet
-    int have_last_beta;  // 1: beta[done_iters] exists as well (two-step driver of a team)
-    int pending_beta;    // > 0: first test beta[pending_beta] for breakdown (it arrived with this batch)
-    int first;           // first decision of a call: reset the state
-    int last;            // last queued decision: if still open, end the iteration at the last size checked (status 1)
-    int normalised;      // the basis holds normalised v_q for q >= 1 (two-step driver); else unnormalised x_q (divide by beta_q)
-    int m_max;
-    double tol;
-};
-constexpr int LZ_HOST_M = 380, LZ_HOST_STEPNORM = 381, LZ_HOST_STATUS = 382, LZ_HOST_SEQ = 383, LZ_HOST_OPEN = 384;   // (OPEN: calls so far that ended with status != 0)   // slots of the host mirror (sch) the decision writes
-void launch_lz_decide(const LzDecide &d, double *scal, LzState *st, double *sch, double seq, hipStream_t s);
-bool lz_decide_supported(int m_hi);   // the eigenvectors of both sizes fit the LDS of one workgroup
-// tag_s (nullable): out[i].w = the particle's index in the caller's arrays, so the rows can be scattered by ranks that did not sort them
-void launch_sum_rows(const double4 *a, const double4 *b, const double4 *c, double4 *out, int lo, int hi, hipStream_t s,
-                     const unsigned *tag_s = nullptr);
-void launch_pick(const int *cell_off, const int *idx, int n, int *out, hipStream_t s);
-// vel[tag].xyz = a + b + c (each may be null), keep w;  tag_s = null: the tag travels in a[s].w (launch_sum_rows)
-void launch_scatter_sum(const double4 *a, const double4 *b, const double4 *c, const unsigned *tag_s, int N,
-                        double4 *vel, hipStream_t s);
-void launch_integrate(double4 *pos, const double4 *vel, double3 *accel, int3 *image, const double4 *force,
-                      const unsigned *group, int N, DBox box, double dt, double shear_rate, hipStream_t s);
 void launch_eval_fg(const double *r, int n, const double *coef, double *f, double *g, hipStream_t s);
 
 }  // namespace pse

@@ -12,6 +12,8 @@
 // size c_g rows -- no count ever has to reach a host.
 #pragma once
 #include "pse_kernels.h"
+#include "pse_farfield.h"
+#include "pse_vectors.h"
 
 namespace pse {
 

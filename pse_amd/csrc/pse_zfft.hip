@@ -1,6 +1,6 @@
 // The z half of K4 / K7 (the reference's cuFFT C2C transforms, PSEv1/Brownian.cu:844-846,867-869) at the grid sizes of the
 // reference's own rule that are not 256 or 512 (PSEv1/Stokes.cc:143-199: next 2^a 3^b 5^c -- 360 at the metric point, 270 / 360 at
-// BASELINE config 3, 500 at config 4): k_zfft_rows (pse_kernels.hip) generalised from NC = R0 x 8 x 8 to NC = R0 x R1 x R2.
+// BASELINE config 3, 500 at config 4): k_zfft_rows (pse_fft.hip) generalised from NC = R0 x 8 x 8 to NC = R0 x R1 x R2.
 // A wavefront owns RW rows at a time; a row's N reals are NC = N / 2 complex points z[n] = x[2n] + i x[2n + 1]; lane l < L = R1 R2
 // holds z[l + L r], r < R0 (coalesced 16-byte loads of the row as it lies); stage 1 is a radix-R0 butterfly in registers, stages 2
 // (radix R1 on R0 R2 lanes per row) and 3 (radix R2 on R0 R1 lanes per row) trade their points through the wave's own LDS columns
@@ -10,7 +10,7 @@
 // against numpy.fft for every size instantiated here.
 //   forward:  X[k] = (Z[k] + conj Z[NC - k]) / 2 - i/2 W_N^k (Z[k] - conj Z[NC - k]),  k = 0 .. NC      (Z[NC] = Z[0])
 //   inverse:  Z[k] = (X[k] + conj X[NC - k]) + i conj W_N^k (X[k] - conj X[NC - k]),   k = 0 .. NC - 1;  x = N x the true inverse
-#include "pse_kernels.h"
+#include "pse_fft.h"
 #include "pse_dft.h"
 
 namespace pse {

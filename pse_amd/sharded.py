@@ -69,7 +69,7 @@ def row_map(ranges):
 
 
 def two_step_block(G, alpha_prev, beta, uu, first):
-    """The scalars of one two-iteration Lanczos block from its Gram sums (k_lz_block in csrc/pse_kernels.hip), for tests: G =
+    """The scalars of one two-iteration Lanczos block from its Gram sums (k_lz_block in csrc/pse_vectors.hip), for tests: G =
     dict with the eight sums qw1, w1w1, w1w2, w2w2, pw1, pw2, uw2, qq of q = v_j (unnormalised in the first block), p = v_{j-1},
     u = M p, w1 = M q, w2 = M w1.  Returns alpha_j, beta_{j+1}, alpha_{j+1}, beta_{j+2}, |M v_{j+1}|^2."""
     import math

@@ -1,4 +1,4 @@
-"""Host-side mirrors of the index algebra of the register x / y passes (pse_amd/csrc/pse_kernels.hip: k_xfft_scale_cols, k_yfft_regs,
+"""Host-side mirrors of the index algebra of the register x / y passes (pse_amd/csrc/pse_fft.hip: k_xfft_scale_cols, k_yfft_regs,
 dft_small<6>, dft_small<10>), in numpy: the three-stage decimation in frequency that leaves X[k0 + R0 k1 + R0 R1 k2] in "register k2 of
 lane (k0, k1)", its inverse from that digit-reversed order, the Good-Thomas maps of the radix-6 / radix-10 butterflies, the
 natural-order hand-over of the y pass, and the LDS paddings the kernels are instantiated with (bank model of

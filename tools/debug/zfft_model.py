@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""NumPy model of the wave-per-row z transforms (k_zfft_rows in csrc/pse_kernels.hip: NC = R0 x 8 x 8 at Nz = 256 / 512; k_zfft_rows_g
+"""NumPy model of the wave-per-row z transforms (k_zfft_rows in csrc/pse_fft.hip: NC = R0 x 8 x 8 at Nz = 256 / 512; k_zfft_rows_g
 in csrc/pse_zfft.hip: NC = R0 x R1 x R2 at the other 2^a 3^b 5^c sizes): the index algebra of the three stages (lane l < L = NC / R0 holds
 the points l + L r), the real <-> half-spectrum step around them, and the normalisation (unnormalised both ways, as rocFFT's real
 transforms) -- checked against numpy.fft for every size the kernels are instantiated at."""
@@ -57,7 +57,7 @@ def c2r(X, f):
     return x
 
 
-# Nz -> (R0, R1, R2) of the instantiations (pse_zfft.hip ZFFT_SIZES; 256 / 512: pse_kernels.hip)
+# Nz -> (R0, R1, R2) of the instantiations (pse_zfft.hip ZFFT_SIZES; 256 / 512: pse_fft.hip)
 SIZES = {256: (2, 8, 8), 512: (4, 8, 8), 360: (3, 6, 10), 270: (3, 5, 9), 180: (2, 5, 9), 240: (2, 6, 10), 300: (3, 5, 10), 320: (4, 4, 10),
          384: (3, 8, 8), 400: (4, 5, 10), 450: (5, 5, 9), 480: (4, 6, 10), 500: (5, 5, 10)}
 
