@@ -525,7 +525,61 @@ int pse_bond_order_histogram(pse_bond_order *b, const double *values /* DEVICE, 
                              const unsigned *group, unsigned N, int nbins, double lo, double hi,
                              unsigned long long *counts /* DEVICE, ntypes x nbins, 8-byte aligned, ADDED to */);
 
-/* ---- bonded forces: HOOMD's bond.harmonic and bond.fene (no reference counterpart: the reference leaves forces to HOOMD) ----
+/* ---- chain conformations: the gyration tensor and the end-to-end vector of every molecule of a bond topology (no reference counterpart) ----
+ * A pse_molecules object fixes the molecules: the connected components with at least two particles of the nbonds bonds pairs_host
+ * (CALLER-order indices below n), laid out by pse_host_molecule_rows (below, which documents numbering, spanning tree, ends and tiles),
+ * one type per MOLECULE (mol_types_host: nmol entries below ntypes <= 8 in the order of the molecule numbers, NULL: one type; copied at
+ * creation) and nbins bins for the histogram of Rg on [0, rg_max) and of |R| on [0, ree_max) (nbins == 0: no histograms).  There is no
+ * group argument: the topology names its particles.  Every particle has mass 1.
+ * pse_molecules_compute, per molecule of m members, in the handle's CURRENT box (pse_set_box, tilt included):
+ *   UNFOLDING.  The offset of member i from the root is u_i = the sum along the tree path root -> i of min_image(r_child - r_parent), the
+ *   minimum image of the force passes (y first with the tilt taken off x, then x, then z; one rint per axis).  It is right through any
+ *   number of Lees-Edwards flips and whatever image the integrator left a bead in, and VALID WHILE EVERY TREE EDGE IS SHORTER THAN HALF OF
+ *   min(Lx, Ly, Lz); this is documented, not checked.  The sum runs by pointer jumping: round k adds to every member's partial sum the
+ *   partial sum of its 2^k-th ancestor, so u_i is the balanced-tree sum of its path's edges, pairs first (a function of the layout alone).
+ *   CENTRE.  su = sum of u_i by a halving tree over the breadth-first positions (position p adds position p + s for s = the powers of
+ *   two below m, descending, where p + s < m);  c = r_root + su / m, NOT re-wrapped into the box.
+ *   SECOND PASS.  v_i = u_i - su / m;  G_ab = (sum of v_a v_b, the same tree) / m;  Rg^2 = (G_xx + G_yy) + G_zz;  for a linear molecule
+ *   R = u_hi - u_lo and R^2 = fma(R_z, R_z, fma(R_y, R_y, R_x R_x)): three roundings.
+ *   rows[mol PSE_MOL_COLS + ...] = c(3), G_xx, G_yy, G_zz, G_xy, G_xz, G_yz, Rg^2, R(3), R^2; the four R columns are NaN for a molecule
+ *   without ends.  unfolded[i] = (r_root + u_i, the molecule number in w) for every member i; rows of non-members are not touched.
+ *   sums and sample, per molecule type a, PSE_MOL_COLS columns: 0-5 the sum of G_ab in the order above, 6 the sum of (Rg^2)^2, 7-12 the
+ *   sum of R_a R_b in the same order, 13 the sum of (R^2)^2; 7-13 over the linear molecules only.  `sample` is WRITTEN with this call's
+ *   sums alone, `sums` is ADDED to.  A type without molecules adds exactly +0.0.
+ *   hist: row (0, a) bins Rg = sqrt(Rg^2), row (1, a) bins |R| = sqrt(R^2) (linear molecules), nbins + 1 counters a row, ADDED to:
+ *   bin = (int)(value f), f = nbins / max formed once on the host; a value with value f >= nbins goes to the extra last counter.
+ * One workgroup of PSE_MOL_TILE lanes handles one tile: it gathers the positions of its members once, keeps the partial sums of the
+ * pointer jumping in two LDS buffers (56 KB), and reduces first the members of every molecule, then the molecules of every type with
+ * halving trees whose order the layout alone fixes; it writes one partial row per type into a workspace the object owns, and a
+ * finishing kernel adds the tiles in a fixed order, writes `sample` and adds to `sums`.  A 1024-bead chain costs 10 rounds.  No
+ * floating-point atomics (the counters of hist are integers): equal inputs give equal bits.  The call only queues work on the handle's
+ * stream and reads nothing back; it can be captured in a graph.  It does not sort and touches neither the cell list nor the kept
+ * neighbour list, and it works on a slab rank's handle (positions are replicated there).
+ * pse_molecules_count writes to HOST memory: *nmol, and per type the linear molecules and all molecules (ntypes entries each).
+ * The object belongs to its handle exactly as a pse_msd does: pse_destroy frees the objects still alive, pse_molecules_destroy waits for
+ * the stream.  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.
+ * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, internal-distance curves R^2(s) and the persistence length,
+ * the hydrodynamic radius (a pair sum, which belongs on another pass), time correlations of R, and owned-particle ranks (local_rows).
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_molecules_create, in this order: a null out or
+ * h, n == 0 or n > n_max, nbonds == 0, a null pairs_host, every refusal of pse_host_molecule_rows in its order, ntypes outside [1, 8], a
+ * molecule type >= ntypes, nbins outside [0, 4096], with nbins > 0 an rg_max and then a ree_max that is not finite and positive (*out is
+ * null after a refusal).  pse_molecules_compute, in this order: a null m, a null pos, every output NULL, rows, unfolded, sums, sample
+ * or hist not aligned (8 bytes; unfolded 16), hist given to an object with nbins == 0.  pse_molecules_count: a null m, every output NULL. */
+#define PSE_MOL_TILE 1024   /* members of one tile, and of the largest molecule */
+#define PSE_MOL_COLS 14
+typedef struct pse_molecules pse_molecules;
+int pse_molecules_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host /* nbonds x 2 particle indices */,
+                         const unsigned *mol_types_host /* nmol, or NULL: one type */, int ntypes, int nbins, double rg_max, double ree_max,
+                         pse_molecules **out);
+int pse_molecules_destroy(pse_molecules *m);
+int pse_molecules_count(pse_molecules *m, unsigned *nmol, unsigned *nlinear /* ntypes */, unsigned *nmol_type /* ntypes */);
+int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, double *rows /* DEVICE, nmol x 14, may be NULL */,
+                          pse_double4 *unfolded /* DEVICE, caller order, may be NULL; non-members untouched */,
+                          double *sums /* DEVICE, ntypes x 14, ADDED to, may be NULL */,
+                          double *sample /* DEVICE, ntypes x 14, WRITTEN, may be NULL */,
+                          unsigned long long *hist /* DEVICE, 2 x ntypes x (nbins + 1), ADDED to, may be NULL */);
+
+/* ---- bonded forces: HOOMD's bond.harmonic and bond.fene(no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
  * each with one of ntypes <= 64 parameter sets (kind, k, r0).  With d = r_i - r_j (minimum image in the handle's current box,
  * pse_set_box) and r = |d|, the force ON i FROM j is c d:
@@ -923,6 +977,24 @@ int pse_host_exclusion_rows(unsigned n, unsigned npairs, const unsigned *pairs, 
  * rmin < 0, rmax <= rmin.  Nothing is written after a refusal. */
 int pse_host_typed_table_layout(int ntypes, const int *width, const double *rmin, const double *rmax,
                                 int *base /* npt */, double *scale /* npt */, double *rmax2 /* npt */, int *total);
+/* host-only: the layout a pse_molecules object stores (pse_molecules_create calls this after validating).  The MOLECULES are the
+ * connected components of the bond graph with at least two particles, numbered by their smallest member, which is the ROOT;
+ * mol_of[i] = the molecule of particle i, or -1 for a particle without a bond.  Per molecule a breadth-first SPANNING TREE from the root,
+ * the neighbours visited in ascending index: `members` holds the caller indices of molecule after molecule in breadth-first order,
+ * molecule mol at members[mol_off[mol]] .. members[mol_off[mol + 1]); parent[s] = the breadth-first POSITION (0 .. m - 1) of the parent
+ * of the member in slot s, always smaller than its own position, the root being its own parent; depth[s] = its distance from the root
+ * in tree edges.  Bonds that close rings are not tree edges: nring[mol] counts them, they are otherwise ignored.  A molecule is
+ * LINEAR if it is a tree with exactly two members of degree 1 and all others of degree 2 (a dimer is): ends[2 mol], ends[2 mol + 1] =
+ * the positions of the two, the one with the lower caller index first; 0xffffffff twice for any other molecule.  TILES: the molecules
+ * are packed in order into tiles of at most PSE_MOL_TILE members, a molecule never straddles a tile and a tile is closed when the next
+ * molecule does not fit: tile t holds the molecules tile_mol[t] .. tile_mol[t + 1), and tile_rounds[t] = ceil(log2(its largest depth + 1))
+ * rounds of pointer jumping.  counts = (nmol, members in all, ntiles).  The layout is a function of the bond SET.
+ * PSE_ERR_INVALID, in this order: a null array, n == 0, nbonds == 0 (no molecule at all) or > 2^30, in the order of the list an endpoint
+ * >= n or a bond (i, i), a bond listed twice in either order, a molecule of more than PSE_MOL_TILE members. */
+int pse_host_molecule_rows(unsigned n, unsigned nbonds, const unsigned *pairs, int *mol_of /* n */, unsigned *members /* n */,
+                           unsigned *parent /* n */, unsigned *depth /* n */, unsigned *mol_off /* n / 2 + 1 */, unsigned *ends /* 2 (n / 2) */,
+                           unsigned *nring /* n / 2 */, unsigned *tile_mol /* n / 2 + 1 */, unsigned *tile_rounds /* n / 2 */,
+                           unsigned *counts /* 3 */);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,11 @@ SYMBOLS = {
     "pse_bond_order_destroy": (_i, [_vp]),
     "pse_bond_order_compute": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _i, _d, _u, _vp, _vp, _vp]),
     "pse_bond_order_histogram": (_i, [_vp, _vp, _i, _vp, _u, _i, _d, _d, _vp]),
+    "pse_molecules_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _i, _d, _d, _vp]),
+    "pse_molecules_destroy": (_i, [_vp]),
+    "pse_molecules_count": (_i, [_vp, _vp, _vp, _vp]),
+    "pse_molecules_compute": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pse_host_molecule_rows": (_i, [_u, _u] + [_vp] * 11),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

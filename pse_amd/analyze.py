@@ -10,7 +10,10 @@ Clusters says which particles hang together: the connected components of a dista
 over the sorted rows (pse_clusters_label), with the number of clusters, the largest one and the size distribution n(s) per sample.
 BondOrder says whether a neighbourhood is ordered: the Steinhardt q_l, the neighbour-averaged q-bar_l and the solid-like bonds of
 every particle (pse_bond_order_compute: spherical harmonics up to degree 12 summed over the neighbours on the cell list), with their
-per-type distributions and the solid-like fraction per sample."""
+per-type distributions and the solid-like fraction per sample.
+Conformations measures the molecules that a bond topology defines: every molecule unfolded along its own bonds in the box of the
+step, its gyration tensor, Rg^2 and end-to-end vector reduced on the device (pse_molecules_compute: pointer jumping and fixed-order
+trees in LDS, one workgroup per tile of molecules), per-type sums, a ring of per-sample sums and the histograms of Rg and |R|."""
 import contextlib
 import math
 
@@ -894,3 +897,249 @@ class BondOrder(_TypedAnalyzer, _SampleRing):
         """The solid-like members of type `a` (None: all) over the samples kept, divided by the members."""
         self._solid()
         return solid_fraction_of(self.table()[:, 1:].reshape(-1, self.ntypes, 2), None if a is None else _type_codes([a], self.type_names)[0])
+
+
+def molecules_of(n, bonds):
+    """The molecules of a bond list by the rule of pse_host_molecule_rows, NumPy only: (mol_of, nmol).  The molecules are the connected
+    components of the (nbonds, 2) index pairs `bonds` among n particles with at least two members, numbered in the order of their
+    smallest member; mol_of (n,) int64 holds the molecule of every particle, -1 for a particle without a bond.  For building one type
+    per molecule (Conformations(molecule_types=...)).  A bond (i, i) makes no molecule here; the library refuses it."""
+    import numpy as np
+    n = int(n)
+    b = np.asarray(bonds)
+    if b.ndim != 2 or b.shape[1] != 2 or b.shape[0] == 0 or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError("bonds must be a non-empty integer (nbonds, 2) array of particle indices")
+    if n < 1 or b.min() < 0 or b.max() >= n:
+        raise ValueError(f"bonds holds an index outside [0, n = {n})")
+    i, j = b[:, 0].astype(np.int64), b[:, 1].astype(np.int64)
+    label = np.arange(n, dtype=np.int64)
+    while True:   # the smallest label of a component spreads along the bonds, and every label jumps to its own label's label
+        new = label.copy()
+        np.minimum.at(new, i, label[j])
+        np.minimum.at(new, j, label[i])
+        new = new[new]
+        if np.array_equal(new, label):
+            break
+        label = new
+    bonded = np.zeros(n, dtype=bool)
+    bonded[i[i != j]] = True
+    bonded[j[i != j]] = True
+    roots = np.unique(label[bonded])
+    mol_of = np.where(bonded, np.searchsorted(roots, label), -1)
+    return mol_of, int(roots.shape[0])
+
+
+def tensor_of(cols):
+    """(..., 6) columns xx, yy, zz, xy, xz, yz as symmetric (..., 3, 3) tensors."""
+    import numpy as np
+    c = np.asarray(cols, dtype=np.float64)
+    return np.stack([np.stack([c[..., 0], c[..., 3], c[..., 4]], -1), np.stack([c[..., 3], c[..., 1], c[..., 5]], -1),
+                     np.stack([c[..., 4], c[..., 5], c[..., 2]], -1)], -2)
+
+
+def shape_of(G):
+    """The shape descriptors of gyration tensors G (..., 3, 3): (eigenvalues (..., 3) in ascending order l1 <= l2 <= l3, asphericity
+    b = l3 - (l1 + l2)/2, acylindricity c = l2 - l1, relative shape anisotropy kappa^2 = (b^2 + 3/4 c^2) / (l1 + l2 + l3)^2: 0 for a
+    sphere, 1 for a rod)."""
+    import numpy as np
+    lam = np.linalg.eigvalsh(np.asarray(G, dtype=np.float64))
+    b = lam[..., 2] - 0.5 * (lam[..., 0] + lam[..., 1])
+    c = lam[..., 1] - lam[..., 0]
+    return lam, b, c, (b * b + 0.75 * c * c) / lam.sum(axis=-1) ** 2
+
+
+def orientation_angle(G):
+    """The orientation angle chi of tensors G (..., 3, 3) in the flow-gradient plane: tan 2 chi = 2 G_xy / (G_xx - G_yy), chi in
+    (-pi/2, pi/2], the angle of the major axis of the xy block against the flow direction x."""
+    import numpy as np
+    G = np.asarray(G, dtype=np.float64)
+    return 0.5 * np.arctan2(2.0 * G[..., 0, 1], G[..., 0, 0] - G[..., 1, 1])
+
+
+MOL_MAX_TYPES = 8   # molecule types of one Conformations
+
+
+def _conformation_arguments(bonds, molecule_types, type_names, period, nbins, rg_max, ree_max, capacity):
+    """What Conformations checks before it touches the device, from the (nbonds, 2) pairs `bonds` (the molecules and their numbers do
+    not depend on how many particles there are beyond the largest index).  Returns (pairs
+    uint32, molecule types uint32 (nmol,) or None, ntypes, names or None, period, nbins, rg_max, ree_max, capacity, sizes (nmol,),
+    size_values: the molecule size of every type with molecule_types="size", else None)."""
+    import numpy as np
+    from .engine import _molecule_arguments
+    names = None if type_names is None else list(type_names)
+    if names is not None and (not names or len(set(names)) != len(names) or not all(isinstance(v, str) for v in names)):
+        raise ValueError("type_names must be distinct strings")
+    if int(period) < 1:
+        raise ValueError("period must be positive")
+    if int(capacity) < 1:
+        raise ValueError("capacity must be positive")
+    b = np.asarray(bonds)
+    if b.ndim != 2 or b.shape[1:] != (2,) or b.shape[0] == 0 or not np.issubdtype(b.dtype, np.integer) or b.min() < 0:
+        raise ValueError("bonds must be a forces.Bonds or a non-empty integer (nbonds, 2) array of particle indices")
+    mol_of, nmol = molecules_of(int(b.max()) + 1, b)
+    if nmol == 0:
+        raise ValueError("bonds makes no molecule")
+    sizes = np.bincount(mol_of[mol_of >= 0], minlength=nmol)
+    size_values = None
+    if molecule_types is None:
+        if names is not None and len(names) != 1:
+            raise ValueError("type_names without molecule_types: there is one type")
+        types, ntypes = None, 1
+    elif isinstance(molecule_types, str):
+        if molecule_types != "size":
+            raise ValueError('molecule_types must be None, "size" or one code or name per molecule')
+        size_values = np.unique(sizes)
+        if size_values.shape[0] > MOL_MAX_TYPES:
+            raise ValueError(f"molecule_types=\"size\": {size_values.shape[0]} distinct molecule sizes, more than {MOL_MAX_TYPES} types")
+        types, ntypes = np.searchsorted(size_values, sizes), int(size_values.shape[0])
+        if names is not None and len(names) != ntypes:
+            raise ValueError(f"type_names has {len(names)} entries, the molecules {ntypes} sizes")
+    else:
+        types = np.asarray(_type_codes(molecule_types.tolist() if hasattr(molecule_types, "tolist") else list(molecule_types), names))
+        if types.ndim != 1 or not np.issubdtype(types.dtype, np.integer) or (types.shape[0] and types.min() < 0):
+            raise ValueError("molecule_types must be a 1-D sequence of non-negative integers or names, one per molecule")
+        if types.shape[0] != nmol:
+            raise ValueError(f"molecule_types has {types.shape[0]} entries, the bonds make {nmol} molecules")
+        ntypes = max(int(types.max()) + 1, len(names or ()))
+    ntypes = _ntypes_argument(ntypes)
+    pairs, types, ntypes, nbins, rg_max, ree_max = _molecule_arguments(bonds, types, ntypes, nbins, rg_max, ree_max)
+    return pairs, types, ntypes, names, int(period), nbins, rg_max, ree_max, int(capacity), sizes, size_values
+
+
+class Conformations(_TypedAnalyzer, _SampleRing):
+    """The conformation of the molecules that a bond topology defines: every `period` steps one pass (pse_molecules_compute) unfolds
+    every molecule along its own bonds by the minimum image in the box of that step -- right through any number of Lees-Edwards
+    flips, while every bond is shorter than half the smallest box length -- and reduces its gyration tensor G, Rg^2 and, for a linear
+    molecule, its end-to-end vector R.  `bonds`: a forces.Bonds, whose pairs are reused, or an (nbonds, 2) array of particle indices;
+    the molecules are its connected components (molecules_of).  `molecule_types`: None (one type), one code or name (`type_names=`) per
+    molecule, or "size": the distinct molecule sizes in ascending order are the types (at most 8).  Each sample adds its per-type sums
+    to the accumulated `sums`, writes them alone into a device ring of `capacity` rows -- once full, the oldest rows are replaced --
+    and, with nbins > 0, counts Rg on [0, rg_max) and |R| on [0, ree_max).  Sampling only queues work; the readers are the only places
+    that wait for the device.  Every particle has mass 1.  Not measured: molecules of more than 1024 members, internal distances and
+    the persistence length, the hydrodynamic radius, time correlations of R.
+
+    nmol, nlinear, nmol_type, sizes();  gyration_tensor(a), rg2(a), rg4(a), ree_tensor(a), ree2(a), ree4(a) -- means over the molecules
+    (R: the linear ones) of type `a` (None: all) and over the samples since reset();  series() -- (samples kept, 1 + ntypes 14): the
+    timestep and every type's sums of that sample (COLUMNS);  per_molecule() -- (nmol, 14) at the current positions (ROW_COLUMNS);
+    unfolded();  histogram(which, a);  samples;  reset()."""
+
+    COLUMNS = ("Gxx", "Gyy", "Gzz", "Gxy", "Gxz", "Gyz", "Rg4", "RxRx", "RyRy", "RzRz", "RxRy", "RxRz", "RyRz", "R4")
+    ROW_COLUMNS = ("cx", "cy", "cz", "Gxx", "Gyy", "Gzz", "Gxy", "Gxz", "Gyz", "Rg2", "Rx", "Ry", "Rz", "R2")
+
+    def __init__(self, integrator, bonds, molecule_types=None, type_names=None, period=1, nbins=0, rg_max=None, ree_max=None, capacity=1024):
+        import torch
+        from .engine import MOL_COLS, MoleculeTopology
+        lst = getattr(bonds, "_list", None)
+        pairs = lst.index if lst is not None and hasattr(lst, "index") else bonds
+        (pairs, types, self.ntypes, self.type_names, self.period, self.nbins, self.rg_max, self.ree_max, self.capacity, self._sizes,
+         self.size_values) = _conformation_arguments(pairs, molecule_types, type_names, period, nbins, rg_max, ree_max, capacity)
+        with self._attach(integrator, None) as system:          # (the line above raises before the integrator is touched)
+            if int(pairs.max()) >= system.n:
+                raise ValueError(f"bonds holds the index {int(pairs.max())}, the system has {system.n} particles")
+            self.molecule_types = types
+            self._mol = MoleculeTopology(integrator.engine, pairs, types, self.ntypes, self.nbins, self.rg_max, self.ree_max, system.n)
+            self.nmol, self.nlinear, self.nmol_type = self._mol.nmol, self._mol.nlinear, self._mol.nmol_type
+            dev = system.pos.device
+            self._sums = torch.zeros((self.ntypes, MOL_COLS), dtype=torch.float64, device=dev)
+            self._rows = torch.zeros((self.capacity, self.ntypes, MOL_COLS), dtype=torch.float64, device=dev)
+            self._hist = torch.zeros((2, self.ntypes, self.nbins + 1), dtype=torch.int64, device=dev) if self.nbins else None
+            self._ring_reset()
+
+    def analyze(self, timestep):
+        if not self._due(timestep):
+            return
+        q = self._slot()
+        self.integrator.engine.molecules_compute(self.system.pos, self._mol, sums=self._sums, sample=self._rows[q], hist=self._hist)
+        self._record(q, timestep)
+
+    def reset(self):
+        self._sums.zero_(); self._rows.zero_()
+        if self._hist is not None:
+            self._hist.zero_()
+        self._ring_reset()
+
+    def sizes(self):
+        """(nmol,) int64: the number of members of every molecule."""
+        return self._sizes.astype("int64")
+
+    def sums(self):
+        """(ntypes, 14) float64: the accumulated sums (COLUMNS) since the last reset()."""
+        return self._sums.cpu().numpy()
+
+    def _mean(self, a, cols, counts):
+        import numpy as np
+        self._sampled()
+        s = self.sums()
+        if a is None:
+            return s[:, cols].sum(axis=0) / (self.samples * counts.sum())
+        a = self._code(a)
+        return s[a, cols] / (self.samples * counts[a]) if counts[a] else np.full(len(range(*cols.indices(14))), np.nan)
+
+    def gyration_tensor(self, a=None):
+        """(3, 3): the mean gyration tensor of the molecules of type `a` (None: of all)."""
+        return tensor_of(self._mean(a, slice(0, 6), self.nmol_type))
+
+    def rg2(self, a=None):
+        """<Rg^2>, the trace of gyration_tensor(a)."""
+        return float(self._mean(a, slice(0, 3), self.nmol_type).sum())
+
+    def rg4(self, a=None):
+        """<(Rg^2)^2>."""
+        return float(self._mean(a, slice(6, 7), self.nmol_type)[0])
+
+    def ree_tensor(self, a=None):
+        """(3, 3): <R_a R_b> over the linear molecules of type `a` (None: of all)."""
+        return tensor_of(self._mean(a, slice(7, 13), self.nlinear))
+
+    def ree2(self, a=None):
+        """<R^2> over the linear molecules."""
+        return float(self._mean(a, slice(7, 10), self.nlinear).sum())
+
+    def ree4(self, a=None):
+        """<(R^2)^2> over the linear molecules."""
+        return float(self._mean(a, slice(13, 14), self.nlinear)[0])
+
+    def series(self):
+        """(samples kept, 1 + ntypes 14) float64, oldest first: the timestep, then for every type the 14 sums (COLUMNS) of that sample
+        alone (one copy from the device).  Divide by nmol_type (columns 0-6) or nlinear (7-13) for means."""
+        import numpy as np
+        n = min(self.samples, self.capacity)
+        dev = self._rows.cpu().numpy().reshape(self.capacity, -1)
+        out = np.zeros((n, 1 + dev.shape[1]))
+        for r in range(n):
+            q = (self.samples - n + r) % self.capacity
+            out[r, 0], out[r, 1:] = self._steps[q], dev[q]
+        return out
+
+    table = series   # (the ring's rows are doubles here: the integer table of _SampleRing would truncate them)
+
+    def per_molecule(self):
+        """(nmol, 14) float64: the row of every molecule (ROW_COLUMNS) at the system's current positions; the four R columns are NaN for
+        a molecule that is not linear.  One pass and one copy; no sample is taken."""
+        import torch
+        from .engine import MOL_COLS
+        rows = torch.empty((self.nmol, MOL_COLS), dtype=torch.float64, device=self.system.pos.device)
+        self.integrator.engine.molecules_compute(self.system.pos, self._mol, rows=rows)
+        return rows.cpu().numpy()
+
+    def unfolded(self):
+        """(n, 4) float64: every member's unfolded position r_root + u at the system's current positions and the number of its
+        molecule; (NaN, NaN, NaN, -1) for a particle in no molecule."""
+        import torch
+        out = torch.full((self.system.n, 4), float("nan"), dtype=torch.float64, device=self.system.pos.device)
+        out[:, 3] = -1.0
+        self.integrator.engine.molecules_compute(self.system.pos, self._mol, unfolded=out)
+        return out.cpu().numpy()
+
+    def histogram(self, which, a=None):
+        """(counts (nbins + 1,), edges (nbins + 1,)): the accumulated counts of `which` = "rg" (Rg of every molecule) or "ree" (|R| of
+        the linear ones) for the type `a` (None: all types); counts[b] belongs to [edges[b], edges[b + 1]), the last entry counts the
+        values at or above the maximum."""
+        import numpy as np
+        if which not in ("rg", "ree"):
+            raise ValueError('which must be "rg" or "ree"')
+        if self._hist is None:
+            raise ValueError("this analyzer was made with nbins = 0: it has no histogram")
+        h = self._hist.cpu().numpy()[0 if which == "rg" else 1]
+        counts = h.sum(axis=0) if a is None else h[self._code(a)]
+        return counts, np.arange(self.nbins + 1) * ((self.rg_max if which == "rg" else self.ree_max) / self.nbins)

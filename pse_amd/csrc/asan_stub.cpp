@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -43,6 +43,12 @@ struct pse_structure_factor : Topology { using Topology::Topology; };   // row_o
 struct pse_msd : Topology { using Topology::Topology; int norigins = 0; unsigned long long stored = 0ull; };   // the slots' bookkeeping alone
 struct pse_clusters : Topology { using Topology::Topology; };      // entries: the types (zeros where none were given); the status word is always 0
 struct pse_bond_order : Topology { using Topology::Topology; int ntypes = 1; };   // entries: the types; row_off: the degrees
+struct pse_molecules : Topology {   // the REAL layout (molecule_layout) and the molecule types
+    using Topology::Topology;
+    MoleculeLayout L;
+    std::vector<unsigned> types;
+    int ntypes = 1, nbins = 0;
+};
 struct pse_team { int unused; };
 
 // keeps t on its handle unless the row builder refused the list (rows_rc != 0)
@@ -266,6 +272,28 @@ int pse_bond_order_histogram(pse_bond_order *b, const double *values, int column
                              unsigned long long *counts) {
     return bond_order_histogram_validate(b, b ? (int)b->row_off.size() : 0, b ? b->ntypes : 1, b ? b->h->par.n_max : 0u, values, column, N, nbins,
                                          lo, hi, counts);
+}
+int pse_molecules_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *mol_types_host, int ntypes, int nbins,
+                         double rg_max, double ree_max, pse_molecules **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_molecules_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_molecules_create: null handle");
+    pse_molecules *m = new pse_molecules(h, 0, 0);
+    m->ntypes = ntypes; m->nbins = nbins;
+    const int rc = molecules_create_validate(h->par.n_max, n, nbonds, pairs_host, mol_types_host, ntypes, nbins, rg_max, ree_max, m->L);
+    if (!rc && mol_types_host) m->types.assign(mol_types_host, mol_types_host + m->L.nmol);
+    return topology_adopt(m, rc, out);
+}
+int pse_molecules_destroy(pse_molecules *m) { return topology_destroy(m); }
+int pse_molecules_count(pse_molecules *m, unsigned *nmol, unsigned *nlinear, unsigned *nmol_type) {
+    if (int rc = molecules_count_validate(m, nmol, nlinear, nmol_type)) return rc;
+    molecules_counts(m->L, m->types.empty() ? nullptr : m->types.data(), m->ntypes, nmol, nlinear, nmol_type);
+    return 0;
+}
+// (the arrays are device pointers and there is no device: nothing is read or written)
+int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, double *rows, pse_double4 *unfolded, double *sums, double *sample,
+                          unsigned long long *hist) {
+    return molecules_compute_validate(m, m ? m->nbins : 0, pos, rows, unfolded, sums, sample, hist);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -103,5 +103,25 @@ int bond_order_compute_validate(const void *b, const void *b_handle, int nl, uns
 // the argument checks of pse_bond_order_histogram: the object (nl and ntypes its own, n_max its handle's), N, values, the column, the bins, counts
 int bond_order_histogram_validate(const void *b, int nl, int ntypes, unsigned n_max, const void *values, int column, unsigned N, int nbins,
                                   double lo, double hi, const void *counts);
+// The layout of pse_host_molecule_rows (include/pse_amd.h documents every array) as host vectors: mol_of (n), members, parent and depth
+// (one per member, molecule after molecule in breadth-first order; parent: the position in its molecule), mol_off (nmol + 1), ends
+// (2 nmol positions, 0xffffffff: none), nring (nmol), tile_mol (ntiles + 1), tile_rounds (ntiles).
+struct MoleculeLayout {
+    std::vector<int> mol_of;
+    std::vector<unsigned> members, parent, depth, mol_off, ends, nring, tile_mol, tile_rounds;
+    unsigned nmol = 0, ntiles = 0;
+};
+// 0 and the layout, or PSE_ERR_INVALID with a message under the name `who`: the refusals of pse_host_molecule_rows behind its null arrays
+int molecule_layout(const char *who, unsigned n, unsigned nbonds, const unsigned *pairs, MoleculeLayout &L);
+// the argument checks of pse_molecules_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them,
+// with the handle's n_max; the layout is built on the way (its refusals stand between those of nbonds and of ntypes) and returned
+int molecules_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int nbins,
+                              double rg_max, double ree_max, MoleculeLayout &L);
+// the argument checks of pse_molecules_compute (nbins: the object's) and of pse_molecules_count
+int molecules_compute_validate(const void *m, int nbins, const void *pos, const void *rows, const void *unfolded, const void *sums,
+                               const void *sample, const void *hist);
+int molecules_count_validate(const void *m, const void *nmol, const void *nlinear, const void *nmol_type);
+// what pse_molecules_count writes (each output may be null): the molecules, and per type the linear ones and all of them
+void molecules_counts(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, unsigned *nmol, unsigned *nlinear, unsigned *nmol_type);
 
 }  // namespace pse

@@ -532,6 +532,147 @@ void structure_factor_plan(unsigned nk, const int *modes, std::vector<unsigned> 
     segs.swap(sorted);
 }
 
+// The layout of pse_host_molecule_rows (include/pse_amd.h), under the name `who` of the entry point that asks.  Adjacency rows by a
+// counting sort, each sorted ascending; one breadth-first walk per component from its smallest member; the tiles by a greedy packing.
+int molecule_layout(const char *who, unsigned n, unsigned nbonds, const unsigned *pairs, MoleculeLayout &L) {
+    if (!pairs) return fail(PSE_ERR_INVALID, "%s: null pairs", who);
+    if (n == 0) return fail(PSE_ERR_INVALID, "%s: n = 0", who);
+    if (nbonds == 0) return fail(PSE_ERR_INVALID, "%s: nbonds = 0: there is no molecule at all", who);
+    if (nbonds > (1u << 30)) return fail(PSE_ERR_INVALID, "%s: nbonds = %u outside (0, 2^30]", who, nbonds);
+    std::vector<uint64_t> key(nbonds);
+    for (unsigned b = 0; b < nbonds; ++b) {
+        const unsigned i = pairs[2 * (size_t)b], j = pairs[2 * (size_t)b + 1];
+        if (i >= n || j >= n) return fail(PSE_ERR_INVALID, "%s: bond %u = (%u, %u) has an endpoint >= n = %u", who, b, i, j, n);
+        if (i == j) return fail(PSE_ERR_INVALID, "%s: bond %u joins particle %u to itself", who, b, i);
+        key[b] = ((uint64_t)std::min(i, j) << 32) | std::max(i, j);
+    }
+    std::sort(key.begin(), key.end());
+    for (unsigned b = 1; b < nbonds; ++b)
+        if (key[b] == key[b - 1])
+            return fail(PSE_ERR_INVALID, "%s: the bond (%u, %u) is listed twice", who, (unsigned)(key[b] >> 32), (unsigned)key[b]);
+    // (the keys are sorted by (min, max): walked in that order every row comes out ascending, as in pse_host_exclusion_rows)
+    std::vector<unsigned> off((size_t)n + 1, 0u), adj(2 * (size_t)nbonds);
+    for (uint64_t k : key) { ++off[(unsigned)(k >> 32) + 1]; ++off[(unsigned)k + 1]; }
+    for (unsigned i = 0; i < n; ++i) off[i + 1] += off[i];
+    {
+        std::vector<unsigned> fill(off.begin(), off.begin() + n);
+        for (uint64_t k : key) {
+            const unsigned lo = (unsigned)(k >> 32), hi = (unsigned)k;
+            adj[fill[lo]++] = hi;
+            adj[fill[hi]++] = lo;
+        }
+    }
+    L = MoleculeLayout();
+    L.mol_of.assign(n, -1);
+    L.mol_off.push_back(0u);
+    std::vector<unsigned> slot_of(n, 0u), maxdepth;
+    for (unsigned root = 0; root < n; ++root) {
+        if (L.mol_of[root] >= 0 || off[root + 1] == off[root]) continue;
+        const int mol = (int)L.nring.size();
+        const unsigned first = (unsigned)L.members.size();
+        L.mol_of[root] = mol;
+        slot_of[root] = first;
+        L.members.push_back(root); L.parent.push_back(0u); L.depth.push_back(0u);
+        size_t degsum = 0;
+        unsigned ones = 0, twos = 0, end_lo = 0u, end_hi = 0u, deepest = 0u;
+        for (unsigned q = first; q < L.members.size(); ++q) {   // (the queue is the member list itself)
+            const unsigned i = L.members[q], deg = off[i + 1] - off[i];
+            degsum += deg;
+            if (deg == 1) { (ones == 0 ? end_lo : end_hi) = q; ++ones; }   // (of a linear molecule: its two ends)
+            twos += deg == 2;
+            for (unsigned e = off[i]; e < off[i + 1]; ++e) {
+                const unsigned j = adj[e];
+                if (L.mol_of[j] >= 0) continue;
+                L.mol_of[j] = mol;
+                slot_of[j] = (unsigned)L.members.size();
+                L.members.push_back(j); L.parent.push_back(q - first); L.depth.push_back(L.depth[q] + 1u);
+                deepest = std::max(deepest, L.depth[q] + 1u);
+            }
+        }
+        const unsigned m = (unsigned)L.members.size() - first;
+        if (m > (unsigned)PSE_MOL_TILE)
+            return fail(PSE_ERR_INVALID, "%s: the molecule of particle %u has %u members, more than PSE_MOL_TILE = %d", who, root, m, PSE_MOL_TILE);
+        const unsigned rings = (unsigned)(degsum / 2) - (m - 1u);
+        const bool linear = rings == 0u && ones == 2u && twos == m - 2u;
+        if (linear && L.members[end_lo] > L.members[end_hi]) std::swap(end_lo, end_hi);   // lower caller index first
+        L.nring.push_back(rings);
+        L.ends.push_back(linear ? end_lo - first : 0xffffffffu);
+        L.ends.push_back(linear ? end_hi - first : 0xffffffffu);
+        L.mol_off.push_back((unsigned)L.members.size());
+        maxdepth.push_back(deepest);
+    }
+    L.nmol = (unsigned)L.nring.size();
+    L.tile_mol.push_back(0u);
+    unsigned fill = 0u, deepest = 0u;
+    auto rounds_of = [](unsigned d) { unsigned r = 0; while ((1u << r) < d + 1u) ++r; return r; };
+    for (unsigned mol = 0; mol < L.nmol; ++mol) {
+        const unsigned m = L.mol_off[mol + 1] - L.mol_off[mol];
+        if (fill + m > (unsigned)PSE_MOL_TILE) {
+            L.tile_mol.push_back(mol);
+            L.tile_rounds.push_back(rounds_of(deepest));
+            fill = 0u; deepest = 0u;
+        }
+        fill += m;
+        deepest = std::max(deepest, maxdepth[mol]);
+    }
+    L.tile_mol.push_back(L.nmol);
+    L.tile_rounds.push_back(rounds_of(deepest));
+    L.ntiles = (unsigned)L.tile_rounds.size();
+    return 0;
+}
+
+int molecules_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int nbins,
+                              double rg_max, double ree_max, MoleculeLayout &L) {
+    const char *who = "pse_molecules_create";
+    if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
+    if (nbonds == 0) return fail(PSE_ERR_INVALID, "%s: nbonds = 0: there is no molecule at all", who);
+    if (!pairs) return fail(PSE_ERR_INVALID, "%s: null pairs_host", who);
+    if (int rc = molecule_layout(who, n, nbonds, pairs, L)) return rc;
+    if (ntypes < 1 || ntypes > PAIR_TYPED_MAX_TYPES) return fail(PSE_ERR_INVALID, "%s: ntypes = %d outside [1, %d]", who, ntypes, PAIR_TYPED_MAX_TYPES);
+    if (mol_types)
+        for (unsigned mol = 0; mol < L.nmol; ++mol)
+            if (mol_types[mol] >= (unsigned)ntypes)
+                return fail(PSE_ERR_INVALID, "%s: molecule %u has type %u >= ntypes = %d", who, mol, mol_types[mol], ntypes);
+    if (nbins < 0 || nbins > MOL_MAX_BINS) return fail(PSE_ERR_INVALID, "%s: nbins = %d outside [0, %d]", who, nbins, MOL_MAX_BINS);
+    if (nbins > 0 && !(std::isfinite(rg_max) && rg_max > 0.0)) return fail(PSE_ERR_INVALID, "%s: rg_max = %g must be finite and positive", who, rg_max);
+    if (nbins > 0 && !(std::isfinite(ree_max) && ree_max > 0.0)) return fail(PSE_ERR_INVALID, "%s: ree_max = %g must be finite and positive", who, ree_max);
+    return 0;
+}
+
+int molecules_compute_validate(const void *m, int nbins, const void *pos, const void *rows, const void *unfolded, const void *sums,
+                               const void *sample, const void *hist) {
+    const char *who = "pse_molecules_compute";
+    if (!m) return fail(PSE_ERR_INVALID, "%s: null molecule object", who);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!rows && !unfolded && !sums && !sample && !hist)
+        return fail(PSE_ERR_INVALID, "%s: rows, unfolded, sums, sample and hist are all null: nothing to compute", who);
+    if (((uintptr_t)rows & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: rows = %p is not 8-byte aligned (doubles)", who, rows);
+    if (((uintptr_t)unfolded & 15u) != 0) return fail(PSE_ERR_INVALID, "%s: unfolded = %p is not 16-byte aligned (rows of four doubles)", who, unfolded);
+    if (((uintptr_t)sums & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sums = %p is not 8-byte aligned (doubles)", who, sums);
+    if (((uintptr_t)sample & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sample = %p is not 8-byte aligned (doubles)", who, sample);
+    if (((uintptr_t)hist & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: hist = %p is not 8-byte aligned (64-bit counters)", who, hist);
+    if (hist && nbins == 0) return fail(PSE_ERR_INVALID, "%s: hist given, but the object was created with nbins = 0: it has no histogram", who);
+    return 0;
+}
+
+int molecules_count_validate(const void *m, const void *nmol, const void *nlinear, const void *nmol_type) {
+    const char *who = "pse_molecules_count";
+    if (!m) return fail(PSE_ERR_INVALID, "%s: null molecule object", who);
+    if (!nmol && !nlinear && !nmol_type) return fail(PSE_ERR_INVALID, "%s: nmol, nlinear and nmol_type are all null: nothing to write", who);
+    return 0;
+}
+
+void molecules_counts(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, unsigned *nmol, unsigned *nlinear, unsigned *nmol_type) {
+    if (nmol) *nmol = L.nmol;
+    if (nlinear) std::fill(nlinear, nlinear + ntypes, 0u);
+    if (nmol_type) std::fill(nmol_type, nmol_type + ntypes, 0u);
+    for (unsigned mol = 0; mol < L.nmol; ++mol) {
+        const unsigned a = mol_types ? mol_types[mol] : 0u;
+        if (nmol_type) ++nmol_type[a];
+        if (nlinear && L.ends[2 * (size_t)mol] != 0xffffffffu) ++nlinear[a];
+    }
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -703,4 +844,25 @@ extern "C" int pse_host_typed_table_layout(int ntypes, const int *width, const d
                                            double *rmax2, int *total) {
     if (!base || !scale || !rmax2 || !total) return fail(PSE_ERR_INVALID, "pse_host_typed_table_layout: null array (base, scale, rmax2, total)");
     return typed_layout("pse_host_typed_table_layout", ntypes, width, rmin, rmax, base, scale, rmax2, total);
+}
+
+// The layout of molecule_layout, copied into the caller's arrays.
+extern "C" int pse_host_molecule_rows(unsigned n, unsigned nbonds, const unsigned *pairs, int *mol_of, unsigned *members, unsigned *parent,
+                                      unsigned *depth, unsigned *mol_off, unsigned *ends, unsigned *nring, unsigned *tile_mol,
+                                      unsigned *tile_rounds, unsigned *counts) {
+    if (!pairs || !mol_of || !members || !parent || !depth || !mol_off || !ends || !nring || !tile_mol || !tile_rounds || !counts)
+        return fail(PSE_ERR_INVALID, "pse_host_molecule_rows: null array");
+    MoleculeLayout L;
+    if (int rc = molecule_layout("pse_host_molecule_rows", n, nbonds, pairs, L)) return rc;
+    std::copy(L.mol_of.begin(), L.mol_of.end(), mol_of);
+    std::copy(L.members.begin(), L.members.end(), members);
+    std::copy(L.parent.begin(), L.parent.end(), parent);
+    std::copy(L.depth.begin(), L.depth.end(), depth);
+    std::copy(L.mol_off.begin(), L.mol_off.end(), mol_off);
+    std::copy(L.ends.begin(), L.ends.end(), ends);
+    std::copy(L.nring.begin(), L.nring.end(), nring);
+    std::copy(L.tile_mol.begin(), L.tile_mol.end(), tile_mol);
+    std::copy(L.tile_rounds.begin(), L.tile_rounds.end(), tile_rounds);
+    counts[0] = L.nmol; counts[1] = (unsigned)L.members.size(); counts[2] = L.ntiles;
+    return 0;
 }

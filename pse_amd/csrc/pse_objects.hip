@@ -1,6 +1,6 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
-// typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors and displacement
-// moments.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h or pse_order.h, the objects own their arrays through DeviceObject
+// typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors, displacement
+// moments and chain conformations.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h or pse_molecules.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "pse_forces.h"
 #include "pse_analysis.h"
 #include "pse_order.h"
+#include "pse_molecules.h"
 
 // A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
 // and, for bonds, the counter of overstretched FENE bonds.
@@ -39,6 +40,10 @@ struct pse_clusters : DeviceObject {
 };
 struct pse_bond_order : DeviceObject { BondOrder bo{}; };
 struct pse_structure_factor : DeviceObject { StructureFactor sf{}; };
+struct pse_molecules : DeviceObject {
+    Molecules mo{};
+    std::vector<unsigned> nlinear, nmol_type;   // per type, for pse_molecules_count
+};
 struct pse_msd : DeviceObject {
     MsdOrigins mo{};
     int norigins = 0;
@@ -526,6 +531,73 @@ extern "C" int pse_bond_order_histogram(pse_bond_order *b, const double *values,
                                       counts));
     HIPCHK(hipSetDevice(h->device));
     launch_bond_order_hist(values, b->bo.nl, column, group, (int)N, (unsigned)h->n_max, b->bo, nbins, lo, hi, counts, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Chain conformations (include/pse_amd.h): the layout of pse_host_molecule_rows, packed as the kernel reads it (pse_molecules.h), and
+// the workspace on the device, and the pass.  Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is
+// touched; nothing is read back.
+extern "C" int pse_molecules_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *mol_types_host,
+                                    int ntypes, int nbins, double rg_max, double ree_max, pse_molecules **out) {
+    const char *who = "pse_molecules_create";
+    TRY(create_begin(who, h, out));
+    MoleculeLayout L;
+    TRY(molecules_create_validate((unsigned)h->n_max, n, nbonds, pairs_host, mol_types_host, ntypes, nbins, rg_max, ree_max, L));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nmem = L.members.size();
+    std::vector<unsigned> word(nmem), mol(nmem), info(L.nmol), tile_slot(L.ntiles + 1), tile_word(L.ntiles);
+    auto lg_ceil = [](unsigned v) { unsigned r = 0; while ((1u << r) < v) ++r; return r; };
+    for (unsigned t = 0; t < L.ntiles; ++t) {
+        const unsigned first = L.mol_off[L.tile_mol[t]];
+        unsigned largest = 0;
+        tile_slot[t] = first;
+        for (unsigned q = L.tile_mol[t]; q < L.tile_mol[t + 1]; ++q) {
+            const unsigned o = L.mol_off[q], m = L.mol_off[q + 1] - o;
+            largest = std::max(largest, m);
+            for (unsigned p = 0; p < m; ++p) {
+                word[o + p] = (o - first + L.parent[o + p]) | (p << 10) | ((m - 1u) << 20);
+                mol[o + p] = q;
+            }
+            const bool linear = L.ends[2 * (size_t)q] != 0xffffffffu;
+            info[q] = (linear ? L.ends[2 * (size_t)q] | (L.ends[2 * (size_t)q + 1] << 10) | (1u << 24) : 0u) |
+                      ((mol_types_host ? mol_types_host[q] : 0u) << 20);
+        }
+        tile_word[t] = L.tile_rounds[t] | (lg_ceil(largest) << 8) | (lg_ceil(L.tile_mol[t + 1] - L.tile_mol[t]) << 16);
+    }
+    tile_slot[L.ntiles] = (unsigned)nmem;
+    pse_molecules *m = new pse_molecules();
+    m->h = h;
+    m->nlinear.resize((size_t)ntypes); m->nmol_type.resize((size_t)ntypes);
+    molecules_counts(L, mol_types_host, ntypes, nullptr, m->nlinear.data(), m->nmol_type.data());
+    Molecules &mo = m->mo;
+    mo.nmol = L.nmol; mo.ntiles = L.ntiles; mo.ntypes = ntypes; mo.nbins = nbins;
+    mo.f_rg = nbins > 0 ? (double)nbins / rg_max : 0.0;
+    mo.f_ree = nbins > 0 ? (double)nbins / ree_max : 0.0;
+    hipError_t e = m->put(&mo.member, L.members.data(), nmem);
+    e = m->put(&mo.word, word.data(), nmem);
+    e = m->put(&mo.mol, mol.data(), nmem);
+    e = m->put(&mo.info, info.data(), info.size());
+    e = m->put(&mo.tile_slot, tile_slot.data(), tile_slot.size());
+    e = m->put(&mo.tile_mol, L.tile_mol.data(), L.tile_mol.size());
+    e = m->put(&mo.tile_word, tile_word.data(), tile_word.size());
+    e = m->put(&mo.part, nullptr, (size_t)L.ntiles * ntypes * MOL_COLS);
+    return create_end(who, h, m, e, out);
+}
+extern "C" int pse_molecules_destroy(pse_molecules *m) { return object_destroy(m); }
+extern "C" int pse_molecules_count(pse_molecules *m, unsigned *nmol, unsigned *nlinear, unsigned *nmol_type) {
+    TRY(molecules_count_validate(m, nmol, nlinear, nmol_type));
+    if (nmol) *nmol = m->mo.nmol;
+    if (nlinear) std::copy(m->nlinear.begin(), m->nlinear.end(), nlinear);
+    if (nmol_type) std::copy(m->nmol_type.begin(), m->nmol_type.end(), nmol_type);
+    return 0;
+}
+extern "C" int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, double *rows, pse_double4 *unfolded, double *sums, double *sample,
+                                     unsigned long long *hist) {
+    TRY(molecules_compute_validate(m, m ? m->mo.nbins : 0, pos, rows, unfolded, sums, sample, hist));
+    pse_handle *h = m->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_molecules((const double4 *)pos, h->dbox, m->mo, rows, (double4 *)unfolded, sums, sample, hist, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

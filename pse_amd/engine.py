@@ -191,6 +191,7 @@ class _TopologyList(_DeviceObject):
         index, types = _topology_arrays(index, types, self.COLS, self.INDEX, self.WHAT)
         kind_a, k_a, x_a = _type_params(kinds, k, x, self.X, self.KINDS, self.WHAT, self.WIDTH)
         self.n, self.count = _rows(engine, n), index.shape[0]
+        self.index = index   # (the host copy: analyze.Conformations finds the molecules of a forces.Bonds from it)
         par = (_vp(k_a),) if x_a is None else (_vp(k_a), _vp(x_a))
         self._create(engine, self.CREATE, self.n, self.count, _vp(index), _vp(types), len(kind_a), _vp(kind_a), *par)
 
@@ -481,6 +482,65 @@ class DisplacementOrigins(_TypedObject):
     def __init__(self, engine, types, ntypes, norigins, n=None):
         types, ntypes, self.norigins = _msd_arguments(types, ntypes, norigins)
         self._create(engine, "pse_msd_create", types, ntypes, n, self.norigins)
+
+
+MOL_TILE = 1024       # PSE_MOL_TILE: members of the largest molecule
+MOL_COLS = 14         # PSE_MOL_COLS: columns of a molecule's row and of a type's sums
+MOL_MAX_BINS = 4096   # pse_molecules_create: bins of each histogram
+
+
+def _molecule_arguments(pairs, mol_types, ntypes, nbins, rg_max, ree_max):
+    """The arguments of a MoleculeTopology, checked before the device is touched: (pairs uint32 (nbonds, 2), molecule types uint32
+    (nmol,) or None, ntypes, nbins, rg_max, ree_max).  Whether there is one type per molecule is the library's to say: it finds the
+    molecules."""
+    import numpy as np
+    pairs, _ = _topology_arrays(pairs, None, 2, "bonds", "bond")
+    ntypes = _ntypes_argument(int(ntypes))
+    if mol_types is not None:
+        mol_types = np.asarray(mol_types)
+        if mol_types.ndim != 1 or mol_types.shape[0] == 0 or not np.issubdtype(mol_types.dtype, np.integer) or mol_types.min() < 0:
+            raise ValueError("molecule_types must be a non-empty 1-D array of non-negative integers, one per molecule")
+        if mol_types.max() >= ntypes:
+            raise ValueError(f"molecule_types holds the type {int(mol_types.max())} >= ntypes = {ntypes}")
+        mol_types = np.ascontiguousarray(mol_types, dtype=np.uint32)
+    nbins = int(nbins)
+    if not 0 <= nbins <= MOL_MAX_BINS:
+        raise ValueError(f"nbins = {nbins} outside [0, {MOL_MAX_BINS}]")
+    if nbins > 0:
+        if rg_max is None or ree_max is None:
+            raise ValueError("nbins > 0 needs rg_max and ree_max")
+        rg_max, ree_max = _finite(rg_max, "rg_max"), _finite(ree_max, "ree_max")
+        if not (rg_max > 0.0 and ree_max > 0.0):
+            raise ValueError("rg_max and ree_max must be positive")
+    else:
+        rg_max = ree_max = 0.0
+    return pairs, mol_types, ntypes, nbins, rg_max, ree_max
+
+
+class MoleculeTopology(_DeviceObject):
+    """Owner of a pse_molecules object: the molecules of a bond topology -- the connected components of `pairs`, an (nbonds, 2) array
+    of caller-order particle indices below `n` (default: n_max) -- with one type per molecule (`mol_types`: (nmol,) integers below
+    ntypes in the order of the molecule numbers, or None: one type) and `nbins` bins for the histograms of Rg on [0, rg_max) and of
+    |R| on [0, ree_max) (0: none).  Pass it as `molecules` to Engine.molecules_compute.  nmol, nlinear and nmol_type (per type) are
+    read once at creation (host words: no device wait)."""
+
+    DESTROY = "pse_molecules_destroy"
+
+    def __init__(self, engine, pairs, mol_types=None, ntypes=1, nbins=0, rg_max=None, ree_max=None, n=None):
+        import numpy as np
+        pairs, mol_types, self.ntypes, self.nbins, self.rg_max, self.ree_max = _molecule_arguments(pairs, mol_types, ntypes, nbins, rg_max,
+                                                                                                 ree_max)
+        self.n = _rows(engine, n)
+        if mol_types is not None:   # (the library reads nmol entries: the count has to be right before it does)
+            from .analyze import molecules_of
+            nmol = molecules_of(self.n, pairs)[1]
+            if mol_types.shape[0] != nmol:
+                raise ValueError(f"molecule_types has {mol_types.shape[0]} entries, the bonds make {nmol} molecules")
+        self._create(engine, "pse_molecules_create", self.n, pairs.shape[0], _vp(pairs), _vp(mol_types), self.ntypes, self.nbins,
+                     self.rg_max, self.ree_max)
+        nmol, nlinear, nmol_type = ctypes.c_uint(0), np.zeros(self.ntypes, dtype=np.uint32), np.zeros(self.ntypes, dtype=np.uint32)
+        _lib.check(self._lib.pse_molecules_count(self._obj, ctypes.byref(nmol), _vp(nlinear), _vp(nmol_type)))
+        self.nmol, self.nlinear, self.nmol_type = int(nmol.value), nlinear.astype(np.int64), nmol_type.astype(np.int64)
 
 
 def _cluster_arguments(types, ntypes, rlink, name="rlink"):
@@ -868,6 +928,39 @@ class _ForcePasses:
         _lib.check(self._lib.pse_bond_order_histogram(shells._handle(self), _ptr(values), shells.column(l), _ptr(group), members,
                                                       int(counts.shape[1]), lo, hi, _ptr(counts)))
         return counts
+
+    def molecule_topology(self, pairs, mol_types=None, ntypes=1, nbins=0, rg_max=None, ree_max=None, n=None):
+        """The molecules of a bond topology on the device (pse_molecules_create; see include/pse_amd.h and MoleculeTopology).
+        Returns a MoleculeTopology: the `molecules` of molecules_compute."""
+        return MoleculeTopology(self, pairs, mol_types, ntypes, nbins, rg_max, ree_max, n)
+
+    def molecules_compute(self, pos, molecules, rows=None, unfolded=None, sums=None, sample=None, hist=None):
+        """The conformation of every molecule at `pos` in the engine's current box (pse_molecules_compute): each molecule is unfolded
+        along its own bonds by the minimum image, which is right through any number of Lees-Edwards flips while every bond is shorter
+        than half the smallest box length.  All outputs are contiguous CUDA tensors, any may be None, not all:
+        `rows` (nmol, 14) float64, WRITTEN: c(3), G_xx, G_yy, G_zz, G_xy, G_xz, G_yz, Rg^2, R(3), R^2 (R: NaN without two ends);
+        `unfolded` (N, 4) float64 by caller index, members WRITTEN with (r_root + u, molecule number), other rows left alone;
+        `sums` (ntypes, 14) float64, ADDED to, and `sample` (ntypes, 14) float64, WRITTEN with this call's sums alone: the sums over
+        the molecules of a type of G_ab (6), (Rg^2)^2, R_a R_b (6), (R^2)^2, the last seven over the linear molecules;
+        `hist` (2, ntypes, nbins + 1) int64, ADDED to: Rg and |R|, the last counter for values at or above the maximum.
+        Queue-only: nothing is read back, no floating-point atomics: equal inputs give equal bits.  Returns the five."""
+        import torch
+        _chk4(pos, "pos", molecules.n)
+        shapes = ((rows, "rows", (molecules.nmol, MOL_COLS), torch.float64), (sums, "sums", (molecules.ntypes, MOL_COLS), torch.float64),
+                  (sample, "sample", (molecules.ntypes, MOL_COLS), torch.float64),
+                  (hist, "hist", (2, molecules.ntypes, molecules.nbins + 1), torch.int64))
+        for t, name, shape, dtype in shapes:
+            if t is not None and not (_is_cuda(t, dtype) and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {shape} {dtype} CUDA tensor")
+        if unfolded is not None:
+            _chk4(unfolded, "unfolded", molecules.n)
+        if hist is not None and molecules.nbins == 0:
+            raise ValueError("hist given, but the molecules were made with nbins = 0")
+        if rows is None and unfolded is None and sums is None and sample is None and hist is None:
+            raise ValueError("rows, unfolded, sums, sample and hist are all None: nothing to compute")
+        _lib.check(self._lib.pse_molecules_compute(molecules._handle(self), _ptr(pos), _ptr(rows), _ptr(unfolded), _ptr(sums), _ptr(sample),
+                                                   _ptr(hist)))
+        return rows, unfolded, sums, sample, hist
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
