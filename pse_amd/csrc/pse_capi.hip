@@ -237,7 +237,7 @@ extern "C" int pse_destroy(pse_handle *h) {
     if (h->info_inv) rocfft_execution_info_destroy(h->info_inv);
     void *ptrs[] = {h->keys, h->keys_s, h->vals, h->perm, h->tag_s, h->sort_tmp, h->cell_off, h->cnt_block, h->sw.rec_t, h->sw.fb.off, h->sw.fb.rank_s, h->sw.fb.tmp, h->nb.data, h->nb.cnt, h->vl.idx, h->vl.cnt, h->pos_build, h->pos_s, h->posf_s, h->pv,
                     h->f_s, h->uw_s, h->ur_s, h->ub_s, h->psi_s, h->w_s, h->coef, h->rgrid, h->cgrid, h->sendbuf, h->recvbuf, h->d_bidx, h->d_bounds, h->utot_s, h->w2_s, h->u_s, h->sums_all, h->twiddle, h->twiddle_y_owned, h->twiddle_z_owned, h->fft_work, h->V,
-                    h->scal, h->partials, h->lz_state, h->vq, h->nb64, h->pv_rows};
+                    h->scal, h->partials, h->lz_sums, h->lz_state, h->vq, h->nb64, h->pv_rows};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &p : h->ph) { if (p.a) (void)hipEventDestroy(p.a); if (p.b) (void)hipEventDestroy(p.b); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -630,6 +630,7 @@ static int create_impl(const pse_params *p, pse_handle *h) {
         h->npart_cap = std::max(LZ_NPART, mreal_partials_needed((int)n + 1024));   // + the padding of the row ranges (RowMap)
         TRY(dmalloc(h, &h->partials, (size_t)LZ_NGRAM * h->npart_cap));
     }
+    TRY(dmalloc(h, &h->lz_sums, (size_t)2 * LZ_NPART));
     for (auto &ph : h->ph) { HIPCHK(hipEventCreate(&ph.a)); HIPCHK(hipEventCreate(&ph.b)); }
     TRY(set_lanczos_op(h, h->tun.lz_op));
     h->info.device_bytes = h->bytes;
@@ -1533,7 +1534,7 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
     // the vector part of iteration j: x_{j+1} from the sums that are still in place
     auto vector_part = [&](int j, const int *gate) {
         launch_lz_update(vec(j), h->w_s, j > 0 ? vec(j - 1) : nullptr, h->V + (size_t)(j + 1) * stride, j, h->scal, rg, nrg_all, h->stream,
-                         nullptr, 0, h->sc_host_dev, gate, vq_of(h));   // (+ the mirror of x_{j+1}: the next mat-vec's gathers)
+                         nullptr, 0, h->sc_host_dev, gate, vq_of(h), h->lz_sums);   // (+ the mirror of x_{j+1}: the next mat-vec's gathers, and two of its sums)
     };
     auto iteration = [&](int j, bool scalars_only, const int *gate) -> int {
         const bool have_y = j == 0 && h->w_is_mpsi;
@@ -1543,10 +1544,12 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
             TRY(real(T, j == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)j * stride, 0, N, true));
         }
         const double4 *vjm1 = j > 0 ? vec(j - 1) : nullptr;
+        // from iteration 1 on the mat-vec sums x_j.y alone: x_j.x_j and x_j.x_{j-1} are what the update that wrote x_j left in lz_sums
+        const bool split = fused && j > 0;
         if (fused)
             launch_mreal_lanczos(h->pos_s, vec(j), h->w_s, row_map(0, N), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
-                                 LzFuse{vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr}, h->scal, nullptr, nullptr, h->stream,
-                                 h->vl_use ? h->vl : VerletList{}, 1, gate, DevRowArgs{}, j > 0 ? vq_of(h) : nullptr);
+                                 LzFuse{split ? nullptr : vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr, h->lz_sums, lz_update_grid(N)}, h->scal, nullptr, nullptr, h->stream,
+                                 h->vl_use ? h->vl : VerletList{}, split ? 4 : 1, gate, DevRowArgs{}, j > 0 ? vq_of(h) : nullptr);
         else if (!(j == 0 && h->sums0_done))
             launch_lz_dots(vec(j), h->w_s, vjm1, 0, N, h->partials, h->npart_cap, h->scal, h->stream);
         h->w_is_mpsi = false; h->sums0_done = false;
@@ -1615,10 +1618,13 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
                 const double4 *vjm1 = done > 1 ? h->V + (size_t)(done - 1) * stride : (done == 1 ? h->psi_s : nullptr);   // x_{j-1}, unnormalised
                 if (fused) {
                     const bool ev = timed && h->timing;
+                    // a single GPU, from iteration 1 on: the mat-vec sums x_j.y alone; x_j.x_j and x_j.x_{j-1} are what the update that
+                    // wrote x_j left in lz_sums.  Teams keep the three sums of the mat-vec: they travel with the exchange.
+                    const bool split = done > 0 && T.G <= 1;
                     launch_mreal_lanczos(h->pos_s, xj, h->w_s, row_map(lo, hi), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef,
-                                         h->nb, LzFuse{vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr}, h->scal,
+                                         h->nb, LzFuse{split ? nullptr : vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr, h->lz_sums, lz_update_grid(N)}, h->scal,
                                          ev ? h->ph[PH_MATVEC].a : nullptr, ev ? h->ph[PH_MATVEC].b : nullptr, h->stream,
-                                         h->vl_use ? h->vl : VerletList{}, 1, nullptr, DevRowArgs{}, done > 0 && T.G <= 1 ? vq_of(h) : nullptr);
+                                         h->vl_use ? h->vl : VerletList{}, split ? 4 : 1, nullptr, DevRowArgs{}, done > 0 && T.G <= 1 ? vq_of(h) : nullptr);
                     if (timed) h->matvec_timed = true;
                 } else if (!(done == 0 && h->sums0_done)) {   // (iteration 0: the sums came with the pass that built the pair list)
                     launch_lz_dots(xj, h->w_s, vjm1, lo, hi, h->partials, h->npart_cap, h->scal, h->stream);
@@ -1640,7 +1646,7 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
                 const double4 *xj = done == 0 ? h->psi_s : h->V + (size_t)done * stride;
                 launch_lz_update(xj, h->w_s, done > 1 ? h->V + (size_t)(done - 1) * stride : (done == 1 ? h->psi_s : nullptr),
                                  h->V + (size_t)(done + 1) * stride, done, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0, h == h0 ? h->sc_host_dev : nullptr,
-                                 nullptr, T.G <= 1 ? vq_of(h) : nullptr);
+                                 nullptr, T.G <= 1 ? vq_of(h) : nullptr, T.G <= 1 ? h->lz_sums : nullptr);
             }
         }
         // (alpha, beta and the norm are already on their way: the update kernels write them to the mapped host buffer as well)
@@ -1692,7 +1698,7 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
             const double4 *xj = j == 0 ? h->psi_s : h->V + (size_t)j * stride;
             launch_lz_update(xj, h->w_s, j > 1 ? h->V + (size_t)(j - 1) * stride : (j == 1 ? h->psi_s : nullptr),
                              h->V + (size_t)(j + 1) * stride, j, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0, h == h0 ? h->sc_host_dev : nullptr,
-                             nullptr, T.G <= 1 ? vq_of(h) : nullptr);
+                             nullptr, T.G <= 1 ? vq_of(h) : nullptr, T.G <= 1 ? h->lz_sums : nullptr);
         }
         pending_beta = done;
         target = std::min(M_MAX, done + std::max(2, done / 4));

@@ -163,6 +163,7 @@ struct pse_handle {
     // Lanczos
     double4 *V = nullptr;        // [M_MAX + 1][n_max]
     double *scal = nullptr, *partials = nullptr;
+    double *lz_sums = nullptr;   // [2][LZ_NPART] partial sums of x_{j+1}.x_{j+1}, x_{j+1}.x_j a k_lz_update leaves for iteration j + 1 (pse_vectors.h)
     double *sc_host = nullptr;   // pinned host copy of scal, mapped: the Lanczos kernels write alpha, beta, the norm there as well
     double *sc_host_dev = nullptr;   // its device address
     int *bounds_host_dev = nullptr;  // device address of bounds_host (mapped pinned): k_pick writes the row boundaries straight to the host

@@ -157,12 +157,17 @@ constexpr size_t NB_REC = 64 * 16;   // 64 rows x one 16-byte record
 __host__ __device__ inline size_t nb_list_bytes(size_t rows, int cap) { return ((rows + 63) / 64) * (size_t)cap * NB_REC; }
 enum { MREAL_CELLS = 0, MREAL_BUILD_LIST = 1, MREAL_USE_LIST = 2 };
 // Lanczos sums fused into the pair-list mat-vec (see k_lz_update): with x = vec and y = M x the kernel also leaves the
-// per-block partial sums of x.x, x.y and x.x_{j-1}
+// per-block partial sums of x.x, x.y and x.x_{j-1} -- or (sums = 4, a single GPU from iteration 1 on) of x.y alone: x.x and
+// x.x_{j-1} were summed by the k_lz_update that wrote x, which held both rows in registers (its `next_sums`, pse_vectors.h)
 struct LzFuse {
-    const double4 *vprev;   // x_{j-1}, unnormalised (null for j = 0)
+    const double4 *vprev;   // x_{j-1}, unnormalised (null for j = 0; not read with sums = 4)
     double *partials;       // [LZ_NGRAM][npart_cap]
     int npart_cap;
     const double4 *q, *p, *u;   // two-step blocks of a team (sums = 2, 3): v_j, v_{j-1} (nullable), M v_{j-1} (nullable)
+    // sums = 4: what the update that wrote x left, [2][LZ_NPART] partials of x.x and x.x_{j-1}, n_upd of each: the reduction
+    // launch behind the mat-vec adds them next to the mat-vec's own partials of x.y, so scal[LZ_TMP ..] ends as with sums = 1
+    const double *upd;
+    int n_upd;
 };
 // slots of the Gram sums of a two-step block (k_lz_block): products of q = v_j, p = v_{j-1}, u = M p, w1 = M q, w2 = M w1
 // -- the eight that M = M^T leaves independent: q.w2 = w1.w1, u.w1 = p.w2, q.u = p.w1 (the pair list holds every pair twice with
@@ -184,7 +189,8 @@ void launch_mreal_lanczos(const double4 *pos_s, const double4 *vec_s, double4 *w
                           DBox box, DCells nc, double rcut, double self, const double *coef, NbList nb, LzFuse lz,
                           double *scal, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t s,   // events (nullable) bracket the mat-vec kernel
                           VerletList vl = VerletList{},   // in use this step: rows that overflowed the pair list walk it instead of the cells
-                          int sums = 1,                   // 0 none, 1 one-step Lanczos sums, 2 Gram sums of a two-step block, 3 single step of that driver
+                          int sums = 1,                   // 0 none, 1 one-step Lanczos sums, 2 Gram sums of a two-step block, 3 single step of that driver,
+                                                          // 4 x.y alone; x.x and x.x_{j-1} from lz.upd
                           const int *stop = nullptr,      // nullable: leave at once if *stop != 0 (the device-side Lanczos decision)
                           DevRowArgs dr = DevRowArgs{},   // owned-particle ranks: rows from device memory
                           const void *vec_q = nullptr,    // (sums == 1) the 16-byte mirror of vec_s (launch_lz_update's xq): the neighbours' rows in ONE gather per pair

@@ -711,7 +711,9 @@ __device__ __forceinline__ void eval_fg_lean(double r2, const double *__restrict
 // WSP = 4: the four waves of a workgroup share ONE block of 64 rows and take every fourth group of slots each (partial sums
 // through LDS): the waves resident on a CU then gather from a quarter as many neighbourhoods (the kernel is bound by L1 misses).
 // FUSE: 0 none; 1 the three sums of the one-step iteration; 2 the Gram sums of a two-step block (this launch is its SECOND
-// mat-vec: vec = w1 = M q, result w2); 3 the sums of a single step in the two-step driver (vec = q, result w1).
+// mat-vec: vec = w1 = M q, result w2); 3 the sums of a single step in the two-step driver (vec = q, result w1); 4 the one-step
+// iteration of a single GPU from j = 1 on: x.y alone (slot 1 of the partials) -- x.x and x.x_{j-1} come from the k_lz_update that
+// wrote x (LzFuse.upd), so x_{j-1} is not read here at all.
 // VQ: the neighbours' rows come from the 16-byte mirror of the vector (vq_pack, pse_device.h): ONE gather per pair instead of two.
 // F64: the fp64 operator -- the coefficients from the 32-byte plane nb.c64 (the 16-byte record gives the row and the sign of h), the
 // neighbours' rows as doubles (never VQ), the rows that did not fit the list through pair_coef64: 48 B of list per pair instead of 16.
@@ -728,7 +730,7 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
         nb_live = (rm.list_rows() + (WSP > 1 ? 64 : NT) - 1) / (WSP > 1 ? 64 : NT);
         if ((int)blockIdx.x >= nb_live) {
             if (FUSE && threadIdx.x == 0)
-                for (int t = 0; t < (FUSE >= 2 ? (int)LZ_NGRAM : 3); ++t) lz.partials[(size_t)t * lz.npart_cap + blockIdx.x] = 0.0;
+                for (int t = 0; t < (FUSE == 2 || FUSE == 3 ? (int)LZ_NGRAM : 3); ++t) lz.partials[(size_t)t * lz.npart_cap + blockIdx.x] = 0.0;
             return;
         }
     }
@@ -842,7 +844,7 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
         if (wv > 0) return;
         for (int w = 0; w < WSP - 1; ++w) { ux += red[(w * 3 + 0) * 64 + ln]; uy += red[(w * 3 + 1) * 64 + ln]; uz += red[(w * 3 + 2) * 64 + ln]; }
     }
-    if (FUSE >= 2) {   // two-step driver: the sums the block scalars are derived from (see k_lz_block), slots LZG_*
+    if (FUSE == 2 || FUSE == 3) {   // two-step driver: the sums the block scalars are derived from (see k_lz_block), slots LZG_*
         double g[LZ_NGRAM];
 #pragma unroll
         for (int t = 0; t < LZ_NGRAM; ++t) g[t] = 0.0;
@@ -860,13 +862,17 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                 g[LZG_QQ] = dot(vi, vi.x, vi.y, vi.z);
             }
         }
-        static_assert(FUSE < 2 || NT == 64 || WSP > 1, "Gram sums: one wave per block of rows");
+        static_assert(FUSE < 2 || FUSE == 4 || NT == 64 || WSP > 1, "Gram sums: one wave per block of rows");
 #pragma unroll
         for (int t = 0; t < LZ_NGRAM; ++t) {
             if (FUSE == 3 && t != LZG_QW1 && t != LZG_W1W1 && t != LZG_PW1 && t != LZG_QQ) { if (threadIdx.x == 0) lz.partials[(size_t)t * lz.npart_cap + blockIdx.x] = 0.0; continue; }   // (compile-time: the loop is unrolled)
             const double v = wave_sum(g[t]);
             if (threadIdx.x == 0) lz.partials[(size_t)t * lz.npart_cap + blockIdx.x] = v;
         }
+    } else if (FUSE == 4) {   // x.y alone
+        static_assert(FUSE != 4 || NT == 64 || WSP > 1, "one wave per block of rows");
+        const double b = wave_sum(active ? vi.x * ux + vi.y * uy + vi.z * uz : 0.0);
+        if (threadIdx.x == 0) lz.partials[lz.npart_cap + blockIdx.x] = b;
     } else if (FUSE) {   // x = vec (unnormalised Lanczos vector), y = M x: partial sums of x.x, x.y, x.x_{j-1}
         double a = 0.0, b = 0.0, c = 0.0;
         if (active) {
@@ -967,16 +973,20 @@ void launch_mreal_lanczos(const double4 *pos_s, const double4 *vec_s, double4 *w
 #define PSE_LIST(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr)
 #define PSE_LIST64(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4, false, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr, nullptr)
     if (nb.c64) {   // the fp64 operator: the neighbours' rows as doubles, the mirror vec_q is not read
-        if (sums == 0) PSE_LIST64(0); else if (sums == 1) PSE_LIST64(1); else if (sums == 2) PSE_LIST64(2); else PSE_LIST64(3);
+        if (sums == 0) PSE_LIST64(0); else if (sums == 1) PSE_LIST64(1); else if (sums == 2) PSE_LIST64(2); else if (sums == 3) PSE_LIST64(3); else PSE_LIST64(4);
     } else if (sums == 1 && vec_q)
         hipLaunchKernelGGL((k_mreal_list<1, 4, 256, 4, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr,
                            (const vq4 *)vec_q);
-    else if (sums == 0) PSE_LIST(0); else if (sums == 1) PSE_LIST(1); else if (sums == 2) PSE_LIST(2); else PSE_LIST(3);
+    else if (sums == 4 && vec_q)
+        hipLaunchKernelGGL((k_mreal_list<4, 4, 256, 4, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr,
+                           (const vq4 *)vec_q);
+    else if (sums == 0) PSE_LIST(0); else if (sums == 1) PSE_LIST(1); else if (sums == 2) PSE_LIST(2); else if (sums == 3) PSE_LIST(3); else PSE_LIST(4);
 #undef PSE_LIST64
 #undef PSE_LIST
     if (ev_end) (void)hipEventRecord(ev_end, s);
     if (no_reduce) return;   // (pse_debug_matvec_ms: the mat-vec kernel alone, back to back)
-    if (sums >= 1) launch_lz_reduce(lz.partials, nb64, lz.npart_cap, sums == 1 ? 3 : (int)LZ_NGRAM, scal, stop, s);
+    if (sums == 4) launch_lz_reduce_split(lz.partials + lz.npart_cap, nb64, lz.upd, lz.n_upd, scal, stop, s);
+    else if (sums >= 1) launch_lz_reduce(lz.partials, nb64, lz.npart_cap, sums == 1 ? 3 : (int)LZ_NGRAM, scal, stop, s);
 }
 
 __global__ void k_eval_fg(const double *__restrict__ r, int n, const double *__restrict__ coef, double *f, double *g) {

@@ -40,10 +40,18 @@ void launch_lz_block(const LzBlockArgs &a, bool full, double *scal, const int (*
                      const RowRanges *rg_dev = nullptr, int rows_cap = 0,   // owned-particle ranks: the ranges come from device memory (vectors_off: scalars only)
                      bool vectors_off = false, const int *stop = nullptr);
 void launch_vq_roundtrip(const double *in, double *out, int n, hipStream_t s);   // debug: vq_unpack(vq_pack(row)) of n rows of three doubles
+// Two of the three sums of iteration j, x_j.x_j and x_j.x_{j-1}, need no pass of their own: the update that wrote x_j had both rows
+// in registers.  A launch given next_sums ([2][LZ_NPART]) leaves one pair of partial sums per workgroup there -- x_{j+1}.x_{j+1},
+// then x_{j+1}.x_j; fixed rows per workgroup, so a fixed summation order -- and the pair-list mat-vec of iteration j + 1 then sums
+// x.y alone (launch_mreal_lanczos, sums = 4, LzFuse.upd): the one reduction launch behind it adds these partials as well.
+int lz_update_grid(int rows);   // workgroups launch_lz_update uses for this many rows: the partials per sum it leaves
+// scal[LZ_TMP + 1] = sum of xy[0 .. n_xy), scal[LZ_TMP] and scal[LZ_TMP + 2] = the sums of upd[0 .. n_upd) and upd[LZ_NPART .. + n_upd)
+void launch_lz_reduce_split(const double *xy, int n_xy, const double *upd, int n_upd, double *scal, const int *stop, hipStream_t s);
 void launch_lz_update(const double4 *xin, const double4 *y, const double4 *xprev, double4 *xnext, int j,
                       double *scal, const int (*row_ranges)[2], int n_ranges, hipStream_t s,   // up to three disjoint row ranges in one launch
                       const double *sums_all = nullptr, int nranks = 0, double *sch = nullptr, const int *stop = nullptr,
-                      void *xq = nullptr);   // nullable: [rows] 16-byte mirror of xnext (vq_pack, pse_device.h), written on the same rows
+                      void *xq = nullptr,    // nullable: [rows] 16-byte mirror of xnext (vq_pack, pse_device.h), written on the same rows
+                      double *next_sums = nullptr);   // nullable: see above; not written by a launch without rows (scalars only)
 // ---- the convergence decision of the Lanczos iteration ON THE DEVICE (queue-only Brownian calls: pse_set_async) ----------------
 // Replaces, for calls that may not wait for the host, what the host driver does between batches of iterations (the reference's
 // LAPACKE_spteqr + host loops, PSEv1/Brownian.cu:540-582, and its step-norm test, PSEv1/Brownian.cu:673-724): one workgroup solves

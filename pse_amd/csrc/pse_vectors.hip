@@ -51,12 +51,16 @@ k_lz_dots(const double4 *__restrict__ x, const double4 *__restrict__ y, const do
     if (threadIdx.x == 0) { partials[blockIdx.x] = a; partials[cap + blockIdx.x] = b; partials[2 * cap + blockIdx.x] = c; }
 }
 // this rank's partial sums -> scal[LZ_TMP .. LZ_TMP + nsum) (then all-reduced over the ranks)
+// upd (nullable; then nsum = 3 and `partials` holds sum 1 alone): sums 0 and 2 are those of upd[0 .. n_upd) and
+// upd[LZ_NPART .. LZ_NPART + n_upd), the partials the k_lz_update that wrote the vector left (launch_lz_reduce_split)
 __global__ void __launch_bounds__(1024)
-k_lz_reduce(const double *__restrict__ partials, int npart, int cap, int nsum, double *__restrict__ scal, const int *__restrict__ stop) {
+k_lz_reduce(const double *__restrict__ partials, int npart, int cap, int nsum, double *__restrict__ scal, const int *__restrict__ stop,
+            const double *__restrict__ upd, int n_upd) {
     if (stop && *stop) return;
     __shared__ double sh[16];
     const int q = blockIdx.x;                         // one workgroup per sum, fixed summation order
     const double *p = partials + (size_t)q * cap;
+    if (upd) { p = q == 1 ? partials : upd + (q == 2 ? LZ_NPART : 0); if (q != 1) npart = n_upd; }
     double v = 0.0;
     for (int i = threadIdx.x; i < npart; i += 1024) v += p[i];
     v = wave_sum(v);
@@ -69,13 +73,17 @@ k_lz_reduce(const double *__restrict__ partials, int npart, int cap, int nsum, d
     }
 }
 void launch_lz_reduce(const double *partials, int npart, int cap, int nsum, double *scal, const int *stop, hipStream_t s) {
-    hipLaunchKernelGGL(k_lz_reduce, dim3(nsum), dim3(1024), 0, s, partials, npart, cap, nsum, scal, stop);
+    hipLaunchKernelGGL(k_lz_reduce, dim3(nsum), dim3(1024), 0, s, partials, npart, cap, nsum, scal, stop, (const double *)nullptr, 0);
 }
-// alpha_j, beta_j from the reduced sums; x_{j+1} on the given rows
+void launch_lz_reduce_split(const double *xy, int n_xy, const double *upd, int n_upd, double *scal, const int *stop, hipStream_t s) {
+    hipLaunchKernelGGL(k_lz_reduce, dim3(3), dim3(1024), 0, s, xy, n_xy, 0, 3, scal, stop, upd, n_upd);
+}
+// alpha_j, beta_j from the reduced sums; x_{j+1} on the given rows, and (next_sums) what it contributes to two sums of iteration j + 1
 __global__ void __launch_bounds__(TPB)
 k_lz_update(const double4 *__restrict__ xin, const double4 *__restrict__ y, const double4 *__restrict__ xprev,
             double4 *__restrict__ xnext, int j, double *__restrict__ scal, RowRanges rg,
-            const double *__restrict__ sums_all, int nranks, double *__restrict__ sch, const int *__restrict__ stop, vq4 *__restrict__ xq) {
+            const double *__restrict__ sums_all, int nranks, double *__restrict__ sch, const int *__restrict__ stop, vq4 *__restrict__ xq,
+            double *__restrict__ next_sums) {
     if (stop && *stop) return;
     // the three sums: this GPU's (single GPU), or the ranks' partial sums added in rank order -- every rank holds all of them
     // (they travel with the ghost rows: no separate all-reduce) and adds them in the same order: identical scalars everywhere
@@ -97,6 +105,7 @@ k_lz_update(const double4 *__restrict__ xin, const double4 *__restrict__ y, cons
     }
     const double cp = beta * ibprev;   // beta_j / beta_{j-1}
     const int n0 = rg.hi[0] - rg.lo[0], n1 = rg.n > 1 ? rg.hi[1] - rg.lo[1] : 0, n2 = rg.n > 2 ? rg.hi[2] - rg.lo[2] : 0;
+    double nn = 0.0, np = 0.0;   // x_{j+1}.x_{j+1} and x_{j+1}.x_j over this thread's rows: two of the three sums of iteration j + 1
     for (int t = blockIdx.x * TPB + threadIdx.x; t < n0 + n1 + n2; t += gridDim.x * TPB) {
         const int i = t < n0 ? rg.lo[0] + t : (t < n0 + n1 ? rg.lo[1] + (t - n0) : rg.lo[2] + (t - n0 - n1));
         const double4 p = xin[i], q = y[i];
@@ -104,6 +113,18 @@ k_lz_update(const double4 *__restrict__ xin, const double4 *__restrict__ y, cons
         if (xprev) { const double4 m = xprev[i]; nx -= cp * m.x; ny -= cp * m.y; nz -= cp * m.z; }
         xnext[i] = make_double4(nx, ny, nz, 0.0);
         if (xq) xq[i] = vq_pack(nx, ny, nz);   // the 16-byte mirror the next pair-list mat-vec gathers its neighbours from
+        nn += nx * nx + ny * ny + nz * nz;
+        np += nx * p.x + ny * p.y + nz * p.z;
+    }
+    if (next_sums) {   // (uniform over the launch) one pair per workgroup, both through LDS in one pass
+        __shared__ double sh[2][4];
+        nn = wave_sum(nn); np = wave_sum(np);
+        if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = nn; sh[1][threadIdx.x >> 6] = np; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            next_sums[blockIdx.x] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
+            next_sums[LZ_NPART + blockIdx.x] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+        }
     }
 }
 // ---- two Lanczos iterations per exchange (teams) ---------------------------------------------------------------------------
@@ -377,13 +398,15 @@ void launch_lz_dots(const double4 *x, const double4 *y, const double4 *vprev, in
 }
 void launch_lz_update(const double4 *xin, const double4 *y, const double4 *xprev, double4 *xnext, int j,
                       double *scal, const int (*rg)[2], int nrg, hipStream_t s, const double *sums_all, int nranks, double *sch,
-                      const int *stop, void *xq) {
+                      const int *stop, void *xq, double *next_sums) {
     RowRanges r{};
     r.n = nrg;
     int total = 0;
     for (int q = 0; q < nrg && q < 3; ++q) { r.lo[q] = rg[q][0]; r.hi[q] = rg[q][1]; total += rg[q][1] - rg[q][0]; }
-    hipLaunchKernelGGL(k_lz_update, dim3(vec_grid(std::max(1, total))), dim3(TPB), 0, s, xin, y, xprev, xnext, j, scal, r, sums_all, nranks, sch, stop, (vq4 *)xq);
+    if (total <= 0) next_sums = nullptr;   // scalars only: x_{j+1} is not formed; its sums come with the launch that forms it
+    hipLaunchKernelGGL(k_lz_update, dim3(vec_grid(std::max(1, total))), dim3(TPB), 0, s, xin, y, xprev, xnext, j, scal, r, sums_all, nranks, sch, stop, (vq4 *)xq, next_sums);
 }
+int lz_update_grid(int rows) { return vec_grid(std::max(1, rows)); }
 __global__ void k_vq_roundtrip(const double *__restrict__ in, double *__restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
