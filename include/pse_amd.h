@@ -120,7 +120,7 @@ int pse_set_stream(pse_handle *h, void *hip_stream);
  * captured and replayed like the deterministic ones; on return *lanczos_m is the m of the most recent call whose outcome has
  * already reached the host (feed it to the next call), pse_get_info after a stream synchronisation gives the m, the step norm
  * and pse_info.lanczos_status of the last completed call (1: the queue ran out before the step norm passed).  Starting counts
- * above 96 - PSE_LANCZOS_EXTRA take the host-checked path.  Per-phase timing (pse_set_timing) synchronises by definition and
+ * above 98 minus the gated extras of the call (PSE_LANCZOS_EXTRA, or what pse_set_lanczos_extra set) take the host-checked path.  Per-phase timing (pse_set_timing) synchronises by definition and
  * takes the host-checked path as well.  One warm-up call outside the capture first (kernels set their shared-memory attributes
  * on first use). */
 int pse_set_async(pse_handle *h, int enabled);
@@ -766,6 +766,29 @@ int pse_debug_grid_placement(pse_handle *h, int *tried, float *ms_first, float *
  * and 24 bytes of doubles are two of them per pair.  PSE_VQ=0 reads doubles (A/B).  No reference counterpart (the reference's
  * mat-vec recomputes every pair from single-precision positions, PSEv1/Mobility.cu:495-600). */
 int pse_debug_vq_roundtrip(int n, const double *rows_host, double *out_host);
+/* the device-side Lanczos decision (k_lz_decide: what ends every queue-only Brownian call and every owned-particle team step) on GIVEN
+ * coefficients, for tests: scal_host is one image of the device scalars (PSE_DEBUG_LZ_NSCAL doubles: alpha at 0, beta at 128, the
+ * norm of psi at 256), dec the decisions of one call in the order a driver issues them (fields as LzDecide, pse_vectors.h; seq is the
+ * call's number as the host mirror gets it), open0 the initial value of the mirror's count of calls that ended open.  The decision
+ * state starts as NaN bytes -- the reset under `first` is what makes it valid --, the decisions are launched in order on one stream,
+ * and after each launch the state and the five mirror slots (m, step norm, status, seq, open calls) are copied to out[k].  Current
+ * device, no handle.  PSE_ERR_INVALID, before anything is launched: a null array, n_dec outside [1, 40], a first decision without
+ * `first`, m_hi that pse_debug_lz_decide_supported refuses (the eigenvectors of the sizes m_hi - 1 and m_hi must fit the LDS of one
+ * workgroup: 1 .. 98), m_lo not m_hi - 1 or m_hi or below 1, done_iters < m_hi or > 100, pending_beta outside [0, m_hi], m_max > 100. */
+#define PSE_DEBUG_LZ_NSCAL 400
+typedef struct pse_debug_lz_decision {
+    int m_lo, m_hi, done_iters, have_last_beta, pending_beta, first, last, normalised, m_max;
+    double tol, seq;
+} pse_debug_lz_decision;
+typedef struct pse_debug_lz_outcome {
+    int done, m_final, checked, status;
+    double stepnorm;
+    double t_prev[104];
+    double coef[104];
+    double mirror[5];
+} pse_debug_lz_outcome;
+int pse_debug_lz_decide(const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, double open0, pse_debug_lz_outcome *out);
+int pse_debug_lz_decide_supported(int m_hi);   /* 1: a decision may check the sizes m_hi - 1 and m_hi */
 /* the dominant kernel of a Brownian step by itself: `reps` launches of the pair-list mat-vec of a Lanczos iteration (k_mreal_list; the
  * list, the vectors and the mirror of the Brownian call that has just ended; results go to scratch) back to back on the engine's
  * stream between ONE pair of events -> milliseconds per launch.  What bench.py's `roofline` divides by: an event pair around a single

@@ -96,6 +96,20 @@ class pse_transport(ctypes.Structure):
     _fields_ = [("user", ctypes.c_void_p), ("exchange", EXCHANGE_FN), ("allreduce_sum", ALLREDUCE_FN)]
 
 
+PSE_DEBUG_LZ_NSCAL = 400
+
+
+class pse_debug_lz_decision(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("m_lo", "m_hi", "done_iters", "have_last_beta", "pending_beta", "first", "last",
+                                            "normalised", "m_max")] + [("tol", ctypes.c_double), ("seq", ctypes.c_double)]
+
+
+class pse_debug_lz_outcome(ctypes.Structure):
+    _fields_ = [("done", ctypes.c_int), ("m_final", ctypes.c_int), ("checked", ctypes.c_int), ("status", ctypes.c_int),
+                ("stepnorm", ctypes.c_double), ("t_prev", ctypes.c_double * 104), ("coef", ctypes.c_double * 104),
+                ("mirror", ctypes.c_double * 5)]
+
+
 # every symbol include/pse_amd.h declares: name -> (restype, argtypes)
 _vp, _i, _u, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_double
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -179,6 +193,8 @@ SYMBOLS = {
     "pse_debug_kvector": (_i, [_vp, _i, _ip, _dp]),
     "pse_debug_grid_placement": (_i, [_vp, _ip, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "pse_debug_vq_roundtrip": (_i, [_i, _dp, _dp]),
+    "pse_debug_lz_decide": (_i, [_dp, _i, ctypes.POINTER(pse_debug_lz_decision), _d, ctypes.POINTER(pse_debug_lz_outcome)]),
+    "pse_debug_lz_decide_supported": (_i, [_i]),
     "pse_debug_matvec_ms": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_float)]),
     "pse_team_unique_id": (_i, [_vp]),
     "pse_team_create": (_i, [ctypes.POINTER(_vp), _i, _vp, ctypes.POINTER(_vp)]),

@@ -371,6 +371,8 @@ int pse_debug_fft_path(pse_handle *, int *) { return no_device("pse_debug_fft_pa
 int pse_debug_kvector(pse_handle *, int, const int *, double *) { return no_device("pse_debug_kvector"); }
 int pse_debug_grid_placement(pse_handle *, int *, float *, float *) { return no_device("pse_debug_grid_placement"); }
 int pse_debug_vq_roundtrip(int, const double *, double *) { return no_device("pse_debug_vq_roundtrip"); }
+int pse_debug_lz_decide(const double *, int, const pse_debug_lz_decision *, double, pse_debug_lz_outcome *) { return no_device("pse_debug_lz_decide"); }
+int pse_debug_lz_decide_supported(int) { return 0; }   // (a yes / no answer, not a status: without a device no size is)
 int pse_debug_matvec_ms(pse_handle *, int, float *) { return no_device("pse_debug_matvec_ms"); }
 int pse_set_lanczos_extra(pse_handle *, int) { return no_device("pse_set_lanczos_extra"); }
 // the operator choice is host state (the fp64 plane would be allocated on the device: the stub only records the choice)

@@ -1590,7 +1590,7 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
     int n_exchanges = 0;
     pse_handle *h0 = T.m[0];
     if (h0->async_mode && T.G == 1 && T.solo < 0 && h0->nb.cap > 0 && !h0->timing &&
-        lz_decide_supported(std::min(M_MAX, std::max(std::min(std::max(m_io ? *m_io : 2, 1), M_MAX), 2) + h0->tun.lz_extra)))
+        lz_decide_supported(std::min(M_MAX, std::max(std::min(std::max(m_io ? *m_io : 2, 1), M_MAX), 2) + (h0->lz_extra >= 0 ? h0->lz_extra : h0->tun.lz_extra))))   // (the extras THIS call queues: pse_set_lanczos_extra counts)
         return lanczos_queued(T, N, tol, scale, m_io, before_first_wait, before_combine);
     const size_t stride = h0->n_pad;
     for (pse_handle *h : act(T)) h->lz_last_queued = false;
@@ -2450,6 +2450,53 @@ extern "C" int pse_debug_vq_roundtrip(int n, const double *rows_host, double *ou
     if (e == hipSuccess) e = hipMemcpy(out_host, d_out, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(d_in); (void)hipFree(d_out);
     if (e != hipSuccess) return fail(PSE_ERR_HIP, "pse_debug_vq_roundtrip: %s", hipGetErrorString(e));
+    return 0;
+}
+static_assert(PSE_DEBUG_LZ_NSCAL == LZ_NSCAL && LZ_HOST_OPEN == LZ_HOST_M + 4 && LZ_HOST_OPEN < LZ_NSCAL, "pse_debug_lz_decide: layout of the scalars");
+extern "C" int pse_debug_lz_decide_supported(int m_hi) { return lz_decide_supported(m_hi) ? 1 : 0; }
+extern "C" int pse_debug_lz_decide(const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, double open0, pse_debug_lz_outcome *out) {
+    if (!scal_host || !dec || !out) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: null argument");
+    if (n_dec < 1 || n_dec > 40) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: %d decisions outside [1, 40]", n_dec);
+    if (!dec[0].first) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: the first decision must reset the state (first = 1)");
+    // everything the kernel sizes its LDS and its loops by is checked HERE: no launch with more than the launcher asked for
+    for (int k = 0; k < n_dec; ++k) {
+        const pse_debug_lz_decision &d = dec[k];
+        if (!lz_decide_supported(d.m_hi)) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: m_hi = %d is not supported", k, d.m_hi);
+        if (d.m_lo < 1 || (d.m_lo != d.m_hi && d.m_lo != d.m_hi - 1))
+            return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: m_lo = %d is not m_hi or m_hi - 1 (m_hi = %d)", k, d.m_lo, d.m_hi);
+        if (d.done_iters < d.m_hi || d.done_iters > M_MAX)
+            return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: done_iters = %d outside [m_hi, %d]", k, d.done_iters, M_MAX);
+        if (d.pending_beta < 0 || d.pending_beta > d.m_hi)
+            return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: pending_beta = %d outside [0, m_hi]", k, d.pending_beta);
+        if (d.m_max > M_MAX) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: m_max = %d above %d", k, d.m_max, M_MAX);
+    }
+    double *scal = nullptr, *sch = nullptr;
+    LzState *st = nullptr;
+    std::vector<double> mirror(LZ_NSCAL, 0.0);
+    mirror[LZ_HOST_OPEN] = open0;
+    hipError_t e = hipMalloc((void **)&scal, LZ_NSCAL * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&sch, LZ_NSCAL * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&st, sizeof(LzState));
+    if (e == hipSuccess) e = hipMemcpy(scal, scal_host, LZ_NSCAL * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(sch, mirror.data(), LZ_NSCAL * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(st, 0xff, sizeof(LzState));   // NaN bytes: only the reset under `first` makes the state valid
+    for (int k = 0; k < n_dec && e == hipSuccess; ++k) {
+        LzDecide d{};
+        d.m_lo = dec[k].m_lo; d.m_hi = dec[k].m_hi; d.done_iters = dec[k].done_iters; d.have_last_beta = dec[k].have_last_beta;
+        d.pending_beta = dec[k].pending_beta; d.first = dec[k].first; d.last = dec[k].last; d.normalised = dec[k].normalised;
+        d.m_max = dec[k].m_max; d.tol = dec[k].tol;
+        launch_lz_decide(d, scal, st, sch, dec[k].seq, nullptr);
+        e = hipGetLastError();
+        LzState hs;
+        if (e == hipSuccess) e = hipMemcpy(&hs, st, sizeof(LzState), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out[k].mirror, sch + LZ_HOST_M, 5 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) break;
+        out[k].done = hs.done; out[k].m_final = hs.m_final; out[k].checked = hs.checked; out[k].status = hs.status; out[k].stepnorm = hs.stepnorm;
+        std::copy(hs.t_prev, hs.t_prev + 104, out[k].t_prev);
+        std::copy(hs.coef, hs.coef + 104, out[k].coef);
+    }
+    (void)hipFree(scal); (void)hipFree(sch); (void)hipFree(st);
+    if (e != hipSuccess) return fail(PSE_ERR_HIP, "pse_debug_lz_decide: %s", hipGetErrorString(e));
     return 0;
 }
 extern "C" int pse_debug_grid_placement(pse_handle *h, int *tried, float *ms_first, float *ms_kept) {

@@ -242,7 +242,7 @@ __device__ __forceinline__ void lz_wave_sync() {
 // sizes 6 and 7 took 21 us, most of it waiting for ds_read).  Only the eigenvector columns are in LDS; their update is off the chain.
 struct LzReg {
     double lo, hi;   // entries lane and 64 + lane
-    __device__ __forceinline__ double get(int i) const {
+    __device__ __forceinline__ double get(int i) const {   // ALL lanes of the wave must be running: the select below is a vector instruction
         const double v = i < 64 ? lo : hi;
         const int l = i & 63;
         return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
@@ -301,10 +301,18 @@ __device__ bool lz_sqrt_e1(int m, const double *__restrict__ alpha, const double
     }
     lz_wave_sync();
     if (!ok) return false;
-    for (int i = lane; i < m; i += 64) {
+    // The trip count is the WAVE's, not the lane's: d.get selects lo or hi with a vector instruction before it reads the owning lane,
+    // so every lane must be running where it is called.  (With `for (i = lane; i < m; i += 64)` the second pass of a size above 64
+    // ran on lanes 0 .. m - 65 alone and d.get(j) returned, for every j whose lane sat the pass out, what that lane's copy of the
+    // selected register held from the pass before: t[64 ..] of every size above 64 was wrong by about its own magnitude.)
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int i = i0 + lane;
         double t = 0.0;
-        for (int j = 0; j < m; ++j) t += z[j * m + i] * (sqrt(fmax(d.get(j), 0.0)) * z[j * m]);
-        t_out[i] = t;
+        for (int j = 0; j < m; ++j) {
+            const double w = sqrt(fmax(d.get(j), 0.0)) * z[j * m];
+            if (i < m) t += z[j * m + i] * w;
+        }
+        if (i < m) t_out[i] = t;
     }
     lz_wave_sync();
     return true;

@@ -74,6 +74,39 @@ def host_lanczos_sqrt_e1(alpha, beta):
     return t
 
 
+LZ_DECISION_FIELDS = ("m_lo", "m_hi", "done_iters", "have_last_beta", "pending_beta", "first", "last", "normalised", "m_max", "tol", "seq")
+LZ_MIRROR_FIELDS = ("m", "stepnorm", "status", "seq", "open")
+
+
+def debug_lz_decide_supported(m_hi):
+    """Whether the device-side Lanczos decision can check the sizes m_hi - 1 and m_hi (pse_debug_lz_decide_supported)."""
+    return bool(_lib.load().pse_debug_lz_decide_supported(int(m_hi)))
+
+
+def debug_lz_decide(scal, decisions, open0=0.0):
+    """The device-side Lanczos decision on given coefficients (pse_debug_lz_decide; current device, no engine).  scal: the image of
+    the device scalars (400 doubles: alpha at 0, beta at 128, the norm at 256); decisions: dicts of LZ_DECISION_FIELDS (missing
+    ones 0) in the order a driver issues them; open0: the host mirror's count of open calls before the first.  Returns one dict per
+    launch: done, m_final, checked, status, stepnorm, t_prev[104], coef[104] and mirror (dict of LZ_MIRROR_FIELDS)."""
+    import numpy as np
+    lib = _lib.load()
+    s = np.ascontiguousarray(scal, dtype=np.float64)
+    if s.shape != (_lib.PSE_DEBUG_LZ_NSCAL,):
+        raise ValueError(f"scal must hold {_lib.PSE_DEBUG_LZ_NSCAL} doubles")
+    n = len(decisions)
+    dec = (_lib.pse_debug_lz_decision * max(n, 1))()
+    for k, d in enumerate(decisions):
+        unknown = set(d) - set(LZ_DECISION_FIELDS)
+        if unknown:
+            raise ValueError(f"decision {k}: unknown fields {sorted(unknown)}")
+        for name in LZ_DECISION_FIELDS:
+            setattr(dec[k], name, (float if name in ("tol", "seq") else int)(d.get(name, 0)))
+    out = (_lib.pse_debug_lz_outcome * max(n, 1))()
+    _lib.check(lib.pse_debug_lz_decide(s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, dec, float(open0), out))
+    return [dict(done=o.done, m_final=o.m_final, checked=o.checked, status=o.status, stepnorm=o.stepnorm,
+                 t_prev=np.array(o.t_prev), coef=np.array(o.coef), mirror=dict(zip(LZ_MIRROR_FIELDS, o.mirror))) for o in out[:n]]
+
+
 def _chk_out8(out, pos):
     """Where a pass writes its eight observables: `out`, checked, or a new tensor next to `pos` when out is None."""
     import torch
