@@ -558,8 +558,8 @@ int pse_bond_order_histogram(pse_bond_order *b, const double *values /* DEVICE, 
  * pse_molecules_count writes to HOST memory: *nmol, and per type the linear molecules and all molecules (ntypes entries each).
  * The object belongs to its handle exactly as a pse_msd does: pse_destroy frees the objects still alive, pse_molecules_destroy waits for
  * the stream.  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.
- * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, internal-distance curves R^2(s) and the persistence length,
- * the hydrodynamic radius (a pair sum, which belongs on another pass), time correlations of R, and owned-particle ranks (local_rows).
+ * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, time correlations of R, and owned-particle ranks
+ * (local_rows).  The pair sums of a molecule -- R^2(s), the bond correlation, the hydrodynamic radius -- are pse_molecule_pairs_compute.
  * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_molecules_create, in this order: a null out or
  * h, n == 0 or n > n_max, nbonds == 0, a null pairs_host, every refusal of pse_host_molecule_rows in its order, ntypes outside [1, 8], a
  * molecule type >= ntypes, nbins outside [0, 4096], with nbins > 0 an rg_max and then a ree_max that is not finite and positive (*out is
@@ -578,6 +578,54 @@ int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, double *rows
                           double *sums /* DEVICE, ntypes x 14, ADDED to, may be NULL */,
                           double *sample /* DEVICE, ntypes x 14, WRITTEN, may be NULL */,
                           unsigned long long *hist /* DEVICE, 2 x ntypes x (nbins + 1), ADDED to, may be NULL */);
+
+/* ---- chain statistics: 1/Rh of every molecule, internal distances and bond correlations of the linear ones (no reference counterpart) ----
+ * A pse_molecule_pairs object fixes the molecules of a bond list exactly as a pse_molecules does (its own layout of
+ * pse_host_molecule_rows, one type per molecule, ntypes <= 8; its lifetime is not tied to a pse_molecules), the RANK of every member
+ * (pse_host_chain_order: along the chain from the end with the lower caller index for a linear molecule, the breadth-first position
+ * otherwise) and ns, the number of separations kept, 1 <= ns <= PSE_MOL_TILE.
+ * pse_molecule_pairs_compute, per molecule of m members in the handle's CURRENT box: the offsets u are unfolded by the code of
+ * pse_molecules_compute (the same bits); u_q is the offset of the member of rank q, and for a pair d = u_{c + s} - u_c,
+ * r2 = fma(d_z, d_z, fma(d_y, d_y, d_x d_x)).
+ *   H(s) = sum over c = 0 .. m - 1 - s of 1.0 / sqrt(r2), s = 1 .. m - 1; a pair with r2 == 0 adds nothing (the rule of the pair
+ *   passes).  inv_rh[mol] = 2 (sum of H(s)) / m^2 = 1/Rh (Kirkwood), for every molecule, linear or not.
+ *   For LINEAR molecules and 0 <= s < ns, with b_c = u_{c + 1} - u_c:  D(s) = sum over c = 0 .. m - 1 - s of r2 (D(0) = +0.0);
+ *   C(s) = sum over c = 0 .. m - 2 - s of fma(b_z b'_z, fma(b_y b'_y, b_x b'_x)), b' = b_{c + s}, so that C(0) has the bits of D(1).
+ *   A molecule with m <= s (m - 1 <= s for C) adds +0.0.  curves[(a ns + s) 2 + {0, 1}] += the sum of D(s), C(s) over the linear
+ *   molecules of type a.  sums and sample, per type a, over ALL molecules of the type: column 0 the sum of inv_rh, column 1 the sum of
+ *   inv_rh inv_rh (the product rounded, then added).  `sample` is WRITTEN with this call's sums alone, `sums` and `curves` are ADDED to.
+ *   ORDER OF THE SUMS.  Within a (molecule, s): ascending c, one term after another, from +0.0.  The sum of H(s) over s: the halving
+ *   tree of pse_molecules_compute over the ranks (rank q adds rank q + t for t = the powers of two below the largest molecule of the
+ *   tile, descending, where q < t and q + t < m).  Within a (tile, type, s) and for the sums of a (tile, type): the molecules in
+ *   ascending number, one after another, from +0.0.  Across the tiles: the finishing kernel of pse_molecules_compute (lane k of 64 adds
+ *   the tiles k, k + 64, ... in ascending order, then the xor butterfly).  No floating-point atomics: equal inputs give equal bits.
+ * pse_molecule_pairs_counts writes to HOST memory: *nmol, the molecules of every type, and terms, the number of summands behind each
+ * entry of curves: the sum over the linear molecules of type a of max(m - s, 0) for D and of max(m - 1 - s, 0) for C.
+ * One workgroup of PSE_MOL_TILE lanes handles one tile (the tiles of pse_host_molecule_rows): after the unfolding u lies in LDS as
+ * three planes in rank order per molecule and the bond vectors as three more (56 KB with the plane of the H(s)); the lane of rank q
+ * takes the separation s = q.  The workspaces of per-tile partial sums (ntiles x ntypes x ns x 2 and ntiles x ntypes x 2 doubles)
+ * belong to the object: nothing is allocated in compute.  The call only queues work on the handle's stream and reads nothing back;
+ * it can be captured in a graph.  It does not sort and touches neither the cell list nor the kept neighbour list, and it works on a
+ * slab rank's handle.  The object belongs to its handle exactly as a pse_molecules does.
+ * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, Rh with the RPY regularisation for overlapping beads,
+ * time correlations, owned-particle ranks, histograms of Rh.
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_molecule_pairs_create, in this order:
+ * everything pse_molecules_create refuses up to and including the molecule types, in its order, then ns outside [1, PSE_MOL_TILE].
+ * pse_molecule_pairs_compute, in this order: a null p, a null pos, every output NULL, inv_rh, curves, sums or sample not 8-byte
+ * aligned.  pse_molecule_pairs_counts: a null p, every output NULL. */
+#define PSE_MOLPAIR_COLS 2   /* per separation: D, C */
+#define PSE_MOLPAIR_SUMS 2   /* per type: sum of 1/Rh, sum of (1/Rh)^2 */
+typedef struct pse_molecule_pairs pse_molecule_pairs;
+int pse_molecule_pairs_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host /* nbonds x 2 particle indices */,
+                              const unsigned *mol_types_host /* nmol, or NULL: one type */, int ntypes, int ns, pse_molecule_pairs **out);
+int pse_molecule_pairs_destroy(pse_molecule_pairs *p);
+int pse_molecule_pairs_counts(pse_molecule_pairs *p, unsigned *nmol, unsigned *nmol_type /* ntypes */,
+                              unsigned long long *terms /* HOST, ntypes x ns x 2 */);
+int pse_molecule_pairs_compute(pse_molecule_pairs *p, const pse_double4 *pos,
+                               double *inv_rh /* DEVICE, nmol, WRITTEN, may be NULL */,
+                               double *curves /* DEVICE, ntypes x ns x 2, ADDED to, may be NULL */,
+                               double *sums   /* DEVICE, ntypes x 2, ADDED to, may be NULL */,
+                               double *sample /* DEVICE, ntypes x 2, WRITTEN, may be NULL */);
 
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene(no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
@@ -1018,6 +1066,11 @@ int pse_host_molecule_rows(unsigned n, unsigned nbonds, const unsigned *pairs, i
                            unsigned *parent /* n */, unsigned *depth /* n */, unsigned *mol_off /* n / 2 + 1 */, unsigned *ends /* 2 (n / 2) */,
                            unsigned *nring /* n / 2 */, unsigned *tile_mol /* n / 2 + 1 */, unsigned *tile_rounds /* n / 2 */,
                            unsigned *counts /* 3 */);
+/* The chain rank of every member slot of that layout (parent, mol_off and ends as pse_host_molecule_rows wrote them, nmol = counts[0]):
+ * for a LINEAR molecule rank[slot] = the index 0 .. m - 1 along the chain, counted from ends[2 mol], the end with the lower caller
+ * index; for any other molecule the breadth-first position.  A function of the bond SET.  PSE_ERR_INVALID: a null array. */
+int pse_host_chain_order(unsigned nmol, const unsigned *parent, const unsigned *mol_off /* nmol + 1 */, const unsigned *ends /* 2 nmol */,
+                         unsigned *rank /* one per member slot */);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,11 @@ SYMBOLS = {
     "pse_molecules_count": (_i, [_vp, _vp, _vp, _vp]),
     "pse_molecules_compute": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pse_host_molecule_rows": (_i, [_u, _u] + [_vp] * 11),
+    "pse_host_chain_order": (_i, [_u, _vp, _vp, _vp, _vp]),
+    "pse_molecule_pairs_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _i, _vp]),
+    "pse_molecule_pairs_destroy": (_i, [_vp]),
+    "pse_molecule_pairs_counts": (_i, [_vp, _vp, _vp, _vp]),
+    "pse_molecule_pairs_compute": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

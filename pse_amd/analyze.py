@@ -1015,8 +1015,8 @@ class Conformations(_TypedAnalyzer, _SampleRing):
     molecule, or "size": the distinct molecule sizes in ascending order are the types (at most 8).  Each sample adds its per-type sums
     to the accumulated `sums`, writes them alone into a device ring of `capacity` rows -- once full, the oldest rows are replaced --
     and, with nbins > 0, counts Rg on [0, rg_max) and |R| on [0, ree_max).  Sampling only queues work; the readers are the only places
-    that wait for the device.  Every particle has mass 1.  Not measured: molecules of more than 1024 members, internal distances and
-    the persistence length, the hydrodynamic radius, time correlations of R.
+    that wait for the device.  Every particle has mass 1.  Not measured: molecules of more than 1024 members, time correlations of R.
+    Internal distances, the persistence length and the hydrodynamic radius are ChainStatistics'.
 
     nmol, nlinear, nmol_type, sizes();  gyration_tensor(a), rg2(a), rg4(a), ree_tensor(a), ree2(a), ree4(a) -- means over the molecules
     (R: the linear ones) of type `a` (None: all) and over the samples since reset();  series() -- (samples kept, 1 + ntypes 14): the
@@ -1143,3 +1143,157 @@ class Conformations(_TypedAnalyzer, _SampleRing):
         h = self._hist.cpu().numpy()[0 if which == "rg" else 1]
         counts = h.sum(axis=0) if a is None else h[self._code(a)]
         return counts, np.arange(self.nbins + 1) * ((self.rg_max if which == "rg" else self.ree_max) / self.nbins)
+
+
+def persistence_length_of(s, c, b, smax=1):
+    """The persistence length l_p of a bond correlation c(s) ~ exp(-s b / l_p) with the bond length b: -b / k, k the least-squares slope
+    through the origin of ln c(s) over s = 1 .. smax, k = sum s ln c(s) / sum s^2, stopping before the first c(s) <= 0 (or NaN).  NaN
+    where no separation is left, inf for k == 0."""
+    import numpy as np
+    s, c = np.asarray(s, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    if int(smax) < 1:
+        raise ValueError("smax must be positive")
+    keep = (s >= 1) & (s <= int(smax))
+    s, c = s[keep], c[keep]
+    order = np.argsort(s)
+    s, c = s[order], c[order]
+    bad = np.nonzero(~(c > 0.0))[0]
+    if bad.shape[0]:
+        s, c = s[:bad[0]], c[:bad[0]]
+    if s.shape[0] == 0:
+        return float("nan")
+    k = float((s * np.log(c)).sum() / (s * s).sum())
+    return -float(b) / k if k != 0.0 else float("inf")
+
+
+class ChainStatistics(_TypedAnalyzer, _SampleRing):
+    """The pair statistics of the molecules that a bond topology defines: every `period` steps one pass (pse_molecule_pairs_compute)
+    unfolds every molecule as Conformations does and sums over the pairs of its members: 1/Rh = (1/m^2) sum over i != j of 1/r_ij
+    (Kirkwood's hydrodynamic radius) for every molecule and, for the linear ones, along the chain, the internal distances
+    D(s) = sum_c |r_{c+s} - r_c|^2 and the bond correlations C(s) = sum_c b_c . b_{c+s} for the separations s = 0 .. smax - 1
+    (`smax`: default the largest molecule size).  `bonds`, `molecule_types`, `type_names`, `period`, `capacity` as for Conformations.
+    The curves and the per-type sums of 1/Rh and (1/Rh)^2 accumulate on the device, every sample's sums alone go into a device ring
+    of `capacity` rows.  Sampling only queues work; the readers are the only places that wait for the device.  Every particle has
+    mass 1; a pair at distance 0 adds nothing to 1/Rh.
+
+    nmol, nmol_type, terms (ntypes, smax, 2): the summands behind every entry of the curves in one sample;  internal_distances(a) --
+    (s, <R^2(s)>);  bond_correlation(a) -- (s, <b.b>_s / <b^2>);  bond_length(a) -- <b^2>^(1/2);  persistence_length(a, smax);
+    inv_rh(a) -- <1/Rh>;  rh(a) -- 1 / <1/Rh>;  per_molecule() -- (nmol,) 1/Rh at the current positions;  series() -- (samples kept,
+    1 + ntypes 2): the timestep and every type's sums of 1/Rh and (1/Rh)^2 of that sample;  samples;  reset().  `a`: a type (None: all);
+    NaN for a type without (linear) molecules."""
+
+    COLUMNS = ("inv_rh", "inv_rh2")
+
+    def __init__(self, integrator, bonds, molecule_types=None, type_names=None, period=1, smax=None, capacity=1024):
+        import torch
+        from .engine import MOLPAIR_COLS, MOLPAIR_SUMS, MOL_TILE, MoleculePairs
+        lst = getattr(bonds, "_list", None)
+        pairs = lst.index if lst is not None and hasattr(lst, "index") else bonds
+        (pairs, types, self.ntypes, self.type_names, self.period, _, _, _, self.capacity, self._sizes,
+         self.size_values) = _conformation_arguments(pairs, molecule_types, type_names, period, 0, None, None, capacity)
+        self.smax = int(self._sizes.max()) if smax is None else int(smax)
+        if not 1 <= self.smax <= MOL_TILE:
+            raise ValueError(f"smax = {self.smax} outside [1, {MOL_TILE}]")
+        with self._attach(integrator, None) as system:          # (the lines above raise before the integrator is touched)
+            if int(pairs.max()) >= system.n:
+                raise ValueError(f"bonds holds the index {int(pairs.max())}, the system has {system.n} particles")
+            self.molecule_types = types
+            self._pairs = MoleculePairs(integrator.engine, pairs, types, self.ntypes, self.smax, system.n)
+            self.nmol, self.nmol_type, self.terms = self._pairs.nmol, self._pairs.nmol_type, self._pairs.terms
+            dev = system.pos.device
+            self._curves = torch.zeros((self.ntypes, self.smax, MOLPAIR_COLS), dtype=torch.float64, device=dev)
+            self._sums = torch.zeros((self.ntypes, MOLPAIR_SUMS), dtype=torch.float64, device=dev)
+            self._rows = torch.zeros((self.capacity, self.ntypes, MOLPAIR_SUMS), dtype=torch.float64, device=dev)
+            self._ring_reset()
+
+    def analyze(self, timestep):
+        if not self._due(timestep):
+            return
+        q = self._slot()
+        self.integrator.engine.molecule_pairs_compute(self.system.pos, self._pairs, curves=self._curves, sums=self._sums, sample=self._rows[q])
+        self._record(q, timestep)
+
+    def reset(self):
+        self._curves.zero_(); self._sums.zero_(); self._rows.zero_()
+        self._ring_reset()
+
+    def sizes(self):
+        """(nmol,) int64: the number of members of every molecule."""
+        return self._sizes.astype("int64")
+
+    def curves(self):
+        """(ntypes, smax, 2) float64: the accumulated sums of D(s) and C(s) since the last reset()."""
+        return self._curves.cpu().numpy()
+
+    def sums(self):
+        """(ntypes, 2) float64: the accumulated sums of 1/Rh and (1/Rh)^2 since the last reset()."""
+        return self._sums.cpu().numpy()
+
+    def _curve(self, a, col):
+        """The mean of column `col` of the curves per summand, (smax,): NaN where there is no summand."""
+        import numpy as np
+        self._sampled()
+        c, t = self.curves()[:, :, col], self.terms[:, :, col].astype(np.float64)
+        if a is None:
+            c, t = c.sum(axis=0), t.sum(axis=0)
+        else:
+            a = self._code(a)
+            c, t = c[a], t[a]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(t > 0, c / (self.samples * t), np.nan)
+
+    def internal_distances(self, a=None):
+        """(s (smax,), <R^2(s)> (smax,)): the mean squared distance of two members s bonds apart along the chain, over the linear
+        molecules of type `a` (None: of all) and the samples; NaN where no molecule is that long."""
+        import numpy as np
+        return np.arange(self.smax), self._curve(a, 0)
+
+    def bond_correlation(self, a=None):
+        """(s (smax,), c(s) (smax,)): <b_c . b_{c+s}> / <b^2>, c(0) = 1."""
+        import numpy as np
+        c = self._curve(a, 1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.arange(self.smax), c / c[0]
+
+    def bond_length(self, a=None):
+        """<b^2>^(1/2) over the bonds of the linear molecules."""
+        return float(self._curve(a, 1)[0] ** 0.5)
+
+    def persistence_length(self, a=None, smax=1):
+        """persistence_length_of(bond_correlation(a), bond_length(a), smax): -b / k with k the slope of ln c(s) over s = 1 .. smax."""
+        s, c = self.bond_correlation(a)
+        return persistence_length_of(s, c, self.bond_length(a), smax)
+
+    def inv_rh(self, a=None):
+        """<1/Rh> over the molecules of type `a` (None: of all) and the samples."""
+        self._sampled()
+        s, n = self.sums()[:, 0], self.nmol_type
+        if a is None:
+            return float(s.sum() / (self.samples * n.sum()))
+        a = self._code(a)
+        return float(s[a] / (self.samples * n[a])) if n[a] else float("nan")
+
+    def rh(self, a=None):
+        """1 / <1/Rh>: the hydrodynamic radius."""
+        return 1.0 / self.inv_rh(a)
+
+    def series(self):
+        """(samples kept, 1 + ntypes 2) float64, oldest first: the timestep, then for every type the sums of 1/Rh and (1/Rh)^2 over its
+        molecules in that sample alone (one copy from the device).  Divide by nmol_type for means."""
+        import numpy as np
+        n = min(self.samples, self.capacity)
+        dev = self._rows.cpu().numpy().reshape(self.capacity, -1)
+        out = np.zeros((n, 1 + dev.shape[1]))
+        for r in range(n):
+            q = (self.samples - n + r) % self.capacity
+            out[r, 0], out[r, 1:] = self._steps[q], dev[q]
+        return out
+
+    table = series   # (the ring's rows are doubles here: the integer table of _SampleRing would truncate them)
+
+    def per_molecule(self):
+        """(nmol,) float64: 1/Rh of every molecule at the system's current positions.  One pass and one copy; no sample is taken."""
+        import torch
+        out = torch.empty((self.nmol,), dtype=torch.float64, device=self.system.pos.device)
+        self.integrator.engine.molecule_pairs_compute(self.system.pos, self._pairs, inv_rh=out)
+        return out.cpu().numpy()

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*, pse_molecule_pairs_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -48,6 +48,12 @@ struct pse_molecules : Topology {   // the REAL layout (molecule_layout) and the
     MoleculeLayout L;
     std::vector<unsigned> types;
     int ntypes = 1, nbins = 0;
+};
+struct pse_molecule_pairs : Topology {   // the REAL layout and the molecule types
+    using Topology::Topology;
+    MoleculeLayout L;
+    std::vector<unsigned> types;
+    int ntypes = 1, ns = 1;
 };
 struct pse_team { int unused; };
 
@@ -294,6 +300,29 @@ int pse_molecules_count(pse_molecules *m, unsigned *nmol, unsigned *nlinear, uns
 int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, double *rows, pse_double4 *unfolded, double *sums, double *sample,
                           unsigned long long *hist) {
     return molecules_compute_validate(m, m ? m->nbins : 0, pos, rows, unfolded, sums, sample, hist);
+}
+int pse_molecule_pairs_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *mol_types_host, int ntypes,
+                              int ns, pse_molecule_pairs **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_molecule_pairs_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_molecule_pairs_create: null handle");
+    pse_molecule_pairs *p = new pse_molecule_pairs(h, 0, 0);
+    p->ntypes = ntypes; p->ns = ns;
+    const int rc = molecule_pairs_create_validate(h->par.n_max, n, nbonds, pairs_host, mol_types_host, ntypes, ns, p->L);
+    if (!rc && mol_types_host) p->types.assign(mol_types_host, mol_types_host + p->L.nmol);
+    return topology_adopt(p, rc, out);
+}
+int pse_molecule_pairs_destroy(pse_molecule_pairs *p) { return topology_destroy(p); }
+int pse_molecule_pairs_counts(pse_molecule_pairs *p, unsigned *nmol, unsigned *nmol_type, unsigned long long *terms) {
+    if (int rc = molecule_pairs_counts_validate(p, nmol, nmol_type, terms)) return rc;
+    const unsigned *types = p->types.empty() ? nullptr : p->types.data();
+    molecules_counts(p->L, types, p->ntypes, nmol, nullptr, nmol_type);
+    if (terms) molecule_pairs_terms(p->L, types, p->ntypes, p->ns, terms);
+    return 0;
+}
+// (the arrays are device pointers and there is no device: nothing is read or written)
+int pse_molecule_pairs_compute(pse_molecule_pairs *p, const pse_double4 *pos, double *inv_rh, double *curves, double *sums, double *sample) {
+    return molecule_pairs_compute_validate(p, pos, inv_rh, curves, sums, sample);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -113,6 +113,10 @@ struct MoleculeLayout {
 };
 // 0 and the layout, or PSE_ERR_INVALID with a message under the name `who`: the refusals of pse_host_molecule_rows behind its null arrays
 int molecule_layout(const char *who, unsigned n, unsigned nbonds, const unsigned *pairs, MoleculeLayout &L);
+// what pse_molecules_create and pse_molecule_pairs_create (`who`) refuse alike behind their null-out and null-handle checks, up to and
+// including the molecule types, with the handle's n_max; the layout is built on the way and returned
+int molecule_topology_validate(const char *who, unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types,
+                               int ntypes, MoleculeLayout &L);
 // the argument checks of pse_molecules_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them,
 // with the handle's n_max; the layout is built on the way (its refusals stand between those of nbonds and of ntypes) and returned
 int molecules_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int nbins,
@@ -123,5 +127,16 @@ int molecules_compute_validate(const void *m, int nbins, const void *pos, const 
 int molecules_count_validate(const void *m, const void *nmol, const void *nlinear, const void *nmol_type);
 // what pse_molecules_count writes (each output may be null): the molecules, and per type the linear ones and all of them
 void molecules_counts(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, unsigned *nmol, unsigned *nlinear, unsigned *nmol_type);
+// pse_host_chain_order on a layout: rank (one per member slot)
+void chain_order(const MoleculeLayout &L, std::vector<unsigned> &rank);
+// the argument checks of pse_molecule_pairs_create behind its null-out and null-handle checks: molecule_topology_validate, then ns
+int molecule_pairs_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int ns,
+                                   MoleculeLayout &L);
+// the argument checks of pse_molecule_pairs_compute and of pse_molecule_pairs_counts
+int molecule_pairs_compute_validate(const void *p, const void *pos, const void *inv_rh, const void *curves, const void *sums, const void *sample);
+int molecule_pairs_counts_validate(const void *p, const void *nmol, const void *nmol_type, const void *terms);
+// terms (ntypes x ns x MOLPAIR_COLS): the summands behind every entry of the curves, max(m - s, 0) for D and max(m - 1 - s, 0) for C over
+// the linear molecules of a type
+void molecule_pairs_terms(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, int ns, unsigned long long *terms);
 
 }  // namespace pse

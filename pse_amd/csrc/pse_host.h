@@ -23,6 +23,8 @@ constexpr int BOND_ORDER_MAX_L = 12;        // the largest degree, even degrees 
 constexpr int BOND_ORDER_MAX_COUNTERS = 8192;   // counters of pse_bond_order_histogram, types x bins: 32 KB of LDS
 constexpr int MOL_COLS = 14;          // columns of a molecule's row and of a type's sums (pse_molecules_compute; PSE_MOL_COLS)
 constexpr int MOL_MAX_BINS = 4096;    // bins of each histogram of a molecule object (pse_molecules_create)
+constexpr int MOLPAIR_COLS = 2;       // per separation of a chain-statistics curve: D, C (pse_molecule_pairs_compute; PSE_MOLPAIR_COLS)
+constexpr int MOLPAIR_SUMS = 2;       // per type: the sum of 1/Rh and of (1/Rh)^2 (PSE_MOLPAIR_SUMS)
 constexpr int PAIR_TYPED_MAX_TYPES = 8;     // particle types of a typed pair table (pse_typed_table_create): at most 36 pair types
 constexpr int PAIR_TYPED_MAX_ENTRIES = 3584; // entries of all its tables together: 56 KB of LDS, next to 1.4 KB of static LDS, inside 64 KB
 constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS

@@ -621,9 +621,8 @@ int molecule_layout(const char *who, unsigned n, unsigned nbonds, const unsigned
     return 0;
 }
 
-int molecules_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int nbins,
-                              double rg_max, double ree_max, MoleculeLayout &L) {
-    const char *who = "pse_molecules_create";
+int molecule_topology_validate(const char *who, unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types,
+                               int ntypes, MoleculeLayout &L) {
     if (n == 0 || n > n_max) return fail(PSE_ERR_INVALID, "%s: n = %u outside (0, n_max = %u]", who, n, n_max);
     if (nbonds == 0) return fail(PSE_ERR_INVALID, "%s: nbonds = 0: there is no molecule at all", who);
     if (!pairs) return fail(PSE_ERR_INVALID, "%s: null pairs_host", who);
@@ -633,6 +632,13 @@ int molecules_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const
         for (unsigned mol = 0; mol < L.nmol; ++mol)
             if (mol_types[mol] >= (unsigned)ntypes)
                 return fail(PSE_ERR_INVALID, "%s: molecule %u has type %u >= ntypes = %d", who, mol, mol_types[mol], ntypes);
+    return 0;
+}
+
+int molecules_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int nbins,
+                              double rg_max, double ree_max, MoleculeLayout &L) {
+    const char *who = "pse_molecules_create";
+    if (int rc = molecule_topology_validate(who, n_max, n, nbonds, pairs, mol_types, ntypes, L)) return rc;
     if (nbins < 0 || nbins > MOL_MAX_BINS) return fail(PSE_ERR_INVALID, "%s: nbins = %d outside [0, %d]", who, nbins, MOL_MAX_BINS);
     if (nbins > 0 && !(std::isfinite(rg_max) && rg_max > 0.0)) return fail(PSE_ERR_INVALID, "%s: rg_max = %g must be finite and positive", who, rg_max);
     if (nbins > 0 && !(std::isfinite(ree_max) && ree_max > 0.0)) return fail(PSE_ERR_INVALID, "%s: ree_max = %g must be finite and positive", who, ree_max);
@@ -670,6 +676,65 @@ void molecules_counts(const MoleculeLayout &L, const unsigned *mol_types, int nt
         const unsigned a = mol_types ? mol_types[mol] : 0u;
         if (nmol_type) ++nmol_type[a];
         if (nlinear && L.ends[2 * (size_t)mol] != 0xffffffffu) ++nlinear[a];
+    }
+}
+
+// The rank of every member slot (pse_host_chain_order, include/pse_amd.h) from the spanning tree alone: in a linear molecule the walk
+// from the lower end up to the root counts 0, 1, ..., the walk from the higher end up to the root counts m - 1, m - 2, ...
+static void chain_ranks(unsigned nmol, const unsigned *parent, const unsigned *mol_off, const unsigned *ends, unsigned *rank) {
+    for (unsigned mol = 0; mol < nmol; ++mol) {
+        const unsigned o = mol_off[mol], m = mol_off[mol + 1] - o, lo = ends[2 * (size_t)mol], hi = ends[2 * (size_t)mol + 1];
+        for (unsigned p = 0; p < m; ++p) rank[o + p] = p;
+        if (lo == 0xffffffffu) continue;
+        unsigned r = 0u;
+        for (unsigned p = lo; ; p = parent[o + p]) { rank[o + p] = r++; if (p == 0u) break; }
+        r = m;
+        for (unsigned p = hi; p != 0u; p = parent[o + p]) rank[o + p] = --r;
+    }
+}
+void chain_order(const MoleculeLayout &L, std::vector<unsigned> &rank) {
+    rank.resize(L.members.size());
+    chain_ranks(L.nmol, L.parent.data(), L.mol_off.data(), L.ends.data(), rank.data());
+}
+
+int molecule_pairs_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes, int ns,
+                                   MoleculeLayout &L) {
+    const char *who = "pse_molecule_pairs_create";
+    if (int rc = molecule_topology_validate(who, n_max, n, nbonds, pairs, mol_types, ntypes, L)) return rc;
+    if (ns < 1 || ns > PSE_MOL_TILE) return fail(PSE_ERR_INVALID, "%s: ns = %d outside [1, %d]", who, ns, PSE_MOL_TILE);
+    return 0;
+}
+
+int molecule_pairs_compute_validate(const void *p, const void *pos, const void *inv_rh, const void *curves, const void *sums, const void *sample) {
+    const char *who = "pse_molecule_pairs_compute";
+    if (!p) return fail(PSE_ERR_INVALID, "%s: null molecule-pair object", who);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!inv_rh && !curves && !sums && !sample)
+        return fail(PSE_ERR_INVALID, "%s: inv_rh, curves, sums and sample are all null: nothing to compute", who);
+    if (((uintptr_t)inv_rh & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: inv_rh = %p is not 8-byte aligned (doubles)", who, inv_rh);
+    if (((uintptr_t)curves & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: curves = %p is not 8-byte aligned (doubles)", who, curves);
+    if (((uintptr_t)sums & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sums = %p is not 8-byte aligned (doubles)", who, sums);
+    if (((uintptr_t)sample & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sample = %p is not 8-byte aligned (doubles)", who, sample);
+    return 0;
+}
+
+int molecule_pairs_counts_validate(const void *p, const void *nmol, const void *nmol_type, const void *terms) {
+    const char *who = "pse_molecule_pairs_counts";
+    if (!p) return fail(PSE_ERR_INVALID, "%s: null molecule-pair object", who);
+    if (!nmol && !nmol_type && !terms) return fail(PSE_ERR_INVALID, "%s: nmol, nmol_type and terms are all null: nothing to write", who);
+    return 0;
+}
+
+void molecule_pairs_terms(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, int ns, unsigned long long *terms) {
+    std::fill(terms, terms + (size_t)ntypes * ns * MOLPAIR_COLS, 0ull);
+    for (unsigned mol = 0; mol < L.nmol; ++mol) {
+        if (L.ends[2 * (size_t)mol] == 0xffffffffu) continue;
+        const unsigned a = mol_types ? mol_types[mol] : 0u, m = L.mol_off[mol + 1] - L.mol_off[mol];
+        for (unsigned s = 0; s < (unsigned)ns && s < m; ++s) {
+            unsigned long long *e = terms + ((size_t)a * ns + s) * MOLPAIR_COLS;
+            e[0] += m - s;
+            e[1] += m - 1u - s;
+        }
     }
 }
 
@@ -864,5 +929,12 @@ extern "C" int pse_host_molecule_rows(unsigned n, unsigned nbonds, const unsigne
     std::copy(L.tile_mol.begin(), L.tile_mol.end(), tile_mol);
     std::copy(L.tile_rounds.begin(), L.tile_rounds.end(), tile_rounds);
     counts[0] = L.nmol; counts[1] = (unsigned)L.members.size(); counts[2] = L.ntiles;
+    return 0;
+}
+
+// The rank of every member slot of the layout of pse_host_molecule_rows (see include/pse_amd.h).
+extern "C" int pse_host_chain_order(unsigned nmol, const unsigned *parent, const unsigned *mol_off, const unsigned *ends, unsigned *rank) {
+    if (!parent || !mol_off || !ends || !rank) return fail(PSE_ERR_INVALID, "pse_host_chain_order: null array");
+    chain_ranks(nmol, parent, mol_off, ends, rank);
     return 0;
 }

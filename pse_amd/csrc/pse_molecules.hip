@@ -4,30 +4,11 @@
 
 namespace pse {
 
-static_assert(MOL_TILE == 1024, "the packed words of a member hold 10-bit positions");
-constexpr int MOL_HALF = MOL_TILE / 2;          // the most molecules of a tile (dimers)
-constexpr int MOL_BUF = 3 * MOL_TILE + MOL_HALF;   // doubles of one pointer-jumping buffer: x, y, z and MOL_TILE ancestors (ints)
 static_assert(2 * MOL_BUF * sizeof(double) == 57344 && MOL_COLS * MOL_HALF <= 2 * MOL_BUF && 6 * MOL_TILE <= 2 * MOL_BUF,
               "56 KB of LDS: two buffers of the pointer jumping, reused by the six member sums and by the MOL_COLS molecule sums");
 
-// One level-by-level halving tree over the positions p = 0 .. m - 1 of every molecule of the tile at once, on NC arrays of MOL_TILE
-// doubles: at stride s (the powers of two below the tile's largest molecule, descending) position p adds position p + s where
-// p < s and p + s < m.  The order is a function of m alone; the sum ends at position 0.  Ends behind a barrier.
-template <int NC>
-__device__ __forceinline__ void member_tree(double *sh, int l, bool active, int p, int m, int lgS) {
-    for (int s = (1 << lgS) >> 1; s > 0; s >>= 1) {
-        if (active && p < s && p + s < m) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) sh[c * MOL_TILE + l] += sh[c * MOL_TILE + l + s];
-        }
-        __syncthreads();
-    }
-}
-
 // k_mol_tile: one workgroup of MOL_TILE lanes per tile, one lane per member (pse_molecules.h documents the arrays).
-//  1. the lanes gather their positions through the member list, once, into LDS; a lane takes the minimum image of the bond vector to
-//     its parent and the position of its root from there;
-//  2. pointer jumping between two LDS buffers, one barrier a round: u += u[ancestor], ancestor = ancestor[ancestor];
+//  1., 2. the unfolding of mol_unfold (pse_molecules.h), which the pair pass of pse_molpairs.hip shares;
 //  3. su = sum of u and then sum of v (x) v, v = u - su / m, by member_tree; the lane of the root writes the molecule's row, counts
 //     its Rg and |R|, and keeps the MOL_COLS terms of its type's sums;
 //  4. per type, the same halving tree over the molecules of the tile (a molecule of another type enters as +0.0), one partial row
@@ -41,40 +22,12 @@ k_mol_tile(const double4 *__restrict__ pos, DBox box, Molecules mo, double *__re
     const int t = blockIdx.x, l = threadIdx.x;
     const unsigned start = mo.tile_slot[t], cnt = mo.tile_slot[t + 1] - start, tw = mo.tile_word[t];
     const int rounds = (int)(tw & 255u), lgS = (int)((tw >> 8) & 255u), lgM = (int)((tw >> 16) & 255u);
-    const bool active = (unsigned)l < cnt;
-    unsigned idx = 0u;
-    int par = 0, p = 0, m = 1;
-    double4 r = make_double4(0.0, 0.0, 0.0, 0.0);
-    if (active) {
-        const unsigned w = mo.word[start + l];
-        idx = mo.member[start + l];
-        par = (int)(w & 1023u); p = (int)((w >> 10) & 1023u); m = (int)((w >> 20) & 1023u) + 1;
-        r = pos[idx];
-    }
+    const MolMember q = mol_unfold(sh, pos, box, mo.word, mo.member, start, cnt, rounds);
+    const bool active = q.active;
+    const unsigned idx = q.idx;
+    const int p = q.p, m = q.m;
+    const double rx = q.rx, ry = q.ry, rz = q.rz, ux = q.ux, uy = q.uy, uz = q.uz;
     const bool root = active && p == 0;
-    double *b1 = sh + MOL_BUF;
-    b1[l] = r.x; b1[MOL_TILE + l] = r.y; b1[2 * MOL_TILE + l] = r.z;
-    __syncthreads();
-    double ux = 0.0, uy = 0.0, uz = 0.0;
-    const double rx = b1[l - p], ry = b1[MOL_TILE + l - p], rz = b1[2 * MOL_TILE + l - p];   // the root's position
-    if (active && p != 0) {
-        ux = r.x - b1[par]; uy = r.y - b1[MOL_TILE + par]; uz = r.z - b1[2 * MOL_TILE + par];
-        min_image(box, ux, uy, uz);
-    }
-    __syncthreads();   // (round 0 writes the buffer the positions were in)
-    int anc = active ? par : l;
-    sh[l] = ux; sh[MOL_TILE + l] = uy; sh[2 * MOL_TILE + l] = uz;
-    reinterpret_cast<int *>(sh + 3 * MOL_TILE)[l] = anc;
-    __syncthreads();
-    for (int k = 0; k < rounds; ++k) {
-        const double *src = sh + (k & 1) * MOL_BUF;
-        double *dst = sh + ((k + 1) & 1) * MOL_BUF;
-        ux += src[anc]; uy += src[MOL_TILE + anc]; uz += src[2 * MOL_TILE + anc];
-        anc = reinterpret_cast<const int *>(src + 3 * MOL_TILE)[anc];
-        dst[l] = ux; dst[MOL_TILE + l] = uy; dst[2 * MOL_TILE + l] = uz;
-        reinterpret_cast<int *>(dst + 3 * MOL_TILE)[l] = anc;
-        __syncthreads();
-    }
     // the ends of a linear molecule, read by the lane of its root before the buffers are reused
     unsigned molid = 0u, info = 0u;
     double Rx = 0.0, Ry = 0.0, Rz = 0.0;
@@ -170,12 +123,16 @@ k_mol_finish(const double *__restrict__ part, unsigned ntiles, int ncol, double 
     }
 }
 
+void launch_mol_finish(const double *part, unsigned ntiles, int ncol, double *sums, double *sample, hipStream_t s) {
+    hipLaunchKernelGGL(k_mol_finish, dim3(nblocks(ncol, TPB / 64)), dim3(TPB), 0, s, part, ntiles, ncol, sums, sample);
+}
+
 void launch_molecules(const double4 *pos, DBox box, const Molecules &mo, double *rows, double4 *unfolded, double *sums, double *sample,
                       unsigned long long *hist, hipStream_t s) {
     const bool reduce = sums || sample;
     hipLaunchKernelGGL(k_mol_tile, dim3(mo.ntiles), dim3(MOL_TILE), 0, s, pos, box, mo, rows, unfolded, reduce, hist);
     const int ncol = mo.ntypes * MOL_COLS;
-    if (reduce) hipLaunchKernelGGL(k_mol_finish, dim3(nblocks(ncol, TPB / 64)), dim3(TPB), 0, s, mo.part, mo.ntiles, ncol, sums, sample);
+    if (reduce) launch_mol_finish(mo.part, mo.ntiles, ncol, sums, sample, s);
 }
 
 }  // namespace pse

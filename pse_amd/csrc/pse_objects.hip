@@ -1,6 +1,6 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
 // typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors, displacement
-// moments and chain conformations.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h or pse_molecules.h, the objects own their arrays through DeviceObject
+// moments, chain conformations and chain statistics.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h, pse_molecules.h or pse_molpairs.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 #include "pse_analysis.h"
 #include "pse_order.h"
 #include "pse_molecules.h"
+#include "pse_molpairs.h"
 
 // A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
 // and, for bonds, the counter of overstretched FENE bonds.
@@ -43,6 +44,11 @@ struct pse_structure_factor : DeviceObject { StructureFactor sf{}; };
 struct pse_molecules : DeviceObject {
     Molecules mo{};
     std::vector<unsigned> nlinear, nmol_type;   // per type, for pse_molecules_count
+};
+struct pse_molecule_pairs : DeviceObject {
+    MolPairs mp{};
+    std::vector<unsigned> nmol_type;            // per type, for pse_molecule_pairs_counts
+    std::vector<unsigned long long> terms;      // ntypes x ns x MOLPAIR_COLS
 };
 struct pse_msd : DeviceObject {
     MsdOrigins mo{};
@@ -598,6 +604,73 @@ extern "C" int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, d
     pse_handle *h = m->h;
     HIPCHK(hipSetDevice(h->device));
     launch_molecules((const double4 *)pos, h->dbox, m->mo, rows, (double4 *)unfolded, sums, sample, hist, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Chain statistics (include/pse_amd.h): its own layout of pse_host_molecule_rows with the ranks of pse_host_chain_order, packed as the
+// kernel reads it (pse_molpairs.h), the two workspaces of per-tile partial sums, and the pass.  Queue-only, as pse_molecules_compute.
+extern "C" int pse_molecule_pairs_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *mol_types_host,
+                                         int ntypes, int ns, pse_molecule_pairs **out) {
+    const char *who = "pse_molecule_pairs_create";
+    TRY(create_begin(who, h, out));
+    MoleculeLayout L;
+    TRY(molecule_pairs_create_validate((unsigned)h->n_max, n, nbonds, pairs_host, mol_types_host, ntypes, ns, L));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nmem = L.members.size();
+    std::vector<unsigned> rank, word(nmem), mol_word(L.nmol), tile_slot(L.ntiles + 1), tile_word(L.ntiles);
+    chain_order(L, rank);
+    auto lg_ceil = [](unsigned v) { unsigned r = 0; while ((1u << r) < v) ++r; return r; };
+    for (unsigned t = 0; t < L.ntiles; ++t) {
+        const unsigned first = L.mol_off[L.tile_mol[t]];
+        unsigned largest = 0;
+        tile_slot[t] = first;
+        for (unsigned q = L.tile_mol[t]; q < L.tile_mol[t + 1]; ++q) {
+            const unsigned o = L.mol_off[q], m = L.mol_off[q + 1] - o;
+            largest = std::max(largest, m);
+            for (unsigned p = 0; p < m; ++p) {
+                word[o + p] = (o - first + L.parent[o + p]) | (p << 10) | ((m - 1u) << 20);
+                rank[o + p] |= (q - L.tile_mol[t]) << 10;
+            }
+            const bool linear = L.ends[2 * (size_t)q] != 0xffffffffu;
+            mol_word[q] = (o - first) | ((m - 1u) << 10) | ((mol_types_host ? mol_types_host[q] : 0u) << 20) | (linear ? 1u << 24 : 0u);
+        }
+        tile_word[t] = L.tile_rounds[t] | (lg_ceil(largest) << 8);
+    }
+    tile_slot[L.ntiles] = (unsigned)nmem;
+    pse_molecule_pairs *m = new pse_molecule_pairs();
+    m->h = h;
+    m->nmol_type.resize((size_t)ntypes);
+    molecules_counts(L, mol_types_host, ntypes, nullptr, nullptr, m->nmol_type.data());
+    m->terms.resize((size_t)ntypes * ns * MOLPAIR_COLS);
+    molecule_pairs_terms(L, mol_types_host, ntypes, ns, m->terms.data());
+    MolPairs &mp = m->mp;
+    mp.nmol = L.nmol; mp.ntiles = L.ntiles; mp.ntypes = ntypes; mp.ns = ns;
+    hipError_t e = m->put(&mp.member, L.members.data(), nmem);
+    e = m->put(&mp.word, word.data(), nmem);
+    e = m->put(&mp.rank, rank.data(), nmem);
+    e = m->put(&mp.mol_word, mol_word.data(), mol_word.size());
+    e = m->put(&mp.tile_slot, tile_slot.data(), tile_slot.size());
+    e = m->put(&mp.tile_mol, L.tile_mol.data(), L.tile_mol.size());
+    e = m->put(&mp.tile_word, tile_word.data(), tile_word.size());
+    e = m->put(&mp.part_curves, nullptr, (size_t)L.ntiles * ntypes * ns * MOLPAIR_COLS);
+    e = m->put(&mp.part_sums, nullptr, (size_t)L.ntiles * ntypes * MOLPAIR_SUMS);
+    return create_end(who, h, m, e, out);
+}
+extern "C" int pse_molecule_pairs_destroy(pse_molecule_pairs *p) { return object_destroy(p); }
+extern "C" int pse_molecule_pairs_counts(pse_molecule_pairs *p, unsigned *nmol, unsigned *nmol_type, unsigned long long *terms) {
+    TRY(molecule_pairs_counts_validate(p, nmol, nmol_type, terms));
+    if (nmol) *nmol = p->mp.nmol;
+    if (nmol_type) std::copy(p->nmol_type.begin(), p->nmol_type.end(), nmol_type);
+    if (terms) std::copy(p->terms.begin(), p->terms.end(), terms);
+    return 0;
+}
+extern "C" int pse_molecule_pairs_compute(pse_molecule_pairs *p, const pse_double4 *pos, double *inv_rh, double *curves, double *sums,
+                                          double *sample) {
+    TRY(molecule_pairs_compute_validate(p, pos, inv_rh, curves, sums, sample));
+    pse_handle *h = p->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_molecule_pairs((const double4 *)pos, h->dbox, p->mp, inv_rh, curves, sums, sample, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

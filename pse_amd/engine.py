@@ -576,6 +576,37 @@ class MoleculeTopology(_DeviceObject):
         self.nmol, self.nlinear, self.nmol_type = int(nmol.value), nlinear.astype(np.int64), nmol_type.astype(np.int64)
 
 
+MOLPAIR_COLS = 2      # PSE_MOLPAIR_COLS: per separation D, C
+MOLPAIR_SUMS = 2      # PSE_MOLPAIR_SUMS: per type the sum of 1/Rh and of (1/Rh)^2
+
+
+class MoleculePairs(_DeviceObject):
+    """Owner of a pse_molecule_pairs object: the molecules of a bond topology as for a MoleculeTopology (`pairs`, `mol_types`, `ntypes`,
+    `n`), the chain rank of every member and `ns`, the number of separations of the curves (1 .. 1024).  Pass it as `pairs` to
+    Engine.molecule_pairs_compute.  nmol, nmol_type (per type) and terms (ntypes, ns, 2) -- the number of summands behind every entry
+    of the curves -- are read once at creation (host words: no device wait)."""
+
+    DESTROY = "pse_molecule_pairs_destroy"
+
+    def __init__(self, engine, pairs, mol_types=None, ntypes=1, ns=1, n=None):
+        import numpy as np
+        pairs, mol_types, self.ntypes, _, _, _ = _molecule_arguments(pairs, mol_types, ntypes, 0, None, None)
+        self.ns = int(ns)
+        if not 1 <= self.ns <= MOL_TILE:
+            raise ValueError(f"ns = {self.ns} outside [1, {MOL_TILE}]")
+        self.n = _rows(engine, n)
+        if mol_types is not None:   # (the library reads nmol entries: the count has to be right before it does)
+            from .analyze import molecules_of
+            nmol = molecules_of(self.n, pairs)[1]
+            if mol_types.shape[0] != nmol:
+                raise ValueError(f"molecule_types has {mol_types.shape[0]} entries, the bonds make {nmol} molecules")
+        self._create(engine, "pse_molecule_pairs_create", self.n, pairs.shape[0], _vp(pairs), _vp(mol_types), self.ntypes, self.ns)
+        nmol, nmol_type = ctypes.c_uint(0), np.zeros(self.ntypes, dtype=np.uint32)
+        terms = np.zeros((self.ntypes, self.ns, MOLPAIR_COLS), dtype=np.uint64)
+        _lib.check(self._lib.pse_molecule_pairs_counts(self._obj, ctypes.byref(nmol), _vp(nmol_type), _vp(terms)))
+        self.nmol, self.nmol_type, self.terms = int(nmol.value), nmol_type.astype(np.int64), terms.astype(np.int64)
+
+
 def _cluster_arguments(types, ntypes, rlink, name="rlink"):
     """The arguments of a ClusterLinks, checked before the device is touched: (types uint32 (n,) or None, ntypes, rlink float64 (npt,)).
     `rlink`: a scalar (every pair type), a dict {(a, b): r} in either key order with a missing pair off, or npt entries in the
@@ -994,6 +1025,31 @@ class _ForcePasses:
         _lib.check(self._lib.pse_molecules_compute(molecules._handle(self), _ptr(pos), _ptr(rows), _ptr(unfolded), _ptr(sums), _ptr(sample),
                                                    _ptr(hist)))
         return rows, unfolded, sums, sample, hist
+
+    def molecule_pairs(self, pairs, mol_types=None, ntypes=1, ns=1, n=None):
+        """The molecules of a bond topology with their chain ranks on the device (pse_molecule_pairs_create; see include/pse_amd.h
+        and MoleculePairs).  Returns a MoleculePairs: the `pairs` of molecule_pairs_compute."""
+        return MoleculePairs(self, pairs, mol_types, ntypes, ns, n)
+
+    def molecule_pairs_compute(self, pos, pairs, inv_rh=None, curves=None, sums=None, sample=None):
+        """The pair sums of every molecule at `pos` in the engine's current box (pse_molecule_pairs_compute), on the offsets that
+        molecules_compute unfolds.  All outputs are contiguous float64 CUDA tensors, any may be None, not all:
+        `inv_rh` (nmol,), WRITTEN: 1/Rh = (1/m^2) sum over i != j of 1/r_ij (a pair at distance 0 adds nothing);
+        `curves` (ntypes, ns, 2), ADDED to: per type and separation s the sums over the linear molecules of D(s) = sum |u_{c+s} - u_c|^2
+        and C(s) = sum b_c . b_{c+s};
+        `sums` (ntypes, 2), ADDED to, and `sample` (ntypes, 2), WRITTEN with this call's sums alone: the sum of 1/Rh and of (1/Rh)^2.
+        Queue-only: nothing is read back, no floating-point atomics: equal inputs give equal bits.  Returns the four."""
+        import torch
+        _chk4(pos, "pos", pairs.n)
+        shapes = ((inv_rh, "inv_rh", (pairs.nmol,)), (curves, "curves", (pairs.ntypes, pairs.ns, MOLPAIR_COLS)),
+                  (sums, "sums", (pairs.ntypes, MOLPAIR_SUMS)), (sample, "sample", (pairs.ntypes, MOLPAIR_SUMS)))
+        for t, name, shape in shapes:
+            if t is not None and not (_is_cuda(t, torch.float64) and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {shape} {torch.float64} CUDA tensor")
+        if inv_rh is None and curves is None and sums is None and sample is None:
+            raise ValueError("inv_rh, curves, sums and sample are all None: nothing to compute")
+        _lib.check(self._lib.pse_molecule_pairs_compute(pairs._handle(self), _ptr(pos), _ptr(inv_rh), _ptr(curves), _ptr(sums), _ptr(sample)))
+        return inv_rh, curves, sums, sample
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
