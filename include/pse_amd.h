@@ -816,7 +816,7 @@ int pse_debug_grid_placement(pse_handle *h, int *tried, float *ms_first, float *
 int pse_debug_vq_roundtrip(int n, const double *rows_host, double *out_host);
 /* the device-side Lanczos decision (k_lz_decide: what ends every queue-only Brownian call and every owned-particle team step) on GIVEN
  * coefficients, for tests: scal_host is one image of the device scalars (PSE_DEBUG_LZ_NSCAL doubles: alpha at 0, beta at 128, the
- * norm of psi at 256), dec the decisions of one call in the order a driver issues them (fields as LzDecide, pse_vectors.h; seq is the
+ * norm of psi at 256), dec the decisions of one call in the order a driver issues them (fields as LzDecide, pse_host.h; seq is the
  * call's number as the host mirror gets it), open0 the initial value of the mirror's count of calls that ended open.  The decision
  * state starts as NaN bytes -- the reset under `first` is what makes it valid --, the decisions are launched in order on one stream,
  * and after each launch the state and the five mirror slots (m, step norm, status, seq, open calls) are copied to out[k].  Current
@@ -1001,6 +1001,13 @@ int pse_team_debug_solo(pse_team *team, int slab_rank);
 /* host-only: t = T^{1/2} e_1 of the Lanczos tridiagonal (alpha[0..m), beta[1..m)); replaces LAPACKE_spteqr +
  * the host loops at PSEv1/Brownian.cu:540-582. Exposed so the eigen-solver can be tested without a GPU. */
 int pse_host_lanczos_sqrt_e1(int m, const double *alpha, const double *beta, double *t);
+/* host-only: the Lanczos decision of the host-checked Brownian calls (lz_decide_host: what ends the iteration of every call that is not
+ * queue-only) on GIVEN coefficients -- the arguments, the structs, the initial state of NaN bytes and the outcome per decision of
+ * pse_debug_lz_decide, with the five mirror values kept as the device's decision would leave them, and no device.  A decision may
+ * check any number of sizes (the host drivers' batches grow): PSE_ERR_INVALID for a null array, n_dec outside [1, 40], a first
+ * decision without `first`, anything but 1 <= m_lo <= m_hi <= done_iters <= 100, pending_beta outside [0, m_hi], m_max > 100.  A
+ * non-finite coefficient or a failed eigen-solve is status 2 in the outcome, not an error of this call. */
+int pse_host_lz_decide(const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, double open0, pse_debug_lz_outcome *out);
 /* host-only: the parameter rule of Stokes::setParams (PSEv1/Stokes.cc:129-236,319) without creating a handle */
 int pse_host_select_params(const pse_params *params, pse_info *info);
 /* host-only: the per-particle rows a pse_bonds object stores (pse_bonds_create calls this after validating).  A CSR over the n

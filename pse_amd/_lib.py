@@ -222,6 +222,7 @@ SYMBOLS = {
     "pse_team_set_diag": (_i, [_vp, _i]),
     "pse_team_get_diag": (_i, [_vp, ctypes.POINTER(pse_team_diag)]),
     "pse_host_lanczos_sqrt_e1": (_i, [_i, _dp, _dp, _dp]),
+    "pse_host_lz_decide": (_i, [_dp, _i, ctypes.POINTER(pse_debug_lz_decision), _d, ctypes.POINTER(pse_debug_lz_outcome)]),
     "pse_host_select_params": (_i, [ctypes.POINTER(pse_params), ctypes.POINTER(pse_info)]),
 }
 

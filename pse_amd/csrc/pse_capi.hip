@@ -44,8 +44,6 @@ using namespace pse;
         if (s_ != rocfft_status_success) return fail(PSE_ERR_FFT, "%s failed: rocfft status %d (%s:%d)", #x, (int)s_, __FILE__, __LINE__); \
     } while (0)
 
-constexpr int M_MAX = 100;   // Lanczos basis cap (PSEv1/Brownian.cu:397)
-
 static std::once_flag g_fft_once;
 
 template <class T>
@@ -1510,6 +1508,71 @@ static int real(pse_team &T, double4 *pse_handle::*vec, double4 *pse_handle::*ou
 // rows a rank updates in a Lanczos iteration: its own and the ghost layers its next mat-vec reads
 static int update_ranges(const pse_handle *h, int N, int rg[3][2]) { return row_ranges(h, N, 1, rg); }
 
+// ---- what the four Lanczos drivers below share ------------------------------------------------------------------------------------
+// Lanczos vector q of a handle: psi for q = 0, else parked in V[q] (the members of a team have one n_pad); none for q < 0
+static double4 *lz_vec(const pse_handle *h, int q) { return q < 0 ? nullptr : q == 0 ? h->psi_s : h->V + (size_t)q * h->n_pad; }
+// the two-step block that starts at iteration j (full), or the single step j
+static LzBlockArgs lz_block_args(const pse_handle *h, int j, bool full) {
+    LzBlockArgs a{};
+    a.q = lz_vec(h, j); a.p = lz_vec(h, j - 1); a.w1 = h->w_s; a.w2 = full ? h->w2_s : nullptr;
+    a.u = h->u_s; a.v1 = lz_vec(h, j + 1); a.v2 = full ? lz_vec(h, j + 2) : nullptr;
+    a.j = j;
+    return a;
+}
+// the starting count of a call; its first convergence check is at max(m_in, 2) (Brownian.cu:465-466,606)
+static int lz_m_in(const int *m_io) { return std::min(std::max(m_io ? *m_io : 2, 1), M_MAX); }
+// the gated iterations a queue-only single-GPU call queues behind them (pse_set_lanczos_extra counts)
+static int lz_queued_extra(const pse_handle *h, int m_in) {
+    return std::max(0, std::min(h->lz_extra >= 0 ? h->lz_extra : h->tun.lz_extra, M_MAX - std::max(m_in, 2)));
+}
+
+// ---- ... and the two host-checked ones: a batch of iterations, its scalars read back, ONE decision (lz_decide_host) ---------------
+// (alpha, beta and the norm are already on their way: the update kernels write them to the mapped host buffer as well)
+static int lz_wait_scalars(pse_team &T, bool &hook_done, const std::function<int()> &before_first_wait) {
+    pse_handle *h0 = T.m[0];
+    HIPCHK(hipEventRecord(h0->ev_scal, h0->stream));
+    if (!hook_done) {   // independent work queued behind the read-back keeps the GPU busy while the host decides
+        hook_done = true;
+        for (pse_handle *h : act(T)) TRY(te(h, PH_LANCZOS));
+        if (before_first_wait) TRY(before_first_wait());
+    }
+    HIPCHK(hipEventSynchronize(h0->ev_scal));
+    return 0;
+}
+// The decision on the batch that ends at iteration `done`: the sizes not yet checked, from m_in - 1 on.  d, built anew for every batch,
+// brings `first` and what differs between the drivers (pending_beta; have_last_beta, normalised); the rest is filled in here.  The host
+// mirror of the queue-only calls (LZ_HOST_M ..) is not written: pse_get_info reads it only after such a call, and its count of open
+// calls is sticky.
+static int lz_decide_batch(LzDecide d, int m_in, int done, double tol, const double *sc, LzState &st) {
+    d.m_lo = std::max((d.first ? 0 : st.checked) + 1, std::max(m_in - 1, 1)); d.m_hi = d.done_iters = done; d.m_max = M_MAX; d.tol = tol;
+    int at = 0;
+    const LzFailure f = lz_decide_host(d, sc, st, &at);
+    if (f == LZ_NONFINITE) return fail(PSE_ERR_NUMERIC, "Lanczos produced a non-finite coefficient at iteration %d", at);
+    if (f == LZ_EIGEN_FAILED) return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve failed at m = %d", at);
+    return 0;
+}
+// psi == 0 -> result 0 (the decision's m_final = 0)
+static int lz_zero_result(pse_team &T, int N, int matvecs) {
+    for (pse_handle *h : act(T)) {
+        HIPCHK(hipMemsetAsync(h->ub_s, 0, (size_t)N * sizeof(double4), h->stream));
+        h->info.lanczos_m = 0; h->info.lanczos_matvecs = matvecs; h->info.lanczos_stepnorm = 0.0;
+    }
+    return 0;
+}
+// the final combination on every member's own rows, with the coefficients of the decision (Brownian.cu:716,739)
+static void lz_combine(pse_team &T, int N, double scale, const LzState &st, int matvecs, int exchanges) {
+    BasisCoef tc{};
+    std::copy(st.coef, st.coef + st.m_final, tc.t);
+    for (pse_handle *h : act(T)) {
+        int lo, hi;
+        row_range(h, N, lo, hi);
+        launch_basis_combine(h->psi_s, h->V, h->n_pad, tc, st.m_final, h->scal, scale, 1, h->ub_s, lo, hi, h->stream, h->sink);
+        h->tail_done = h->sink.on;
+        h->info.lanczos_m = st.m_final; h->info.lanczos_matvecs = matvecs; h->info.lanczos_stepnorm = st.stepnorm;
+        h->info.lanczos_exchanges = exchanges;
+    }
+}
+
 // Queue-only Lanczos of a single GPU (pse_set_async): the iterations of the starting count are queued as the host-driven loop
 // below queues them; then ONE launch takes the decision the host would take (k_lz_decide: the tridiagonal square roots of the two
 // sizes m_in - 1 and m_in, the step norm), and `extra` more iterations follow, each with its own decision, every kernel of them
@@ -1521,19 +1584,15 @@ static int update_ranges(const pse_handle *h, int N, int rg[3][2]) { return row_
 static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_io, const std::function<int()> &before_first_wait,
                           const std::function<int()> &before_combine) {
     pse_handle *h = T.m[0];
-    const size_t stride = h->n_pad;
-    const int m_in = std::min(std::max(m_io ? *m_io : 2, 1), M_MAX);
-    const int target = std::max(m_in, 2);
-    const int extra = std::max(0, std::min(h->lz_extra >= 0 ? h->lz_extra : h->tun.lz_extra, M_MAX - target));
+    const int m_in = lz_m_in(m_io), target = std::max(m_in, 2), extra = lz_queued_extra(h, m_in);
     const int *stop = &h->lz_state->done;
     const double seq = (double)++h->lz_seq;
     h->lz_last_queued = true;
     int rg[3][2];
     const int nrg_all = update_ranges(h, N, rg);
-    auto vec = [&](int q) -> const double4 * { return q == 0 ? h->psi_s : h->V + (size_t)q * stride; };
     // the vector part of iteration j: x_{j+1} from the sums that are still in place
     auto vector_part = [&](int j, const int *gate) {
-        launch_lz_update(vec(j), h->w_s, j > 0 ? vec(j - 1) : nullptr, h->V + (size_t)(j + 1) * stride, j, h->scal, rg, nrg_all, h->stream,
+        launch_lz_update(lz_vec(h, j), h->w_s, lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, nrg_all, h->stream,
                          nullptr, 0, h->sc_host_dev, gate, vq_of(h), h->lz_sums);   // (+ the mirror of x_{j+1}: the next mat-vec's gathers, and two of its sums)
     };
     auto iteration = [&](int j, bool scalars_only, const int *gate) -> int {
@@ -1541,19 +1600,19 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
         const bool fused = !have_y && h->nb.cap > 0 && h->nb_valid;
         if (!fused && !have_y) {
             if (gate) return fail(PSE_ERR_NUMERIC, "queued Lanczos: a gated iteration needs the pair list");
-            TRY(real(T, j == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)j * stride, 0, N, true));
+            TRY(real(T, j == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)j * h->n_pad, 0, N, true));
         }
-        const double4 *vjm1 = j > 0 ? vec(j - 1) : nullptr;
+        const double4 *vjm1 = lz_vec(h, j - 1);
         // from iteration 1 on the mat-vec sums x_j.y alone: x_j.x_j and x_j.x_{j-1} are what the update that wrote x_j left in lz_sums
         const bool split = fused && j > 0;
         if (fused)
-            launch_mreal_lanczos(h->pos_s, vec(j), h->w_s, row_map(0, N), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
+            launch_mreal_lanczos(h->pos_s, lz_vec(h, j), h->w_s, row_map(0, N), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
                                  LzFuse{split ? nullptr : vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr, h->lz_sums, lz_update_grid(N)}, h->scal, nullptr, nullptr, h->stream,
                                  h->vl_use ? h->vl : VerletList{}, split ? 4 : 1, gate, DevRowArgs{}, j > 0 ? vq_of(h) : nullptr);
         else if (!(j == 0 && h->sums0_done))
-            launch_lz_dots(vec(j), h->w_s, vjm1, 0, N, h->partials, h->npart_cap, h->scal, h->stream);
+            launch_lz_dots(lz_vec(h, j), h->w_s, vjm1, 0, N, h->partials, h->npart_cap, h->scal, h->stream);
         h->w_is_mpsi = false; h->sums0_done = false;
-        if (scalars_only) launch_lz_update(vec(j), h->w_s, vjm1, h->V + (size_t)(j + 1) * stride, j, h->scal, rg, 0, h->stream, nullptr, 0,
+        if (scalars_only) launch_lz_update(lz_vec(h, j), h->w_s, vjm1, lz_vec(h, j + 1), j, h->scal, rg, 0, h->stream, nullptr, 0,
                                            h->sc_host_dev, gate);
         else vector_part(j, gate);
         return 0;
@@ -1573,7 +1632,7 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
     TRY(te(h, PH_LANCZOS));
     if (before_first_wait) TRY(before_first_wait());
     if (before_combine) TRY(before_combine());
-    launch_basis_combine(h->psi_s, h->V, stride, BasisCoef{}, 0, h->scal, scale, 1, h->ub_s, 0, N, h->stream, h->sink, h->lz_state);
+    launch_basis_combine(h->psi_s, h->V, h->n_pad, BasisCoef{}, 0, h->scal, scale, 1, h->ub_s, 0, N, h->stream, h->sink, h->lz_state);
     h->tail_done = h->sink.on;
     h->info.lanczos_matvecs = done; h->info.lanczos_exchanges = 0;
     // m of this call is known on the device only; what the host hands back is the most recent one that has reached it
@@ -1587,35 +1646,38 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
 // neighbouring cell layers for the vector the next mat-vec reads).
 static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, const std::function<int()> &before_first_wait = nullptr,
                    WavePump *pump = nullptr, const std::function<int()> &before_combine = nullptr) {
-    int n_exchanges = 0;
     pse_handle *h0 = T.m[0];
+    const int m_in = lz_m_in(m_io);
     if (h0->async_mode && T.G == 1 && T.solo < 0 && h0->nb.cap > 0 && !h0->timing &&
-        lz_decide_supported(std::min(M_MAX, std::max(std::min(std::max(m_io ? *m_io : 2, 1), M_MAX), 2) + (h0->lz_extra >= 0 ? h0->lz_extra : h0->tun.lz_extra))))   // (the extras THIS call queues: pse_set_lanczos_extra counts)
+        lz_decide_supported(std::max(m_in, 2) + lz_queued_extra(h0, m_in)))
         return lanczos_queued(T, N, tol, scale, m_io, before_first_wait, before_combine);
-    const size_t stride = h0->n_pad;
     for (pse_handle *h : act(T)) h->lz_last_queued = false;
-    int m_in = m_io ? *m_io : 2;
-    if (m_in < 1) m_in = 1;
-    if (m_in > M_MAX) m_in = M_MAX;
-    std::vector<double> t_prev, t_cur;
-    double *sc = h0->sc_host;   // pinned: the read-back of the device scalars is one DMA, no staging copy
-    int done = 0;                         // iterations launched so far
-    int target = std::max(m_in, 2);       // first convergence check is at m = max(m_in, 2)   (Brownian.cu:465-466,606)
-    int m_final = 0, checked = 0, pending_beta = 0;
-    double stepnorm = 1.0;
+    const double *sc = h0->sc_host;   // pinned: the read-back of the device scalars is one DMA, no staging copy
+    int done = 0, n_exchanges = 0;    // iterations launched so far
+    int target = std::max(m_in, 2);
+    int pending_beta = 0;             // beta_done = |x_done| does not exist when a batch is decided: it arrives with the next one
+    LzState st{0, 0, 0, 0, 1.0, {}, {}};   // as a decision under `first` resets it
     bool hook_done = false;
+    // the update of iteration j: alpha_j, beta_j from the sums in place and, unless scalars_only, x_{j+1} on the own and the ghost rows
+    auto update = [&](int j, bool scalars_only) {
+        for (pse_handle *h : act(T)) {
+            int rg[3][2];
+            const int nrg = scalars_only ? 0 : update_ranges(h, N, rg);
+            launch_lz_update(lz_vec(h, j), h->w_s, lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0,
+                             h == h0 ? h->sc_host_dev : nullptr, nullptr, T.G <= 1 ? vq_of(h) : nullptr, T.G <= 1 ? h->lz_sums : nullptr);
+        }
+    };
     while (true) {
         for (; done < target; ++done) {
             // iteration j = done on the unnormalised x_j (psi for j = 0, else parked in V[j]); see k_lz_update
             const bool have_y = done == 0 && h0->w_is_mpsi;      // M psi came with the pass that built the pair list
             const bool fused = !have_y && h0->nb.cap > 0 && h0->nb_valid;   // sums fused into the pair-list mat-vec
             const bool timed = done == 1 && fused;               // one pair-list mat-vec kernel per call is timed on its own
-            if (!fused && !have_y) TRY(real(T, done == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)done * stride, 0, N, true));
+            if (!fused && !have_y) TRY(real(T, done == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)done * h0->n_pad, 0, N, true));
             for (pse_handle *h : act(T)) {
                 int lo, hi;
                 row_range(h, N, lo, hi);
-                const double4 *xj = done == 0 ? h->psi_s : h->V + (size_t)done * stride;
-                const double4 *vjm1 = done > 1 ? h->V + (size_t)(done - 1) * stride : (done == 1 ? h->psi_s : nullptr);   // x_{j-1}, unnormalised
+                const double4 *xj = lz_vec(h, done), *vjm1 = lz_vec(h, done - 1);   // x_{j-1}, unnormalised
                 if (fused) {
                     const bool ev = timed && h->timing;
                     // a single GPU, from iteration 1 on: the mat-vec sums x_j.y alone; x_j.x_j and x_j.x_{j-1} are what the update that
@@ -1639,86 +1701,29 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
             // The LAST iteration of a batch only derives its scalars (alpha_j, beta_j): whether x_{j+1} is needed at all is what the
             // check below decides -- in the steady state of a time-stepping loop (m_in = m) it is not, and the step saves one vector
             // pass and the reduction of |x_{j+1}| (0.04 ms at the metric point).  If the iteration goes on, the vector part follows.
-            const bool scalars_only = done == target - 1;
-            for (pse_handle *h : act(T)) {
-                int rg[3][2];
-                const int nrg = scalars_only ? 0 : update_ranges(h, N, rg);
-                const double4 *xj = done == 0 ? h->psi_s : h->V + (size_t)done * stride;
-                launch_lz_update(xj, h->w_s, done > 1 ? h->V + (size_t)(done - 1) * stride : (done == 1 ? h->psi_s : nullptr),
-                                 h->V + (size_t)(done + 1) * stride, done, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0, h == h0 ? h->sc_host_dev : nullptr,
-                                 nullptr, T.G <= 1 ? vq_of(h) : nullptr, T.G <= 1 ? h->lz_sums : nullptr);
-            }
+            update(done, done == target - 1);
         }
-        // (alpha, beta and the norm are already on their way: the update kernels write them to the mapped host buffer as well)
-        HIPCHK(hipEventRecord(h0->ev_scal, h0->stream));
-        if (!hook_done) {   // independent work queued behind the read-back keeps the GPU busy while the host decides
-            hook_done = true;
-            for (pse_handle *h : act(T)) TRY(te(h, PH_LANCZOS));
-            if (before_first_wait) TRY(before_first_wait());
-        }
-        HIPCHK(hipEventSynchronize(h0->ev_scal));
-        if (T.solo >= 0) { m_final = done; t_cur.assign(m_final, 0.0); break; }   // timing only (pse_team_debug_solo)
-        const double *alpha = &sc[LZ_ALPHA], *beta = &sc[LZ_BETA];   // alpha_0 .. alpha_{done-1}, beta_1 .. beta_{done-1}; beta_done not yet
-        if (!(sc[LZ_NORM] > 0.0) || !std::isfinite(sc[LZ_NORM])) {   // psi == 0 -> result 0
-            for (pse_handle *h : act(T)) {
-                HIPCHK(hipMemsetAsync(h->ub_s, 0, (size_t)N * sizeof(double4), h->stream));
-                h->info.lanczos_m = 0; h->info.lanczos_matvecs = done; h->info.lanczos_stepnorm = 0.0;
-            }
-            if (m_io) *m_io = m_in;
-            return 0;
-        }
-        // |x_m| of the vector the previous batch ended on arrives with this batch's first mat-vec: its breakdown test comes first
-        if (pending_beta && beta[pending_beta] < 1e-8) { m_final = pending_beta; stepnorm = 0.0; t_cur = t_prev; break; }
-        pending_beta = 0;
-        // walk m upward exactly as the reference's while loop does, one vector at a time
-        for (int m = std::max(checked + 1, std::max(m_in - 1, 1)); m <= done && !m_final; ++m) {
-            const bool last = m == done;                                          // beta_done = |x_done| does not exist yet
-            if (!std::isfinite(alpha[m - 1]) || (!last && !std::isfinite(beta[m])))
-                return fail(PSE_ERR_NUMERIC, "Lanczos produced a non-finite coefficient at iteration %d", m - 1);
-            if (!lanczos_sqrt_e1(m, alpha, beta, t_cur))
-                return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve failed at m = %d", m);
-            if (!last && beta[m] < 1e-8) { m_final = m; stepnorm = 0.0; break; }  // invariant subspace (Brownian.cu:503)
-            if (!t_prev.empty() && (int)t_prev.size() == m - 1) {
-                double s2 = t_cur[m - 1] * t_cur[m - 1];
-                for (int q = 0; q < m - 1; ++q) s2 += (t_cur[q] - t_prev[q]) * (t_cur[q] - t_prev[q]);
-                stepnorm = std::sqrt(s2 / alpha[0]);                               // Brownian.cu:719-724; psi.M.psi/|psi|^2 = alpha_0
-                if (stepnorm <= tol || m >= M_MAX) { m_final = m; break; }
-            }
-            t_prev = t_cur;
-            checked = m;
-        }
-        if (m_final) break;
-        if (done >= M_MAX) { m_final = M_MAX; break; }
+        TRY(lz_wait_scalars(T, hook_done, before_first_wait));
+        if (T.solo >= 0) { st.m_final = done; break; }   // timing only (pse_team_debug_solo): coefficients zero
+        // alpha_0 .. alpha_{done-1}, beta_1 .. beta_{done-1} have arrived
+        LzDecide d{};
+        d.first = pending_beta == 0; d.pending_beta = pending_beta;
+        TRY(lz_decide_batch(d, m_in, done, tol, sc, st));
+        if (st.done) break;   // (always at done = M_MAX: the walk reaches that size, where m >= m_max ends it)
         // not converged: the vector part of the last iteration (its sums are still in place), then the next batch; an x_done that
         // vanishes (invariant subspace) shows in the first sums of that batch
-        for (pse_handle *h : act(T)) {
-            int rg[3][2];
-            const int nrg = update_ranges(h, N, rg);
-            const int j = done - 1;
-            const double4 *xj = j == 0 ? h->psi_s : h->V + (size_t)j * stride;
-            launch_lz_update(xj, h->w_s, j > 1 ? h->V + (size_t)(j - 1) * stride : (j == 1 ? h->psi_s : nullptr),
-                             h->V + (size_t)(j + 1) * stride, j, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0, h == h0 ? h->sc_host_dev : nullptr,
-                             nullptr, T.G <= 1 ? vq_of(h) : nullptr, T.G <= 1 ? h->lz_sums : nullptr);
-        }
+        update(done - 1, false);
         pending_beta = done;
         target = std::min(M_MAX, done + std::max(2, done / 4));
     }
-    if ((int)t_cur.size() != m_final) {
-        if (!lanczos_sqrt_e1(m_final, &sc[LZ_ALPHA], &sc[LZ_BETA], t_cur))
-            return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve failed at m = %d", m_final);
+    if (st.m_final == 0) {
+        if (m_io) *m_io = m_in;
+        return lz_zero_result(T, N, done);
     }
     if (before_combine) TRY(before_combine());   // (the far-field velocities must be in place if the combination adds them)
-    for (pse_handle *h : act(T)) {
-        BasisCoef tc{};   // the basis holds the unnormalised x_q: v_q = x_q / |x_q|, |x_0| = the norm of psi, |x_q| = beta_q
-        for (int q = 0; q < m_final; ++q) tc.t[q] = t_cur[q] / (q == 0 ? sc[LZ_NORM] : sc[LZ_BETA + q]);
-        int lo, hi;
-        row_range(h, N, lo, hi);
-        launch_basis_combine(h->psi_s, h->V, stride, tc, m_final, h->scal, scale, 1, h->ub_s, lo, hi, h->stream, h->sink);   // Brownian.cu:716,739
-        h->tail_done = h->sink.on;
-        h->info.lanczos_m = m_final; h->info.lanczos_matvecs = done; h->info.lanczos_stepnorm = stepnorm;
-        h->info.lanczos_exchanges = T.G > 1 ? n_exchanges : 0;
-    }
-    if (m_io) *m_io = m_final;
+    // the basis holds the unnormalised x_q: v_q = x_q / |x_q|, |x_0| = the norm of psi, |x_q| = beta_q -- normalised = 0
+    lz_combine(T, N, scale, st, done, T.G > 1 ? n_exchanges : 0);
+    if (m_io) *m_io = st.m_final;
     return 0;
 }
 
@@ -1731,41 +1736,31 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
 static int lanczos_team(pse_team &T, int N, double tol, double scale, int *m_io, const std::function<int()> &before_first_wait,
                         WavePump *pump, const std::function<int()> &before_combine = nullptr) {
     pse_handle *h0 = T.m[0];
-    const size_t stride = h0->n_pad;
     for (pse_handle *h : act(T)) h->lz_last_queued = false;
-    int m_in = m_io ? *m_io : 2;
-    m_in = std::min(std::max(m_in, 1), M_MAX);
-    std::vector<double> t_prev, t_cur;
-    double *sc = h0->sc_host;
-    int done = 0, target = std::max(m_in, 2), m_final = 0, checked = 0, n_exchanges = 0, matvecs = 0;
+    const int m_in = lz_m_in(m_io);
+    const double *sc = h0->sc_host;
+    int done = 0, target = std::max(m_in, 2), n_exchanges = 0, matvecs = 0;
     int half_pending = -1;                // j of a single step whose vectors have not been formed yet
-    double stepnorm = 1.0;
+    bool first = true;
+    LzState st{0, 0, 0, 0, 1.0, {}, {}};   // as a decision under `first` resets it
     bool hook_done = false;
-    auto vec = [&](pse_handle *h, int q) { return q == 0 ? h->psi_s : h->V + (size_t)q * stride; };
-    auto block_args = [&](pse_handle *h, int j, bool full) {
-        LzBlockArgs a{};
-        a.q = vec(h, j); a.p = j > 0 ? vec(h, j - 1) : nullptr; a.w1 = h->w_s; a.w2 = full ? h->w2_s : nullptr;
-        a.u = h->u_s; a.v1 = h->V + (size_t)(j + 1) * stride; a.v2 = full ? h->V + (size_t)(j + 2) * stride : nullptr;
-        a.j = j;
-        return a;
-    };
     while (true) {
         while (done < target) {
             if (half_pending >= 0) {      // the iteration goes on past a single step: its vector part (w1 is there on two ghost layers)
                 for (pse_handle *h : act(T)) {
                     int rg[3][2];
                     const int nrg = row_ranges(h, N, 2, rg);
-                    launch_lz_block(block_args(h, half_pending, false), false, h->scal, rg, nrg, h->stream, h->sums_all, T.G, h == h0 ? h->sc_host_dev : nullptr);
+                    launch_lz_block(lz_block_args(h, half_pending, false), false, h->scal, rg, nrg, h->stream, h->sums_all, T.G, h == h0 ? h->sc_host_dev : nullptr);
                 }
                 half_pending = -1;
             }
             const int j = done;
             const bool full = target - done >= 2 && j + 2 <= M_MAX;
             for (pse_handle *h : act(T)) {
-                const LzFuse lz{nullptr, h->partials, h->npart_cap, vec(h, j), j > 0 ? vec(h, j - 1) : nullptr, j > 0 ? h->u_s : nullptr};
+                const LzFuse lz{nullptr, h->partials, h->npart_cap, lz_vec(h, j), lz_vec(h, j - 1), j > 0 ? h->u_s : nullptr};
                 if (j == 0 && !h->w_is_mpsi) return fail(PSE_ERR_NUMERIC, "two-step Lanczos: M psi did not come with the pair list");
                 if (!(j == 0 && h->w_is_mpsi)) {   // w1 = M v_j: own rows + one ghost layer for a block, own rows for a single step
-                    launch_mreal_lanczos(h->pos_s, vec(h, j), h->w_s, rank_rows(h, N, full ? 1 : 0), h->cell_off, h->dbox, h->nc, h->d.rcut,
+                    launch_mreal_lanczos(h->pos_s, lz_vec(h, j), h->w_s, rank_rows(h, N, full ? 1 : 0), h->cell_off, h->dbox, h->nc, h->d.rcut,
                                          h->d.self, h->coef, h->nb, lz, h->scal, nullptr, nullptr, h->stream, VerletList{}, full ? 0 : 3);
                     ++matvecs;
                 } else if (!full) {
@@ -1788,66 +1783,28 @@ static int lanczos_team(pse_team &T, int N, double tol, double scale, int *m_io,
             for (pse_handle *h : act(T)) {
                 int rg[3][2];
                 const int nrg = full ? row_ranges(h, N, 2, rg) : 0;   // a single step derives its scalars only, for now
-                launch_lz_block(block_args(h, j, full), full, h->scal, rg, nrg, h->stream, h->sums_all, T.G, h == h0 ? h->sc_host_dev : nullptr);
+                launch_lz_block(lz_block_args(h, j, full), full, h->scal, rg, nrg, h->stream, h->sums_all, T.G, h == h0 ? h->sc_host_dev : nullptr);
             }
             if (full) done += 2; else { done += 1; half_pending = j; }
         }
-        // (alpha, beta and the norm are already on their way: the update kernels write them to the mapped host buffer as well)
-        HIPCHK(hipEventRecord(h0->ev_scal, h0->stream));
-        if (!hook_done) {   // independent work queued behind the read-back keeps the GPU busy while the host decides
-            hook_done = true;
-            for (pse_handle *h : act(T)) TRY(te(h, PH_LANCZOS));
-            if (before_first_wait) TRY(before_first_wait());
-        }
-        HIPCHK(hipEventSynchronize(h0->ev_scal));
-        if (T.solo >= 0) { m_final = done; t_cur.assign(m_final, 0.0); break; }   // timing only (pse_team_debug_solo)
-        const double *alpha = &sc[LZ_ALPHA], *beta = &sc[LZ_BETA];   // alpha_0 .. alpha_{done-1}, beta_1 .. beta_done
-        if (!(sc[LZ_NORM] > 0.0) || !std::isfinite(sc[LZ_NORM])) {   // psi == 0 -> result 0
-            for (pse_handle *h : act(T)) {
-                HIPCHK(hipMemsetAsync(h->ub_s, 0, (size_t)N * sizeof(double4), h->stream));
-                h->info.lanczos_m = 0; h->info.lanczos_matvecs = matvecs; h->info.lanczos_stepnorm = 0.0;
-            }
-            if (m_io) *m_io = m_in;
-            return 0;
-        }
-        // walk m upward exactly as the reference's while loop does, one vector at a time
-        for (int m = std::max(checked + 1, std::max(m_in - 1, 1)); m <= done && !m_final; ++m) {
-            if (!std::isfinite(alpha[m - 1]) || !std::isfinite(beta[m]))
-                return fail(PSE_ERR_NUMERIC, "Lanczos produced a non-finite coefficient at iteration %d", m - 1);
-            if (!lanczos_sqrt_e1(m, alpha, beta, t_cur))
-                return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve failed at m = %d", m);
-            if (m < done && beta[m] < 1e-8) { m_final = m; stepnorm = 0.0; break; }  // invariant subspace (Brownian.cu:503)
-            if (!t_prev.empty() && (int)t_prev.size() == m - 1) {
-                double s2 = t_cur[m - 1] * t_cur[m - 1];
-                for (int q = 0; q < m - 1; ++q) s2 += (t_cur[q] - t_prev[q]) * (t_cur[q] - t_prev[q]);
-                stepnorm = std::sqrt(s2 / alpha[0]);                               // Brownian.cu:719-724; psi.M.psi/|psi|^2 = alpha_0
-                if (stepnorm <= tol || m >= M_MAX) { m_final = m; break; }
-            }
-            if (m == done && beta[m] < 1e-8) { m_final = m; stepnorm = 0.0; break; }   // the one-step driver sees this with its next sums
-            t_prev = t_cur;
-            checked = m;
-        }
-        if (m_final) break;
-        if (done >= M_MAX) { m_final = M_MAX; break; }
+        TRY(lz_wait_scalars(T, hook_done, before_first_wait));
+        if (T.solo >= 0) { st.m_final = done; break; }   // timing only (pse_team_debug_solo): coefficients zero
+        // alpha_0 .. alpha_{done-1}, beta_1 .. beta_done have arrived
+        LzDecide d{};                     // beta_done arrives with its batch, and the basis holds NORMALISED v_q, except v_0 = psi / |psi|
+        d.first = first; d.have_last_beta = d.normalised = 1;
+        TRY(lz_decide_batch(d, m_in, done, tol, sc, st));
+        if (st.done) break;   // (always at done = M_MAX: the walk reaches that size, where m >= m_max ends it)
+        first = false;
         target = std::min(M_MAX, done + std::max(2, done / 4));
     }
-    if ((int)t_cur.size() != m_final) {
-        if (!lanczos_sqrt_e1(m_final, &sc[LZ_ALPHA], &sc[LZ_BETA], t_cur))
-            return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve failed at m = %d", m_final);
+    if (st.m_final == 0) {
+        if (m_io) *m_io = m_in;
+        return lz_zero_result(T, N, matvecs);
     }
-    if (half_pending >= 0 && m_final > half_pending + 1) return fail(PSE_ERR_NUMERIC, "two-step Lanczos: basis vector %d was never formed", half_pending + 1);
+    if (half_pending >= 0 && st.m_final > half_pending + 1) return fail(PSE_ERR_NUMERIC, "two-step Lanczos: basis vector %d was never formed", half_pending + 1);
     if (before_combine) TRY(before_combine());   // (the far-field velocities must be in place if the combination adds them)
-    for (pse_handle *h : act(T)) {
-        BasisCoef tc{};   // the basis holds NORMALISED v_q here, except v_0 = psi / |psi|
-        for (int q = 0; q < m_final; ++q) tc.t[q] = q == 0 ? t_cur[q] / sc[LZ_NORM] : t_cur[q];
-        int lo, hi;
-        row_range(h, N, lo, hi);
-        launch_basis_combine(h->psi_s, h->V, stride, tc, m_final, h->scal, scale, 1, h->ub_s, lo, hi, h->stream, h->sink);   // Brownian.cu:716,739
-        h->tail_done = h->sink.on;
-        h->info.lanczos_m = m_final; h->info.lanczos_matvecs = matvecs; h->info.lanczos_stepnorm = stepnorm;
-        h->info.lanczos_exchanges = n_exchanges;
-    }
-    if (m_io) *m_io = m_final;
+    lz_combine(T, N, scale, st, matvecs, n_exchanges);
+    if (m_io) *m_io = st.m_final;
     return 0;
 }
 
@@ -2068,21 +2025,12 @@ static LocalRegions local_regions(const pse_handle *h) {
 // on the device only) and go right; they arrive in the ghost regions of the neighbours' w1, w2.
 static int lanczos_local(pse_team &T, double tol, int *m_io, WavePump *pump) {
     pse_handle *h0 = T.m[0];
-    const size_t stride = h0->n_pad;
-    const int m_in = std::min(std::max(m_io ? *m_io : 2, 1), M_MAX), target = std::max(m_in, 2);
+    const int m_in = lz_m_in(m_io), target = std::max(m_in, 2);
     const int extra_blocks = ((T.lz_extra >= 0 ? T.lz_extra : h0->tun.lz_extra) + 1) / 2;
     if (target + 2 * extra_blocks > M_MAX || !lz_decide_supported(target + 2 * extra_blocks))
         return fail(PSE_ERR_INVALID, "owned-particle step: starting count %d of the Lanczos iteration is beyond what the device-side decision takes", m_in);
     int n_exchanges = 0, matvecs = 0, done = 0, half_pending = -1;
-    auto vec = [&](pse_handle *h, int q) { return q == 0 ? h->psi_s : h->V + (size_t)q * stride; };
-    auto block_args = [&](pse_handle *h, int j, bool full) {
-        LzBlockArgs a{};
-        a.q = vec(h, j); a.p = j > 0 ? vec(h, j - 1) : nullptr; a.w1 = h->w_s; a.w2 = full ? h->w2_s : nullptr;
-        a.u = h->u_s; a.v1 = h->V + (size_t)(j + 1) * stride; a.v2 = full ? h->V + (size_t)(j + 2) * stride : nullptr;
-        a.j = j;
-        return a;
-    };
-    auto fuse = [&](pse_handle *h, int j) { return LzFuse{nullptr, h->partials, h->npart_cap, vec(h, j), j > 0 ? vec(h, j - 1) : nullptr, j > 0 ? h->u_s : nullptr}; };
+    auto fuse = [&](pse_handle *h, int j) { return LzFuse{nullptr, h->partials, h->npart_cap, lz_vec(h, j), lz_vec(h, j - 1), j > 0 ? h->u_s : nullptr}; };
     auto exchange = [&](bool full) -> int {
         if (pump) TRY(pump->upto(n_exchanges));
         ++n_exchanges;
@@ -2108,7 +2056,7 @@ static int lanczos_local(pse_team &T, double tol, int *m_io, WavePump *pump) {
             if (j == 0) {
                 if (!h->w_is_mpsi) return fail(PSE_ERR_NUMERIC, "owned-particle step: M psi did not come with the pair list");
             } else {   // w1 = M v_j on the own rows + the adjacent ghost layers
-                launch_mreal_lanczos(h->pos_s, vec(h, j), h->w_s, RowMap{}, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb, fuse(h, j),
+                launch_mreal_lanczos(h->pos_s, lz_vec(h, j), h->w_s, RowMap{}, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb, fuse(h, j),
                                      h->scal, nullptr, nullptr, h->stream, VerletList{}, 0, gate,
                                      DevRowArgs{&R->own1, R, h->loc.stage_w1, h->loc.rows_cap, h->loc.g.c_g});
                 ++matvecs;
@@ -2121,21 +2069,21 @@ static int lanczos_local(pse_team &T, double tol, int *m_io, WavePump *pump) {
         }
         TRY(exchange(true));
         for (pse_handle *h : act(T))
-            launch_lz_block(block_args(h, j, true), true, h->scal, nullptr, 0, h->stream, h->sums_all, T.G, h->sc_host_dev, &h->loc.rows->all,
+            launch_lz_block(lz_block_args(h, j, true), true, h->scal, nullptr, 0, h->stream, h->sums_all, T.G, h->sc_host_dev, &h->loc.rows->all,
                             h->loc.rows_cap, false, gated ? &h->lz_state->done : nullptr);
         return 0;
     };
     auto single = [&](int j, bool gated) -> int {   // an odd starting count ends on one iteration: scalars now, vectors only if the iteration goes on
         for (pse_handle *h : act(T)) {
             const LocalRows *R = h->loc.rows;
-            launch_mreal_lanczos(h->pos_s, vec(h, j), h->w_s, RowMap{}, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb, fuse(h, j), h->scal,
+            launch_mreal_lanczos(h->pos_s, lz_vec(h, j), h->w_s, RowMap{}, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb, fuse(h, j), h->scal,
                                  nullptr, nullptr, h->stream, VerletList{}, 3, gated ? &h->lz_state->done : nullptr,
                                  DevRowArgs{&R->own, R, h->loc.stage_w1, h->loc.g.c_own, h->loc.g.c_g});
             ++matvecs;
         }
         TRY(exchange(false));
         for (pse_handle *h : act(T))
-            launch_lz_block(block_args(h, j, false), false, h->scal, nullptr, 0, h->stream, h->sums_all, T.G, h->sc_host_dev, &h->loc.rows->all,
+            launch_lz_block(lz_block_args(h, j, false), false, h->scal, nullptr, 0, h->stream, h->sums_all, T.G, h->sc_host_dev, &h->loc.rows->all,
                             h->loc.rows_cap, true, gated ? &h->lz_state->done : nullptr);
         half_pending = j;
         return 0;
@@ -2157,7 +2105,7 @@ static int lanczos_local(pse_team &T, double tol, int *m_io, WavePump *pump) {
     for (int x = 0; x < extra_blocks; ++x) {
         if (half_pending >= 0) {   // the vector part of the single step (its sums are still in place)
             for (pse_handle *h : act(T))
-                launch_lz_block(block_args(h, half_pending, false), false, h->scal, nullptr, 0, h->stream, h->sums_all, T.G, h->sc_host_dev,
+                launch_lz_block(lz_block_args(h, half_pending, false), false, h->scal, nullptr, 0, h->stream, h->sums_all, T.G, h->sc_host_dev,
                                 &h->loc.rows->all, h->loc.rows_cap, false, &h->lz_state->done);
             half_pending = -1;
         }
@@ -2455,20 +2403,13 @@ extern "C" int pse_debug_vq_roundtrip(int n, const double *rows_host, double *ou
 static_assert(PSE_DEBUG_LZ_NSCAL == LZ_NSCAL && LZ_HOST_OPEN == LZ_HOST_M + 4 && LZ_HOST_OPEN < LZ_NSCAL, "pse_debug_lz_decide: layout of the scalars");
 extern "C" int pse_debug_lz_decide_supported(int m_hi) { return lz_decide_supported(m_hi) ? 1 : 0; }
 extern "C" int pse_debug_lz_decide(const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, double open0, pse_debug_lz_outcome *out) {
-    if (!scal_host || !dec || !out) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: null argument");
-    if (n_dec < 1 || n_dec > 40) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: %d decisions outside [1, 40]", n_dec);
-    if (!dec[0].first) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: the first decision must reset the state (first = 1)");
+    if (int rc = lz_decisions_validate("pse_debug_lz_decide", scal_host, n_dec, dec, out)) return rc;
     // everything the kernel sizes its LDS and its loops by is checked HERE: no launch with more than the launcher asked for
     for (int k = 0; k < n_dec; ++k) {
         const pse_debug_lz_decision &d = dec[k];
         if (!lz_decide_supported(d.m_hi)) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: m_hi = %d is not supported", k, d.m_hi);
-        if (d.m_lo < 1 || (d.m_lo != d.m_hi && d.m_lo != d.m_hi - 1))
+        if (d.m_lo < d.m_hi - 1)
             return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: m_lo = %d is not m_hi or m_hi - 1 (m_hi = %d)", k, d.m_lo, d.m_hi);
-        if (d.done_iters < d.m_hi || d.done_iters > M_MAX)
-            return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: done_iters = %d outside [m_hi, %d]", k, d.done_iters, M_MAX);
-        if (d.pending_beta < 0 || d.pending_beta > d.m_hi)
-            return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: pending_beta = %d outside [0, m_hi]", k, d.pending_beta);
-        if (d.m_max > M_MAX) return fail(PSE_ERR_INVALID, "pse_debug_lz_decide: decision %d: m_max = %d above %d", k, d.m_max, M_MAX);
     }
     double *scal = nullptr, *sch = nullptr;
     LzState *st = nullptr;
@@ -2481,19 +2422,13 @@ extern "C" int pse_debug_lz_decide(const double *scal_host, int n_dec, const pse
     if (e == hipSuccess) e = hipMemcpy(sch, mirror.data(), LZ_NSCAL * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(st, 0xff, sizeof(LzState));   // NaN bytes: only the reset under `first` makes the state valid
     for (int k = 0; k < n_dec && e == hipSuccess; ++k) {
-        LzDecide d{};
-        d.m_lo = dec[k].m_lo; d.m_hi = dec[k].m_hi; d.done_iters = dec[k].done_iters; d.have_last_beta = dec[k].have_last_beta;
-        d.pending_beta = dec[k].pending_beta; d.first = dec[k].first; d.last = dec[k].last; d.normalised = dec[k].normalised;
-        d.m_max = dec[k].m_max; d.tol = dec[k].tol;
-        launch_lz_decide(d, scal, st, sch, dec[k].seq, nullptr);
+        launch_lz_decide(lz_decision(dec[k]), scal, st, sch, dec[k].seq, nullptr);
         e = hipGetLastError();
         LzState hs;
         if (e == hipSuccess) e = hipMemcpy(&hs, st, sizeof(LzState), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(out[k].mirror, sch + LZ_HOST_M, 5 * sizeof(double), hipMemcpyDeviceToHost);
         if (e != hipSuccess) break;
-        out[k].done = hs.done; out[k].m_final = hs.m_final; out[k].checked = hs.checked; out[k].status = hs.status; out[k].stepnorm = hs.stepnorm;
-        std::copy(hs.t_prev, hs.t_prev + 104, out[k].t_prev);
-        std::copy(hs.coef, hs.coef + 104, out[k].coef);
+        lz_outcome(hs, &out[k]);
     }
     (void)hipFree(scal); (void)hipFree(sch); (void)hipFree(st);
     if (e != hipSuccess) return fail(PSE_ERR_HIP, "pse_debug_lz_decide: %s", hipGetErrorString(e));

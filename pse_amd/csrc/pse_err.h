@@ -18,6 +18,13 @@ void fill_info(const Derived &d, pse_info *o);
 // coarsest of the three grid spacings (an override the reference's rule cannot produce) -- shared by pse_create, pse_set_box,
 // pse_host_select_params and the sanitizer build's stand-in, so that all agree on which configurations are valid
 int gaussian_fits(const Derived &d, double hx, double hy, double hz);
+// 0, or PSE_ERR_INVALID with a message under the name `who`: what pse_host_lz_decide and pse_debug_lz_decide refuse alike -- a null
+// array, n_dec outside [1, 40], a first decision without `first`, and per decision anything but 1 <= m_lo <= m_hi <= done_iters <=
+// M_MAX, pending_beta in [0, m_hi], m_max <= M_MAX (the device entry point adds what its kernel is sized for)
+int lz_decisions_validate(const char *who, const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, const void *out);
+// what the two entry points hand on and hand back: a decision of the C-ABI as the contract's, a state as the C-ABI's outcome (mirror aside)
+LzDecide lz_decision(const pse_debug_lz_decision &d);
+void lz_outcome(const LzState &st, pse_debug_lz_outcome *o);
 // 0, or PSE_ERR_INVALID with a message: the argument checks of pse_pair_repulsion (virial = false) and pse_pair_repulsion_virial
 // (virial = true) behind the null-handle check, with the handle's rcut, n_max and n_slabs -- shared by the device library and the
 // sanitizer build's stand-in, in the order include/pse_amd.h promises

@@ -67,4 +67,40 @@ bool tridiag_eigen(int n, std::vector<double> &d, std::vector<double> &e, std::v
 // t = T^{1/2} e_1 for the Lanczos tridiagonal T(alpha[0..m), beta[1..m)) (PSEv1/Brownian.cu:563-582).
 bool lanczos_sqrt_e1(int m, const double *alpha, const double *beta, std::vector<double> &t);
 
+// ---- the convergence decision of the Lanczos iteration: ONE contract, LzDecide in, LzState out --------------------------------------
+// What ends the iteration is the reference's while loop (its breakdown test, PSEv1/Brownian.cu:503, the eigen-solve and the step-norm
+// test, PSEv1/Brownian.cu:540-582,606-724): walk m upward one size at a time and stop once the step norm is below the tolerance.  A
+// driver issues one decision per batch of iterations; the state carries the walk from one decision to the next.  Two implementations:
+// k_lz_decide (pse_vectors.hip) for the queue-only drivers, which may not wait for the host, and lz_decide_host (pse_params.cpp) for
+// the host-checked ones.
+constexpr int M_MAX = 100;   // Lanczos basis cap (PSEv1/Brownian.cu:397)
+constexpr int LZ_ALPHA = 0, LZ_BETA = 128, LZ_NORM = 256;   // slots of the scalars (device doubles, and the host's copy): alpha_j, beta_j, the norm of psi
+struct LzState {
+    int done;            // the iteration has ended: m_final and coef are valid; later iteration kernels leave at once
+    int m_final;
+    int checked;         // t_prev holds T^{1/2} e_1 of this size (0: nothing yet)
+    int status;          // 0 converged, 1 the queued iterations ran out first (result from the last size checked), 2 non-finite coefficient / eigen-solve failure
+    double stepnorm;
+    double t_prev[104];
+    double coef[104];    // coefficients of the basis vectors in the final combination (t divided by the norms the basis carries)
+};
+struct LzDecide {
+    int m_lo, m_hi;      // sizes to check (the device: at most two, m_lo = m_hi - 1 or m_hi)
+    int done_iters;      // iterations whose alpha exists; one-step driver: beta[done_iters] does not exist yet
+    int have_last_beta;  // 1: beta[done_iters] exists as well (two-step driver of a team)
+    int pending_beta;    // > 0: first test beta[pending_beta] for breakdown (it arrived with this batch)
+    int first;           // first decision of a call: reset the state
+    int last;            // last queued decision: if still open, end the iteration at the last size checked (status 1)
+    int normalised;      // the basis holds normalised v_q for q >= 1 (two-step driver); else unnormalised x_q (divide by beta_q)
+    int m_max;
+    double tol;
+};
+// The host twin of k_lz_decide, its body line for line, on the host's copy of the scalars; every size of m_lo .. m_hi is solved by
+// lanczos_sqrt_e1 (host batches grow, so the range may hold any number of sizes).  Both failures are status 2 in the state; the
+// return value tells them apart and `at` names the place: the iteration j of the coefficient, or the size m of the eigen-solve.
+// One value differs from the device's: after a failure before any size was solved coef[0] is NaN here, whatever the solver's buffer
+// held there -- the host drivers never read it: they return an error on either failure.
+enum LzFailure { LZ_OK = 0, LZ_NONFINITE, LZ_EIGEN_FAILED };
+LzFailure lz_decide_host(const LzDecide &d, const double *scal, LzState &st, int *at);
+
 }  // namespace pse

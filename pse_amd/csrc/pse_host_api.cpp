@@ -1,6 +1,7 @@
 // The part of the C-ABI (include/pse_amd.h) that never touches a device: the error text, the parameter rule of
-// Stokes::setParams without a handle (PSEv1/Stokes.cc:129-236,319) and the Lanczos tridiagonal square root
-// (LAPACKE_spteqr + the host loops at PSEv1/Brownian.cu:540-582).  Plain C++: linked into libpse_amd.so, and -- with
+// Stokes::setParams without a handle (PSEv1/Stokes.cc:129-236,319), the Lanczos tridiagonal square root
+// (LAPACKE_spteqr + the host loops at PSEv1/Brownian.cu:540-582) and the host-checked drivers' decision on given
+// coefficients (lz_decide_host).  Plain C++: linked into libpse_amd.so, and -- with
 // pse_params.cpp and a stub of the device entry points -- into the sanitizer build that the CPU tests run against.
 #include <algorithm>
 #include <cmath>
@@ -47,6 +48,35 @@ int gaussian_fits(const Derived &d, double hx, double hy, double hz) {
         return fail(PSE_ERR_INVALID, "grid spacings (%g, %g, %g) too unequal for the spreading Gaussian of P = %d points, eta = %g: "
                     "exp(+-%.0f) over its support on the coarsest axis", hx, hy, hz, d.P, d.eta, worst);
     return 0;
+}
+
+int lz_decisions_validate(const char *who, const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, const void *out) {
+    if (!scal_host || !dec || !out) return fail(PSE_ERR_INVALID, "%s: null argument", who);
+    if (n_dec < 1 || n_dec > 40) return fail(PSE_ERR_INVALID, "%s: %d decisions outside [1, 40]", who, n_dec);
+    if (!dec[0].first) return fail(PSE_ERR_INVALID, "%s: the first decision must reset the state (first = 1)", who);
+    for (int k = 0; k < n_dec; ++k) {
+        const pse_debug_lz_decision &d = dec[k];
+        if (d.m_lo < 1 || d.m_lo > d.m_hi) return fail(PSE_ERR_INVALID, "%s: decision %d: m_lo = %d outside [1, m_hi = %d]", who, k, d.m_lo, d.m_hi);
+        if (d.done_iters < d.m_hi || d.done_iters > M_MAX)
+            return fail(PSE_ERR_INVALID, "%s: decision %d: done_iters = %d outside [m_hi, %d]", who, k, d.done_iters, M_MAX);
+        if (d.pending_beta < 0 || d.pending_beta > d.m_hi)
+            return fail(PSE_ERR_INVALID, "%s: decision %d: pending_beta = %d outside [0, m_hi]", who, k, d.pending_beta);
+        if (d.m_max > M_MAX) return fail(PSE_ERR_INVALID, "%s: decision %d: m_max = %d above %d", who, k, d.m_max, M_MAX);
+    }
+    return 0;
+}
+
+LzDecide lz_decision(const pse_debug_lz_decision &d) {
+    LzDecide a{};
+    a.m_lo = d.m_lo; a.m_hi = d.m_hi; a.done_iters = d.done_iters; a.have_last_beta = d.have_last_beta; a.pending_beta = d.pending_beta;
+    a.first = d.first; a.last = d.last; a.normalised = d.normalised; a.m_max = d.m_max; a.tol = d.tol;
+    return a;
+}
+
+void lz_outcome(const LzState &st, pse_debug_lz_outcome *o) {
+    o->done = st.done; o->m_final = st.m_final; o->checked = st.checked; o->status = st.status; o->stepnorm = st.stepnorm;
+    std::copy(st.t_prev, st.t_prev + 104, o->t_prev);
+    std::copy(st.coef, st.coef + 104, o->coef);
 }
 
 static int count_in_range(unsigned n_max, unsigned N) {
@@ -760,6 +790,25 @@ extern "C" int pse_host_lanczos_sqrt_e1(int m, const double *alpha, const double
     std::vector<double> tv;
     if (!lanczos_sqrt_e1(m, alpha, beta, tv)) return fail(PSE_ERR_NUMERIC, "tridiagonal eigen-solve did not converge");
     std::copy(tv.begin(), tv.end(), t);
+    return 0;
+}
+
+extern "C" int pse_host_lz_decide(const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, double open0, pse_debug_lz_outcome *out) {
+    if (int rc = lz_decisions_validate("pse_host_lz_decide", scal_host, n_dec, dec, out)) return rc;
+    LzState st;
+    memset(&st, 0xff, sizeof st);   // NaN bytes: only the reset under `first` makes the state valid
+    double mirror[5] = {0.0, 0.0, 0.0, 0.0, open0};   // m, step norm, status, seq, open calls: what the device's decision leaves the host
+    for (int k = 0; k < n_dec; ++k) {
+        const bool was_done = !dec[k].first && st.done;
+        int at = 0;
+        (void)lz_decide_host(lz_decision(dec[k]), scal_host, st, &at);   // (a failure is status 2 in the state: what the caller asked to see)
+        if (st.done && !was_done) {
+            mirror[0] = (double)st.m_final; mirror[1] = st.stepnorm; mirror[2] = (double)st.status; mirror[3] = dec[k].seq;
+            if (st.status != 0) mirror[4] += 1.0;
+        }
+        lz_outcome(st, &out[k]);
+        std::copy(mirror, mirror + 5, out[k].mirror);
+    }
     return 0;
 }
 

@@ -1,6 +1,6 @@
-// Host-side set-up of the PSE engine: parameter selection, real-space function table, and the small
-// tridiagonal eigen-solver the Lanczos driver needs.  Replaces Stokes::setParams
-// (PSEv1/Stokes.cc:129-424) and LAPACKE_spteqr (PSEv1/Brownian.cu:540,673).
+// Host-side set-up of the PSE engine: parameter selection, real-space function table, the small tridiagonal
+// eigen-solver the Lanczos drivers need and the decision that ends their iteration.  Replaces Stokes::setParams
+// (PSEv1/Stokes.cc:129-424), LAPACKE_spteqr (PSEv1/Brownian.cu:540,673) and the while loop around it (Brownian.cu:606-724).
 #include "pse_host.h"
 
 #include <algorithm>
@@ -211,6 +211,56 @@ bool lanczos_sqrt_e1(int m, const double *alpha, const double *beta, std::vector
         for (int i = 0; i < m; ++i) t[i] += z[(size_t)i * m + j] * s;
     }
     return true;
+}
+
+// The Lanczos decision on the host (contract and return value: pse_host.h), statement by statement what thread 0 of k_lz_decide
+// does behind the eigen-solves.  The step norm is summed as it always was here -- t[m-1]^2 first, then the differences in order of
+// q -- so m, the step norm and the coefficients of a call do not depend on how its batches were cut.
+LzFailure lz_decide_host(const LzDecide &a, const double *scal, LzState &st, int *at) {
+    if (a.first) { st.done = 0; st.m_final = 0; st.checked = 0; st.status = 0; st.stepnorm = 1.0; }
+    else if (st.done) return LZ_OK;
+    const double *alpha = scal + LZ_ALPHA, *beta = scal + LZ_BETA;
+    const double norm = scal[LZ_NORM];
+    int m_final = 0, status = 0, checked = st.checked;
+    double stepnorm = st.stepnorm;
+    std::vector<double> t_cur;
+    const double *t_fin = nullptr;
+    LzFailure failure = LZ_OK;
+    if (!(norm > 0.0) || !std::isfinite(norm)) {                  // psi == 0: the result is zero
+        m_final = -1;
+    } else if (a.pending_beta > 0 && beta[a.pending_beta] < 1e-8) {   // |x_m| of the vector the previous batch ended on: invariant subspace
+        m_final = a.pending_beta; stepnorm = 0.0; t_fin = st.t_prev;
+    } else {
+        for (int m = a.m_lo; m <= a.m_hi && !m_final; ++m) {      // walk m upward as the reference's while loop does (PSEv1/Brownian.cu:606-724)
+            const bool have_beta = m < a.done_iters || a.have_last_beta;
+            if (!std::isfinite(alpha[m - 1]) || (have_beta && !std::isfinite(beta[m]))) { failure = LZ_NONFINITE; *at = m - 1; }
+            else if (!lanczos_sqrt_e1(m, alpha, beta, t_cur)) { failure = LZ_EIGEN_FAILED; *at = m; }
+            if (failure) { m_final = std::max(checked, 1); status = 2; t_fin = checked ? st.t_prev : nullptr; break; }
+            if (m < a.done_iters && beta[m] < 1e-8) { m_final = m; stepnorm = 0.0; t_fin = t_cur.data(); break; }   // invariant subspace (Brownian.cu:503)
+            if (checked == m - 1 && checked > 0) {
+                double s2 = t_cur[m - 1] * t_cur[m - 1];
+                for (int q = 0; q < m - 1; ++q) s2 += (t_cur[q] - st.t_prev[q]) * (t_cur[q] - st.t_prev[q]);
+                stepnorm = std::sqrt(s2 / alpha[0]);               // Brownian.cu:719-724; psi.M.psi / |psi|^2 = alpha_0
+                if (stepnorm <= a.tol || m >= a.m_max) { m_final = m; t_fin = t_cur.data(); break; }
+            }
+            if (a.have_last_beta && m == a.done_iters && beta[m] < 1e-8) { m_final = m; stepnorm = 0.0; t_fin = t_cur.data(); break; }
+            std::copy(t_cur.begin(), t_cur.end(), st.t_prev);
+            checked = m;
+        }
+        if (!m_final && (a.last || a.done_iters >= a.m_max)) {     // nothing more is queued: end with what there is
+            m_final = checked; t_fin = st.t_prev; status = a.done_iters >= a.m_max ? 0 : 1;
+        }
+    }
+    st.checked = checked;
+    st.stepnorm = stepnorm;
+    if (m_final) {
+        const int m = std::max(m_final, 0);
+        // (status 2 before any size was solved: the one coefficient has no value -- the device leaves whatever its solver held)
+        for (int q = 0; q < m; ++q) st.coef[q] = t_fin ? t_fin[q] / (q == 0 ? norm : (a.normalised ? 1.0 : beta[q])) : std::nan("");
+        st.m_final = m; st.status = status;
+        st.done = 1;
+    }
+    return failure;
 }
 
 }  // namespace pse

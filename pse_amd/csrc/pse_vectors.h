@@ -1,5 +1,6 @@
 // Launch wrappers of the vector kernels (defined in pse_vectors.hip).  All take the stream explicitly.
 #pragma once
+#include "pse_host.h"
 #include "pse_kernels.h"
 
 namespace pse {
@@ -7,8 +8,8 @@ namespace pse {
 // ---- vector kernels (K10-K14) ----------------------------------------------------------------------------
 void launch_psi(double4 *psi_s, const unsigned *tag_s, int N, uint32_t seed, uint32_t timestep, hipStream_t s,
                 CellRanges need = CellRanges{}, const int *cell_off = nullptr);
-// scal layout (device doubles): [0..127] alpha, [128..255] beta, [256] psi norm, [257] scratch
-constexpr int LZ_ALPHA = 0, LZ_BETA = 128, LZ_NORM = 256, LZ_TMP = 257, LZ_UU = 272, LZ_NSCAL = 400;   // TMP: 3 sums (one-step) or the LZ_NGRAM sums of a two-step block; UU[j] = |M v_{j-1}|^2 of the block that starts at j
+// scal layout (device doubles): [0..127] alpha, [128..255] beta, [256] psi norm (LZ_ALPHA, LZ_BETA, LZ_NORM: pse_host.h), [257] scratch
+constexpr int LZ_TMP = 257, LZ_UU = 272, LZ_NSCAL = 400;   // TMP: 3 sums (one-step) or the LZ_NGRAM sums of a two-step block; UU[j] = |M v_{j-1}|^2 of the block that starts at j
 constexpr int LZ_NPART = 1024;  // partial-sum slots
 // scal[LZ_TMP + q] = sum of partials[q * cap .. q * cap + npart), q < nsum, in a fixed order; stop (nullable): leave at once if *stop != 0
 void launch_lz_reduce(const double *partials, int npart, int cap, int nsum, double *scal, const int *stop, hipStream_t s);
@@ -57,27 +58,8 @@ void launch_lz_update(const double4 *xin, const double4 *y, const double4 *xprev
 // LAPACKE_spteqr + host loops, PSEv1/Brownian.cu:540-582, and its step-norm test, PSEv1/Brownian.cu:673-724): one workgroup solves
 // the tridiagonal eigenproblems of the sizes to be checked (one wavefront each, implicit QL as tridiag_eigen in pse_params.cpp),
 // walks m upward exactly as the host does and, once the step norm is below the tolerance, closes the gate `done` that every later
-// kernel of the iteration reads, and leaves the coefficients of the final combination for k_basis_combine.
-struct LzState {
-    int done;            // the iteration has ended: m_final and coef are valid; later iteration kernels leave at once
-    int m_final;
-    int checked;         // t_prev holds T^{1/2} e_1 of this size (0: nothing yet)
-    int status;          // 0 converged, 1 the queued iterations ran out first (result from the last size checked), 2 non-finite coefficient / eigen-solve failure
-    double stepnorm;
-    double t_prev[104];
-    double coef[104];    // coefficients of the basis vectors in the final combination (t divided by the norms the basis carries)
-};
-struct LzDecide {
-    int m_lo, m_hi;      // sizes to check, at most two (m_lo = m_hi - 1 or m_hi)
-    int done_iters;      // iterations whose alpha exists; one-step driver: beta[done_iters] does not exist yet
-    int have_last_beta;  // 1: beta[done_iters] exists as well (two-step driver of a team)
-    int pending_beta;    // > 0: first test beta[pending_beta] for breakdown (it arrived with this batch)
-    int first;           // first decision of a call: reset the state
-    int last;            // last queued decision: if still open, end the iteration at the last size checked (status 1)
-    int normalised;      // the basis holds normalised v_q for q >= 1 (two-step driver); else unnormalised x_q (divide by beta_q)
-    int m_max;
-    double tol;
-};
+// kernel of the iteration reads, and leaves the coefficients of the final combination for k_basis_combine.  LzState and LzDecide,
+// the contract it shares with the host drivers' lz_decide_host: pse_host.h.
 constexpr int LZ_HOST_M = 380, LZ_HOST_STEPNORM = 381, LZ_HOST_STATUS = 382, LZ_HOST_SEQ = 383, LZ_HOST_OPEN = 384;   // (OPEN: calls so far that ended with status != 0)   // slots of the host mirror (sch) the decision writes
 void launch_lz_decide(const LzDecide &d, double *scal, LzState *st, double *sch, double seq, hipStream_t s);
 bool lz_decide_supported(int m_hi);   // the eigenvectors of both sizes fit the LDS of one workgroup

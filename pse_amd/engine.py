@@ -88,6 +88,16 @@ def debug_lz_decide(scal, decisions, open0=0.0):
     the device scalars (400 doubles: alpha at 0, beta at 128, the norm at 256); decisions: dicts of LZ_DECISION_FIELDS (missing
     ones 0) in the order a driver issues them; open0: the host mirror's count of open calls before the first.  Returns one dict per
     launch: done, m_final, checked, status, stepnorm, t_prev[104], coef[104] and mirror (dict of LZ_MIRROR_FIELDS)."""
+    return _lz_decide("pse_debug_lz_decide", scal, decisions, open0)
+
+
+def host_lz_decide(scal, decisions, open0=0.0):
+    """The Lanczos decision of the host-checked drivers on given coefficients (pse_host_lz_decide; no device): arguments and result
+    as debug_lz_decide; a decision may check any number of sizes."""
+    return _lz_decide("pse_host_lz_decide", scal, decisions, open0)
+
+
+def _lz_decide(entry, scal, decisions, open0):
     import numpy as np
     lib = _lib.load()
     s = np.ascontiguousarray(scal, dtype=np.float64)
@@ -102,7 +112,7 @@ def debug_lz_decide(scal, decisions, open0=0.0):
         for name in LZ_DECISION_FIELDS:
             setattr(dec[k], name, (float if name in ("tol", "seq") else int)(d.get(name, 0)))
     out = (_lib.pse_debug_lz_outcome * max(n, 1))()
-    _lib.check(lib.pse_debug_lz_decide(s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, dec, float(open0), out))
+    _lib.check(getattr(lib, entry)(s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, dec, float(open0), out))
     return [dict(done=o.done, m_final=o.m_final, checked=o.checked, status=o.status, stepnorm=o.stepnorm,
                  t_prev=np.array(o.t_prev), coef=np.array(o.coef), mirror=dict(zip(LZ_MIRROR_FIELDS, o.mirror))) for o in out[:n]]
 

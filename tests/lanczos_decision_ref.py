@@ -128,9 +128,10 @@ DECISION_DEFAULTS = dict(m_lo=0, m_hi=0, done_iters=0, have_last_beta=0, pending
 
 
 def walk(dec, alpha, beta, norm, state, mirror, t_of):
-    """One decision, as the reference's while loop prescribes it (PSEv1/Brownian.cu:503, 606-724, in the form the host driver
-    `lanczos` of pse_capi.hip restates it) with t_of(m) in place of an eigen-solver: t_of returns T_m^{1/2} e_1 as a sequence of m
-    numbers, or None where no solver can succeed (a non-finite entry inside T_m).
+    """One decision, as the reference's while loop prescribes it (PSEv1/Brownian.cu:503, 606-724) under the contract LzDecide ->
+    LzState of pse_host.h, which the device's k_lz_decide and the host drivers' lz_decide_host both implement, with t_of(m) in place
+    of an eigen-solver: t_of returns T_m^{1/2} e_1 as a sequence of m numbers, or None where no solver can succeed (a non-finite
+    entry inside T_m).
 
     state: None before the first decision, else what the previous call returned; mirror: dict of MIRROR_FIELDS.  Returns the new
     (state, mirror); state = dict(done, m_final, status, checked, stepnorm, t_prev, coef): t_prev the vector of size `checked`, coef
@@ -197,7 +198,7 @@ def stepnorm_bound(m, e_ref, alpha0):
     return (math.sqrt(m) + math.sqrt(m - 1)) * FACTOR * e_ref / math.sqrt(alpha0)
 
 
-# ---- the sequences of decisions the two drivers issue (pse_capi.hip) ---------------------------------------------------------------------
+# ---- the sequences of decisions the four drivers issue (pse_capi.hip) --------------------------------------------------------------------
 def queued_decisions(m_in, extra, tol, m_max=100, seq=1.0):
     """lanczos_queued: the pair (m_in - 1, m_in), then `extra` gated single sizes, each with the beta that arrived pending."""
     target = max(m_in, 2)
@@ -220,6 +221,19 @@ def local_decisions(m_in, extra_blocks, tol, m_max=100, seq=1.0):
         out.append(dict(m_lo=done + 1, m_hi=done + 2, done_iters=done + 2, have_last_beta=1, first=0, last=int(x == extra_blocks - 1),
                         normalised=1, m_max=m_max, tol=tol, seq=seq))
         done += 2
+    return out
+
+
+def host_decisions(m_in, batches, two_step, tol, m_max=100, seq=1.0):
+    """lanczos (one iteration per exchange) and lanczos_team (two_step), host-checked: batches up to max(m_in, 2), then up to
+    done + max(2, done / 4), not beyond m_max; each decision checks every size not yet checked, from m_in - 1 on.  The one-step driver
+    gets beta[done] with its next batch (pending_beta); the two-step driver has it, and a normalised basis."""
+    out, done, target = [], 0, max(m_in, 2)
+    for k in range(batches):
+        d = dict(m_lo=max(done + 1, m_in - 1, 1), m_hi=target, done_iters=target, first=int(k == 0), last=0, m_max=m_max, tol=tol, seq=seq)
+        d.update(dict(have_last_beta=1, normalised=1) if two_step else dict(pending_beta=done))
+        out.append(d)
+        done, target = target, min(m_max, target + max(2, target // 4))
     return out
 
 
@@ -329,3 +343,44 @@ class Fixture:
 @functools.lru_cache(maxsize=None)
 def fixture():
     return Fixture()
+
+
+# ---- the checker: an implementation of the contract against the reference walk, after every decision ---------------------------------
+def bits(o):
+    """Everything a launch leaves, as bytes: for 'this launch changed nothing'."""
+    return (o["done"], o["m_final"], o["checked"], o["status"], np.float64(o["stepnorm"]).tobytes(), o["t_prev"].tobytes(),
+            o["coef"].tobytes(), tuple(np.float64(o["mirror"][k]).tobytes() for k in MIRROR_FIELDS))
+
+
+def run_case(fx, case, decide, open0=None):
+    """decide: pse_amd.debug_lz_decide (the device) or pse_amd.host_lz_decide (the host drivers' twin)."""
+    alpha, beta, norm, _, scal, _ = fx.case_inputs(case)
+    open0 = case["open0"] if open0 is None else open0
+    ref = fx.case_reference(dict(case, open0=open0))
+    out = decide(scal, case["decisions"], open0)
+    fam, a0 = case["family"], fx.coeffs(case["family"], 1)[0][0]
+    for k, (d, o, (r, rm)) in enumerate(zip(case["decisions"], out, ref)):
+        where = (case["name"], k)
+        assert (o["done"], o["m_final"], o["status"], o["checked"]) == (r["done"], r["m_final"], r["status"], r["checked"]), where
+        if k > 0 and ref[k - 1][0]["done"]:
+            assert bits(o) == bits(out[k - 1]), where               # after done: a further decision leaves state and mirror as they are
+        e_step = max([fx.e_ref(fam, m) for m in range(max(d["m_lo"] - 1, 1), d["m_hi"] + 1)])
+        bound = stepnorm_bound(d["m_hi"], e_step, a0)
+        assert abs(o["stepnorm"] - float(r["stepnorm"])) <= bound, where + (o["stepnorm"], float(r["stepnorm"]), bound)
+        if r["checked"] and np.isfinite(norm) and norm > 0:
+            c = r["checked"]
+            assert max_abs_err(o["t_prev"][:c], r["t_prev"]) <= FACTOR * fx.e_ref(fam, c), where
+            assert np.isnan(o["t_prev"][c:]).all(), where
+        m = r["m_final"]
+        if r["done"] and r["coef"] is not None:
+            e = fx.e_ref(fam, m)
+            for q in range(m):
+                assert abs(o["coef"][q] - float(r["coef"][q])) <= FACTOR * e / coef_divisor(d, beta, norm, q), where + (q,)
+        if r["done"]:
+            assert np.isnan(o["coef"][m:]).all(), where              # nothing beyond m_final was written
+        for f in ("m", "status", "seq", "open"):
+            assert o["mirror"][f] == float(rm[f]), where + (f, o["mirror"][f], float(rm[f]))
+        assert abs(o["mirror"]["stepnorm"] - float(rm["stepnorm"])) <= bound, where
+        if r["done"]:
+            assert o["mirror"]["stepnorm"] == o["stepnorm"], where
+    return out

@@ -1,7 +1,8 @@
 """The device-side Lanczos decision (k_lz_decide, lz_sqrt_e1 in pse_vectors.hip) by itself, on given coefficients, at every size it
 supports (pse_debug_lz_decide): the square root t = T^{1/2} e_1 of one wavefront against 40-digit references on Krylov, Toeplitz,
 Wilkinson, graded and indefinite tridiagonals (tests/lanczos_decision_ref.py, tests/golden/lanczos_decision.json.gz), and the walk --
-the sequences of decisions lanczos_queued and lanczos_local issue -- against the reference walk after every launch.
+the sequences of decisions lanczos_queued and lanczos_local issue -- against the reference walk after every launch, by the checker
+that tests/test_lanczos_decision_cpu.py holds the host drivers' twin to (R.run_case).
 
 Above m = 64 entries 64 .. of d and e live in a second register, every lane owns two eigenvector rows, and from the pair (55, 56) on
 the dynamic LDS passes 48 KB: none of that ran in the suite before (its largest device-side decision was at m = 20).
@@ -20,12 +21,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def fx():
     return R.fixture()
-
-
-def bits(o):
-    """Everything a launch leaves, as bytes: for 'this launch changed nothing'."""
-    return (o["done"], o["m_final"], o["checked"], o["status"], np.float64(o["stepnorm"]).tobytes(), o["t_prev"].tobytes(),
-            o["coef"].tobytes(), tuple(np.float64(o["mirror"][k]).tobytes() for k in R.MIRROR_FIELDS))
 
 
 def sqrt_single(fx, fam, m, poison=True):
@@ -85,41 +80,12 @@ def test_square_roots_of_both_wavefronts_at_every_pair_of_sizes(fx):
 def test_entries_the_decision_has_no_right_to_read_do_not_matter(fx, m):
     """alpha[q >= done_iters], beta[q > done_iters], beta[done_iters] without have_last_beta, beta[0] and every other slot: NaN in all
     the other tests; here against the full coefficient arrays in a zeroed image."""
-    assert bits(sqrt_single(fx, "K3", m, poison=True)) == bits(sqrt_single(fx, "K3", m, poison=False))
+    assert R.bits(sqrt_single(fx, "K3", m, poison=True)) == R.bits(sqrt_single(fx, "K3", m, poison=False))
 
 
 def run_case(fx, case, open0=None):
     import pse_amd
-    alpha, beta, norm, _, scal, _ = fx.case_inputs(case)
-    open0 = case["open0"] if open0 is None else open0
-    ref = fx.case_reference(dict(case, open0=open0))
-    out = pse_amd.debug_lz_decide(scal, case["decisions"], open0)
-    fam, a0 = case["family"], fx.coeffs(case["family"], 1)[0][0]
-    for k, (d, o, (r, rm)) in enumerate(zip(case["decisions"], out, ref)):
-        where = (case["name"], k)
-        assert (o["done"], o["m_final"], o["status"], o["checked"]) == (r["done"], r["m_final"], r["status"], r["checked"]), where
-        if k > 0 and ref[k - 1][0]["done"]:
-            assert bits(o) == bits(out[k - 1]), where               # after done: a further decision leaves state and mirror as they are
-        e_step = max([fx.e_ref(fam, m) for m in range(max(d["m_lo"] - 1, 1), d["m_hi"] + 1)])
-        bound = R.stepnorm_bound(d["m_hi"], e_step, a0)
-        assert abs(o["stepnorm"] - float(r["stepnorm"])) <= bound, where + (o["stepnorm"], float(r["stepnorm"]), bound)
-        if r["checked"] and np.isfinite(norm) and norm > 0:
-            c = r["checked"]
-            assert R.max_abs_err(o["t_prev"][:c], r["t_prev"]) <= R.FACTOR * fx.e_ref(fam, c), where
-            assert np.isnan(o["t_prev"][c:]).all(), where
-        m = r["m_final"]
-        if r["done"] and r["coef"] is not None:
-            e = fx.e_ref(fam, m)
-            for q in range(m):
-                assert abs(o["coef"][q] - float(r["coef"][q])) <= R.FACTOR * e / R.coef_divisor(d, beta, norm, q), where + (q,)
-        if r["done"]:
-            assert np.isnan(o["coef"][m:]).all(), where              # nothing beyond m_final was written
-        for f in ("m", "status", "seq", "open"):
-            assert o["mirror"][f] == float(rm[f]), where + (f, o["mirror"][f], float(rm[f]))
-        assert abs(o["mirror"]["stepnorm"] - float(rm["stepnorm"])) <= bound, where
-        if r["done"]:
-            assert o["mirror"]["stepnorm"] == o["stepnorm"], where
-    return out
+    return R.run_case(fx, case, pse_amd.debug_lz_decide, open0)
 
 
 def case_ids():
