@@ -558,8 +558,9 @@ int pse_bond_order_histogram(pse_bond_order *b, const double *values /* DEVICE, 
  * pse_molecules_count writes to HOST memory: *nmol, and per type the linear molecules and all molecules (ntypes entries each).
  * The object belongs to its handle exactly as a pse_msd does: pse_destroy frees the objects still alive, pse_molecules_destroy waits for
  * the stream.  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.
- * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, time correlations of R, and owned-particle ranks
- * (local_rows).  The pair sums of a molecule -- R^2(s), the bond correlation, the hydrodynamic radius -- are pse_molecule_pairs_compute.
+ * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, and owned-particle ranks
+ * (local_rows).  The pair sums of a molecule -- R^2(s), the bond correlation, the hydrodynamic radius -- are pse_molecule_pairs_compute;
+ * the time correlations of R and of the normal modes are pse_chain_modes_correlate.
  * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_molecules_create, in this order: a null out or
  * h, n == 0 or n > n_max, nbonds == 0, a null pairs_host, every refusal of pse_host_molecule_rows in its order, ntypes outside [1, 8], a
  * molecule type >= ntypes, nbins outside [0, 4096], with nbins > 0 an rg_max and then a ree_max that is not finite and positive (*out is
@@ -608,7 +609,7 @@ int pse_molecules_compute(pse_molecules *m, const pse_double4 *pos, double *rows
  * it can be captured in a graph.  It does not sort and touches neither the cell list nor the kept neighbour list, and it works on a
  * slab rank's handle.  The object belongs to its handle exactly as a pse_molecules does.
  * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, Rh with the RPY regularisation for overlapping beads,
- * time correlations, owned-particle ranks, histograms of Rh.
+ * owned-particle ranks, histograms of Rh.  Time correlations of a chain are pse_chain_modes_correlate.
  * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_molecule_pairs_create, in this order:
  * everything pse_molecules_create refuses up to and including the molecule types, in its order, then ns outside [1, PSE_MOL_TILE].
  * pse_molecule_pairs_compute, in this order: a null p, a null pos, every output NULL, inv_rh, curves, sums or sample not 8-byte
@@ -626,6 +627,75 @@ int pse_molecule_pairs_compute(pse_molecule_pairs *p, const pse_double4 *pos,
                                double *curves /* DEVICE, ntypes x ns x 2, ADDED to, may be NULL */,
                                double *sums   /* DEVICE, ntypes x 2, ADDED to, may be NULL */,
                                double *sample /* DEVICE, ntypes x 2, WRITTEN, may be NULL */);
+
+/* ---- chain normal modes: K linear functionals of every linear molecule and their time correlations (no reference counterpart) ----
+ * A pse_chain_modes object fixes the molecules of a bond list exactly as a pse_molecule_pairs does (its own layout of
+ * pse_host_molecule_rows, one type per molecule, ntypes <= 8, the ranks q = 0 .. m - 1 of pse_host_chain_order), K = nmodes <=
+ * PSE_CHAIN_MODES_MAX weight rows per distinct size of its LINEAR molecules, and norigins <= 64 stored time origins (0: static only).
+ * Only the linear molecules (the `ends` of the layout) take part: nlin of them, numbered j = 0 .. nlin - 1 in ascending molecule
+ * number.  sizes_host lists the distinct sizes m of the linear molecules in ascending order, weights_host holds, size after size, a
+ * K x m row-major block of doubles w_{k,q}, copied at creation (the device keeps each block transposed).  The device layer knows no
+ * trigonometry: Rouse modes are one choice of weights, made by pse_host_rouse_weights (below).
+ * pse_chain_modes_compute, per linear molecule, in the handle's CURRENT box: X_k = sum over q of w_{k,q} u_q for k = 0 .. K - 1, u_q
+ * the offset of the member of rank q as mol_unfold produces it -- the bits of pse_molecules_compute; no other unwrapping is used, so X is
+ * continuous through Lees-Edwards flips wherever pse_molecules_compute is.  X goes into the object's CURRENT BUFFER, and to
+ * modes[(j K + k) 3 + axis] if modes is given.  sums (ADDED to) and sample (WRITTEN), per type a and per k, PSE_CHAIN_MODES_STATIC
+ * columns at ((a K + k) 6 + column): the sums over the linear molecules of the type of X_x^2, X_y^2, X_z^2, X_x X_y, X_x X_z, X_y X_z.
+ * A type without linear molecules adds exactly +0.0.  Each of the three outputs may be NULL, and all three: the current buffer is an output.
+ * pse_chain_modes_store copies the current buffer into origin slot `slot` (a device-to-device copy on the handle's stream) and marks
+ * the slot stored (host bookkeeping, as pse_msd_store).
+ * pse_chain_modes_correlate, for every listed pair (slot, row), every type a and every k, over the linear molecules of type a:
+ *   corr[((row ntypes + a) K + k) PSE_CHAIN_MODES_CORR + 3 alpha + beta] += sum of X_alpha(current buffer) X_beta(slot);
+ * all nine are kept because under shear <X_x(t) X_y(0)> != <X_y(t) X_x(0)>.  At most 64 pairs, by value in the launch.
+ *   ORDER OF THE SUMS.  X_k: the ranks of a molecule in chunks of 16 (chunk c: q = 16 c .. min(16 c + 16, m) - 1); within a chunk
+ *   ascending q, acc = fma(w, u, acc) from +0.0, per axis; then the chunks in ascending order, X += chunk, from +0.0: a function of m
+ *   alone.  Static sums, within a (tile, type, k, column): the linear molecules of the tile in ascending number, acc = fma(X_a, X_b,
+ *   acc) from +0.0; across the tiles the finishing kernel of pse_molecules_compute (lane l of 64 adds the tiles l, l + 64, ... in
+ *   ascending order, then the xor butterfly: every lane adds the lane l xor o for o = 32, 16, ..., 1).  Correlations: the linear
+ *   molecules in blocks of 256 consecutive j; lane l of 64 takes j0 + l, j0 + 64 + l, j0 + 128 + l, j0 + 192 + l in that order, acc =
+ *   fma(X_alpha(now), X_beta(slot), acc) from +0.0 over those of type a (none: +0.0), then the xor butterfly: one partial row per (block,
+ *   pair, type, k); across the blocks the same finishing rule (lane l adds the blocks l, l + 64, ..., then the butterfly), then the
+ *   one addition to corr.  No floating-point atomics anywhere: equal inputs give equal bits.
+ * pse_chain_modes_counts writes to HOST memory: *nmol, *nlin, the linear molecules of every type, and the molecule number and the
+ * size of every linear molecule.
+ * One workgroup of PSE_MOL_TILE lanes handles one tile: after the unfolding u lies in LDS as three padded planes in rank order; one
+ * lane takes one (molecule, k, chunk), so that a tile of many short chains and a tile of one 1024-bead chain both fill their lanes;
+ * 56 KB of LDS.  The weight tables, the current buffer, the norigins origin buffers (3 K nlin doubles each) and the workspaces of
+ * partial sums (ntiles x ntypes x K x 6 and ceil(nlin / 256) x 64 x ntypes x K x 9 doubles) are allocated at creation: nothing is
+ * allocated later.  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.  The four device calls only
+ * queue work on the handle's stream and read nothing back; they can be captured in a graph.  They use no sort, no cell list and no
+ * kept neighbour list, and they work on a slab rank's handle.  The object belongs to its handle exactly as a pse_molecule_pairs does:
+ * pse_destroy frees the objects still alive, pse_chain_modes_destroy waits for the stream.
+ * OUT OF SCOPE: mass weighting, molecules of more than PSE_MOL_TILE members, non-linear molecules, the centre-of-mass mode p = 0 and
+ * chain diffusion (that needs the unwrapped root, with the limit analyze.unwrap documents), owned-particle ranks (local_rows),
+ * multi-tau (logarithmic) lag schemes.
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_chain_modes_create, in this order:
+ * everything pse_molecules_create refuses up to and including the molecule types, in its order, then nmodes outside [1,
+ * PSE_CHAIN_MODES_MAX], norigins outside [0, 64], a bond set without a linear molecule, nsizes < 1, a null sizes_host, a null
+ * weights_host, a size list that is not exactly the ascending set of the sizes of the linear molecules, a weight that is not finite
+ * (*out is null after a refusal).  pse_chain_modes_counts: a null obj, every output NULL.  pse_chain_modes_compute, in this order: a
+ * null obj, a null pos, modes, sums or sample not 8-byte aligned.  pse_chain_modes_store: a null obj, an object with norigins == 0,
+ * slot outside [0, norigins), no compute since create.  pse_chain_modes_correlate, in this order: a null obj, an object with
+ * norigins == 0, no compute since create, npairs outside [1, 64], a null slots_host, a null rows_host, nrows < 1, in the order of the
+ * list a slot outside [0, norigins), then a slot never stored, then a row outside [0, nrows), then a row listed twice, then a null
+ * corr or one that is not 8-byte aligned. */
+#define PSE_CHAIN_MODES_MAX 32     /* functionals of one object */
+#define PSE_CHAIN_MODES_STATIC 6   /* xx, yy, zz, xy, xz, yz */
+#define PSE_CHAIN_MODES_CORR 9     /* 3 alpha + beta: alpha of now, beta of the origin */
+typedef struct pse_chain_modes pse_chain_modes;
+int pse_chain_modes_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host /* nbonds x 2 particle indices */,
+                           const unsigned *mol_types_host /* nmol, or NULL: one type */, int ntypes, int nmodes, int nsizes,
+                           const unsigned *sizes_host /* nsizes, ascending */,
+                           const double *weights_host /* size after size nmodes x m, row-major */, int norigins, pse_chain_modes **out);
+int pse_chain_modes_destroy(pse_chain_modes *obj);
+int pse_chain_modes_counts(pse_chain_modes *obj, unsigned *nmol, unsigned *nlin, unsigned *nlin_type /* ntypes */,
+                           unsigned *lin_mol /* HOST, nlin */, unsigned *lin_size /* HOST, nlin */);
+int pse_chain_modes_compute(pse_chain_modes *obj, const pse_double4 *pos, double *modes /* DEVICE, nlin x K x 3, WRITTEN, may be NULL */,
+                            double *sums   /* DEVICE, ntypes x K x 6, ADDED to, may be NULL */,
+                            double *sample /* DEVICE, ntypes x K x 6, WRITTEN, may be NULL */);
+int pse_chain_modes_store(pse_chain_modes *obj, int slot);
+int pse_chain_modes_correlate(pse_chain_modes *obj, int npairs, const int *slots_host, const int *rows_host, int nrows,
+                              double *corr /* DEVICE, nrows x ntypes x K x 9, ADDED to */);
 
 /* ---- bonded forces: HOOMD's bond.harmonic and bond.fene(no reference counterpart: the reference leaves forces to HOOMD) ----
  * A pse_bonds object is a fixed bond topology on the device: nbonds pairs of particle indices into the caller-order arrays of n rows,
@@ -1078,6 +1148,13 @@ int pse_host_molecule_rows(unsigned n, unsigned nbonds, const unsigned *pairs, i
  * index; for any other molecule the breadth-first position.  A function of the bond SET.  PSE_ERR_INVALID: a null array. */
 int pse_host_chain_order(unsigned nmol, const unsigned *parent, const unsigned *mol_off /* nmol + 1 */, const unsigned *ends /* 2 nmol */,
                          unsigned *rank /* one per member slot */);
+/* host-only: the weights of pse_chain_modes_create for a linear chain of m members, nmodes rows of m doubles, row-major.  Row 0 is the
+ * end-to-end functional (-1, 0, ..., 0, +1); rows p = 1 .. nmodes - 1 are the Rouse modes w_{p,q} = cos(pi p (2 q + 1) / (2 m)) / m.
+ * The argument is reduced IN INTEGERS: j = p (2 q + 1) mod 4 m, the angle pi j / (2 m), folded into the first quadrant (j > 2 m:
+ * j = 4 m - j; j > m: j = 2 m - j and the sign flips) before the one cos call; j == m gives exactly 0.  So w_{p,m-1-q} = -w_{p,q} bit
+ * for bit for odd p and = w_{p,q} for even p.  PSE_ERR_INVALID, in this order: a null out, m < 2, nmodes outside [1,
+ * PSE_CHAIN_MODES_MAX], nmodes - 1 >= m. */
+int pse_host_rouse_weights(unsigned m, int nmodes, double *out /* nmodes x m */);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,13 @@ SYMBOLS = {
     "pse_molecule_pairs_destroy": (_i, [_vp]),
     "pse_molecule_pairs_counts": (_i, [_vp, _vp, _vp, _vp]),
     "pse_molecule_pairs_compute": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pse_chain_modes_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "pse_chain_modes_destroy": (_i, [_vp]),
+    "pse_chain_modes_counts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pse_chain_modes_compute": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "pse_chain_modes_store": (_i, [_vp, _i]),
+    "pse_chain_modes_correlate": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
+    "pse_host_rouse_weights": (_i, [_u, _i, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),
     "pse_bond_forces": (_i, [_vp, _vp, _vp, _i, _vp]),

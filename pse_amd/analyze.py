@@ -13,7 +13,10 @@ every particle (pse_bond_order_compute: spherical harmonics up to degree 12 summ
 per-type distributions and the solid-like fraction per sample.
 Conformations measures the molecules that a bond topology defines: every molecule unfolded along its own bonds in the box of the
 step, its gyration tensor, Rg^2 and end-to-end vector reduced on the device (pse_molecules_compute: pointer jumping and fixed-order
-trees in LDS, one workgroup per tile of molecules), per-type sums, a ring of per-sample sums and the histograms of Rg and |R|."""
+trees in LDS, one workgroup per tile of molecules), per-type sums, a ring of per-sample sums and the histograms of Rg and |R|.
+RouseModes is their dynamic counterpart: the normal modes X_p and the end-to-end vector of every linear chain in the same unfolded
+coordinates (pse_chain_modes_compute), kept for up to 64 time origins on the device (pse_chain_modes_store) and correlated with them
+per type and mode (pse_chain_modes_correlate): amplitudes, <X_p(t) X_p(0)> and the relaxation times tau_p."""
 import contextlib
 import math
 
@@ -1015,8 +1018,9 @@ class Conformations(_TypedAnalyzer, _SampleRing):
     molecule, or "size": the distinct molecule sizes in ascending order are the types (at most 8).  Each sample adds its per-type sums
     to the accumulated `sums`, writes them alone into a device ring of `capacity` rows -- once full, the oldest rows are replaced --
     and, with nbins > 0, counts Rg on [0, rg_max) and |R| on [0, ree_max).  Sampling only queues work; the readers are the only places
-    that wait for the device.  Every particle has mass 1.  Not measured: molecules of more than 1024 members, time correlations of R.
-    Internal distances, the persistence length and the hydrodynamic radius are ChainStatistics'.
+    that wait for the device.  Every particle has mass 1.  Not measured: molecules of more than 1024 members.
+    Internal distances, the persistence length and the hydrodynamic radius are ChainStatistics', the time correlations of R and of
+    the normal modes are RouseModes'.
 
     nmol, nlinear, nmol_type, sizes();  gyration_tensor(a), rg2(a), rg4(a), ree_tensor(a), ree2(a), ree4(a) -- means over the molecules
     (R: the linear ones) of type `a` (None: all) and over the samples since reset();  series() -- (samples kept, 1 + ntypes 14): the
@@ -1296,4 +1300,184 @@ class ChainStatistics(_TypedAnalyzer, _SampleRing):
         import torch
         out = torch.empty((self.nmol,), dtype=torch.float64, device=self.system.pos.device)
         self.integrator.engine.molecule_pairs_compute(self.system.pos, self._pairs, inv_rh=out)
+        return out.cpu().numpy()
+
+
+def linear_molecules_of(n, bonds):
+    """molecules_of and, per molecule, its size and whether it is LINEAR by the rule of pse_host_molecule_rows -- a tree with exactly
+    two members of degree 1 and all others of degree 2 (a dimer is): (mol_of, nmol, sizes (nmol,), linear (nmol,) bool).  NumPy only;
+    every bond is taken to be listed once (the library refuses a bond listed twice)."""
+    import numpy as np
+    mol_of, nmol = molecules_of(n, bonds)
+    b = np.asarray(bonds).astype(np.int64)
+    b = b[b[:, 0] != b[:, 1]]
+    deg = np.bincount(b.ravel(), minlength=int(n))
+    member = mol_of >= 0
+    sizes = np.bincount(mol_of[member], minlength=nmol)
+    nb = np.bincount(mol_of[b[:, 0]], minlength=nmol)
+    ones = np.bincount(mol_of[member], weights=(deg[member] == 1), minlength=nmol)
+    twos = np.bincount(mol_of[member], weights=(deg[member] == 2), minlength=nmol)
+    return mol_of, nmol, sizes, (nb == sizes - 1) & (ones == 2) & (twos == sizes - 2)
+
+
+def relaxation_time_of(lags, c):
+    """The time at which a normalised correlation c(t), given at the ascending times `lags`, first falls to 1/e: between the first
+    two consecutive points with c[i - 1] > 1/e >= c[i], interpolated linearly in ln c (linearly in c where c[i] <= 0), which is exact
+    for exp(-t / tau).  NaN if the curve never crosses.  NumPy only."""
+    import numpy as np
+    t, c = np.asarray(lags, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    if t.ndim != 1 or c.shape != t.shape:
+        raise ValueError("lags and c must be 1-D sequences of one length")
+    level = math.exp(-1.0)
+    for i in range(1, t.shape[0]):
+        if c[i - 1] > level >= c[i]:
+            if c[i] > 0.0:
+                f = (math.log(c[i - 1]) + 1.0) / (math.log(c[i - 1]) - math.log(c[i]))
+            else:
+                f = (c[i - 1] - level) / (c[i - 1] - c[i])
+            return float(t[i - 1] + (t[i] - t[i - 1]) * f)
+    return float("nan")
+
+
+ROUSE_MAX_MODES = 31   # nmodes of one RouseModes: with the end-to-end row, PSE_CHAIN_MODES_MAX functionals
+
+
+def _rouse_arguments(bonds, nmodes, nlags, origin_every, molecule_types, type_names, period):
+    """What RouseModes checks before it touches the device.  Returns (schedule, pairs uint32, molecule types uint32 (nmol,) or None,
+    ntypes, names or None, period, K = nmodes + 1, the distinct sizes of the linear molecules, size_values)."""
+    import numpy as np
+    schedule = MSDSchedule(nlags, origin_every)
+    nmodes = int(nmodes)
+    if not 1 <= nmodes <= ROUSE_MAX_MODES:
+        raise ValueError(f"nmodes = {nmodes} outside [1, {ROUSE_MAX_MODES}]")
+    pairs, types, ntypes, names, period, _, _, _, _, _, size_values = _conformation_arguments(bonds, molecule_types, type_names, period, 0,
+                                                                                           None, None, 1)
+    _, _, sizes, linear = linear_molecules_of(int(pairs.max()) + 1, pairs)
+    if not linear.any():
+        raise ValueError("bonds makes no linear molecule: there is no chain to project")
+    lin_sizes = np.unique(sizes[linear])
+    if nmodes >= int(lin_sizes[0]):
+        raise ValueError(f"nmodes = {nmodes} needs chains of more than {nmodes} members, the smallest linear molecule has {int(lin_sizes[0])}")
+    return schedule, pairs, types, ntypes, names, period, nmodes + 1, lin_sizes, size_values
+
+
+class RouseModes(_TypedAnalyzer):
+    """The normal modes of the linear molecules that a bond topology defines, and their time correlations: every `period` steps (a
+    sample) one pass (pse_chain_modes_compute) unfolds every molecule as Conformations does and projects every linear one onto K =
+    nmodes + 1 weight rows -- row 0 the end-to-end vector R, rows p = 1 .. nmodes the Rouse modes X_p = (1/m) sum_q cos(pi p (2 q + 1) /
+    (2 m)) u_q (pse_host_rouse_weights, one table per distinct size) --, adds the static second moments per molecule type, correlates
+    the sample with every live origin (pse_chain_modes_correlate: all nine <X_alpha(t) X_beta(0)>) and, every `origin_every` samples,
+    stores it as a new origin (pse_chain_modes_store).  Lags run from 1 to `nlags` samples by MSDSchedule; ceil(nlags / origin_every)
+    <= 64 origins are kept on the device.  `bonds`, `molecule_types` (None, one code or name per molecule, or "size") and `type_names`
+    as for Conformations; nmodes < the size of the smallest linear molecule.  Rings, stars and other non-linear molecules are
+    skipped.  Sampling only queues work; the readers below are the only places that wait for the device.
+
+    X is built from bond vectors alone, so it is continuous through Lees-Edwards flips wherever Conformations is.  Under shear the
+    chain is deformed affinely with the flow: the xx, xy and xz entries of the tensors contain that deformation, and nothing is
+    subtracted; <X_x(t) X_y(0)> and <X_y(t) X_x(0)> differ, which is why correlation_tensor keeps all nine entries.  Not measured:
+    the centre-of-mass mode p = 0 and chain diffusion (MSD of the beads is analyze.MSD), mass weighting, multi-tau lag schemes.
+
+    lags -- in steps;  counts -- origins per lag;  nlin, nlin_type;  amplitude_tensor(a) -- (K, 3, 3) <X_k X_k^T>;  amplitudes(a) --
+    (K,) <X_k . X_k>, entry 0 = <R^2>;  correlation_tensor(a) -- (nlags, K, 3, 3), [alpha, beta] = <X_alpha(t) X_beta(0)>;
+    autocorrelation(a) -- (nlags + 1, K): the trace over the static amplitude, lag 0 = 1;  relaxation_times(a) -- (K,) by
+    relaxation_time_of;  per_molecule() -- (nlin, K, 3) at the current positions;  reset().  a = None: all types together; NaN for a
+    type without linear molecules."""
+
+    def __init__(self, integrator, bonds, nmodes=8, nlags=64, origin_every=1, molecule_types=None, type_names=None, period=1):
+        import numpy as np
+        import torch
+        from .engine import CHAIN_MODES_STATIC, ChainModes, host_rouse_weights
+        lst = getattr(bonds, "_list", None)
+        pairs = lst.index if lst is not None and hasattr(lst, "index") else bonds
+        (self._schedule, pairs, types, self.ntypes, self.type_names, self.period, self.K, self.linear_sizes,
+         self.size_values) = _rouse_arguments(pairs, nmodes, nlags, origin_every, molecule_types, type_names, period)
+        self.nmodes = self.K - 1
+        with self._attach(integrator, None) as system:          # (the lines above raise before the integrator is touched)
+            if int(pairs.max()) >= system.n:
+                raise ValueError(f"bonds holds the index {int(pairs.max())}, the system has {system.n} particles")
+            self.molecule_types = types
+            self.nlags, self.origin_every, self.norigins = self._schedule.nlags, self._schedule.origin_every, self._schedule.norigins
+            weights = [host_rouse_weights(int(m), self.K) for m in self.linear_sizes]
+            self._modes = ChainModes(integrator.engine, pairs, self.linear_sizes, weights, types, self.ntypes, self.norigins, system.n)
+            self.nmol, self.nlin, self.nlin_type = self._modes.nmol, self._modes.nlin, self._modes.nlin_type
+            self.lin_mol, self.lin_size = self._modes.lin_mol, self._modes.lin_size
+            dev = system.pos.device
+            self._sums = torch.zeros((self.ntypes, self.K, CHAIN_MODES_STATIC), dtype=torch.float64, device=dev)
+            self._corr = torch.zeros((self.nlags, self.ntypes, self.K, 3, 3), dtype=torch.float64, device=dev)
+
+    def analyze(self, timestep):
+        if not self._due(timestep):
+            return
+        e, m = self.integrator.engine, self._modes
+        e.chain_modes_compute(self.system.pos, m, sums=self._sums)
+        self._schedule.sample(lambda slots, rows: e.chain_modes_correlate(m, slots, rows, self._corr),
+                              lambda slot: e.chain_modes_store(m, slot))
+
+    def reset(self):
+        """Forget the sums, the correlations, the counts and the origins."""
+        self._sums.zero_(); self._corr.zero_()
+        self._schedule.reset()
+
+    @property
+    def samples(self):
+        return self._schedule.samples
+
+    @property
+    def lags(self):
+        import numpy as np
+        return np.arange(1, self.nlags + 1) * self.period
+
+    @property
+    def counts(self):
+        import numpy as np
+        return np.array(self._schedule.counts, dtype=np.int64)
+
+    def _of_type(self, x, a, axis):
+        """(the sum over the types or the entry of type `a` along `axis`, the number of linear molecules behind it)"""
+        if a is None:
+            return x.sum(axis=axis), int(self.nlin_type.sum())
+        a = self._code(a)
+        return x.take(a, axis=axis), int(self.nlin_type[a])
+
+    def amplitude_tensor(self, a=None):
+        """(K, 3, 3): <X_k X_k^T> over the linear molecules of type `a` (None: of all) and the samples since reset()."""
+        import numpy as np
+        self._sampled()
+        s, n = self._of_type(self._sums.cpu().numpy(), a, 0)
+        return tensor_of(s / (self.samples * n)) if n else np.full((self.K, 3, 3), np.nan)
+
+    def amplitudes(self, a=None):
+        """(K,): <X_k . X_k>, the traces of amplitude_tensor(a); entry 0 is <R^2>."""
+        import numpy as np
+        return np.trace(self.amplitude_tensor(a), axis1=-2, axis2=-1)
+
+    def correlation_tensor(self, a=None):
+        """(nlags, K, 3, 3): [lag - 1, k, alpha, beta] = <X_alpha(t + lag) X_beta(t)> of functional k over the linear molecules of type
+        `a` (None: of all) and the origins of that lag; NaN where a lag has no origin yet."""
+        import numpy as np
+        c, n = self._of_type(self._corr.cpu().numpy(), a, 1)
+        den = (self.counts * n).astype(np.float64)[:, None, None, None]
+        return np.divide(c, den, out=np.full(c.shape, np.nan), where=den > 0.0)
+
+    def autocorrelation(self, a=None):
+        """(nlags + 1, K): <X_k(t + lag) . X_k(t)> / <X_k . X_k> for lag = 0 .. nlags samples; row 0 is 1."""
+        import numpy as np
+        amp = self.amplitudes(a)
+        tr = np.trace(self.correlation_tensor(a), axis1=-2, axis2=-1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.concatenate([np.where(np.isnan(amp), np.nan, 1.0)[None, :], tr / amp[None, :]], axis=0)
+
+    def relaxation_times(self, a=None):
+        """(K,): relaxation_time_of every column of autocorrelation(a), in steps; entry 0 is the relaxation time of R."""
+        import numpy as np
+        c = self.autocorrelation(a)
+        t = np.concatenate([[0], self.lags])
+        return np.array([relaxation_time_of(t, c[:, k]) for k in range(self.K)])
+
+    def per_molecule(self):
+        """(nlin, K, 3) float64: X_k of every linear molecule (lin_mol, lin_size) at the system's current positions.  One pass and one
+        copy; no sample is taken."""
+        import torch
+        out = torch.empty((self.nlin, self.K, 3), dtype=torch.float64, device=self.system.pos.device)
+        self.integrator.engine.chain_modes_compute(self.system.pos, self._modes, out=out)
         return out.cpu().numpy()

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*, pse_molecule_pairs_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*, pse_molecule_pairs_*, pse_chain_modes_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -54,6 +54,14 @@ struct pse_molecule_pairs : Topology {   // the REAL layout and the molecule typ
     MoleculeLayout L;
     std::vector<unsigned> types;
     int ntypes = 1, ns = 1;
+};
+struct pse_chain_modes : Topology {   // the REAL layout and the molecule types; the slots' bookkeeping
+    using Topology::Topology;
+    MoleculeLayout L;
+    std::vector<unsigned> types;
+    int ntypes = 1, norigins = 0;
+    bool computed = false;
+    unsigned long long stored = 0ull;
 };
 struct pse_team { int unused; };
 
@@ -323,6 +331,45 @@ int pse_molecule_pairs_counts(pse_molecule_pairs *p, unsigned *nmol, unsigned *n
 // (the arrays are device pointers and there is no device: nothing is read or written)
 int pse_molecule_pairs_compute(pse_molecule_pairs *p, const pse_double4 *pos, double *inv_rh, double *curves, double *sums, double *sample) {
     return molecule_pairs_compute_validate(p, pos, inv_rh, curves, sums, sample);
+}
+int pse_chain_modes_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *mol_types_host, int ntypes,
+                           int nmodes, int nsizes, const unsigned *sizes_host, const double *weights_host, int norigins, pse_chain_modes **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_chain_modes_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_chain_modes_create: null handle");
+    pse_chain_modes *m = new pse_chain_modes(h, 0, 0);
+    m->ntypes = ntypes; m->norigins = norigins;
+    const int rc = chain_modes_create_validate(h->par.n_max, n, nbonds, pairs_host, mol_types_host, ntypes, nmodes, nsizes, sizes_host, weights_host,
+                                               norigins, m->L);
+    if (!rc && mol_types_host) m->types.assign(mol_types_host, mol_types_host + m->L.nmol);
+    return topology_adopt(m, rc, out);
+}
+int pse_chain_modes_destroy(pse_chain_modes *obj) { return topology_destroy(obj); }
+int pse_chain_modes_counts(pse_chain_modes *obj, unsigned *nmol, unsigned *nlin, unsigned *nlin_type, unsigned *lin_mol, unsigned *lin_size) {
+    if (int rc = chain_modes_counts_validate(obj, nmol, nlin, nlin_type, lin_mol, lin_size)) return rc;
+    std::vector<unsigned> mol, size, per_type;
+    chain_modes_linear(obj->L, obj->types.empty() ? nullptr : obj->types.data(), obj->ntypes, mol, size, per_type);
+    if (nmol) *nmol = obj->L.nmol;
+    if (nlin) *nlin = (unsigned)mol.size();
+    if (nlin_type) std::copy(per_type.begin(), per_type.end(), nlin_type);
+    if (lin_mol) std::copy(mol.begin(), mol.end(), lin_mol);
+    if (lin_size) std::copy(size.begin(), size.end(), lin_size);
+    return 0;
+}
+// (the arrays are device pointers and there is no device: nothing is read or written; a compute and a store mark the bookkeeping)
+int pse_chain_modes_compute(pse_chain_modes *obj, const pse_double4 *pos, double *modes, double *sums, double *sample) {
+    if (int rc = chain_modes_compute_validate(obj, pos, modes, sums, sample)) return rc;
+    obj->computed = true;
+    return 0;
+}
+int pse_chain_modes_store(pse_chain_modes *obj, int slot) {
+    if (int rc = chain_modes_store_validate(obj, obj ? obj->norigins : 0, obj ? obj->computed : false, slot)) return rc;
+    obj->stored |= 1ull << slot;
+    return 0;
+}
+int pse_chain_modes_correlate(pse_chain_modes *obj, int npairs, const int *slots_host, const int *rows_host, int nrows, double *corr) {
+    return chain_modes_correlate_validate(obj, obj ? obj->norigins : 0, obj ? obj->computed : false, obj ? obj->stored : 0ull, npairs, slots_host,
+                                          rows_host, nrows, corr);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

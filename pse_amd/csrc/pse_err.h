@@ -145,5 +145,20 @@ int molecule_pairs_counts_validate(const void *p, const void *nmol, const void *
 // terms (ntypes x ns x MOLPAIR_COLS): the summands behind every entry of the curves, max(m - s, 0) for D and max(m - 1 - s, 0) for C over
 // the linear molecules of a type
 void molecule_pairs_terms(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, int ns, unsigned long long *terms);
+// the linear molecules of a layout in ascending molecule number: their molecule numbers and sizes, and per type how many there are
+void chain_modes_linear(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, std::vector<unsigned> &lin_mol,
+                        std::vector<unsigned> &lin_size, std::vector<unsigned> &nlin_type);
+// the argument checks of pse_chain_modes_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them:
+// molecule_topology_validate, nmodes, norigins, a linear molecule, the size list against the layout, the weights
+int chain_modes_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes,
+                                int nmodes, int nsizes, const unsigned *sizes, const double *weights, int norigins, MoleculeLayout &L);
+// the argument checks of pse_chain_modes_counts, pse_chain_modes_compute, pse_chain_modes_store and pse_chain_modes_correlate
+// (norigins: the object's; computed: a compute has run since create; stored: bit s = slot s holds a buffer)
+int chain_modes_counts_validate(const void *obj, const void *nmol, const void *nlin, const void *nlin_type, const void *lin_mol,
+                                const void *lin_size);
+int chain_modes_compute_validate(const void *obj, const void *pos, const void *modes, const void *sums, const void *sample);
+int chain_modes_store_validate(const void *obj, int norigins, bool computed, int slot);
+int chain_modes_correlate_validate(const void *obj, int norigins, bool computed, unsigned long long stored, int npairs, const int *slots,
+                                   const int *rows, int nrows, const void *corr);
 
 }  // namespace pse

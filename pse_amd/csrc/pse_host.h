@@ -25,6 +25,9 @@ constexpr int MOL_COLS = 14;          // columns of a molecule's row and of a ty
 constexpr int MOL_MAX_BINS = 4096;    // bins of each histogram of a molecule object (pse_molecules_create)
 constexpr int MOLPAIR_COLS = 2;       // per separation of a chain-statistics curve: D, C (pse_molecule_pairs_compute; PSE_MOLPAIR_COLS)
 constexpr int MOLPAIR_SUMS = 2;       // per type: the sum of 1/Rh and of (1/Rh)^2 (PSE_MOLPAIR_SUMS)
+constexpr int CHAIN_MODES_MAX = 32;   // functionals of one chain-modes object (pse_chain_modes_create; PSE_CHAIN_MODES_MAX)
+constexpr int CHAIN_MODES_STATIC = 6; // per type and functional: the sums of X_x^2, X_y^2, X_z^2, X_x X_y, X_x X_z, X_y X_z (PSE_CHAIN_MODES_STATIC)
+constexpr int CHAIN_MODES_CORR = 9;   // per row, type and functional: the sums of X_a(now) X_b(slot), 3 a + b (PSE_CHAIN_MODES_CORR)
 constexpr int PAIR_TYPED_MAX_TYPES = 8;     // particle types of a typed pair table (pse_typed_table_create): at most 36 pair types
 constexpr int PAIR_TYPED_MAX_ENTRIES = 3584; // entries of all its tables together: 56 KB of LDS, next to 1.4 KB of static LDS, inside 64 KB
 constexpr int BOND_MAX_TYPES = 64;   // parameter sets of a bond object (pse_bonds_create): staged in 2 KB of LDS

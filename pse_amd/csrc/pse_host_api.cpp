@@ -768,6 +768,102 @@ void molecule_pairs_terms(const MoleculeLayout &L, const unsigned *mol_types, in
     }
 }
 
+void chain_modes_linear(const MoleculeLayout &L, const unsigned *mol_types, int ntypes, std::vector<unsigned> &lin_mol,
+                        std::vector<unsigned> &lin_size, std::vector<unsigned> &nlin_type) {
+    lin_mol.clear(); lin_size.clear();
+    nlin_type.assign((size_t)ntypes, 0u);
+    for (unsigned mol = 0; mol < L.nmol; ++mol) {
+        if (L.ends[2 * (size_t)mol] == 0xffffffffu) continue;
+        lin_mol.push_back(mol);
+        lin_size.push_back(L.mol_off[mol + 1] - L.mol_off[mol]);
+        ++nlin_type[mol_types ? mol_types[mol] : 0u];
+    }
+}
+
+int chain_modes_create_validate(unsigned n_max, unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *mol_types, int ntypes,
+                                int nmodes, int nsizes, const unsigned *sizes, const double *weights, int norigins, MoleculeLayout &L) {
+    const char *who = "pse_chain_modes_create";
+    if (int rc = molecule_topology_validate(who, n_max, n, nbonds, pairs, mol_types, ntypes, L)) return rc;
+    if (nmodes < 1 || nmodes > CHAIN_MODES_MAX) return fail(PSE_ERR_INVALID, "%s: nmodes = %d outside [1, %d]", who, nmodes, CHAIN_MODES_MAX);
+    if (norigins < 0 || norigins > MSD_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: norigins = %d outside [0, %d]", who, norigins, MSD_MAX_ORIGINS);
+    std::vector<unsigned> present;   // the distinct sizes of the linear molecules, ascending
+    for (unsigned mol = 0; mol < L.nmol; ++mol)
+        if (L.ends[2 * (size_t)mol] != 0xffffffffu) present.push_back(L.mol_off[mol + 1] - L.mol_off[mol]);
+    if (present.empty()) return fail(PSE_ERR_INVALID, "%s: none of the %u molecules is linear: there is no chain to project", who, L.nmol);
+    std::sort(present.begin(), present.end());
+    present.erase(std::unique(present.begin(), present.end()), present.end());
+    if (nsizes < 1) return fail(PSE_ERR_INVALID, "%s: nsizes = %d, need at least one size", who, nsizes);
+    if (!sizes) return fail(PSE_ERR_INVALID, "%s: null sizes_host", who);
+    if (!weights) return fail(PSE_ERR_INVALID, "%s: null weights_host", who);
+    for (int s = 0; s < nsizes || s < (int)present.size(); ++s) {
+        if (s >= nsizes)
+            return fail(PSE_ERR_INVALID, "%s: sizes_host has %d entries, the linear molecules %zu sizes: %u is missing", who, nsizes, present.size(),
+                        present[s]);
+        if (s >= (int)present.size() || sizes[s] != present[s])
+            return fail(PSE_ERR_INVALID, "%s: sizes_host[%d] = %u is not the %d-th size of the linear molecules in ascending order", who, s, sizes[s], s);
+    }
+    size_t at = 0;
+    for (int s = 0; s < nsizes; ++s)
+        for (int k = 0; k < nmodes; ++k)
+            for (unsigned q = 0; q < sizes[s]; ++q, ++at)
+                if (!std::isfinite(weights[at]))
+                    return fail(PSE_ERR_INVALID, "%s: the weight of size %u, row %d, rank %u is %g, which is not finite", who, sizes[s], k, q, weights[at]);
+    return 0;
+}
+
+int chain_modes_counts_validate(const void *obj, const void *nmol, const void *nlin, const void *nlin_type, const void *lin_mol,
+                                const void *lin_size) {
+    const char *who = "pse_chain_modes_counts";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null chain-modes object", who);
+    if (!nmol && !nlin && !nlin_type && !lin_mol && !lin_size)
+        return fail(PSE_ERR_INVALID, "%s: nmol, nlin, nlin_type, lin_mol and lin_size are all null: nothing to write", who);
+    return 0;
+}
+
+int chain_modes_compute_validate(const void *obj, const void *pos, const void *modes, const void *sums, const void *sample) {
+    const char *who = "pse_chain_modes_compute";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null chain-modes object", who);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (((uintptr_t)modes & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: modes = %p is not 8-byte aligned (doubles)", who, modes);
+    if (((uintptr_t)sums & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sums = %p is not 8-byte aligned (doubles)", who, sums);
+    if (((uintptr_t)sample & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sample = %p is not 8-byte aligned (doubles)", who, sample);
+    return 0;
+}
+
+int chain_modes_store_validate(const void *obj, int norigins, bool computed, int slot) {
+    const char *who = "pse_chain_modes_store";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null chain-modes object", who);
+    if (norigins == 0) return fail(PSE_ERR_INVALID, "%s: the object was created with norigins = 0: it has no origin slots", who);
+    if (slot < 0 || slot >= norigins) return fail(PSE_ERR_INVALID, "%s: slot = %d outside [0, norigins = %d)", who, slot, norigins);
+    if (!computed) return fail(PSE_ERR_INVALID, "%s: no pse_chain_modes_compute since create: the current buffer holds nothing", who);
+    return 0;
+}
+
+int chain_modes_correlate_validate(const void *obj, int norigins, bool computed, unsigned long long stored, int npairs, const int *slots,
+                                   const int *rows, int nrows, const void *corr) {
+    const char *who = "pse_chain_modes_correlate";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null chain-modes object", who);
+    if (norigins == 0) return fail(PSE_ERR_INVALID, "%s: the object was created with norigins = 0: it has no origin slots", who);
+    if (!computed) return fail(PSE_ERR_INVALID, "%s: no pse_chain_modes_compute since create: the current buffer holds nothing", who);
+    if (npairs < 1 || npairs > MSD_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: npairs = %d outside [1, %d]", who, npairs, MSD_MAX_ORIGINS);
+    if (!slots) return fail(PSE_ERR_INVALID, "%s: null slots_host", who);
+    if (!rows) return fail(PSE_ERR_INVALID, "%s: null rows_host", who);
+    if (nrows < 1) return fail(PSE_ERR_INVALID, "%s: nrows = %d, need at least one row", who, nrows);
+    for (int q = 0; q < npairs; ++q)
+        if (slots[q] < 0 || slots[q] >= norigins)
+            return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d outside [0, norigins = %d)", who, q, slots[q], norigins);
+    for (int q = 0; q < npairs; ++q)
+        if (!((stored >> slots[q]) & 1ull)) return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d, which was never stored", who, q, slots[q]);
+    for (int q = 0; q < npairs; ++q)
+        if (rows[q] < 0 || rows[q] >= nrows) return fail(PSE_ERR_INVALID, "%s: pair %d names the row %d outside [0, nrows = %d)", who, q, rows[q], nrows);
+    for (int q = 0; q < npairs; ++q)
+        for (int p = 0; p < q; ++p)
+            if (rows[p] == rows[q]) return fail(PSE_ERR_INVALID, "%s: pairs %d and %d both name the row %d", who, p, q, rows[q]);
+    if (!corr) return fail(PSE_ERR_INVALID, "%s: null corr", who);
+    if (((uintptr_t)corr & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: corr = %p is not 8-byte aligned (doubles)", who, corr);
+    return 0;
+}
+
 }  // namespace pse
 
 using namespace pse;
@@ -985,5 +1081,29 @@ extern "C" int pse_host_molecule_rows(unsigned n, unsigned nbonds, const unsigne
 extern "C" int pse_host_chain_order(unsigned nmol, const unsigned *parent, const unsigned *mol_off, const unsigned *ends, unsigned *rank) {
     if (!parent || !mol_off || !ends || !rank) return fail(PSE_ERR_INVALID, "pse_host_chain_order: null array");
     chain_ranks(nmol, parent, mol_off, ends, rank);
+    return 0;
+}
+
+// The angle pi p (2 q + 1) / (2 m) as the integer j = p (2 q + 1) mod 4 m of quarter turns / m, folded into the first quadrant, so
+// that mirrored ranks meet the same cos call; the call and the division by m in extended precision, rounded once.
+extern "C" int pse_host_rouse_weights(unsigned m, int nmodes, double *out) {
+    const char *who = "pse_host_rouse_weights";
+    if (!out) return fail(PSE_ERR_INVALID, "%s: null out", who);
+    if (m < 2) return fail(PSE_ERR_INVALID, "%s: m = %u, a chain has at least two members", who, m);
+    if (nmodes < 1 || nmodes > CHAIN_MODES_MAX) return fail(PSE_ERR_INVALID, "%s: nmodes = %d outside [1, %d]", who, nmodes, CHAIN_MODES_MAX);
+    if ((unsigned)(nmodes - 1) >= m) return fail(PSE_ERR_INVALID, "%s: nmodes - 1 = %d modes, a chain of m = %u members has only %u", who, nmodes - 1, m, m - 1u);
+    std::fill(out, out + m, 0.0);
+    out[0] = -1.0; out[m - 1] = 1.0;
+    const uint64_t M = m;
+    const long double pi = 3.14159265358979323846264338327950288L;
+    for (int p = 1; p < nmodes; ++p)
+        for (uint64_t q = 0; q < M; ++q) {
+            uint64_t j = ((uint64_t)p * (2u * q + 1u)) % (4u * M);
+            bool neg = false;
+            if (j > 2u * M) j = 4u * M - j;
+            if (j > M) { j = 2u * M - j; neg = true; }
+            const double c = j == M ? 0.0 : (double)(cosl(pi * (long double)j / (long double)(2u * M)) / (long double)M);
+            out[(size_t)p * m + q] = neg ? -c : c;
+        }
     return 0;
 }

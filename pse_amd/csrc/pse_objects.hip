@@ -1,6 +1,6 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
 // typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors, displacement
-// moments, chain conformations and chain statistics.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h, pse_molecules.h or pse_molpairs.h, the objects own their arrays through DeviceObject
+// moments, chain conformations, chain statistics and chain normal modes.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h, pse_molecules.h, pse_molpairs.h or pse_molmodes.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,7 @@
 #include "pse_order.h"
 #include "pse_molecules.h"
 #include "pse_molpairs.h"
+#include "pse_molmodes.h"
 
 // A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
 // and, for bonds, the counter of overstretched FENE bonds.
@@ -49,6 +50,13 @@ struct pse_molecule_pairs : DeviceObject {
     MolPairs mp{};
     std::vector<unsigned> nmol_type;            // per type, for pse_molecule_pairs_counts
     std::vector<unsigned long long> terms;      // ntypes x ns x MOLPAIR_COLS
+};
+struct pse_chain_modes : DeviceObject {
+    MolModes mm{};
+    int norigins = 0;
+    bool computed = false;                      // a pse_chain_modes_compute has been queued since create
+    unsigned long long stored = 0ull;           // bit s = slot s holds a buffer
+    std::vector<unsigned> lin_mol, lin_size, nlin_type;   // for pse_chain_modes_counts
 };
 struct pse_msd : DeviceObject {
     MsdOrigins mo{};
@@ -671,6 +679,126 @@ extern "C" int pse_molecule_pairs_compute(pse_molecule_pairs *p, const pse_doubl
     pse_handle *h = p->h;
     HIPCHK(hipSetDevice(h->device));
     launch_molecule_pairs((const double4 *)pos, h->dbox, p->mp, inv_rh, curves, sums, sample, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Chain normal modes (include/pse_amd.h): its own layout of pse_host_molecule_rows with the ranks of pse_host_chain_order, packed as the
+// kernels read it (pse_molmodes.h), the transposed weight tables, the current buffer, the origin slots and the two workspaces of
+// partial sums -- everything is placed here --, and the passes.  Queue-only, as pse_molecules_compute.
+extern "C" int pse_chain_modes_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *mol_types_host,
+                                      int ntypes, int nmodes, int nsizes, const unsigned *sizes_host, const double *weights_host, int norigins,
+                                      pse_chain_modes **out) {
+    const char *who = "pse_chain_modes_create";
+    TRY(create_begin(who, h, out));
+    MoleculeLayout L;
+    TRY(chain_modes_create_validate((unsigned)h->n_max, n, nbonds, pairs_host, mol_types_host, ntypes, nmodes, nsizes, sizes_host, weights_host,
+                                    norigins, L));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nmem = L.members.size();
+    const int K = nmodes;
+    // the tables transposed (entry q K + k of a size's block is w_{k,q}), and where the block of every size begins
+    std::vector<size_t> table_off((size_t)nsizes + 1, 0);
+    for (int s = 0; s < nsizes; ++s) table_off[s + 1] = table_off[s] + (size_t)K * sizes_host[s];
+    std::vector<double> wt(table_off[nsizes]);
+    for (int s = 0; s < nsizes; ++s)
+        for (int k = 0; k < K; ++k)
+            for (unsigned q = 0; q < sizes_host[s]; ++q) wt[table_off[s] + (size_t)q * K + k] = weights_host[table_off[s] + (size_t)k * sizes_host[s] + q];
+    std::vector<unsigned> rank, word(nmem), mol_word(L.nmol), mol_chunk(L.nmol, 0u), mol_lin(L.nmol, 0xffffffffu), mol_wt(L.nmol, 0u),
+        tile_slot(L.ntiles + 1), tile_word(L.ntiles);
+    chain_order(L, rank);
+    pse_chain_modes *m = new pse_chain_modes();
+    m->h = h;
+    m->norigins = norigins;
+    chain_modes_linear(L, mol_types_host, ntypes, m->lin_mol, m->lin_size, m->nlin_type);
+    const size_t nlin = m->lin_mol.size();
+    std::vector<unsigned char> lin_type(nlin);
+    auto lg_ceil = [](unsigned v) { unsigned r = 0; while ((1u << r) < v) ++r; return r; };
+    unsigned jl = 0;
+    for (unsigned t = 0; t < L.ntiles; ++t) {
+        const unsigned first = L.mol_off[L.tile_mol[t]];
+        unsigned largest = 0, chunks = 0;
+        tile_slot[t] = first;
+        for (unsigned q = L.tile_mol[t]; q < L.tile_mol[t + 1]; ++q) {
+            const unsigned o = L.mol_off[q], sz = L.mol_off[q + 1] - o, type = mol_types_host ? mol_types_host[q] : 0u;
+            largest = std::max(largest, sz);
+            for (unsigned p = 0; p < sz; ++p) {
+                word[o + p] = (o - first + L.parent[o + p]) | (p << 10) | ((sz - 1u) << 20);
+                rank[o + p] |= (q - L.tile_mol[t]) << 10;
+            }
+            const bool linear = L.ends[2 * (size_t)q] != 0xffffffffu;
+            mol_word[q] = (o - first) | ((sz - 1u) << 10) | (type << 20) | (linear ? 1u << 24 : 0u);
+            if (!linear) continue;
+            mol_chunk[q] = chunks;
+            chunks += (sz + MODE_CHUNK - 1u) / MODE_CHUNK;
+            mol_lin[q] = jl;
+            lin_type[jl++] = (unsigned char)type;
+            mol_wt[q] = (unsigned)table_off[std::lower_bound(sizes_host, sizes_host + nsizes, sz) - sizes_host];
+        }
+        tile_word[t] = L.tile_rounds[t] | (lg_ceil(largest) << 8) | (chunks << 16);
+    }
+    tile_slot[L.ntiles] = (unsigned)nmem;
+    MolModes &mm = m->mm;
+    mm.nmol = L.nmol; mm.ntiles = L.ntiles; mm.nlin = (unsigned)nlin; mm.nblocks = (unsigned)((nlin + MODE_BLOCK - 1) / MODE_BLOCK);
+    mm.ntypes = ntypes; mm.K = K;
+    const size_t buf = (size_t)3 * K * nlin;
+    hipError_t e = m->put(&mm.member, L.members.data(), nmem);
+    e = m->put(&mm.word, word.data(), nmem);
+    e = m->put(&mm.rank, rank.data(), nmem);
+    e = m->put(&mm.mol_word, mol_word.data(), mol_word.size());
+    e = m->put(&mm.mol_chunk, mol_chunk.data(), mol_chunk.size());
+    e = m->put(&mm.mol_lin, mol_lin.data(), mol_lin.size());
+    e = m->put(&mm.mol_wt, mol_wt.data(), mol_wt.size());
+    e = m->put(&mm.tile_slot, tile_slot.data(), tile_slot.size());
+    e = m->put(&mm.tile_mol, L.tile_mol.data(), L.tile_mol.size());
+    e = m->put(&mm.tile_word, tile_word.data(), tile_word.size());
+    e = m->put(&mm.lin_type, lin_type.data(), nlin);
+    e = m->put(&mm.weights, wt.data(), wt.size());
+    e = m->put(&mm.cur, nullptr, buf, true);
+    if (norigins > 0) {
+        e = m->put(&mm.slots, nullptr, buf * (size_t)norigins, true);
+        e = m->put(&mm.part_corr, nullptr, (size_t)mm.nblocks * MODE_MAX_PAIRS * ntypes * K * CHAIN_MODES_CORR);
+    }
+    e = m->put(&mm.part_static, nullptr, (size_t)L.ntiles * ntypes * K * CHAIN_MODES_STATIC);
+    return create_end(who, h, m, e, out);
+}
+extern "C" int pse_chain_modes_destroy(pse_chain_modes *obj) { return object_destroy(obj); }
+extern "C" int pse_chain_modes_counts(pse_chain_modes *obj, unsigned *nmol, unsigned *nlin, unsigned *nlin_type, unsigned *lin_mol, unsigned *lin_size) {
+    TRY(chain_modes_counts_validate(obj, nmol, nlin, nlin_type, lin_mol, lin_size));
+    if (nmol) *nmol = obj->mm.nmol;
+    if (nlin) *nlin = obj->mm.nlin;
+    if (nlin_type) std::copy(obj->nlin_type.begin(), obj->nlin_type.end(), nlin_type);
+    if (lin_mol) std::copy(obj->lin_mol.begin(), obj->lin_mol.end(), lin_mol);
+    if (lin_size) std::copy(obj->lin_size.begin(), obj->lin_size.end(), lin_size);
+    return 0;
+}
+extern "C" int pse_chain_modes_compute(pse_chain_modes *obj, const pse_double4 *pos, double *modes, double *sums, double *sample) {
+    TRY(chain_modes_compute_validate(obj, pos, modes, sums, sample));
+    pse_handle *h = obj->h;
+    HIPCHK(hipSetDevice(h->device));
+    launch_chain_modes((const double4 *)pos, h->dbox, obj->mm, modes, sums, sample, h->stream);
+    HIPCHK(hipGetLastError());
+    obj->computed = true;
+    return 0;
+}
+extern "C" int pse_chain_modes_store(pse_chain_modes *obj, int slot) {
+    TRY(chain_modes_store_validate(obj, obj ? obj->norigins : 0, obj ? obj->computed : false, slot));
+    pse_handle *h = obj->h;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t buf = (size_t)3 * obj->mm.K * obj->mm.nlin;
+    HIPCHK(hipMemcpyAsync(obj->mm.slots + (size_t)slot * buf, obj->mm.cur, buf * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    obj->stored |= 1ull << slot;
+    return 0;
+}
+extern "C" int pse_chain_modes_correlate(pse_chain_modes *obj, int npairs, const int *slots_host, const int *rows_host, int nrows, double *corr) {
+    TRY(chain_modes_correlate_validate(obj, obj ? obj->norigins : 0, obj ? obj->computed : false, obj ? obj->stored : 0ull, npairs, slots_host,
+                                       rows_host, nrows, corr));
+    pse_handle *h = obj->h;
+    HIPCHK(hipSetDevice(h->device));
+    ModePairs pairs{};
+    pairs.npairs = npairs;
+    for (int q = 0; q < npairs; ++q) { pairs.slot[q] = (unsigned char)slots_host[q]; pairs.row[q] = rows_host[q]; }
+    launch_chain_modes_correlate(obj->mm, pairs, corr, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -617,6 +617,79 @@ class MoleculePairs(_DeviceObject):
         self.nmol, self.nmol_type, self.terms = int(nmol.value), nmol_type.astype(np.int64), terms.astype(np.int64)
 
 
+CHAIN_MODES_MAX = 32      # PSE_CHAIN_MODES_MAX: functionals of one ChainModes
+CHAIN_MODES_STATIC = 6    # PSE_CHAIN_MODES_STATIC: xx, yy, zz, xy, xz, yz
+CHAIN_MODES_CORR = 9      # PSE_CHAIN_MODES_CORR: 3 alpha + beta, alpha of now, beta of the origin
+
+
+def host_rouse_weights(m, nmodes):
+    """The (nmodes, m) weights of pse_host_rouse_weights for a chain of m members (host only): row 0 the end-to-end functional
+    (-1, 0, ..., 0, +1), rows p >= 1 the Rouse modes cos(pi p (2 q + 1) / (2 m)) / m with the argument reduced in integers."""
+    import numpy as np
+    m, nmodes = int(m), int(nmodes)
+    if not 0 <= m <= 2 ** 24 or not -2 ** 31 <= nmodes < 2 ** 31:
+        raise ValueError("m outside [0, 2^24] or nmodes no C int")
+    out = np.zeros((min(max(nmodes, 1), CHAIN_MODES_MAX), max(m, 1)))   # (the library refuses what would not fit before it writes)
+    _lib.check(_lib.load().pse_host_rouse_weights(m, nmodes, _vp(out)))
+    return out
+
+
+def _chain_modes_arguments(sizes, weights, norigins):
+    """The tables of a ChainModes, checked before the device is touched: (sizes uint32 (nsizes,), weights float64 flat, K, norigins).
+    `sizes`: the distinct sizes of the linear molecules, ascending; `weights`: one (K, m) array per size, finite."""
+    import numpy as np
+    sizes = np.asarray(sizes)
+    if sizes.ndim != 1 or sizes.shape[0] == 0 or not np.issubdtype(sizes.dtype, np.integer) or sizes.min() < 2 or np.any(np.diff(sizes) <= 0):
+        raise ValueError("sizes must be a non-empty ascending 1-D sequence of distinct molecule sizes >= 2")
+    tables = [np.asarray(w, dtype=np.float64) for w in weights]
+    if len(tables) != sizes.shape[0]:
+        raise ValueError(f"weights has {len(tables)} tables, sizes {sizes.shape[0]} entries")
+    K = tables[0].shape[0] if tables[0].ndim == 2 else 0
+    if not 1 <= K <= CHAIN_MODES_MAX:
+        raise ValueError(f"a weight table must be (K, m) with K in [1, {CHAIN_MODES_MAX}]")
+    for m, w in zip(sizes.tolist(), tables):
+        if w.shape != (K, m):
+            raise ValueError(f"the weight table of size {m} has the shape {w.shape}, not {(K, m)}")
+        if not np.isfinite(w).all():
+            raise ValueError(f"the weight table of size {m} holds a value that is not finite")
+    norigins = int(norigins)
+    if not 0 <= norigins <= MSD_MAX_ORIGINS:
+        raise ValueError(f"norigins = {norigins} outside [0, {MSD_MAX_ORIGINS}]")
+    flat = np.ascontiguousarray(np.concatenate([w.ravel() for w in tables]))
+    return np.ascontiguousarray(sizes, dtype=np.uint32), flat, K, norigins
+
+
+class ChainModes(_DeviceObject):
+    """Owner of a pse_chain_modes object: the molecules of a bond topology as for a MoleculeTopology (`pairs`, `mol_types`, `ntypes`,
+    `n`), K weight rows per distinct size of the LINEAR molecules (`sizes` ascending, `weights` one (K, m) array per size) and
+    `norigins` <= 64 origin slots (0: static only).  Pass it as `modes` to Engine.chain_modes_compute, chain_modes_store and
+    chain_modes_correlate.  nmol, nlin, nlin_type (per type), lin_mol and lin_size (per linear molecule, in the order of the device
+    arrays) are read once at creation (host words: no device wait)."""
+
+    DESTROY = "pse_chain_modes_destroy"
+
+    def __init__(self, engine, pairs, sizes, weights, mol_types=None, ntypes=1, norigins=0, n=None):
+        import numpy as np
+        pairs, mol_types, self.ntypes, _, _, _ = _molecule_arguments(pairs, mol_types, ntypes, 0, None, None)
+        sizes, flat, self.K, self.norigins = _chain_modes_arguments(sizes, weights, norigins)
+        self.n = _rows(engine, n)
+        if mol_types is not None:   # (the library reads nmol entries: the count has to be right before it does)
+            from .analyze import molecules_of
+            nmol = molecules_of(self.n, pairs)[1]
+            if mol_types.shape[0] != nmol:
+                raise ValueError(f"molecule_types has {mol_types.shape[0]} entries, the bonds make {nmol} molecules")
+        self._create(engine, "pse_chain_modes_create", self.n, pairs.shape[0], _vp(pairs), _vp(mol_types), self.ntypes, self.K,
+                     int(sizes.shape[0]), _vp(sizes), _vp(flat), self.norigins)
+        c_nmol, c_nlin, nlin_type = ctypes.c_uint(0), ctypes.c_uint(0), np.zeros(self.ntypes, dtype=np.uint32)
+        _lib.check(self._lib.pse_chain_modes_counts(self._obj, ctypes.byref(c_nmol), ctypes.byref(c_nlin), _vp(nlin_type), None, None))
+        self.nmol, self.nlin, self.nlin_type = int(c_nmol.value), int(c_nlin.value), nlin_type.astype(np.int64)
+        lin_mol, lin_size = np.zeros(self.nlin, dtype=np.uint32), np.zeros(self.nlin, dtype=np.uint32)
+        _lib.check(self._lib.pse_chain_modes_counts(self._obj, None, None, None, _vp(lin_mol), _vp(lin_size)))
+        self.lin_mol, self.lin_size = lin_mol.astype(np.int64), lin_size.astype(np.int64)
+        self.computed = False     # chain_modes_compute has been queued
+        self.stored = set()       # the slots that hold a buffer
+
+
 def _cluster_arguments(types, ntypes, rlink, name="rlink"):
     """The arguments of a ClusterLinks, checked before the device is touched: (types uint32 (n,) or None, ntypes, rlink float64 (npt,)).
     `rlink`: a scalar (every pair type), a dict {(a, b): r} in either key order with a missing pair off, or npt entries in the
@@ -1060,6 +1133,60 @@ class _ForcePasses:
             raise ValueError("inv_rh, curves, sums and sample are all None: nothing to compute")
         _lib.check(self._lib.pse_molecule_pairs_compute(pairs._handle(self), _ptr(pos), _ptr(inv_rh), _ptr(curves), _ptr(sums), _ptr(sample)))
         return inv_rh, curves, sums, sample
+
+    def chain_modes(self, pairs, sizes, weights, mol_types=None, ntypes=1, norigins=0, n=None):
+        """The linear molecules of a bond topology with K weight rows per size and `norigins` origin slots on the device
+        (pse_chain_modes_create; see include/pse_amd.h and ChainModes).  Returns a ChainModes: the `modes` of chain_modes_compute,
+        chain_modes_store and chain_modes_correlate."""
+        return ChainModes(self, pairs, sizes, weights, mol_types, ntypes, norigins, n)
+
+    def chain_modes_compute(self, pos, modes, out=None, sums=None, sample=None):
+        """X_k = sum_q w_{k,q} u_q of every linear molecule at `pos` in the engine's current box (pse_chain_modes_compute), on the
+        offsets that molecules_compute unfolds, into the object's current buffer.  All outputs are contiguous float64 CUDA tensors,
+        any may be None, and all of them: `out` (nlin, K, 3), WRITTEN; `sums` (ntypes, K, 6), ADDED to, and `sample` (ntypes, K, 6),
+        WRITTEN with this call's sums alone: per type and k the sums over the linear molecules of X_x^2, X_y^2, X_z^2, X_x X_y,
+        X_x X_z, X_y X_z.  Queue-only: nothing is read back, no floating-point atomics: equal inputs give equal bits.  Returns the three."""
+        import torch
+        _chk4(pos, "pos", modes.n)
+        shapes = ((out, "out", (modes.nlin, modes.K, 3)), (sums, "sums", (modes.ntypes, modes.K, CHAIN_MODES_STATIC)),
+                  (sample, "sample", (modes.ntypes, modes.K, CHAIN_MODES_STATIC)))
+        for t, name, shape in shapes:
+            if t is not None and not (_is_cuda(t, torch.float64) and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {shape} {torch.float64} CUDA tensor")
+        _lib.check(self._lib.pse_chain_modes_compute(modes._handle(self), _ptr(pos), _ptr(out), _ptr(sums), _ptr(sample)))
+        modes.computed = True
+        return out, sums, sample
+
+    def chain_modes_store(self, modes, slot):
+        """The current buffer of `modes` into its origin slot `slot` (pse_chain_modes_store).  Queue-only."""
+        slot = int(slot)
+        if not 0 <= slot < modes.norigins:
+            raise ValueError(f"slot = {slot} outside [0, {modes.norigins})")
+        if not modes.computed:
+            raise ValueError("no chain_modes_compute yet: the current buffer holds nothing")
+        _lib.check(self._lib.pse_chain_modes_store(modes._handle(self), slot))
+        modes.stored.add(slot)
+
+    def chain_modes_correlate(self, modes, slots, rows, corr):
+        """One sample of the time correlations (pse_chain_modes_correlate): for every pair (slots[q], rows[q]), type a and k,
+        corr[rows[q], a, k, alpha, beta] += the sum over the linear molecules of type a of X_alpha(current buffer) X_beta(slot).
+        `corr`: a contiguous (nrows, ntypes, K, 3, 3) float64 CUDA tensor, ADDED to; at most 64 pairs, every slot stored before, no
+        row twice.  Queue-only: nothing is read back, no atomics, equal inputs give equal bits.  Returns corr."""
+        import torch
+        if not (_is_cuda(corr, torch.float64) and corr.dim() == 5 and corr.shape[0] >= 1
+                and tuple(corr.shape[1:]) == (modes.ntypes, modes.K, 3, 3)):
+            raise ValueError(f"corr must be a contiguous (nrows, {modes.ntypes}, {modes.K}, 3, 3) float64 CUDA tensor")
+        if modes.norigins == 0:
+            raise ValueError("these modes were made with norigins = 0: there is no origin to correlate with")
+        if not modes.computed:
+            raise ValueError("no chain_modes_compute yet: the current buffer holds nothing")
+        slots, rows = _msd_pairs(slots, rows, modes.norigins, int(corr.shape[0]))
+        missing = sorted(set(slots.tolist()) - modes.stored)
+        if missing:
+            raise ValueError(f"slot {missing[0]} was never stored")
+        _lib.check(self._lib.pse_chain_modes_correlate(modes._handle(self), int(slots.shape[0]), _vp(slots), _vp(rows), int(corr.shape[0]),
+                                                       _ptr(corr)))
+        return corr
 
     def exclusions(self, pairs, n=None):
         """A set of excluded pairs on the device (pse_exclusions_create; HOOMD's nlist.reset_exclusions): `pairs` (npairs, 2)
