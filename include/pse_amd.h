@@ -193,7 +193,11 @@ int pse_random_psi(pse_handle *h, pse_double4 *psi, const unsigned int *group_me
 
 /* -- introspection used by the parity tests ------------------------------------------------------------ */
 /* evaluate the device's real-space functions f(r), g(r) (the replacement of the m_ewaldC1 table,
- * PSEv1/Stokes.cc:334-422) at n host radii -> host arrays */
+ * PSEv1/Stokes.cc:334-422) at n host radii -> host arrays.  Accuracy: the table is degree 9 on intervals of width 1/8, and what that
+ * format costs depends on xi (tests/realspace_ref.py format_eps, from the closed forms alone): below 3e-15 for xi <= 2, 7e-15 at 3,
+ * 6.6e-14 at 4 -- the contract |f - f_ref|, |g - g_ref| < 2e-13 holds up to XI_TABLE = 4 -- then 4.9e-13 at xi = 6, 2.1e-10 at 10,
+ * 2e-8 at 20 (larger xi is admitted, at that accuracy).  PSE_ERR_INVALID for an r outside (0, (ceil(8 rcut) + 1) / 8 (1 - 2^-50)): the
+ * kernel looks up r^2 rsqrt(r^2), which may exceed r in its last bits, and no interval lies behind the last one. */
 int pse_eval_realspace(pse_handle *h, const double *r_host, int n, double *f_host, double *g_host);
 /* Force provider next to the path (the step consumes net_force from its host, PSEv1/Stokes.cc:447, and the
  * reference's example has none): soft repulsion F_i = sum_j k (sigma - r)(r_i - r_j)/r over minimum-image pairs with
@@ -1078,6 +1082,12 @@ int pse_host_lanczos_sqrt_e1(int m, const double *alpha, const double *beta, dou
  * decision without `first`, anything but 1 <= m_lo <= m_hi <= done_iters <= 100, pending_beta outside [0, m_hi], m_max > 100.  A
  * non-finite coefficient or a failed eigen-solve is status 2 in the outcome, not an error of this call. */
 int pse_host_lz_decide(const double *scal_host, int n_dec, const pse_debug_lz_decision *dec, double open0, pse_debug_lz_outcome *out);
+/* host-only: the real-space table a handle of (xi, rcut) holds on the device (build_realspace_table, pse_params.cpp), without creating
+ * one.  n_intervals = ceil(8 rcut) + 1 intervals of width 1/8; interval k is 20 doubles at coef[20 k]: ten coefficients of f_w and ten
+ * of g_w in powers of t = 2 (8 r - k) - 1, lowest first (the smooth parts: f = f_RPY - f_w, g = g_RPY - g_w).  *n_intervals is set
+ * whenever xi and rcut are valid, so a first call with cap = 0 sizes the array.  PSE_ERR_INVALID: xi or rcut not positive,
+ * 8 rcut >= 1e6, a null pointer, cap (in doubles) below 20 n_intervals. */
+int pse_host_realspace_table(double xi, double rcut, int cap, double *coef, int *n_intervals);
 /* host-only: the parameter rule of Stokes::setParams (PSEv1/Stokes.cc:129-236,319) without creating a handle */
 int pse_host_select_params(const pse_params *params, pse_info *info);
 /* host-only: the per-particle rows a pse_bonds object stores (pse_bonds_create calls this after validating).  A CSR over the n

@@ -231,6 +231,7 @@ SYMBOLS = {
     "pse_host_lanczos_sqrt_e1": (_i, [_i, _dp, _dp, _dp]),
     "pse_host_lz_decide": (_i, [_dp, _i, ctypes.POINTER(pse_debug_lz_decision), _d, ctypes.POINTER(pse_debug_lz_outcome)]),
     "pse_host_select_params": (_i, [ctypes.POINTER(pse_params), ctypes.POINTER(pse_info)]),
+    "pse_host_realspace_table": (_i, [_d, _d, _i, _dp, ctypes.POINTER(ctypes.c_int)]),
 }
 
 _lib = None

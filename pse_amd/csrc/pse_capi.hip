@@ -2341,8 +2341,10 @@ extern "C" int pse_random_psi(pse_handle *h, pse_double4 *psi, const unsigned *g
 extern "C" int pse_eval_realspace(pse_handle *h, const double *r_host, int n, double *f_host, double *g_host) {
     if (!h || !r_host || !f_host || !g_host || n <= 0) return fail(PSE_ERR_INVALID, "bad argument");
     HIPCHK(hipSetDevice(h->device));
+    // The kernel looks up r' = r^2 rsqrt(r^2), not r: three roundings, r' <= r (1 + 2^-51).  An r within that of the table's end could
+    // index the interval behind the last one, so the end is refused with that margin (2^-50: the product below rounds once more).
     for (int i = 0; i < n; ++i)
-        if (!(r_host[i] > 0.0) || r_host[i] * RS_PER_UNIT >= h->n_intervals)
+        if (!(r_host[i] > 0.0) || r_host[i] * RS_PER_UNIT * (1.0 + 0x1p-50) >= h->n_intervals)
             return fail(PSE_ERR_INVALID, "r[%d] = %g outside the table range (0, %g)", i, r_host[i], (double)h->n_intervals / RS_PER_UNIT);
     double *buf = nullptr;
     HIPCHK(hipMalloc((void **)&buf, (size_t)3 * n * sizeof(double)));

@@ -61,6 +61,7 @@ std::string select_params(const Box &box, double xi, double error, double max_st
 // are the *smooth* (free-space wave) parts; the device adds the analytic RPY branch:
 //   f = f_RPY - f_w, g = g_RPY - g_w   (replaces m_ewaldC1, PSEv1/Stokes.cc:334-422).
 void build_realspace_table(double xi, double rcut, std::vector<double> &coef, int &n_intervals);
+int realspace_table_intervals(double rcut);   // ceil(8 rcut) + 1: the interval that holds rcut, and one beyond
 
 // Symmetric tridiagonal eigen-decomposition (implicit QL), replaces LAPACKE_spteqr (PSEv1/Brownian.cu:540).
 // d[0..n) diagonal, e[0..n-1) off-diagonal. On return d = eigenvalues, z (n x n, row-major) = eigenvectors in

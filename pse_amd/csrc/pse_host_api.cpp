@@ -881,6 +881,22 @@ extern "C" int pse_host_select_params(const pse_params *p, pse_info *info) {
     return 0;
 }
 
+extern "C" int pse_host_realspace_table(double xi, double rcut, int cap, double *coef, int *n_intervals) {
+    const char *who = "pse_host_realspace_table";
+    if (!n_intervals) return fail(PSE_ERR_INVALID, "%s: null n_intervals", who);
+    if (!(xi > 0.0) || !std::isfinite(xi)) return fail(PSE_ERR_INVALID, "%s: xi = %g must be positive", who, xi);
+    if (!(rcut > 0.0) || !(rcut * RS_PER_UNIT < 1e6)) return fail(PSE_ERR_INVALID, "%s: rcut = %g outside (0, %g)", who, rcut, 1e6 / RS_PER_UNIT);
+    *n_intervals = realspace_table_intervals(rcut);
+    if (!coef) return fail(PSE_ERR_INVALID, "%s: null coef", who);
+    if (cap < *n_intervals * 2 * RS_NCOEF)
+        return fail(PSE_ERR_INVALID, "%s: cap = %d doubles, the table of rcut = %g has %d intervals of %d", who, cap, rcut, *n_intervals, 2 * RS_NCOEF);
+    std::vector<double> c;
+    int n = 0;
+    build_realspace_table(xi, rcut, c, n);
+    std::copy(c.begin(), c.end(), coef);
+    return 0;
+}
+
 extern "C" int pse_host_lanczos_sqrt_e1(int m, const double *alpha, const double *beta, double *t) {
     if (m < 1 || m > 4096 || !alpha || !beta || !t) return fail(PSE_ERR_INVALID, "bad argument");
     std::vector<double> tv;

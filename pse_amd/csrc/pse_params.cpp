@@ -92,9 +92,16 @@ static ld sph_j1_over_x(ld x) {
 //   M_wave(r) = (1/(2pi)^3) Int (6 pi / k^2) H(k) sinc^2(k a) (I - kk) e^{ik.r} d^3k,  H = (1+k^2/4xi^2) e^{-k^2/4xi^2}
 // (k-space factor: PSEv1/Helper.cu:326 x PSEv1/Mobility.cu:290), after the angular integration:
 //   f_w = (3/pi) Int_0^inf H sinc^2 [ j0(kr) - j1(kr)/(kr) ] dk,   g_w = (3/pi) Int_0^inf H sinc^2 2 j1(kr)/(kr) dk.
+// Panels of the composite rule: at most half a period of the fastest factor, pi / (r + 3), AND at most 4 xi, a fraction of the width
+// 2 xi of H -- without the second bound a small xi put the whole of H (1 down to 1e-19) into one 16-point panel and the table was off
+// by 6.6e-10 at xi = 0.05.  How the 4 was chosen: over xi = 0.02 .. 20 and r = 1e-3 .. rcut, halving the factor from 4 (and from 2, 1,
+// ... 1/8) moves no value by more than 9e-18, the rounding of the long-double sums, while from 8 it moves them by 1e-16; the rule's
+// error goes like the 32nd power of the width, so 4 is nine orders below that.  Tables of xi >= pi / 12 = 0.262 are bit for bit what
+// they were: there pi / (r + 3) is the smaller bound at every r.
+static const ld PANEL_PER_XI = 4.0L;
 static void wave_fg(ld r, ld xi, ld &f, ld &g) {
     const ld kmax = 2.0L * xi * sqrtl(48.0L);
-    ld dk = PI_L / (r + 3.0L);
+    ld dk = std::min(PI_L / (r + 3.0L), PANEL_PER_XI * xi);
     const int np = (int)ceill(kmax / dk);
     dk = kmax / np;
     ld sf = 0, sg = 0;
@@ -116,7 +123,7 @@ static void wave_fg(ld r, ld xi, ld &f, ld &g) {
 }
 
 void build_realspace_table(double xi, double rcut, std::vector<double> &coef, int &n_intervals) {
-    n_intervals = (int)std::ceil(rcut * RS_PER_UNIT) + 1;
+    n_intervals = realspace_table_intervals(rcut);
     coef.assign((size_t)n_intervals * 2 * RS_NCOEF, 0.0);
     const int n = RS_NCOEF;
     // Chebyshev -> monomial conversion matrix T_q(t) = sum_p C[q][p] t^p
@@ -156,6 +163,8 @@ void build_realspace_table(double xi, double rcut, std::vector<double> &coef, in
         pool.emplace_back([&, w] { for (int k = w; k < n_intervals; k += nt) fit(k); });
     for (auto &th : pool) th.join();
 }
+
+int realspace_table_intervals(double rcut) { return (int)std::ceil(rcut * RS_PER_UNIT) + 1; }
 
 // ---- symmetric tridiagonal eigen-solver (implicit QL with Wilkinson shifts) ------------------------------
 bool tridiag_eigen(int n, std::vector<double> &d, std::vector<double> &e_in, std::vector<double> &z) {

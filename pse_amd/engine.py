@@ -62,6 +62,18 @@ def host_select_params(box, xi=0.5, error=1e-3, max_strain=0.5, grid=(0, 0, 0), 
     return info.as_dict()
 
 
+def host_realspace_table(xi, rcut):
+    """The real-space table of (xi, rcut) as the device holds it, host only: array (n_intervals, 2, 10) -- per interval of width 1/8
+    the coefficients of f_w and of g_w in powers of t = 2 (8 r - k) - 1, lowest first."""
+    import numpy as np
+    lib = _lib.load()
+    n = ctypes.c_int(0)
+    lib.pse_host_realspace_table(xi, rcut, 0, None, ctypes.byref(n))   # sizes the array (and reports a bad xi or rcut below)
+    coef = np.zeros(max(n.value, 0) * 20)
+    _lib.check(lib.pse_host_realspace_table(xi, rcut, len(coef), coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(n)))
+    return coef.reshape(n.value, 2, 10)
+
+
 def host_lanczos_sqrt_e1(alpha, beta):
     """t = T^{1/2} e_1 (host); alpha[0..m), beta[0..m] with beta[0] unused."""
     import numpy as np

@@ -43,7 +43,17 @@ C_S = 2.0                    # the c of eps_ij (derivation above: 1.9198 rounded
 EPS_F = 2.0 ** -25           # rounding of fr
 EPS_ABS = 2.0 ** -198        # an exponent clamped at -100
 VEC_ROWS = math.sqrt(3.0) * 2.0 ** -39
-TABLE = 6e-13                # the device's f, g come from a table held to the closed forms at 2e-13 each (|df| + |d(g - f)|)
+
+
+def table(xi, rcut):
+    """What the device's table adds to a pair term, |df| + |d(g - f)| <= 3 max(|df|, |dg|).  Up to xi = XI_TABLE the table is held to
+    the closed forms at 2e-13 each (tests/test_realspace_table_cpu.py: the format allows it): 6e-13.  Beyond, degree 9 on eighths
+    cannot follow a function of scale 1 / xi and the table is as good as its format: 3 format_eps(xi, rcut), from the mpmath closed
+    forms alone (tests/realspace_ref.py) -- 6.2e-10 at xi = 10, still below the 2^-25 of the records."""
+    import realspace_ref
+    if xi <= realspace_ref.XI_TABLE:
+        return 6e-13
+    return 3.0 * realspace_ref.format_eps(xi, rcut)
 
 
 def pair_eps(f, g, r=None):

@@ -98,6 +98,7 @@ def test_mreal_on_every_pass(name):
         f, g = eng.eval_realspace(r)
         fo, go = oracle.fg_real(r, c["xi"])
         print(f"global_table: max |f - f_ref| = {np.abs(f - fo).max():.3e}, max |g - g_ref| = {np.abs(g - go).max():.3e}", flush=True)
+        # 2e-13: the table's contract for xi <= XI_TABLE = 4 (tests/test_realspace_table_cpu.py: the format allows it there, no further)
         assert np.abs(f - fo).max() < 2e-13 and np.abs(g - go).max() < 2e-13                     # MI355X: 1.2e-16, 1.7e-16
     ref = oracle.mobility_real(pos, force, box, c["xi"], c["rcut"], rounded=False)
     _, b0, r0 = eng.neighbor_stats()

@@ -44,8 +44,11 @@ def _child(code, env_extra):
 # -- 1. the truth where the records fail ------------------------------------------------------------------------------------------
 # Measured on an MI355X (relative error against M^{1/2} psi of the dense un-rounded operator; the records measured 2.7e-7 at c and 7.0e-7
 # at f, tests/test_gpu_lanczos_truth.py): 4e-12 at a, m = 20, tol 1e-10; c (r = 1e-3 .. 2: condition 3.6e3, m = 95 without
-# reorthogonalisation) 1.0e-8; f (xi = 10) 2.4e-9 at m = 13 -- above the table's own bound (record_bound.TABLE: <= 4e-11 at every
-# geometry), so the floor there is not the operator's rounding.  FLOOR holds every geometry an order below what the records reach.
+# reorthogonalisation) 1.0e-8; f (xi = 10) 2.4e-9 at m = 13.  That last floor is the table's: at xi = 10 degree 9 on eighths follows f, g
+# to 2.1e-10 only (format_eps, tests/realspace_ref.py; record_bound.table(10, rcut) = 6.2e-10), and the dense un-rounded M_real of that
+# geometry with f, g read from the host's table instead of the closed forms moves M^{1/2} psi by 2.43e-9 relative
+# (tests/test_realspace_table_cpu.py test_table_error_accounts_for_the_fp64_floor_at_xi_10) -- the operator's arithmetic adds nothing
+# that can be seen.  FLOOR holds every geometry an order below what the records reach.
 FLOOR = 2e-8
 
 

@@ -37,7 +37,7 @@ def test_sqrt_mreal_against_the_unrounded_operator(torch_cuda, oracle, name):
     psi = np.random.default_rng(n).normal(size=(n, 3))
     eng = pse_amd.Engine(n, box, xi=xi, error=g["error"])
     assert abs(eng.info()["rcut"] - g["rcut"]) < 1e-12
-    t = rb.truth(oracle, pos, box, xi, g["rcut"], psi, extra_pair=rb.TABLE, vector_rows=True)
+    t = rb.truth(oracle, pos, box, xi, g["rcut"], psi, extra_pair=rb.table(xi, g["rcut"]), vector_rows=True)
     # tol = 1e-10 where the iteration converges within the basis cap; otherwise the smallest tolerance that does, added to the bound
     for tol in (1e-10, 1e-9, 1e-8):
         out, m = eng.sqrt_mreal(to4(pos), to4(psi), tol=tol)

@@ -31,6 +31,8 @@ def test_realspace_functions_match_closed_form(torch_cuda, oracle):
         r = np.concatenate([np.random.default_rng(1).uniform(1e-3, rcut, 2000), [2.0, 1.999999, 2.000001, 0.125, 1e-4]])
         f, g = eng.eval_realspace(r)
         fo, go = oracle.fg_real(r, xi)
+        # 2e-13: the table's contract for xi <= XI_TABLE = 4 -- the format itself allows it there and not beyond (format_eps < 2e-13,
+        # tests/test_realspace_table_cpu.py; the oracle is held to the closed forms at 2 u in the same file)
         assert np.abs(f - fo).max() < 2e-13, (xi, np.abs(f - fo).max())
         assert np.abs(g - go).max() < 2e-13, (xi, np.abs(g - go).max())
         eng.close()
@@ -150,7 +152,7 @@ def test_lanczos_sqrt_matches_dense(torch_cuda, oracle):
     M = np.stack([oracle.mobility_real(pos, eye[c].reshape(n, 3), box, 0.5, rcut, rounded=True).ravel() for c in range(3 * n)], 1)
     psi = np.random.default_rng(5).normal(size=(n, 3))
     ref = (sl.sqrtm(M).real @ psi.ravel()).reshape(n, 3)
-    truth = record_bound.truth(oracle, pos, box, 0.5, rcut, psi, extra_pair=record_bound.TABLE, vector_rows=True)
+    truth = record_bound.truth(oracle, pos, box, 0.5, rcut, psi, extra_pair=record_bound.table(0.5, rcut), vector_rows=True)
     for tol, bound in ((1e-3, 5e-3), (1e-8, 1e-7)):
         out, m = eng.sqrt_mreal(to4(pos), to4(psi), tol=tol)
         e = rel(out.cpu().numpy()[:, :3], ref)
