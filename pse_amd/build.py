@@ -1,6 +1,6 @@
 """Builds libpse_amd.so (HIP kernels + C-ABI) and the pybind11 host module in-tree with hipcc for gfx950.
 
-Run as `python -m pse_amd.build` or through __graft_entry__.build(). No cmake: one hipcc call per translation unit (LIB_UNITS) and one link.  Of the units, pse_capi.hip (the driver) and pse_objects.hip (the device
+Run as `python -m pse_amd.build` or through __graft_entry__.build(). No cmake: one hipcc call per translation unit (LIB_UNITS) and one link.  Of the units, pse_engine.hip (the handle's life cycle), pse_capi.hip (the driver) and pse_objects.hip (the device
 objects and their entry points) are host code that launches through the wrappers of the kernel units: pse_kernels.hip (cell sort, near
 field), pse_farfield.hip (spread, gather), pse_fft.hip and pse_zfft.hip (the transforms), pse_vectors.hip (Lanczos, integrator),
 pse_local.hip (owned-particle ranks), pse_forces.hip (the force providers), pse_analysis.hip (histogram, clusters, structure factor,
@@ -51,7 +51,7 @@ def _all_sources():
     return out
 
 
-LIB_UNITS = (("pse_kernels.hip", HIPFLAGS), ("pse_farfield.hip", HIPFLAGS + FARFLAGS), ("pse_capi.hip", HIPFLAGS), ("pse_local.hip", HIPFLAGS), ("pse_zfft.hip", HIPFLAGS),
+LIB_UNITS = (("pse_kernels.hip", HIPFLAGS), ("pse_farfield.hip", HIPFLAGS + FARFLAGS), ("pse_capi.hip", HIPFLAGS), ("pse_engine.hip", HIPFLAGS), ("pse_local.hip", HIPFLAGS), ("pse_zfft.hip", HIPFLAGS),
              ("pse_fft.hip", HIPFLAGS), ("pse_vectors.hip", HIPFLAGS),
              ("pse_forces.hip", HIPFLAGS), ("pse_analysis.hip", HIPFLAGS), ("pse_order.hip", HIPFLAGS), ("pse_molecules.hip", HIPFLAGS), ("pse_molpairs.hip", HIPFLAGS), ("pse_molmodes.hip", HIPFLAGS), ("pse_objects.hip", HIPFLAGS),
              ("pse_params.cpp", ["-x", "c++"]), ("pse_host_api.cpp", ["-x", "c++"]))

@@ -1,5 +1,6 @@
-// What the units of the C-ABI share (pse_capi.hip: the handle's life cycle and the step driver; pse_objects.hip: the device objects and
-// their passes): the handle, the error macros, prepare() and the base of the device objects.  Internal to those two units.
+// What the units of the C-ABI share (pse_engine.hip: the handle's life cycle; pse_capi.hip: the step driver and the teams;
+// pse_objects.hip: the device objects and their passes): the handle, the owners of what it acquires, the error macros, the few
+// functions that two units call and the base of the device objects.  Internal to those three units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
@@ -12,6 +13,7 @@
 #include "pse_host.h"
 #include "pse_kernels.h"
 #include "pse_farfield.h"
+#include "pse_fft.h"
 #include "pse_vectors.h"
 #include "pse_local.h"
 
@@ -27,6 +29,101 @@ using namespace pse;
         int r_ = (x);       \
         if (r_) return r_;  \
     } while (0)
+
+#define FFTCHK(x)                                                                                      \
+    do {                                                                                               \
+        rocfft_status s_ = (x);                                                                        \
+        if (s_ != rocfft_status_success) return fail(PSE_ERR_FFT, "%s failed: rocfft status %d (%s:%d)", #x, (int)s_, __FILE__, __LINE__); \
+    } while (0)
+
+// The owners of what a handle, a team or a device object acquires, one per kind of resource.  A resource is registered where it is
+// made, by the owner's make function, and released with the owner -- by release() or by the destructor, however far a create got.
+struct DeviceArrays {
+    DeviceArrays() = default;
+    DeviceArrays(const DeviceArrays &) = delete;
+    ~DeviceArrays() { release(); }
+    hipError_t make(void **p, size_t bytes) {
+        *p = nullptr;
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) v.push_back(*p);
+        return e;
+    }
+    void replace(void *was, void *now) {   // `now` is owned in place of `was`, which goes back to the caller (place_grids)
+        for (void *&q : v) if (q == was) q = now;
+    }
+    void release() { for (void *p : v) (void)hipFree(p); v.clear(); }
+private:
+    std::vector<void *> v;
+};
+struct PinnedBuffers {
+    PinnedBuffers() = default;
+    PinnedBuffers(const PinnedBuffers &) = delete;
+    ~PinnedBuffers() { for (void *p : v) (void)hipHostFree(p); }
+    hipError_t make(void **p, size_t bytes, unsigned flags = hipHostMallocDefault) {
+        *p = nullptr;
+        const hipError_t e = hipHostMalloc(p, bytes, flags);
+        if (e == hipSuccess) v.push_back(*p);
+        return e;
+    }
+    void drop(void *p) {   // one buffer ahead of the rest (a staging buffer that was outgrown); null: nothing
+        for (size_t k = 0; k < v.size(); ++k) if (v[k] == p) { (void)hipHostFree(p); v.erase(v.begin() + k); return; }
+    }
+private:
+    std::vector<void *> v;
+};
+struct Events {
+    Events() = default;
+    Events(const Events &) = delete;
+    ~Events() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+    hipError_t make(hipEvent_t *ev, unsigned flags = hipEventDefault) {
+        *ev = nullptr;
+        const hipError_t e = hipEventCreateWithFlags(ev, flags);
+        if (e == hipSuccess) v.push_back(*ev);
+        return e;
+    }
+private:
+    std::vector<hipEvent_t> v;
+};
+struct Streams {
+    Streams() = default;
+    Streams(const Streams &) = delete;
+    ~Streams() { for (hipStream_t s : v) (void)hipStreamDestroy(s); }
+    hipError_t make(hipStream_t *s, unsigned flags, const int *priority = nullptr) {   // priority null: the default one
+        *s = nullptr;
+        const hipError_t e = priority ? hipStreamCreateWithPriority(s, flags, *priority) : hipStreamCreateWithFlags(s, flags);
+        if (e == hipSuccess) v.push_back(*s);
+        return e;
+    }
+    void synchronize() { for (hipStream_t s : v) (void)hipStreamSynchronize(s); }
+private:
+    std::vector<hipStream_t> v;
+};
+struct FftPlans {   // rocFFT plans (double precision) and execution infos
+    FftPlans() = default;
+    FftPlans(const FftPlans &) = delete;
+    ~FftPlans() { release(); }
+    rocfft_status plan(rocfft_plan *p, rocfft_result_placement placement, rocfft_transform_type type, size_t dims, const size_t *len, size_t batch,
+                       rocfft_plan_description desc) {
+        *p = nullptr;
+        const rocfft_status s = rocfft_plan_create(p, placement, type, rocfft_precision_double, dims, len, batch, desc);
+        if (s == rocfft_status_success) plans.push_back(*p);
+        return s;
+    }
+    rocfft_status info(rocfft_execution_info *i) {
+        *i = nullptr;
+        const rocfft_status s = rocfft_execution_info_create(i);
+        if (s == rocfft_status_success) infos.push_back(*i);
+        return s;
+    }
+    void release() {
+        for (rocfft_plan p : plans) rocfft_plan_destroy(p);
+        for (rocfft_execution_info i : infos) rocfft_execution_info_destroy(i);
+        plans.clear(); infos.clear();
+    }
+private:
+    std::vector<rocfft_plan> plans;
+    std::vector<rocfft_execution_info> infos;
+};
 
 constexpr int PH_COUNT_ = 13;   // timed phases (enum PH_* below)
 
@@ -47,7 +144,7 @@ struct pse_handle {
     hipStream_t stream = nullptr;    // main chain: sort, near field, Lanczos, update (caller-visible ordering)
     hipStream_t wstream = nullptr;   // wave-space chain; == stream unless the two chains overlap (single GPU)
     hipStream_t side = nullptr;      // non-blocking stream behind wstream (an in-process team shares one among its members)
-    hipStream_t side_owned = nullptr;
+    hipStream_t side_owned = nullptr; // the one this handle made (streams)
     int *bounds_host = nullptr;      // pinned: slab row boundaries on their way back from the device
     hipEvent_t ev_bounds = nullptr;
     bool bounds_pending = false;
@@ -89,6 +186,13 @@ struct pse_handle {
     int *cell_off = nullptr;
     double *pv_rows = nullptr;   // pse_pair_repulsion_virial: one row of eight partial sums per workgroup of its cell pass
     std::vector<DeviceObject *> topologies;   // the bond, angle and dihedral objects created on this handle and still alive (pse_destroy frees them)
+    // what the handle has acquired, at create or later (the fp64 plane of the pair list, the buffers of the redistribution): every
+    // device array (dmalloc), pinned buffer, event, stream, rocFFT plan and execution info named below belongs to one of these
+    DeviceArrays arrays;
+    FftPlans fft;
+    PinnedBuffers pinned;
+    Streams streams;
+    Events events;
     int *cnt_block = nullptr; // [far-field bin counts | the two flags of the kept neighbour list | cell counts]: zeroed by ONE memset per call
     size_t cnt_bins = 0;      // ints of the bin counts (incl. the sentinel)
     SpreadWork sw = {};       // far-field bins and the bin-ordered particle records (origins, prefac * force, separable weights)
@@ -153,9 +257,8 @@ struct pse_handle {
     void *vq = nullptr;          // [n] 16-byte mirror of the newest Lanczos vector (single GPU; k_lz_update writes it, the pair-list mat-vec gathers from it)
     int place_tried = 0; float place_ms_first = 0, place_ms_kept = 0;   // place_grids: pairs tried, the probe's time on the first and on the kept one
     bool own_z = false;                                      // z transforms by k_zfft_rows (Nz = 256, 512): rocFFT is then off the path
-    double2 *twiddle_z = nullptr, *twiddle_z_owned = nullptr;   // [Nz] exp(-2 pi i m / Nz)
+    double2 *twiddle_z = nullptr;                            // [Nz] exp(-2 pi i m / Nz) (== twiddle when Nz == Nx)
     double2 *twiddle_y = nullptr;                            // [Ny] exp(-2 pi i m / Ny) (== twiddle when Ny == Nx)
-    double2 *twiddle_y_owned = nullptr;
     int grid_slabs = 1;   // slabs the far-field grid is cut into: n_slabs, or 1 when every rank keeps the whole grid
     double2 *twiddle = nullptr;                              // [Nx] exp(-2 pi i m / Nx)
     void *fft_work = nullptr;
@@ -200,23 +303,37 @@ struct pse_handle {
     bool matvec_timed = false;
 };
 
+// *p = a device array of n T (n = 0: of one) that the handle owns and counts in its bytes
+template <class T>
+int dmalloc(pse_handle *h, T **p, size_t n) {
+    if (n == 0) n = 1;
+    const hipError_t e = h->arrays.make((void **)p, n * sizeof(T));
+    if (e != hipSuccess) return fail(PSE_ERR_HIP, "hipMalloc((void **)p, n * sizeof(T)) failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    h->bytes += n * sizeof(T);
+    return 0;
+}
+// pse_engine.hip, called by the driver too: the cell grid of a box, and the rocFFT execution infos bound to h->wstream
+int cells_for(const Box &box, double rc, double gamma, int n_slabs, int bz_want, DCells &out, int xpad = 0);
+int bind_wave_stream(pse_handle *h);
+// pse_capi.hip, called by pse_create too
+ScaleArgs scale_args(pse_handle *h, bool noise, double kT, double dt, unsigned timestep, double xi = 0.0, double eta = 0.0);
+bool team_sstep(const pse_handle *h);
+void roctx_lookup();   // PSE_ROCTX, read once per process
 // The sort, the cell list and the sorted copies of a call's arrays (pse_capi.hip, which also holds the default arguments)
 struct PrepExtra { bool psi; unsigned timestep; };   // psi: the pass also draws the particle noise of this step into psi_s
 int prepare(pse_handle *h, const double4 *pos, const double4 *vec, const unsigned *group, int N, bool defer_bounds, bool need_cells, PrepExtra px,
             bool with_real);
 
+
 // A device object of the C-ABI (pse_objects.hip).  It belongs to the handle it was created on, which deletes what is still alive in
-// pse_destroy, and it owns the device arrays that put() made: the destructor frees them, however far a create got.
+// pse_destroy, and it owns the device arrays that put() made: they are freed with it, however far a create got.
 struct DeviceObject {
     pse_handle *h = nullptr;
     hipError_t err = hipSuccess;   // the first failure of a put()
     size_t bytes = 0;              // asked for so far
     bool zeroed = false;           // a put() zeroed memory (hipMemset on the null stream, which may return early)
     DeviceObject() = default;
-    DeviceObject(const DeviceObject &) = delete;
-    virtual ~DeviceObject() {
-        for (void *p : arrays) (void)hipFree(p);
-    }
+    virtual ~DeviceObject() = default;
     // *dst = a device array of n T: a copy of the host's `src`; src null: zeroed with `zero`, else as allocated.  Returns the first
     // failure of this object: once one put() has failed, the later ones do nothing.
     template <class T>
@@ -225,13 +342,12 @@ struct DeviceObject {
         if (err != hipSuccess) return err;
         void *p = nullptr;
         bytes += n * sizeof(T);
-        if ((err = hipMalloc(&p, n * sizeof(T))) != hipSuccess) return err;
-        arrays.push_back(p);
+        if ((err = arrays.make(&p, n * sizeof(T))) != hipSuccess) return err;
         *dst = (T *)p;
         if (src) err = hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
         else if (zero) { err = hipMemset(p, 0, n * sizeof(T)); zeroed = true; }
         return err;
     }
 private:
-    std::vector<void *> arrays;
+    DeviceArrays arrays;
 };

@@ -12,7 +12,7 @@ from .distributed import _to4
 
 
 def slab_plan(grid, world):
-    """Which x planes / y rows of the far-field grid each rank owns (mirrors create_impl in csrc/pse_capi.hip)."""
+    """Which x planes / y rows of the far-field grid each rank owns (mirrors create_impl in csrc/pse_engine.hip)."""
     nx, ny = grid[0], grid[1]
     if nx % world or ny % world:
         raise ValueError(f"slab decomposition needs Nx and Ny divisible by the number of ranks ({nx} x {ny} over {world})")
@@ -22,13 +22,13 @@ def slab_plan(grid, world):
 
 def halo_planes(P):
     """(below, above): planes a rank stores beside its own x slab so that every particle whose own plane lies in the slab
-    has its whole support available for the gather (create_impl in csrc/pse_capi.hip)."""
+    has its whole support available for the gather (create_impl in csrc/pse_engine.hip)."""
     return (P - 1) // 2, (P + 1) // 2
 
 
 def cell_slabs(ncx, world):
     """Cell layers along x owned by each rank: the near field is sharded by whole cell layers, so the rows of a rank are
-    one contiguous block of the cell-sorted particle arrays (set_cells in csrc/pse_capi.hip rounds ncx down to a
+    one contiguous block of the cell-sorted particle arrays (set_cells in csrc/pse_engine.hip rounds ncx down to a
     multiple of the number of ranks)."""
     ncx = ncx // world * world
     if ncx < max(3, world):
@@ -405,7 +405,7 @@ class LocalLoopbackSimulation:
 
 
 def host_layers(box, world, xi=0.5, error=1e-3, max_strain=0.5, grid=(0, 0, 0), P=0, rcut=0.0, **_):
-    """Cell layers along x of a team of `world` ranks (cells_for in csrc/pse_capi.hip): floor(width / rcut) rounded down to a
+    """Cell layers along x of a team of `world` ranks (cells_for in csrc/pse_engine.hip): floor(width / rcut) rounded down to a
     multiple of the rank count, the width taken at the largest tilt the box will see."""
     from .engine import host_select_params
     info = host_select_params(box, xi=xi, error=error, max_strain=max_strain, grid=grid, P=P, rcut=rcut)

@@ -2,7 +2,7 @@
 planted here is really there) and tests/test_gpu_cell_grids.py (which holds the device's cell-list passes to the O(N^2) references on
 them).  NumPy only; `port` is oracle.pse_port, handed in as in pair_table_ref.py.  Not a test module: nothing here is collected.
 
-The cell rule of the engine (pse_capi.hip cells_for), restated: perpendicular widths w = (Lx / sqrt(1 + g^2), Ly, Lz) with
+The cell rule of the engine (pse_engine.hip cells_for), restated: perpendicular widths w = (Lx / sqrt(1 + g^2), Ly, Lz) with
 g = max(|xy|, max_strain); n = floor(w / r) cells per axis, fewer than three count as one; the cells are stored in blocks of bz = 6
 along z once nz >= 12, else bz = nz.  A handle uses r = rcut + skin while it keeps a neighbour list across calls and r = rcut while
 it does not; skin = 0.4 unless the f, g table is too large for its LDS copy (then 0: one grid).  Every box below is chosen so that
@@ -85,7 +85,7 @@ def pair_sites(n):
 
 
 def kept_list_capacity(n, box, rcut, skin):
-    """Entries per row of the neighbour list kept across calls (pse_capi.hip pse_create): twice the mean count within rcut + skin at the
+    """Entries per row of the neighbour list kept across calls (pse_engine.hip pse_create): twice the mean count within rcut + skin at the
     density of n particles, + 32, at most 512, rounded up to whole groups of four."""
     nbar = n / (box[0] * box[1] * box[2]) * 4.18879020478639 * (rcut + skin) ** 3
     return (max(16, min(int(math.ceil(2.0 * nbar + 32.0)), 512)) + 3) & ~3

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The grid-placement planner of pse_create (place_grids, PSE_PLACE_TRIALS) off / on, alternating, fresh processes in ONE box:
+# The grid-placement planner of pse_create (place_grids in pse_engine.hip, PSE_PLACE_TRIALS) off / on, alternating, fresh processes in ONE box:
 # step time, far-field phases, the candidates' probe times, and what the planner costs at create.
 #   bash tools/debug/place_ab.sh [repeats] [extra bench arguments, e.g. "--n 4194304 --phi 0.3 --grid 512 --steps 8 --warmup 3"]
 mkdir -p gpurun_out/place
