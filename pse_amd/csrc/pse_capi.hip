@@ -855,13 +855,36 @@ static int real(pse_team &T, double4 *pse_handle::*vec, double4 *pse_handle::*ou
 static int update_ranges(const pse_handle *h, int N, int rg[3][2]) { return row_ranges(h, N, 1, rg); }
 
 // ---- what the four Lanczos drivers below share ------------------------------------------------------------------------------------
-// Lanczos vector q of a handle: psi for q = 0, else parked in V[q] (the members of a team have one n_pad); none for q < 0
-static double4 *lz_vec(const pse_handle *h, int q) { return q < 0 ? nullptr : q == 0 ? h->psi_s : h->V + (size_t)q * h->n_pad; }
+// Lanczos vector q of a handle: psi for q = 0, else parked in V[q] (the members of a team have one n_pad); none for q < 0.  THE place
+// that knows the layout of the basis: psi is double4 always, V[q >= 1] rows of three doubles on a rows24 handle (pse_handle.h).
+static VecOut lz_vec(const pse_handle *h, int q) {
+    if (q < 0) return VecOut(nullptr);
+    if (q == 0) return VecOut(h->psi_s);
+    if (h->rows24) return VecOut(reinterpret_cast<double *>(h->V) + (size_t)3 * q * h->n_pad, 1);
+    return VecOut(h->V + (size_t)q * h->n_pad);
+}
+// ... as a double4 array: the drivers of a team, whose kernels (k_lz_block, the Gram sums) read nothing else; never a rows24 handle
+static double4 *lz_vec4(const pse_handle *h, int q) { return reinterpret_cast<double4 *>(lz_vec(h, q).p); }
+// the whole basis for the final combination (row q * n_pad + i in either layout)
+static VecIn lz_basis(const pse_handle *h) { return VecIn(reinterpret_cast<const double *>(h->V), h->rows24 ? 1 : 0); }
+// where a pair-list mat-vec of the iteration leaves y = M x_j: the packed buffer of a rows24 handle, else w_s (where the build pass
+// and real() leave theirs on every handle)
+static VecOut lz_y(const pse_handle *h, bool from_list) { return from_list && h->rows24 ? VecOut(h->w24, 1) : VecOut(h->w_s); }
+// A mat-vec through real() reads its vector as double4 (k_mreal_cells gathers neighbours' rows from it): on a rows24 handle only psi
+// may go that way.  With a pair list (the condition of rows24) the drivers reach real() at iteration 0 alone -- it builds the list,
+// and every later iteration runs on it -- unless a call between the build and the iteration invalidated the list while M psi was
+// kept (pse_set_lanczos_operator): that iteration is refused before anything is read.
+static int lz_real_ok(const pse_handle *h, int j) {
+    if (j > 0 && h->rows24)
+        return fail(PSE_ERR_INVALID, "Lanczos iteration %d would walk the cells on a basis in 24-byte rows: the pair list of this call is "
+                    "no longer valid (was the Lanczos operator changed after the list was built?); repeat the call", j);
+    return 0;
+}
 // the two-step block that starts at iteration j (full), or the single step j
 static LzBlockArgs lz_block_args(const pse_handle *h, int j, bool full) {
     LzBlockArgs a{};
-    a.q = lz_vec(h, j); a.p = lz_vec(h, j - 1); a.w1 = h->w_s; a.w2 = full ? h->w2_s : nullptr;
-    a.u = h->u_s; a.v1 = lz_vec(h, j + 1); a.v2 = full ? lz_vec(h, j + 2) : nullptr;
+    a.q = lz_vec4(h, j); a.p = lz_vec4(h, j - 1); a.w1 = h->w_s; a.w2 = full ? h->w2_s : nullptr;
+    a.u = h->u_s; a.v1 = lz_vec4(h, j + 1); a.v2 = full ? lz_vec4(h, j + 2) : nullptr;
     a.j = j;
     return a;
 }
@@ -912,7 +935,7 @@ static void lz_combine(pse_team &T, int N, double scale, const LzState &st, int 
     for (pse_handle *h : act(T)) {
         int lo, hi;
         row_range(h, N, lo, hi);
-        launch_basis_combine(h->psi_s, h->V, h->n_pad, tc, st.m_final, h->scal, scale, 1, h->ub_s, lo, hi, h->stream, h->sink);
+        launch_basis_combine(h->psi_s, lz_basis(h), h->n_pad, tc, st.m_final, h->scal, scale, 1, h->ub_s, lo, hi, h->stream, h->sink);
         h->tail_done = h->sink.on;
         h->info.lanczos_m = st.m_final; h->info.lanczos_matvecs = matvecs; h->info.lanczos_stepnorm = st.stepnorm;
         h->info.lanczos_exchanges = exchanges;
@@ -937,8 +960,9 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
     int rg[3][2];
     const int nrg_all = update_ranges(h, N, rg);
     // the vector part of iteration j: x_{j+1} from the sums that are still in place
+    VecOut y = lz_y(h, false);   // where y = M x_j of the iteration in hand lies (a deferred vector part belongs to an iteration j >= 1: the list's)
     auto vector_part = [&](int j, const int *gate) {
-        launch_lz_update(lz_vec(h, j), h->w_s, lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, nrg_all, h->stream,
+        launch_lz_update(lz_vec(h, j), y, lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, nrg_all, h->stream,
                          nullptr, 0, h->sc_host_dev, gate, vq_of(h), h->lz_sums);   // (+ the mirror of x_{j+1}: the next mat-vec's gathers, and two of its sums)
     };
     auto iteration = [&](int j, bool scalars_only, const int *gate) -> int {
@@ -946,19 +970,21 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
         const bool fused = !have_y && h->nb.cap > 0 && h->nb_valid;
         if (!fused && !have_y) {
             if (gate) return fail(PSE_ERR_NUMERIC, "queued Lanczos: a gated iteration needs the pair list");
+            TRY(lz_real_ok(h, j));
             TRY(real(T, j == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)j * h->n_pad, 0, N, true));
         }
-        const double4 *vjm1 = lz_vec(h, j - 1);
+        y = lz_y(h, fused);
+        const double4 *vjm1 = lz_vec4(h, j - 1);   // for the kernels that read double4 alone: the mat-vec of iteration 0 (none) and k_lz_dots (iteration 0 on a rows24 handle: lz_real_ok)
         // from iteration 1 on the mat-vec sums x_j.y alone: x_j.x_j and x_j.x_{j-1} are what the update that wrote x_j left in lz_sums
         const bool split = fused && j > 0;
         if (fused)
-            launch_mreal_lanczos(h->pos_s, lz_vec(h, j), h->w_s, row_map(0, N), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
+            launch_mreal_lanczos(h->pos_s, lz_vec(h, j), y, row_map(0, N), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
                                  LzFuse{split ? nullptr : vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr, h->lz_sums, lz_update_grid(N)}, h->scal, nullptr, nullptr, h->stream,
                                  h->vl_use ? h->vl : VerletList{}, split ? 4 : 1, gate, DevRowArgs{}, j > 0 ? vq_of(h) : nullptr);
         else if (!(j == 0 && h->sums0_done))
-            launch_lz_dots(lz_vec(h, j), h->w_s, vjm1, 0, N, h->partials, h->npart_cap, h->scal, h->stream);
+            launch_lz_dots(lz_vec4(h, j), h->w_s, vjm1, 0, N, h->partials, h->npart_cap, h->scal, h->stream);
         h->w_is_mpsi = false; h->sums0_done = false;
-        if (scalars_only) launch_lz_update(lz_vec(h, j), h->w_s, vjm1, lz_vec(h, j + 1), j, h->scal, rg, 0, h->stream, nullptr, 0,
+        if (scalars_only) launch_lz_update(lz_vec(h, j), y, lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, 0, h->stream, nullptr, 0,
                                            h->sc_host_dev, gate);
         else vector_part(j, gate);
         return 0;
@@ -978,7 +1004,7 @@ static int lanczos_queued(pse_team &T, int N, double tol, double scale, int *m_i
     TRY(te(h, PH_LANCZOS));
     if (before_first_wait) TRY(before_first_wait());
     if (before_combine) TRY(before_combine());
-    launch_basis_combine(h->psi_s, h->V, h->n_pad, BasisCoef{}, 0, h->scal, scale, 1, h->ub_s, 0, N, h->stream, h->sink, h->lz_state);
+    launch_basis_combine(h->psi_s, lz_basis(h), h->n_pad, BasisCoef{}, 0, h->scal, scale, 1, h->ub_s, 0, N, h->stream, h->sink, h->lz_state);
     h->tail_done = h->sink.on;
     h->info.lanczos_matvecs = done; h->info.lanczos_exchanges = 0;
     // m of this call is known on the device only; what the host hands back is the most recent one that has reached it
@@ -1004,12 +1030,13 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
     int pending_beta = 0;             // beta_done = |x_done| does not exist when a batch is decided: it arrives with the next one
     LzState st{0, 0, 0, 0, 1.0, {}, {}};   // as a decision under `first` resets it
     bool hook_done = false;
+    bool y_from_list = false;   // y = M x_j of the iteration in hand came from a pair-list mat-vec (lz_y; a deferred vector part is of an iteration j >= 1)
     // the update of iteration j: alpha_j, beta_j from the sums in place and, unless scalars_only, x_{j+1} on the own and the ghost rows
     auto update = [&](int j, bool scalars_only) {
         for (pse_handle *h : act(T)) {
             int rg[3][2];
             const int nrg = scalars_only ? 0 : update_ranges(h, N, rg);
-            launch_lz_update(lz_vec(h, j), h->w_s, lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0,
+            launch_lz_update(lz_vec(h, j), lz_y(h, y_from_list), lz_vec(h, j - 1), lz_vec(h, j + 1), j, h->scal, rg, nrg, h->stream, h->sums_all, T.G > 1 ? T.G : 0,
                              h == h0 ? h->sc_host_dev : nullptr, nullptr, T.G <= 1 ? vq_of(h) : nullptr, T.G <= 1 ? h->lz_sums : nullptr);
         }
     };
@@ -1019,23 +1046,29 @@ static int lanczos(pse_team &T, int N, double tol, double scale, int *m_io, cons
             const bool have_y = done == 0 && h0->w_is_mpsi;      // M psi came with the pass that built the pair list
             const bool fused = !have_y && h0->nb.cap > 0 && h0->nb_valid;   // sums fused into the pair-list mat-vec
             const bool timed = done == 1 && fused;               // one pair-list mat-vec kernel per call is timed on its own
-            if (!fused && !have_y) TRY(real(T, done == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)done * h0->n_pad, 0, N, true));
+            if (!fused && !have_y) {
+                TRY(lz_real_ok(h0, done));
+                TRY(real(T, done == 0 ? &pse_handle::psi_s : &pse_handle::V, &pse_handle::w_s, (size_t)done * h0->n_pad, 0, N, true));
+            }
+            y_from_list = fused;
             for (pse_handle *h : act(T)) {
                 int lo, hi;
                 row_range(h, N, lo, hi);
-                const double4 *xj = lz_vec(h, done), *vjm1 = lz_vec(h, done - 1);   // x_{j-1}, unnormalised
+                // x_{j-1}, unnormalised, for the kernels that read double4 alone: the mat-vec of iteration 0 (none), of a team, and k_lz_dots
+                // (iteration 0 on a rows24 handle: lz_real_ok)
+                const double4 *vjm1 = lz_vec4(h, done - 1);
                 if (fused) {
                     const bool ev = timed && h->timing;
                     // a single GPU, from iteration 1 on: the mat-vec sums x_j.y alone; x_j.x_j and x_j.x_{j-1} are what the update that
                     // wrote x_j left in lz_sums.  Teams keep the three sums of the mat-vec: they travel with the exchange.
                     const bool split = done > 0 && T.G <= 1;
-                    launch_mreal_lanczos(h->pos_s, xj, h->w_s, row_map(lo, hi), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef,
+                    launch_mreal_lanczos(h->pos_s, lz_vec(h, done), lz_y(h, true), row_map(lo, hi), h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef,
                                          h->nb, LzFuse{split ? nullptr : vjm1, h->partials, h->npart_cap, nullptr, nullptr, nullptr, h->lz_sums, lz_update_grid(N)}, h->scal,
                                          ev ? h->ph[PH_MATVEC].a : nullptr, ev ? h->ph[PH_MATVEC].b : nullptr, h->stream,
                                          h->vl_use ? h->vl : VerletList{}, split ? 4 : 1, nullptr, DevRowArgs{}, done > 0 && T.G <= 1 ? vq_of(h) : nullptr);
                     if (timed) h->matvec_timed = true;
                 } else if (!(done == 0 && h->sums0_done)) {   // (iteration 0: the sums came with the pass that built the pair list)
-                    launch_lz_dots(xj, h->w_s, vjm1, lo, hi, h->partials, h->npart_cap, h->scal, h->stream);
+                    launch_lz_dots(lz_vec4(h, done), h->w_s, vjm1, lo, hi, h->partials, h->npart_cap, h->scal, h->stream);
                 }
                 h->w_is_mpsi = false; h->sums0_done = false;
             }
@@ -1103,7 +1136,7 @@ static int lanczos_team(pse_team &T, int N, double tol, double scale, int *m_io,
             const int j = done;
             const bool full = target - done >= 2 && j + 2 <= M_MAX;
             for (pse_handle *h : act(T)) {
-                const LzFuse lz{nullptr, h->partials, h->npart_cap, lz_vec(h, j), lz_vec(h, j - 1), j > 0 ? h->u_s : nullptr};
+                const LzFuse lz{nullptr, h->partials, h->npart_cap, lz_vec4(h, j), lz_vec4(h, j - 1), j > 0 ? h->u_s : nullptr};
                 if (j == 0 && !h->w_is_mpsi) return fail(PSE_ERR_NUMERIC, "two-step Lanczos: M psi did not come with the pair list");
                 if (!(j == 0 && h->w_is_mpsi)) {   // w1 = M v_j: own rows + one ghost layer for a block, own rows for a single step
                     launch_mreal_lanczos(h->pos_s, lz_vec(h, j), h->w_s, rank_rows(h, N, full ? 1 : 0), h->cell_off, h->dbox, h->nc, h->d.rcut,
@@ -1375,7 +1408,7 @@ static int lanczos_local(pse_team &T, double tol, int *m_io, WavePump *pump) {
     if (target + 2 * extra_blocks > M_MAX || !lz_decide_supported(target + 2 * extra_blocks))
         return fail(PSE_ERR_INVALID, "owned-particle step: starting count %d of the Lanczos iteration is beyond what the device-side decision takes", m_in);
     int n_exchanges = 0, matvecs = 0, done = 0, half_pending = -1;
-    auto fuse = [&](pse_handle *h, int j) { return LzFuse{nullptr, h->partials, h->npart_cap, lz_vec(h, j), lz_vec(h, j - 1), j > 0 ? h->u_s : nullptr}; };
+    auto fuse = [&](pse_handle *h, int j) { return LzFuse{nullptr, h->partials, h->npart_cap, lz_vec4(h, j), lz_vec4(h, j - 1), j > 0 ? h->u_s : nullptr}; };
     auto exchange = [&](bool full) -> int {
         if (pump) TRY(pump->upto(n_exchanges));
         ++n_exchanges;
@@ -1709,7 +1742,6 @@ extern "C" int pse_debug_matvec_ms(pse_handle *h, int reps, float *ms_per_launch
     HIPCHK(hipSetDevice(h->device));
     if (h->n_slabs != 1 || !h->nb_valid || h->nb.cap <= 0 || h->sorted_N <= 0)
         return fail(PSE_ERR_INVALID, "pse_debug_matvec_ms: needs the pair list of a Brownian call on a single-GPU engine (call it right after one)");
-    const size_t stride = h->n_pad;
     const int N = h->sorted_N;
     RowMap rm{};
     rm.n = 1; rm.lo[0] = 0; rm.hi[0] = N;
@@ -1717,7 +1749,7 @@ extern "C" int pse_debug_matvec_ms(pse_handle *h, int reps, float *ms_per_launch
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     auto run = [&](int n) {   // the launch of a Lanczos iteration j >= 1 (vector V[1], its mirror, the sums against V[0] = psi), the kernel alone
         for (int r = 0; r < n; ++r)
-            launch_mreal_lanczos(h->pos_s, h->V + stride, h->w_s, rm, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
+            launch_mreal_lanczos(h->pos_s, lz_vec(h, 1), lz_y(h, true), rm, h->cell_off, h->dbox, h->nc, h->d.rcut, h->d.self, h->coef, h->nb,
                                  LzFuse{h->psi_s, h->partials, h->npart_cap, nullptr, nullptr, nullptr}, h->scal, nullptr, nullptr, h->stream,
                                  VerletList{}, 1, nullptr, DevRowArgs{}, vq_of(h), true);   // (the mat-vec of the handle's current operator)
     };

@@ -125,6 +125,41 @@ __device__ __forceinline__ double block_sum(double v, double *sh /* >= 4 doubles
     __syncthreads();
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
+// ---- a vector row in 24 bytes: (x, y, z) without the padding word of a double4 --------------------------------------------------
+// The Lanczos vectors that only coalesced kernels touch (the basis V[j >= 1] and the results of the pair-list mat-vecs of a single
+// GPU: pse_handle.rows24) are stored as three doubles per row.  Row i is three 8-byte accesses; the 64 lanes of a wave together
+// cover 1536 contiguous bytes, so every fetched line is used -- no shuffles between lanes.  A kernel that can meet either layout
+// takes it per POINTER, uniform over the launch: VecIn / VecOut name the array and its layout.
+struct VecOut {   // rows of a double4 array (packed = 0: what a plain double4 pointer converts to) or of a packed one (1); p may be null
+    double *p; int packed;
+    VecOut() = default;
+    __host__ __device__ VecOut(double4 *a) : p(reinterpret_cast<double *>(a)), packed(0) {}
+    __host__ __device__ VecOut(double *a, int pk) : p(a), packed(pk) {}
+};
+struct VecIn {
+    const double *p; int packed;
+    VecIn() = default;
+    __host__ __device__ VecIn(const double4 *a) : p(reinterpret_cast<const double *>(a)), packed(0) {}
+    __host__ __device__ VecIn(const double *a, int pk) : p(a), packed(pk) {}
+    __host__ __device__ VecIn(const VecOut &v) : p(v.p), packed(v.packed) {}
+};
+__device__ __forceinline__ void row24_load(const double *__restrict__ a, size_t i, double &x, double &y, double &z) {
+    const double *r = a + 3 * i;
+    x = r[0]; y = r[1]; z = r[2];
+}
+__device__ __forceinline__ void row24_store(double *__restrict__ a, size_t i, double x, double y, double z) {
+    double *r = a + 3 * i;
+    r[0] = x; r[1] = y; r[2] = z;
+}
+__device__ __forceinline__ void row_load(const VecIn &v, size_t i, double &x, double &y, double &z) {
+    if (v.packed) { row24_load(v.p, i, x, y, z); return; }
+    const double4 q = reinterpret_cast<const double4 *>(v.p)[i];
+    x = q.x; y = q.y; z = q.z;
+}
+__device__ __forceinline__ void row_store(const VecOut &v, size_t i, double x, double y, double z) {
+    if (v.packed) { row24_store(v.p, i, x, y, z); return; }
+    reinterpret_cast<double4 *>(v.p)[i] = make_double4(x, y, z, 0.0);
+}
 // every block reduces the same partial array in the same order -> identical value everywhere
 __device__ __forceinline__ double reduce_partials(const double *partials, int n, double *sh) {
     double v = 0.0;

@@ -290,6 +290,7 @@ static int create_impl(const pse_params *p, pse_handle *h) {
         t.place_trials = std::max(0, std::min(12, ienv("PSE_PLACE_TRIALS", 10)));
         t.vq = ienv("PSE_VQ", 1);
         if (const char *v = getenv("PSE_LANCZOS_OP")) t.lz_op = !strcmp(v, "fp64") ? PSE_LANCZOS_FP64 : PSE_LANCZOS_RECORDS16;
+        t.rows24 = ienv("PSE_ROWS24", 1);
         if (const char *v = getenv("PSE_TEAM_SCHED")) {
             int a = 1, b = 2, c = 3;
             if (sscanf(v, "%d,%d,%d", &a, &b, &c) == 3) { t.team_sched[0] = a; t.team_sched[1] = b; t.team_sched[2] = c; }
@@ -491,7 +492,15 @@ static int create_impl(const pse_params *p, pse_handle *h) {
     if (h->tun.place_trials > 1 && h->own_z && h->own_y && h->grid_slabs == 1)
         TRY(place_grids(h, (size_t)(G.nxl + G.hl + G.nhalo) * G.Ny * G.Nz, (size_t)G.nxl * G.Ny * G.Nzp));
 
-    TRY(dmalloc(h, &h->V, (size_t)(M_MAX + 1) * n));
+    // The basis in 24-byte rows where only the coalesced kernels of the single-GPU pair-list path touch it (k_lz_update, k_mreal_list's own
+    // row, k_basis_combine): a quarter of every double4 row they moved was the padding word.  Everything a team, an owned-particle rank,
+    // k_lz_block, k_lz_dots or a cell pass reads stays double4 -- so does a handle created with the fp64 operator, whose mat-vec gathers
+    // its neighbours' rows from the basis itself.
+    h->rows24 = h->n_slabs == 1 && !h->loc.on && h->nb.cap > 0 && h->tun.lz_op != PSE_LANCZOS_FP64 && h->tun.rows24 != 0;
+    if (h->rows24) {
+        TRY(dmalloc(h, &h->V, ((size_t)(M_MAX + 1) * n * 3 + 3) / 4));   // (counted in double4: three quarters of them)
+        h->w24 = reinterpret_cast<double *>(h->V);                       // slot 0 of the basis: x_0 = psi is never copied into it
+    } else TRY(dmalloc(h, &h->V, (size_t)(M_MAX + 1) * n));
     // single GPU: the newest Lanczos vector also in 16 bytes per row (vq_pack): what the pair-list mat-vec gathers its neighbours from
     if (h->n_slabs == 1 && !h->loc.on && h->tun.vq > 0) TRY(dmalloc(h, (char **)&h->vq, (size_t)16 * n));
     TRY(dmalloc(h, &h->pv_rows, pair_virial_rows((int)n)));

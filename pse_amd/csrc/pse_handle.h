@@ -171,6 +171,7 @@ struct pse_handle {
         int place_trials = 10;       // PSE_PLACE_TRIALS=K: the two grids are allocated up to K times and the pair the x + inverse y + z passes run fastest on is kept (0, 1: off)
         int lz_extra = 2;            // PSE_LANCZOS_EXTRA: iterations a queue-only Brownian call queues beyond the starting count (gated on the device-side decision)
         int lz_op = PSE_LANCZOS_RECORDS16;   // PSE_LANCZOS_OP=fp64: the handle starts with the fp64 Lanczos operator (pse_set_lanczos_operator)
+        int rows24 = 1;              // PSE_ROWS24=0: the Lanczos basis and the pair-list mat-vec results of a single GPU stay double4 (tests, bisecting)
     } tun;
     DCells bidx_nc = {0, 0, 0};      // cell grid the boundary-cell indices on the device belong to
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -264,7 +265,12 @@ struct pse_handle {
     void *fft_work = nullptr;
     size_t fft_work_bytes = 0;
     // Lanczos
-    double4 *V = nullptr;        // [M_MAX + 1][n_max]
+    double4 *V = nullptr;        // [M_MAX + 1][n_max] double4 rows -- or, rows24, as many rows of three doubles (lz_vec in pse_capi.hip knows)
+    // Decided once, in pse_create: single GPU, a pair list, the records operator at create, PSE_ROWS24 != 0.  Then V[j >= 1] and w24 hold
+    // 24-byte rows (pse_device.h): only k_lz_update, k_mreal_list and k_basis_combine touch them, each told the layout per pointer.
+    bool rows24 = false;
+    double *w24 = nullptr;       // rows24: [n_max][3], the results of the pair-list mat-vecs of the iteration, in the basis' unused slot 0 (the
+                                 // build pass's M psi stays in w_s)
     double *scal = nullptr, *partials = nullptr;
     double *lz_sums = nullptr;   // [2][LZ_NPART] partial sums of x_{j+1}.x_{j+1}, x_{j+1}.x_j a k_lz_update leaves for iteration j + 1 (pse_vectors.h)
     double *sc_host = nullptr;   // pinned host copy of scal, mapped: the Lanczos kernels write alpha, beta, the norm there as well

@@ -185,7 +185,9 @@ void launch_mreal(const double4 *pos_s, const float4 *posf_s, const double4 *vec
                   DevRowArgs dr = DevRowArgs{});                         // owned-particle ranks: the rows come from device memory (cell passes only; stage_hi takes out2)
 bool mreal_table_in_lds(int ncoef);   // the neighbour list across steps needs the LDS copy of the table
 // pair-list mat-vec + Lanczos sums; leaves the three reduced sums in scal[LZ_TMP .. LZ_TMP + 2]
-void launch_mreal_lanczos(const double4 *pos_s, const double4 *vec_s, double4 *w, RowMap rows, const int *cell_off,
+// vec and out: each in its own row layout (pse_device.h VecIn / VecOut; a plain double4 pointer converts to the double4 layout).  The
+// mirror vec_q, lz.vprev and the vectors of the two-step blocks are what they were.
+void launch_mreal_lanczos(const double4 *pos_s, VecIn vec, VecOut out, RowMap rows, const int *cell_off,
                           DBox box, DCells nc, double rcut, double self, const double *coef, NbList nb, LzFuse lz,
                           double *scal, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t s,   // events (nullable) bracket the mat-vec kernel
                           VerletList vl = VerletList{},   // in use this step: rows that overflowed the pair list walk it instead of the cells

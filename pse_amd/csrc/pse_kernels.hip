@@ -717,13 +717,18 @@ __device__ __forceinline__ void eval_fg_lean(double r2, const double *__restrict
 // VQ: the neighbours' rows come from the 16-byte mirror of the vector (vq_pack, pse_device.h): ONE gather per pair instead of two.
 // F64: the fp64 operator -- the coefficients from the 32-byte plane nb.c64 (the 16-byte record gives the row and the sign of h), the
 // neighbours' rows as doubles (never VQ), the rows that did not fit the list through pair_coef64: 48 B of list per pair instead of 16.
+// packed: vec_s and / or out_s hold 24-byte rows (a rows24 handle: the basis and the results of these mat-vecs); every read of vec_s --
+// the own row, the neighbours of a row that walks the cells or the kept list, the gathers without VQ -- and the one store go by it.
 template <int FUSE, int UNROLL, int NT, int WSP = 1, bool VQ = false, bool F64 = false>
 __global__ void __launch_bounds__(NT, (WSP == 4 ? 5 : 1))   // the split kernel: <= 96 VGPRs, five workgroups per CU (it is bound by the round trips its waves have in flight)
 k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_s, double4 *__restrict__ out_s, RowMap rm_arg,
              DBox box, double self, NbList nb, LzFuse lz,
              const int *__restrict__ cell_off, DCells nc, double rcut2, const double *__restrict__ coef, VerletList vl,
-             const int *__restrict__ stop, DevRowArgs dr, const vq4 *__restrict__ vec_q = nullptr) {
+             const int *__restrict__ stop, DevRowArgs dr, const vq4 *__restrict__ vec_q = nullptr, int packed = 0) {
     if (stop && *stop) return;   // the Lanczos iteration has ended (device-side decision)
+    // packed (uniform over the launch): bit 0 -- vec_s holds 24-byte rows, bit 1 -- out_s does (pse_device.h VecIn / VecOut)
+    const VecIn vin{reinterpret_cast<const double *>(vec_s), packed & 1};
+    const VecOut vout{reinterpret_cast<double *>(out_s), (packed >> 1) & 1};
     const RowMapRegs rm(rm_arg, dr.rm);
     int nb_live = gridDim.x;
     if (dr.rm) {   // an owned-particle rank: rows from device memory; workgroups past the last one still own a slot of the partial sums
@@ -744,7 +749,7 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
     double ux = 0.0, uy = 0.0, uz = 0.0;
     double4 vi = make_double4(0.0, 0.0, 0.0, 0.0);
     if (active) {
-        vi = vec_s[i];
+        row_load(vin, i, vi.x, vi.y, vi.z);
         const int cnt = nb.cnt[i];
         if (cnt >= 0) {
             if (wv == 0) { ux = self * vi.x; uy = self * vi.y; uz = self * vi.z; }
@@ -773,6 +778,7 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
                     if (VQ && !F64) { vq[u] = vec_q[e[u] & JMASK]; continue; }   // the row in 16 bytes: one gather
+                    if (vin.packed) { row24_load(vin.p, e[u] & JMASK, vxy[u].x, vxy[u].y, vz[u]); continue; }
                     const double4 *vj = vec_s + (e[u] & JMASK);   // 24 of the row's 32 bytes: a 16- and an 8-byte gather from one line
                     vxy[u] = *reinterpret_cast<const double2 *>(vj);
                     vz[u] = vj->z;
@@ -807,7 +813,8 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                 if (r2 < rcut2 && r2 > 0.0) {
                     double f, h;
                     eval_fg_lean(r2, coef, f, h);
-                    const double4 Fj = vec_s[j];
+                    double3 Fj;
+                    row_load(vin, j, Fj.x, Fj.y, Fj.z);
                     if (F64) pair_apply64(pair_coef64(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
                     else pair_apply(pair_coef(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);   // (the coefficients the list would have carried)
                 }
@@ -828,7 +835,8 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
                     if (r2 < rcut2 && j != i && r2 > 0.0) {
                         double f, h;
                         eval_fg_lean(r2, coef, f, h);
-                        const double4 Fj = vec_s[j];
+                        double3 Fj;
+                        row_load(vin, j, Fj.x, Fj.y, Fj.z);
                         if (F64) pair_apply64(pair_coef64(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
                         else pair_apply(pair_coef(f, h, dx, dy, dz), Fj.x, Fj.y, Fj.z, ux, uy, uz);
                     }
@@ -890,7 +898,7 @@ k_mreal_list(const double4 *__restrict__ pos_s, const double4 *__restrict__ vec_
         }
     }
     if (active) {
-        out_s[i] = make_double4(ux, uy, uz, 0.0);
+        row_store(vout, i, ux, uy, uz);
         if (dr.stage_hi) {   // rows of the last layers: parked for the exchange with the right neighbour
             const int lb = dr.lr->last_begin, no = dr.lr->n_own;
             if (i >= lb && i < no && i - lb < dr.stage_cap) dr.stage_hi[i - lb] = make_double4(ux, uy, uz, 0.0);
@@ -961,25 +969,29 @@ void launch_mreal(const double4 *pos_s, const float4 *posf_s, const double4 *vec
 }
 
 int mreal_partials_needed(int rows) { return nblocks(std::max(rows, 1), 64); }   // one per 64 rows (the split mat-vec); the plain one uses a quarter
-void launch_mreal_lanczos(const double4 *pos_s, const double4 *vec_s, double4 *w, RowMap rm, const int *cell_off,
+void launch_mreal_lanczos(const double4 *pos_s, VecIn vec, VecOut out, RowMap rm, const int *cell_off,
                           DBox box, DCells nc, double rcut, double self, const double *coef, NbList nb, LzFuse lz,
                           double *scal, hipEvent_t ev_begin, hipEvent_t ev_end, hipStream_t s, VerletList vl,
                           int sums, const int *stop, DevRowArgs dr, const void *vec_q, bool no_reduce) {
+    // the kernel takes plain pointers and the two layouts as one launch-uniform word
+    const double4 *vec_s = reinterpret_cast<const double4 *>(vec.p);
+    double4 *w = reinterpret_cast<double4 *>(out.p);
+    const int packed = (vec.packed ? 1 : 0) | (out.packed ? 2 : 0);
     const int rows = std::max(dr.rm ? dr.rows_cap : rm.list_rows(), 1);
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
     // Four waves per block of 64 rows, each taking every fourth group of slots: 0.166 ms against 0.191 with four blocks of rows
     // per workgroup (two waves: 0.182, eight: 0.196).
     const int nb64 = nblocks(rows, 64);
-#define PSE_LIST(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr)
-#define PSE_LIST64(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4, false, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr, nullptr)
+#define PSE_LIST(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr, nullptr, packed)
+#define PSE_LIST64(F) hipLaunchKernelGGL((k_mreal_list<F, 4, 256, 4, false, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr, nullptr, packed)
     if (nb.c64) {   // the fp64 operator: the neighbours' rows as doubles, the mirror vec_q is not read
         if (sums == 0) PSE_LIST64(0); else if (sums == 1) PSE_LIST64(1); else if (sums == 2) PSE_LIST64(2); else if (sums == 3) PSE_LIST64(3); else PSE_LIST64(4);
     } else if (sums == 1 && vec_q)
         hipLaunchKernelGGL((k_mreal_list<1, 4, 256, 4, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr,
-                           (const vq4 *)vec_q);
+                           (const vq4 *)vec_q, packed);
     else if (sums == 4 && vec_q)
         hipLaunchKernelGGL((k_mreal_list<4, 4, 256, 4, true>), dim3(nb64), dim3(256), 0, s, pos_s, vec_s, w, rm, box, self, nb, lz, cell_off, nc, rcut * rcut, coef, vl, stop, dr,
-                           (const vq4 *)vec_q);
+                           (const vq4 *)vec_q, packed);
     else if (sums == 0) PSE_LIST(0); else if (sums == 1) PSE_LIST(1); else if (sums == 2) PSE_LIST(2); else if (sums == 3) PSE_LIST(3); else PSE_LIST(4);
 #undef PSE_LIST64
 #undef PSE_LIST

@@ -19,7 +19,8 @@ struct BasisCoef { double t[104]; };   // the m <= 100 coefficients of the final
 // sink.on: the result is not stored in out_s but added to add_a + add_b (nullable) of the row and sent on: vel[tag].xyz (single GPU) or
 // rows[i] = (sum, tag) (a team's all-gathered array)
 struct CombineSink { bool on; const double4 *add_a, *add_b; const unsigned *tag_s; double4 *vel; double4 *rows; };
-void launch_basis_combine(const double4 *x0, const double4 *V, size_t stride, const BasisCoef &t, int m, const double *scal,
+// x0 and V each in their own layout (pse_device.h VecIn); stride: ROWS from one basis vector to the next
+void launch_basis_combine(VecIn x0, VecIn V, size_t stride, const BasisCoef &t, int m, const double *scal,
                           double scale, int use_norm, double4 *out_s, int lo, int hi, hipStream_t s, CombineSink sink = CombineSink{},
                           const struct LzState *st = nullptr);   // st: m and the coefficients come from the device-side decision
 // Lanczos iteration on the own rows [lo, hi) (see k_lz_update in pse_vectors.hip).  dots: sums of x.x, x.y, x.vprev ->
@@ -48,7 +49,8 @@ void launch_vq_roundtrip(const double *in, double *out, int n, hipStream_t s);  
 int lz_update_grid(int rows);   // workgroups launch_lz_update uses for this many rows: the partials per sum it leaves
 // scal[LZ_TMP + 1] = sum of xy[0 .. n_xy), scal[LZ_TMP] and scal[LZ_TMP + 2] = the sums of upd[0 .. n_upd) and upd[LZ_NPART .. + n_upd)
 void launch_lz_reduce_split(const double *xy, int n_xy, const double *upd, int n_upd, double *scal, const int *stop, hipStream_t s);
-void launch_lz_update(const double4 *xin, const double4 *y, const double4 *xprev, double4 *xnext, int j,
+// xin, y, xprev (p null: none), xnext: each array with its own row layout (pse_device.h VecIn / VecOut)
+void launch_lz_update(VecIn xin, VecIn y, VecIn xprev, VecOut xnext, int j,
                       double *scal, const int (*row_ranges)[2], int n_ranges, hipStream_t s,   // up to three disjoint row ranges in one launch
                       const double *sums_all = nullptr, int nranks = 0, double *sch = nullptr, const int *stop = nullptr,
                       void *xq = nullptr,    // nullable: [rows] 16-byte mirror of xnext (vq_pack, pse_device.h), written on the same rows

@@ -80,8 +80,7 @@ void launch_lz_reduce_split(const double *xy, int n_xy, const double *upd, int n
 }
 // alpha_j, beta_j from the reduced sums; x_{j+1} on the given rows, and (next_sums) what it contributes to two sums of iteration j + 1
 __global__ void __launch_bounds__(TPB)
-k_lz_update(const double4 *__restrict__ xin, const double4 *__restrict__ y, const double4 *__restrict__ xprev,
-            double4 *__restrict__ xnext, int j, double *__restrict__ scal, RowRanges rg,
+k_lz_update(VecIn xin, VecIn y, VecIn xprev, VecOut xnext, int j, double *__restrict__ scal, RowRanges rg,
             const double *__restrict__ sums_all, int nranks, double *__restrict__ sch, const int *__restrict__ stop, vq4 *__restrict__ xq,
             double *__restrict__ next_sums) {
     if (stop && *stop) return;
@@ -108,10 +107,11 @@ k_lz_update(const double4 *__restrict__ xin, const double4 *__restrict__ y, cons
     double nn = 0.0, np = 0.0;   // x_{j+1}.x_{j+1} and x_{j+1}.x_j over this thread's rows: two of the three sums of iteration j + 1
     for (int t = blockIdx.x * TPB + threadIdx.x; t < n0 + n1 + n2; t += gridDim.x * TPB) {
         const int i = t < n0 ? rg.lo[0] + t : (t < n0 + n1 ? rg.lo[1] + (t - n0) : rg.lo[2] + (t - n0 - n1));
-        const double4 p = xin[i], q = y[i];
+        double3 p, q;   // (each array in its own layout, uniform over the launch: psi and the build pass's M psi are double4)
+        row_load(xin, i, p.x, p.y, p.z); row_load(y, i, q.x, q.y, q.z);
         double nx = (q.x - alpha * p.x) * inv, ny = (q.y - alpha * p.y) * inv, nz = (q.z - alpha * p.z) * inv;
-        if (xprev) { const double4 m = xprev[i]; nx -= cp * m.x; ny -= cp * m.y; nz -= cp * m.z; }
-        xnext[i] = make_double4(nx, ny, nz, 0.0);
+        if (xprev.p) { double3 m; row_load(xprev, i, m.x, m.y, m.z); nx -= cp * m.x; ny -= cp * m.y; nz -= cp * m.z; }
+        row_store(xnext, i, nx, ny, nz);
         if (xq) xq[i] = vq_pack(nx, ny, nz);   // the 16-byte mirror the next pair-list mat-vec gathers its neighbours from
         nn += nx * nx + ny * ny + nz * nz;
         np += nx * p.x + ny * p.y + nz * p.z;
@@ -404,7 +404,7 @@ void launch_lz_dots(const double4 *x, const double4 *y, const double4 *vprev, in
     hipLaunchKernelGGL(k_lz_dots, dim3(g), dim3(TPB), 0, s, x, y, vprev, lo, hi, partials, cap);
     launch_lz_reduce(partials, g, cap, y ? 3 : 1, scal, nullptr, s);
 }
-void launch_lz_update(const double4 *xin, const double4 *y, const double4 *xprev, double4 *xnext, int j,
+void launch_lz_update(VecIn xin, VecIn y, VecIn xprev, VecOut xnext, int j,
                       double *scal, const int (*rg)[2], int nrg, hipStream_t s, const double *sums_all, int nranks, double *sch,
                       const int *stop, void *xq, double *next_sums) {
     RowRanges r{};
@@ -454,7 +454,7 @@ void launch_pick(const int *cell_off, const int *idx, int n, int *out, hipStream
 // goes straight to where the step wants the sum (a team: the row of the all-gathered array, tag in .w; a single GPU: vel[tag].xyz),
 // so ub_s is neither written nor read back (K10 gpu_stokes_LinearCombination_kernel, PSEv1/Helper.cu:113-133)
 __global__ void __launch_bounds__(TPB)
-k_basis_combine(const double4 *__restrict__ x0, const double4 *__restrict__ V, size_t stride, BasisCoef tc, int m,
+k_basis_combine(VecIn x0, VecIn V, size_t stride, BasisCoef tc, int m,
                 const double *__restrict__ scal, double scale, int use_norm, double4 *__restrict__ out, int lo, int N, CombineSink sink,
                 const LzState *__restrict__ st) {
     const double *t = tc.t;   // kernel arguments: no host-to-device copy whose source the host would have to keep alive
@@ -463,7 +463,8 @@ k_basis_combine(const double4 *__restrict__ x0, const double4 *__restrict__ V, s
     for (int i = lo + blockIdx.x * TPB + threadIdx.x; i < N; i += gridDim.x * TPB) {
         double x = 0, y = 0, z = 0;
         for (int q = 0; q < m; ++q) {
-            const double4 v = q == 0 ? x0[i] : V[(size_t)q * stride + i];   // x_0 = psi was never copied into the basis
+            double3 v;   // x_0 = psi was never copied into the basis; stride: rows of one basis vector, in either layout
+            if (q == 0) row_load(x0, i, v.x, v.y, v.z); else row_load(V, (size_t)q * stride + i, v.x, v.y, v.z);
             const double tq = t[q];
             x += tq * v.x; y += tq * v.y; z += tq * v.z;
         }
@@ -479,7 +480,7 @@ k_basis_combine(const double4 *__restrict__ x0, const double4 *__restrict__ V, s
         else sink.rows[i] = make_double4(sx, sy, sz, (double)idx);
     }
 }
-void launch_basis_combine(const double4 *x0, const double4 *V, size_t stride, const BasisCoef &t_dev, int m, const double *scal,
+void launch_basis_combine(VecIn x0, VecIn V, size_t stride, const BasisCoef &t_dev, int m, const double *scal,
                           double scale, int use_norm, double4 *out_s, int lo, int hi, hipStream_t s, CombineSink sink, const LzState *st) {
     hipLaunchKernelGGL(k_basis_combine, dim3(std::min(2048, std::max(1, nblocks(hi - lo, TPB)))), dim3(TPB), 0, s, x0, V, stride,
                        t_dev, m, scal, scale, use_norm, out_s, lo, hi, sink, st);
