@@ -425,6 +425,70 @@ int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_int3 *image
 int pse_msd_displacement(pse_msd *m, int slot, const pse_double4 *pos, const pse_int3 *image, const unsigned *group, unsigned N, double strain,
                          pse_double4 *out /* DEVICE, caller order: d.xyz, |d|^2 in w; rows outside the group untouched */);
 
+/* ---- intermediate scattering functions: the self part F_s(k, t) and the collective part F(k, t) against up to 64 time origins (no reference counterpart) ----
+ * A pse_isf object fixes the types of the particles and a list of nk <= PSE_ISF_MAX_MODES integer modes exactly as a
+ * pse_structure_factor does (types_host, ntypes <= 8, |m_i| <= PSE_SF_MAX_INDEX; (0, 0, 0), a mode with its negative and duplicates are
+ * allowed) and holds a CURRENT BUFFER and norigins <= PSE_ISF_MAX_ORIGINS slots of the same shape: three planes of n_max doubles with
+ * the fractional coordinates s of a sample, indexed by the caller-order particle index, and the densities rho of that sample.
+ * Conventions are those of pse_structure_factor_accumulate: in the handle's CURRENT box, s_x = fma(-xy, y, x) / Lx (two roundings), s_y =
+ * y / Ly, s_z = z / Lz (one each), not shifted, not wrapped; rho_a(m) = sum_{type(j) = a} exp(-2 pi i m.s_j).
+ * pse_isf_sample fills the current buffer from the N group members: s of every member, and rho of the sample by the pass of
+ * pse_structure_factor_accumulate itself -- the rho it writes (ntypes x nk x 2, (re, im), or NULL) and what it ADDS to static_sums
+ * (npt x nk, or NULL) are the bits of that call on the same inputs.  It remembers N and the group pointer for pse_isf_correlate.  Every
+ * sample of one object must use the same group (documented; N is checked).
+ * pse_isf_store copies the current buffer into origin slot `slot` (a device-to-device copy on the handle's stream) and marks the slot
+ * stored with the N of the sample (host bookkeeping, as pse_msd_store).
+ * pse_isf_correlate, for every listed pair (slot, row), types a and b and mode q, with the current buffer as `now`:
+ *   self[((row ntypes + a) nk + q) 2 + {0, 1}] += sum over the members j of type a of (re, im) exp(-2 pi i m_q.(s_j(now) - s_j(slot)))
+ *   coll[((row ntypes + a) ntypes + b) nk + q] += Re(rho_a(m_q; now) conj rho_b(m_q; slot))
+ * F_s = Re self / (origins N_a) and F_ab = coll / (origins sqrt(N_a N_b)) (pse_amd.analyze.IntermediateScattering does this).  The phase
+ * of the self part uses fractional coordinates and integer modes: it needs NO images and NO unwrapping -- a particle that wrapped by any
+ * lattice vector between the origin and now gives the same value.  In a tilting box the integer mode is the ADVECTED wave vector k(t)
+ * = 2 pi (mx/Lx, my/Ly - xy(t) mx/Lx, mz/Lz): purely affine motion leaves self = N_a, the usual choice under shear.  A Lees-Edwards
+ * flip relabels the modes (s_x changes by a multiple of s_y): slots stored before a flip must not be correlated with samples after
+ * it -- the caller's rule, not checked here.  The collective block is ORDERED: a is the type now, b the type at the origin, all
+ * ntypes^2 blocks are kept, because under shear <rho_a(t) rho_b*(0)> != <rho_b(t) rho_a*(0)> (as the nine entries of
+ * PSE_CHAIN_MODES_CORR).  At most 64 pairs, by value in the launch: no copy, no wait.  A slot may be listed for several rows; rows that
+ * no pair names are not touched.  A type without members adds exactly +0.0; (0, 0, 0) gives self = (N_a, 0) and coll = N_a N_b
+ * exactly; a mode listed twice is computed once and has the same bits in every place.
+ *   ORDER OF THE SUMS.  Self part, per particle: ds_c = s_c(now) - s_c(slot), one subtraction per component; the distinct modes in the
+ *   segments of the structure-factor plan (arithmetic progressions m0 + t d of at most 8 modes); f_c = fma(m_c, ds_c, -rint(m_c ds_c))
+ *   -- the integer part goes exactly --, t = (f_x + f_y) + f_z, t -= rint(t), sincospi(-2 t) for m0 and for d, then one complex
+ *   multiplication per further mode of the segment: no sine or cosine of a large argument is taken.  Per (pair, type, mode): the group
+ *   members in spans of `span` consecutive positions of the group (span: a multiple of 256 fixed at creation from n_max, ntypes, nk),
+ *   within a span in ascending order from +0.0 by one lane; across the spans lane l of 64 adds the spans l, l + 64, ... in ascending
+ *   order from +0.0, then the xor butterfly (every lane adds the lane l xor o for o = 32, 16, ..., 1); then the one addition to self.
+ *   The value of a mode is a function of the mode SET, not of the order of the list.  Collective part: re_a re_b + im_a im_b (the
+ *   compiler may fuse one product), then the one addition to coll.  No floating-point atomics anywhere: equal inputs give equal bits.
+ * Everything is allocated at creation: the plan, the workspace of the structure-factor pass, the current buffer, norigins slots (3 n_max
+ * + 2 ntypes nk doubles each) and the workspace of the self part, one complex number per (span, pair, type, mode) for 64 pairs, at
+ * most 256 MB (which is why nk <= 4096 here).  A failed allocation returns PSE_ERR_HIP, frees what it took and leaves *out null.  The
+ * device calls only queue work on the handle's stream and read nothing back; they can be captured in a graph.  They use no sort, no
+ * cell list and no kept neighbour list, and they work on a slab rank's handle (positions are replicated there).  The object belongs to
+ * its handle exactly as a pse_msd does: pse_destroy frees the objects still alive, pse_isf_destroy waits for the stream.
+ * OUT OF SCOPE: owned-particle ranks (local_rows), multi-tau lag schemes, the van Hove function in real space, re-labelling origins
+ * through a flip, wave vectors off the reciprocal lattice.
+ * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_isf_create, in this order: everything
+ * pse_structure_factor_create refuses, in its order, with nk > 4096 in place of nk > 32768, then norigins outside [1, 64] (*out is
+ * null after a refusal).  pse_isf_sample, in this order: a null f, N == 0 or N > n_max, a null pos, rho or static_sums not 8-byte
+ * aligned.  pse_isf_store: a null f, slot outside [0, norigins), no sample since create.  pse_isf_correlate, in this order: a null f,
+ * no sample since create, npairs outside [1, 64], a null slots_host, a null rows_host, nrows < 1, in the order of the list a slot
+ * outside [0, norigins), then a slot never stored, then a slot stored with another N than the current sample's, then a row outside
+ * [0, nrows), then a row listed twice, then self and coll both null, then either not 8-byte aligned. */
+#define PSE_ISF_MAX_ORIGINS 64
+#define PSE_ISF_MAX_MODES   4096      /* |m_i| <= PSE_SF_MAX_INDEX as for the structure factor */
+typedef struct pse_isf pse_isf;
+int pse_isf_create(pse_handle *h, unsigned n, const unsigned *types_host /* n, or NULL: one type */, int ntypes, unsigned nk,
+                   const int *modes_host /* nk x 3 */, int norigins, pse_isf **out);
+int pse_isf_destroy(pse_isf *f);
+int pse_isf_sample(pse_isf *f, const pse_double4 *pos, const unsigned *group, unsigned N,
+                   double *rho         /* DEVICE, ntypes x nk x 2 (re, im), WRITTEN, may be NULL */,
+                   double *static_sums /* DEVICE, npt x nk, ADDED to, may be NULL */);
+int pse_isf_store(pse_isf *f, int slot);
+int pse_isf_correlate(pse_isf *f, int npairs, const int *slots_host, const int *rows_host, int nrows,
+                      double *self /* DEVICE, nrows x ntypes x nk x 2, ADDED to, may be NULL */,
+                      double *coll /* DEVICE, nrows x ntypes x ntypes x nk, ADDED to, may be NULL */);
+
 /* ---- cluster analysis: the connected components of a distance criterion (no reference counterpart) ----
  * A pse_clusters object fixes the types of the particles and the link distances: types_host, ntypes <= 8 and the pair types
  * p(a, b) exactly as for pse_pair_hist_create (NULL: one type; a caller index >= n acts as type 0); rlink_host holds one link

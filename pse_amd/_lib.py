@@ -181,6 +181,11 @@ SYMBOLS = {
     "pse_chain_modes_compute": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "pse_chain_modes_store": (_i, [_vp, _i]),
     "pse_chain_modes_correlate": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
+    "pse_isf_create": (_i, [_vp, _u, _vp, _i, _u, _vp, _i, _vp]),
+    "pse_isf_destroy": (_i, [_vp]),
+    "pse_isf_sample": (_i, [_vp, _vp, _vp, _u, _vp, _vp]),
+    "pse_isf_store": (_i, [_vp, _i]),
+    "pse_isf_correlate": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "pse_host_rouse_weights": (_i, [_u, _i, _vp]),
     "pse_bonds_create": (_i, [_vp, _u, _u, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pse_bonds_destroy": (_i, [_vp]),

@@ -16,13 +16,15 @@ step, its gyration tensor, Rg^2 and end-to-end vector reduced on the device (pse
 trees in LDS, one workgroup per tile of molecules), per-type sums, a ring of per-sample sums and the histograms of Rg and |R|.
 RouseModes is their dynamic counterpart: the normal modes X_p and the end-to-end vector of every linear chain in the same unfolded
 coordinates (pse_chain_modes_compute), kept for up to 64 time origins on the device (pse_chain_modes_store) and correlated with them
-per type and mode (pse_chain_modes_correlate): amplitudes, <X_p(t) X_p(0)> and the relaxation times tau_p."""
+per type and mode (pse_chain_modes_correlate): amplitudes, <X_p(t) X_p(0)> and the relaxation times tau_p.
+IntermediateScattering is the dynamic counterpart of StructureFactor: the self part F_s(k, t) and the collective part F(k, t) of the
+density correlations over up to 64 time origins (pse_isf_sample, pse_isf_store, pse_isf_correlate), on the integer modes of the box."""
 import contextlib
 import math
 
 from .engine import (BOND_ORDER_MAX_COUNTERS, MSD_MAX_ORIGINS, MSD_MOMENTS, SF_MAX_MODES, BondOrderShells, ClusterLinks, DisplacementOrigins,
-                     PairHistogram, StructureFactorModes, _bond_order_arguments, _cluster_arguments, _msd_arguments, _ntypes_argument,
-                     _pair_hist_arguments, _structure_factor_arguments, _types_argument, pair_type_index)
+                     PairHistogram, ScatteringOrigins, StructureFactorModes, _bond_order_arguments, _cluster_arguments, _isf_arguments,
+                     _msd_arguments, _ntypes_argument, _pair_hist_arguments, _structure_factor_arguments, _types_argument, pair_type_index)
 from .forces import _excl_list
 
 
@@ -459,7 +461,8 @@ class MSDSchedule:
     accumulated against every origin j = 0, 1, ... with 1 <= s - j origin_every <= nlags, into row lag - 1, and then (2), if s is a
     multiple of origin_every, is stored as origin s / origin_every in slot (s / origin_every) % norigins, norigins =
     ceil(nlags / origin_every): a slot is overwritten only after its origin's lag nlags has been taken.  `counts[lag - 1]`: the origins
-    that lag has been taken against so far; `live[slot]`: the sample stored in that slot since the last reset()."""
+    that lag has been taken against so far; `live[slot]`: the sample stored in that slot since the last reset().  drop_origins():
+    the origins stored so far are no longer paired with later samples (their slots leave `live`); sums and counts stay."""
 
     def __init__(self, nlags, origin_every=1):
         self.nlags, self.origin_every = int(nlags), int(origin_every)
@@ -472,13 +475,18 @@ class MSDSchedule:
         self.reset()
 
     def reset(self):
-        self.samples, self.counts, self.live = 0, [0] * self.nlags, {}
+        self.samples, self.counts, self.live, self._first = 0, [0] * self.nlags, {}, 0
+
+    def drop_origins(self):
+        """Every origin older than the next sample is no longer paired: the next sample, if it is an origin, is the oldest one."""
+        self._first = -(-self.samples // self.origin_every)  # the smallest j with j oe >= samples
+        self.live = {}
 
     def pairs(self, s=None):
         """[(slot, row)] of sample s (default: the next one), oldest origin first."""
         s = self.samples if s is None else int(s)
         oe = self.origin_every
-        first = max(0, -(-(s - self.nlags) // oe))          # the smallest j with s - j oe <= nlags
+        first = max(self._first, -(-(s - self.nlags) // oe))   # the smallest j with s - j oe <= nlags that was not dropped
         last = (s - 1) // oe if s >= 1 else -1               # the largest j with s - j oe >= 1
         return [(j % self.norigins, s - j * oe - 1) for j in range(first, last + 1)]
 
@@ -1481,3 +1489,173 @@ class RouseModes(_TypedAnalyzer):
         out = torch.empty((self.nlin, self.K, 3), dtype=torch.float64, device=self.system.pos.device)
         self.integrator.engine.chain_modes_compute(self.system.pos, self._modes, out=out)
         return out.cpu().numpy()
+
+
+def _isf_analyzer_arguments(modes, nlags, origin_every, types, type_names, period, self_part, collective):
+    """What IntermediateScattering checks before it touches the device.  Returns (schedule, types uint32 or None, ntypes, modes int32
+    (nk, 3), names or None, period)."""
+    schedule = MSDSchedule(nlags, origin_every)
+    types, ntypes, names, period = _typed_arguments(types, type_names, period)
+    types, ntypes, modes, _ = _isf_arguments(types, ntypes, modes, schedule.norigins)
+    if not (self_part or collective):
+        raise ValueError("self_part and collective are both off: nothing to measure")
+    return schedule, types, ntypes, modes, names, period
+
+
+class IntermediateScattering(_TypedAnalyzer):
+    """Intermediate scattering functions of a run over many time origins: every `period` steps (a sample) the fractional coordinates
+    of the integrator's group and its densities rho_a(m) on the integer modes `modes` (nk, 3) go into a buffer on the device
+    (pse_isf_sample, which also adds the static Re(rho_a conj rho_b) exactly as StructureFactor does), the sample is correlated with
+    every live origin (pse_isf_correlate) and, every `origin_every` samples, stored as a new origin (pse_isf_store).  Lags run from 1
+    to `nlags` samples by MSDSchedule; ceil(nlags / origin_every) <= 64 origins are kept.  `types`, `type_names`: as for RDF; at most 8
+    types, 4096 modes, |m_i| <= 4096.  Sampling only queues work; the readers below are the only places that wait for the device.
+
+    Self part: F_s(m, t) = <exp(-2 pi i m.(s_j(t) - s_j(0)))> over the particles of a type, s the fractional coordinates: no images and
+    no unwrapping are needed, a particle that wrapped around the box gives the same value.  Collective part: F_ab(m, t) =
+    <rho_a(m, t) conj rho_b(m, 0)> / sqrt(N_a N_b), a the type NOW and b the type AT THE ORIGIN; both orders are kept, they differ
+    under shear.  In a tilting box an integer mode is the ADVECTED wave vector k(t) = 2 pi (mx/Lx, my/Ly - xy(t) mx/Lx, mz/Lz), the
+    usual choice under shear: purely affine motion leaves F_s = 1.  A Lees-Edwards flip relabels the integer modes (s_x changes by a
+    multiple of s_y), so when system.tilt_flips differs from its value at the previous sample the live origins are dropped
+    (MSDSchedule.drop_origins; sums and counts stay): lags that span a flip are never sampled, and with a flip every T samples the
+    lags >= T stay empty (NaN).  `k` and `shell_average` raise ValueError when the samples' boxes differ, as StructureFactor's do.
+
+    samples;  lags -- in steps;  counts -- origins per lag;  self_sums -- (nlags, ntypes, nk) complex;  collective_sums -- (nlags,
+    ntypes, ntypes, nk);  static_sums -- (npt, nk);  boxes;  Fs(a) -- (nlags, nk) = Re self / (counts N_a);  F(a, b) = coll / (counts
+    sqrt(N_a N_b)), F() the total sum_ab coll / (counts N);  S(a, b), S() -- the static structure factor of the samples;  f(a, b) =
+    F / S;  k -- (nk, 3);  shell_average(values, nbins, kmax=None) -- the mean of values (nk,) or (rows, nk) over bins of |k|:
+    (centres, means, counts);  relaxation_times(which="self" | "collective", a=None) -- (nk,), in steps, by relaxation_time_of;
+    reset().  a = None: all types together; NaN where a lag has no origin yet or a type no particle."""
+
+    def __init__(self, integrator, modes, nlags, origin_every=1, types=None, type_names=None, period=1, self_part=True, collective=True):
+        import torch
+        self._schedule, types, self.ntypes, self.modes, self.type_names, self.period = _isf_analyzer_arguments(
+            modes, nlags, origin_every, types, type_names, period, self_part, collective)   # (raises before the device is touched)
+        with self._attach(integrator, types) as system:
+            self.nlags, self.origin_every, self.norigins = self._schedule.nlags, self._schedule.origin_every, self._schedule.norigins
+            self._isf = ScatteringOrigins(integrator.engine, types, self.ntypes, self.modes, self.norigins, system.n)
+            self.npt, self.nk = self._isf.npt, self._isf.nk
+            dev = system.pos.device
+            self._self = torch.zeros((self.nlags, self.ntypes, self.nk, 2), dtype=torch.float64, device=dev) if self_part else None
+            self._coll = torch.zeros((self.nlags, self.ntypes, self.ntypes, self.nk), dtype=torch.float64, device=dev) if collective else None
+            self._static = torch.zeros((self.npt, self.nk), dtype=torch.float64, device=dev)
+            self.boxes, self._flips = [], None
+
+    def analyze(self, timestep):
+        if not self._due(timestep):
+            return
+        s, e, f = self.system, self.integrator.engine, self._isf
+        if self._flips is not None and s.tilt_flips != self._flips:
+            self._schedule.drop_origins()   # (the stored origins are in the old labelling of the modes)
+        self._flips = s.tilt_flips
+        e.isf_sample(s.pos, f, static_sums=self._static, group=self.integrator.group.members)
+        self._schedule.sample(lambda slots, rows: e.isf_correlate(f, slots, rows, self._self, self._coll), lambda slot: e.isf_store(f, slot))
+        self.boxes.append(tuple(s.box))
+
+    def reset(self):
+        """Forget the sums, the counts, the boxes and the origins."""
+        for t in (self._self, self._coll, self._static):
+            if t is not None:
+                t.zero_()
+        self._schedule.reset()
+        self.boxes, self._flips = [], None
+
+    @property
+    def samples(self):
+        return self._schedule.samples
+
+    @property
+    def lags(self):
+        import numpy as np
+        return np.arange(1, self.nlags + 1) * self.period
+
+    @property
+    def counts(self):
+        import numpy as np
+        return np.array(self._schedule.counts, dtype=np.int64)
+
+    @property
+    def self_sums(self):
+        if self._self is None:
+            raise ValueError("this analyzer was made with self_part=False")
+        r = self._self.cpu().numpy()
+        return r[..., 0] + 1j * r[..., 1]
+
+    @property
+    def collective_sums(self):
+        if self._coll is None:
+            raise ValueError("this analyzer was made with collective=False")
+        return self._coll.cpu().numpy()
+
+    @property
+    def static_sums(self):
+        return self._static.cpu().numpy()
+
+    def _per_lag(self, tot, n):
+        import numpy as np
+        den = self.counts.astype(np.float64)[:, None] * n
+        return np.divide(tot, den, out=np.full(tot.shape, np.nan), where=den > 0.0)
+
+    def Fs(self, a=None):
+        """(nlags, nk): the self part of type `a` (None: of all particles)."""
+        import numpy as np
+        r, nc = self.self_sums.real, self._type_counts()
+        return self._per_lag(r.sum(axis=1), float(np.sum(nc))) if a is None else self._per_lag(r[:, self._code(a)], float(nc[self._code(a)]))
+
+    def F(self, a=None, b=None):
+        """(nlags, nk): F_ab, a the type now and b the type at the origin; without arguments the total."""
+        import numpy as np
+        if (a is None) != (b is None):
+            raise ValueError("F() takes both types or neither")
+        c, nc = self.collective_sums, self._type_counts()
+        if a is None:
+            return self._per_lag(c.sum(axis=(1, 2)), float(np.sum(nc)))
+        a, b = self._code(a), self._code(b)
+        return self._per_lag(c[:, a, b], math.sqrt(float(nc[a]) * float(nc[b])))
+
+    def S(self, a=None, b=None):
+        """S_ab per mode, (nk,), of the samples taken; without arguments the total S."""
+        if (a is None) != (b is None):
+            raise ValueError("S() takes both types or neither")
+        self._sampled()
+        if a is not None:
+            a, b = self._code(a), self._code(b)
+        return S_of_sums(self.static_sums, self.samples, self._type_counts(), a, b)
+
+    def f(self, a=None, b=None):
+        """(nlags, nk): F / S, the normalised collective part; NaN or inf at a mode where S vanishes."""
+        import numpy as np
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.F(a, b) / self.S(a, b)[None, :]
+
+    def _box(self):
+        if not self.boxes:
+            raise ValueError("no samples yet")
+        if any(bx != self.boxes[0] for bx in self.boxes):
+            raise ValueError("the boxes of the samples differ (a tilting box): the sums are per integer mode, there is no one k; sample "
+                             "at a period over which the tilt repeats")
+        return self.boxes[0]
+
+    @property
+    def k(self):
+        return k_vectors(self.modes, self._box())
+
+    def shell_average(self, values, nbins, kmax=None):
+        """The mean of `values` -- (nk,), or (rows, nk) row by row -- over nbins bins of |k|: (centres, means, counts)."""
+        import numpy as np
+        k, values = self.k, np.asarray(values, dtype=np.float64)   # (the differing-box check comes first)
+        if values.ndim == 1:
+            return shell_average_of(k, values, nbins, kmax)
+        if values.ndim != 2 or values.shape[1] != self.nk:
+            raise ValueError(f"values must be ({self.nk},) or (rows, {self.nk})")
+        out = [shell_average_of(k, row, nbins, kmax) for row in values]
+        return out[0][0], np.stack([o[1] for o in out]), out[0][2]
+
+    def relaxation_times(self, which="self", a=None):
+        """(nk,): the time, in steps, at which F_s(m, t) (which="self") or f(m, t) = F / S of type `a` with itself (which="collective";
+        a = None: the totals) first falls to 1/e, by relaxation_time_of with the value 1 at lag 0; NaN where it never does."""
+        import numpy as np
+        if which not in ("self", "collective"):
+            raise ValueError('which must be "self" or "collective"')
+        c = self.Fs(a) if which == "self" else self.f(a, a)
+        t = np.concatenate([[0], self.lags])
+        return np.array([relaxation_time_of(t, np.concatenate([[1.0], c[:, q]])) for q in range(self.nk)])

@@ -4,7 +4,7 @@
 // exercised under -fsanitize=address,undefined against this stand-in.  The calls the host classes make (pse_create,
 // pse_destroy, pse_set_box, pse_get_info, pse_step, pse_set_lanczos_operator) and the force entry points that the CPU tests call through
 // ctypes (pse_pair_repulsion, pse_pair_repulsion_virial, pse_pair_table, their _excl forms, pse_bonds_*, pse_angles_*,
-// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*, pse_molecule_pairs_*, pse_chain_modes_*) keep a small host object that runs the REAL parameter
+// pse_dihedrals_*, pse_exclusions_*, pse_typed_table_*, pse_pair_table_typed, pse_pair_hist_*, pse_structure_factor_*, pse_msd_*, pse_clusters_*, pse_bond_order_*, pse_molecules_*, pse_molecule_pairs_*, pse_chain_modes_*, pse_isf_*) keep a small host object that runs the REAL parameter
 // rule and table builder; every entry point that would need a device returns PSE_ERR_HIP.  No test takes a number from here.
 #include <algorithm>
 #include <cmath>
@@ -62,6 +62,11 @@ struct pse_chain_modes : Topology {   // the REAL layout and the molecule types;
     int ntypes = 1, norigins = 0;
     bool computed = false;
     unsigned long long stored = 0ull;
+};
+struct pse_isf : Topology {   // row_off: the REAL plan (structure_factor_plan), entries: its permutation; the buffers' bookkeeping
+    using Topology::Topology;
+    int norigins = 0;
+    unsigned sample_N = 0u, slot_N[ISF_MAX_ORIGINS] = {};
 };
 struct pse_team { int unused; };
 
@@ -370,6 +375,34 @@ int pse_chain_modes_store(pse_chain_modes *obj, int slot) {
 int pse_chain_modes_correlate(pse_chain_modes *obj, int npairs, const int *slots_host, const int *rows_host, int nrows, double *corr) {
     return chain_modes_correlate_validate(obj, obj ? obj->norigins : 0, obj ? obj->computed : false, obj ? obj->stored : 0ull, npairs, slots_host,
                                           rows_host, nrows, corr);
+}
+int pse_isf_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, unsigned nk, const int *modes_host, int norigins,
+                   pse_isf **out) {
+    if (!out) return fail(PSE_ERR_INVALID, "pse_isf_create: null out");
+    *out = nullptr;
+    if (!h) return fail(PSE_ERR_INVALID, "pse_isf_create: null handle");
+    if (int rc = isf_create_validate(h->par.n_max, n, types_host, ntypes, nk, modes_host, norigins)) return rc;
+    pse_isf *f = new pse_isf(h, 0, 0);
+    f->norigins = norigins;
+    std::vector<unsigned> uoff;
+    structure_factor_plan(nk, modes_host, f->entries, uoff, f->row_off);
+    return topology_adopt(f, 0, out);
+}
+int pse_isf_destroy(pse_isf *f) { return topology_destroy(f); }
+// (the arrays are device pointers and there is no device: nothing is read or written; a sample and a store mark the bookkeeping)
+int pse_isf_sample(pse_isf *f, const pse_double4 *pos, const unsigned *, unsigned N, double *rho, double *static_sums) {
+    if (int rc = isf_sample_validate(f, f ? f->h->par.n_max : 0u, N, pos, rho, static_sums)) return rc;
+    f->sample_N = N;
+    return 0;
+}
+int pse_isf_store(pse_isf *f, int slot) {
+    if (int rc = isf_store_validate(f, f ? f->norigins : 0, f ? f->sample_N : 0u, slot)) return rc;
+    f->slot_N[slot] = f->sample_N;
+    return 0;
+}
+int pse_isf_correlate(pse_isf *f, int npairs, const int *slots_host, const int *rows_host, int nrows, double *self, double *coll) {
+    return isf_correlate_validate(f, f ? f->norigins : 0, f ? f->sample_N : 0u, f ? f->slot_N : nullptr, npairs, slots_host, rows_host, nrows,
+                                  self, coll);
 }
 int pse_bonds_create(pse_handle *h, unsigned n, unsigned nbonds, const unsigned *pairs_host, const unsigned *types_host, int ntypes,
                      const int *kind_host, const double *k_host, const double *r0_host, pse_bonds **out) {

@@ -90,6 +90,17 @@ int msd_displacement_validate(unsigned long long stored, int slot, const void *o
 // the argument checks of pse_msd_accumulate
 int msd_accumulate_validate(const void *m, int norigins, unsigned long long stored, unsigned n_max, unsigned N, const void *pos,
                             const void *image, double strain, int npairs, const int *slots, const int *rows, int nrows, const void *sums);
+// the argument checks of pse_isf_create behind its null-out and null-handle checks: those of pse_structure_factor_create, in its
+// order, with nk capped at ISF_MAX_MODES, then norigins
+int isf_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes, int norigins);
+// the argument checks of pse_isf_sample, pse_isf_store and pse_isf_correlate, in the order include/pse_amd.h lists them (n_max: the
+// handle's; norigins: the object's; sample_N: N of the sample in the current buffer, 0: none since create; slot_N[s]: N of the sample
+// stored in slot s, 0: never stored).  A slot holds one sample whole, so the checks of a pair's slot -- in range, stored, the N of the
+// current sample -- run over the list one after another, as those of pse_msd_accumulate do
+int isf_sample_validate(const void *obj, unsigned n_max, unsigned N, const void *pos, const void *rho, const void *static_sums);
+int isf_store_validate(const void *obj, int norigins, unsigned sample_N, int slot);
+int isf_correlate_validate(const void *obj, int norigins, unsigned sample_N, const unsigned *slot_N, int npairs, const int *slots, const int *rows,
+                           int nrows, const void *self, const void *coll);
 // the argument checks of pse_clusters_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them
 // (types may be null: one type), with the handle's rcut and n_max
 int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rlink);

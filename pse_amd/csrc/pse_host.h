@@ -18,6 +18,8 @@ constexpr int SF_RUN = 8;              // modes of one segment: a lane of k_sf_p
 constexpr int SF_SHORT = 2;            // a segment of at most this many modes is walked by the short form of the kernel (k_sf_partial<SF_SHORT>)
 constexpr int MSD_MAX_ORIGINS = 64;   // slots of one displacement object, and pairs (slot, row) of one pse_msd_accumulate (PSE_MSD_MAX_ORIGINS)
 constexpr int MSD_MOMENTS = 10;       // dx dy dz, dx^2 dy^2 dz^2 dxdy dxdz dydz, |d|^4 (PSE_MSD_MOMENTS)
+constexpr int ISF_MAX_ORIGINS = 64;   // slots of one scattering object, and pairs (slot, row) of one pse_isf_correlate (PSE_ISF_MAX_ORIGINS)
+constexpr int ISF_MAX_MODES = 4096;   // modes of one scattering object (PSE_ISF_MAX_MODES): the self pass keeps a partial sum per (span, pair, type, mode)
 constexpr int BOND_ORDER_MAX_DEGREES = 4;   // degrees of one bond-order object (pse_bond_order_create; PSE_BOND_ORDER_MAX_DEGREES)
 constexpr int BOND_ORDER_MAX_L = 12;        // the largest degree, even degrees 2..12 (PSE_BOND_ORDER_MAX_L)
 constexpr int BOND_ORDER_MAX_COUNTERS = 8192;   // counters of pse_bond_order_histogram, types x bins: 32 KB of LDS

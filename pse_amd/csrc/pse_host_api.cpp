@@ -333,10 +333,11 @@ int pair_hist_validate(const void *g, const void *g_handle, unsigned n_max, unsi
     return 0;
 }
 
-int structure_factor_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes) {
-    const char *who = "pse_structure_factor_create";
+// what pse_structure_factor_create and pse_isf_create (`who`) refuse alike: the sizes, nk against the cap of the object, the modes, the types
+static int mode_list_validate(const char *who, unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, int nk_max,
+                              const int *modes) {
     if (int rc = sizes_in_range(who, n_max, n, ntypes)) return rc;
-    if (nk == 0 || nk > (unsigned)SF_MAX_MODES) return fail(PSE_ERR_INVALID, "%s: nk = %u outside [1, %d]", who, nk, SF_MAX_MODES);
+    if (nk == 0 || nk > (unsigned)nk_max) return fail(PSE_ERR_INVALID, "%s: nk = %u outside [1, %d]", who, nk, nk_max);
     if (!modes) return fail(PSE_ERR_INVALID, "%s: null modes_host", who);
     for (unsigned q = 0; q < nk; ++q)
         for (int c = 0; c < 3; ++c)
@@ -344,6 +345,10 @@ int structure_factor_create_validate(unsigned n_max, unsigned n, const unsigned 
                 return fail(PSE_ERR_INVALID, "%s: mode %u has the index m%c = %d beyond +-%d", who, q, "xyz"[c], modes[3 * (size_t)q + c], SF_MAX_INDEX);
     if (int rc = types_in_range(who, n, types, ntypes)) return rc;
     return 0;
+}
+
+int structure_factor_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes) {
+    return mode_list_validate("pse_structure_factor_create", n_max, n, types, ntypes, nk, SF_MAX_MODES, modes);
 }
 
 int structure_factor_validate(const void *f, unsigned n_max, unsigned N, const void *pos, const void *rho, const void *sums) {
@@ -408,6 +413,61 @@ int msd_accumulate_validate(const void *m, int norigins, unsigned long long stor
             if (rows[p] == rows[q]) return fail(PSE_ERR_INVALID, "%s: pairs %d and %d both name the row %d", who, p, q, rows[q]);
     if (!sums) return fail(PSE_ERR_INVALID, "%s: null sums", who);
     if (((uintptr_t)sums & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: sums = %p is not 8-byte aligned (doubles)", who, sums);
+    return 0;
+}
+
+int isf_create_validate(unsigned n_max, unsigned n, const unsigned *types, int ntypes, unsigned nk, const int *modes, int norigins) {
+    const char *who = "pse_isf_create";
+    if (int rc = mode_list_validate(who, n_max, n, types, ntypes, nk, ISF_MAX_MODES, modes)) return rc;
+    if (norigins < 1 || norigins > ISF_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: norigins = %d outside [1, %d]", who, norigins, ISF_MAX_ORIGINS);
+    return 0;
+}
+
+int isf_sample_validate(const void *obj, unsigned n_max, unsigned N, const void *pos, const void *rho, const void *static_sums) {
+    const char *who = "pse_isf_sample";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null scattering object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (((uintptr_t)rho & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: rho = %p is not 8-byte aligned (doubles)", who, rho);
+    if (((uintptr_t)static_sums & 7u) != 0)
+        return fail(PSE_ERR_INVALID, "%s: static_sums = %p is not 8-byte aligned (doubles)", who, static_sums);
+    return 0;
+}
+
+int isf_store_validate(const void *obj, int norigins, unsigned sample_N, int slot) {
+    const char *who = "pse_isf_store";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null scattering object", who);
+    if (slot < 0 || slot >= norigins) return fail(PSE_ERR_INVALID, "%s: slot = %d outside [0, norigins = %d)", who, slot, norigins);
+    if (!sample_N) return fail(PSE_ERR_INVALID, "%s: no pse_isf_sample since create: the current buffer holds nothing", who);
+    return 0;
+}
+
+int isf_correlate_validate(const void *obj, int norigins, unsigned sample_N, const unsigned *slot_N, int npairs, const int *slots, const int *rows,
+                           int nrows, const void *self, const void *coll) {
+    const char *who = "pse_isf_correlate";
+    if (!obj) return fail(PSE_ERR_INVALID, "%s: null scattering object", who);
+    if (!sample_N) return fail(PSE_ERR_INVALID, "%s: no pse_isf_sample since create: the current buffer holds nothing", who);
+    if (npairs < 1 || npairs > ISF_MAX_ORIGINS) return fail(PSE_ERR_INVALID, "%s: npairs = %d outside [1, %d]", who, npairs, ISF_MAX_ORIGINS);
+    if (!slots) return fail(PSE_ERR_INVALID, "%s: null slots_host", who);
+    if (!rows) return fail(PSE_ERR_INVALID, "%s: null rows_host", who);
+    if (nrows < 1) return fail(PSE_ERR_INVALID, "%s: nrows = %d, need at least one row", who, nrows);
+    for (int q = 0; q < npairs; ++q)
+        if (slots[q] < 0 || slots[q] >= norigins)
+            return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d outside [0, norigins = %d)", who, q, slots[q], norigins);
+    for (int q = 0; q < npairs; ++q)
+        if (!slot_N[slots[q]]) return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d, which was never stored", who, q, slots[q]);
+    for (int q = 0; q < npairs; ++q)
+        if (slot_N[slots[q]] != sample_N)
+            return fail(PSE_ERR_INVALID, "%s: pair %d names the slot %d, stored with N = %u: the current sample has N = %u", who, q, slots[q],
+                        slot_N[slots[q]], sample_N);
+    for (int q = 0; q < npairs; ++q)
+        if (rows[q] < 0 || rows[q] >= nrows) return fail(PSE_ERR_INVALID, "%s: pair %d names the row %d outside [0, nrows = %d)", who, q, rows[q], nrows);
+    for (int q = 0; q < npairs; ++q)
+        for (int p = 0; p < q; ++p)
+            if (rows[p] == rows[q]) return fail(PSE_ERR_INVALID, "%s: pairs %d and %d both name the row %d", who, p, q, rows[q]);
+    if (!self && !coll) return fail(PSE_ERR_INVALID, "%s: self and coll are both null: nothing to compute", who);
+    if (((uintptr_t)self & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: self = %p is not 8-byte aligned (doubles)", who, self);
+    if (((uintptr_t)coll & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: coll = %p is not 8-byte aligned (doubles)", who, coll);
     return 0;
 }
 

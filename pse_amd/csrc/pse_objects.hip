@@ -1,6 +1,6 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
 // typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors, displacement
-// moments, chain conformations, chain statistics and chain normal modes.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h, pse_molecules.h, pse_molpairs.h or pse_molmodes.h, the objects own their arrays through DeviceObject
+// moments, chain conformations, chain statistics, chain normal modes and intermediate scattering functions.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h, pse_molecules.h, pse_molpairs.h, pse_molmodes.h or pse_scatter.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "pse_molecules.h"
 #include "pse_molpairs.h"
 #include "pse_molmodes.h"
+#include "pse_scatter.h"
 
 // A bonded topology on the device (include/pse_amd.h): the rows of pse_host_bond_rows, pse_host_angle_rows or pse_host_dihedral_rows, the per-type parameters
 // and, for bonds, the counter of overstretched FENE bonds.
@@ -62,6 +63,13 @@ struct pse_msd : DeviceObject {
     MsdOrigins mo{};
     int norigins = 0;
     unsigned long long stored = 0ull;       // bit s = slot s holds positions
+};
+struct pse_isf : DeviceObject {
+    Scatter sc{};
+    int norigins = 0;
+    unsigned sample_N = 0u;                     // N of the sample in the current buffer (0: no pse_isf_sample since create)
+    const unsigned *group = nullptr;            // ... and its group
+    unsigned slot_N[ISF_MAX_ORIGINS] = {};      // N of the sample stored in a slot (0: never stored)
 };
 
 // ---- what every pse_*_create shares (`who`: its name) --------------------------------------------------------------------------------
@@ -451,6 +459,73 @@ extern "C" int pse_msd_accumulate(pse_msd *m, const pse_double4 *pos, const pse_
     for (int q = 0; q < npairs; ++q) { pairs.slot[q] = (unsigned char)slots_host[q]; pairs.row[q] = rows_host[q]; }
     launch_msd_accumulate((const double4 *)pos, (const int3 *)image, group, (int)N, h->dbox.Lx, h->dbox.Ly, h->dbox.Lz, strain * h->dbox.Ly,
                           m->mo, pairs, sums, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Intermediate scattering functions (include/pse_amd.h): the types, the plan of the modes and the workspace of the structure-factor
+// pass, the current buffer, the origin slots and the workspace of the self pass -- everything is placed here --, and the passes.
+// Queue-only: no prepare(), no sort, nothing of the cell list or the kept neighbour list is touched; nothing is read back.
+extern "C" int pse_isf_create(pse_handle *h, unsigned n, const unsigned *types_host, int ntypes, unsigned nk, const int *modes_host, int norigins,
+                              pse_isf **out) {
+    const char *who = "pse_isf_create";
+    TRY(create_begin(who, h, out));
+    TRY(isf_create_validate((unsigned)h->n_max, n, types_host, ntypes, nk, modes_host, norigins));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<unsigned> perm, uoff;
+    std::vector<int> segs;
+    structure_factor_plan(nk, modes_host, perm, uoff, segs);
+    pse_isf *f = new pse_isf();
+    f->h = h;
+    f->norigins = norigins;
+    Scatter &sc = f->sc;
+    StructureFactor &sf = sc.sf;
+    sf.n = n; sf.ntypes = ntypes; sf.nk = (int)nk;
+    sf.nseg = (int)(segs.size() / 8);
+    for (size_t g = 0; g < segs.size(); g += 8) sf.nlong += segs[g + 3] > SF_SHORT;
+    sf.nu = (int)uoff.size() - 1; sf.span = sf_span((unsigned)h->n_max, ntypes, (int)nk);
+    sc.n_max = (size_t)h->n_max; sc.buf = 3 * sc.n_max + 2 * (size_t)ntypes * nk;
+    sc.span = isf_span((unsigned)h->n_max, ntypes, (int)nk);
+    hipError_t e = f->put(&sf.types, type_bytes(types_host, n).data(), n);
+    e = f->put(&sf.segs, (const int4 *)segs.data(), segs.size() / 4);
+    e = f->put(&sf.perm, perm.data(), perm.size());
+    e = f->put(&sf.uoff, uoff.data(), uoff.size());
+    e = f->put(&sf.rows, nullptr, sf_workspace((unsigned)h->n_max, ntypes, (int)nk));
+    e = f->put(&sc.cur, nullptr, sc.buf, true);
+    e = f->put(&sc.slots, nullptr, sc.buf * (size_t)norigins, true);
+    e = f->put(&sc.part, nullptr, isf_workspace((unsigned)h->n_max, ntypes, (int)nk));
+    return create_end(who, h, f, e, out);
+}
+extern "C" int pse_isf_destroy(pse_isf *f) { return object_destroy(f); }
+extern "C" int pse_isf_sample(pse_isf *f, const pse_double4 *pos, const unsigned *group, unsigned N, double *rho, double *static_sums) {
+    pse_handle *h = f ? f->h : nullptr;
+    TRY(isf_sample_validate(f, h ? (unsigned)h->n_max : 0u, N, pos, rho, static_sums));
+    HIPCHK(hipSetDevice(h->device));
+    launch_isf_sample((const double4 *)pos, group, (int)N, h->dbox, f->sc, static_sums, h->stream);
+    HIPCHK(hipGetLastError());
+    f->sample_N = N; f->group = group;
+    if (rho)
+        HIPCHK(hipMemcpyAsync(rho, f->sc.cur + 3 * f->sc.n_max, (f->sc.buf - 3 * f->sc.n_max) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+extern "C" int pse_isf_store(pse_isf *f, int slot) {
+    TRY(isf_store_validate(f, f ? f->norigins : 0, f ? f->sample_N : 0u, slot));
+    pse_handle *h = f->h;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(f->sc.slots + (size_t)slot * f->sc.buf, f->sc.cur, f->sc.buf * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    f->slot_N[slot] = f->sample_N;
+    return 0;
+}
+extern "C" int pse_isf_correlate(pse_isf *f, int npairs, const int *slots_host, const int *rows_host, int nrows, double *self, double *coll) {
+    TRY(isf_correlate_validate(f, f ? f->norigins : 0, f ? f->sample_N : 0u, f ? f->slot_N : nullptr, npairs, slots_host, rows_host, nrows, self,
+                               coll));
+    pse_handle *h = f->h;
+    HIPCHK(hipSetDevice(h->device));
+    ScatterPairs pairs{};
+    pairs.npairs = npairs;
+    for (int q = 0; q < npairs; ++q) { pairs.slot[q] = (unsigned char)slots_host[q]; pairs.row[q] = rows_host[q]; }
+    if (self) launch_isf_self(f->sc, f->group, (int)f->sample_N, pairs, self, h->stream);
+    if (coll) launch_isf_coll(f->sc, pairs, coll, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -539,6 +539,37 @@ class DisplacementOrigins(_TypedObject):
         self._create(engine, "pse_msd_create", types, ntypes, n, self.norigins)
 
 
+ISF_MAX_ORIGINS = 64   # pse_isf_create: slots of one object, and pairs (slot, row) of one pse_isf_correlate
+ISF_MAX_MODES = 4096   # ... and the number of modes
+
+
+def _isf_arguments(types, ntypes, modes, norigins):
+    """The arguments of a scattering object, checked before the device is touched: (types uint32 (n,) or None, ntypes, modes int32
+    (nk, 3), norigins): those of a structure-factor object with at most ISF_MAX_MODES modes, and 1 <= norigins <= ISF_MAX_ORIGINS."""
+    types, ntypes, modes = _structure_factor_arguments(types, ntypes, modes)
+    if modes.shape[0] > ISF_MAX_MODES:
+        raise ValueError(f"{modes.shape[0]} modes, more than {ISF_MAX_MODES}")
+    norigins = int(norigins)
+    if not 1 <= norigins <= ISF_MAX_ORIGINS:
+        raise ValueError(f"norigins = {norigins} outside [1, {ISF_MAX_ORIGINS}]")
+    return types, ntypes, modes, norigins
+
+
+class ScatteringOrigins(_TypedObject):
+    """Owner of a pse_isf object: one type per particle, a list of integer modes (mx, my, mz) of the box's reciprocal lattice, a
+    current buffer and `norigins` origin slots of fractional coordinates and densities on the device.  `types`, `modes`: as for
+    StructureFactorModes, at most 4096 modes.  Pass it as `isf` to Engine.isf_sample, isf_store and isf_correlate.  sample_n: N of the
+    sample in the current buffer (0: none yet); slot_n[s]: N of the sample stored in slot s (0: never stored)."""
+
+    DESTROY = "pse_isf_destroy"
+
+    def __init__(self, engine, types, ntypes, modes, norigins, n=None):
+        types, ntypes, self.modes, self.norigins = _isf_arguments(types, ntypes, modes, norigins)
+        self.nk = int(self.modes.shape[0])
+        self._create(engine, "pse_isf_create", types, ntypes, n, self.nk, _vp(self.modes), self.norigins)
+        self.sample_n, self.slot_n = 0, [0] * self.norigins
+
+
 MOL_TILE = 1024       # PSE_MOL_TILE: members of the largest molecule
 MOL_COLS = 14         # PSE_MOL_COLS: columns of a molecule's row and of a type's sums
 MOL_MAX_BINS = 4096   # pse_molecules_create: bins of each histogram
@@ -978,6 +1009,64 @@ class _ForcePasses:
         _lib.check(self._lib.pse_msd_displacement(origins._handle(self), slot, _ptr(pos), _ptr(image), _ptr(group), n,
                                                   _finite(strain, "strain"), _ptr(out)))
         return out
+
+    def isf_origins(self, types, ntypes, modes, norigins, n=None):
+        """Scattering origins on the device (pse_isf_create; see include/pse_amd.h): `types` (n,) the type of every caller-order
+        particle, below `ntypes` <= 8, or None: one type; `modes` (nk, 3) integers (mx, my, mz) within +-4096, at most 4096, of the
+        reciprocal lattice of whatever box the engine has when a sample is taken; `norigins` <= 64 slots; `n`: how many of `types` to
+        use (default: all; without types: n_max).  Returns a ScatteringOrigins with nk, ntypes, npt, norigins and close()."""
+        return ScatteringOrigins(self, types, ntypes, modes, norigins, n)
+
+    def isf_sample(self, pos, isf, rho=None, static_sums=None, group=None):
+        """One sample into the current buffer of `isf` (pse_isf_sample): the fractional coordinates of the group in the engine's
+        current box and the densities rho_a(m), by the pass of structure_factor_accumulate -- `rho` (a contiguous (ntypes, nk, 2)
+        float64 CUDA tensor, WRITTEN) and `static_sums` ((npt, nk), ADDED to) get its bits; either may be None, and both.  Every
+        sample of one object must use the same group.  Queue-only.  Returns (rho, static_sums)."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        for t, name, shape in ((rho, "rho", (isf.ntypes, isf.nk, 2)), (static_sums, "static_sums", (isf.npt, isf.nk))):
+            if t is not None and not (_is_cuda(t, torch.float64) and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {shape} float64 CUDA tensor")
+        _lib.check(self._lib.pse_isf_sample(isf._handle(self), _ptr(pos), _ptr(group), n, _ptr(rho), _ptr(static_sums)))
+        isf.sample_n, isf._group = int(n), group   # (the device object remembers the group's pointer: the tensor must live as long)
+        return rho, static_sums
+
+    def isf_store(self, isf, slot):
+        """The current buffer of `isf` into its origin slot `slot` (pse_isf_store).  Queue-only."""
+        slot = int(slot)
+        if not 0 <= slot < isf.norigins:
+            raise ValueError(f"slot = {slot} outside [0, {isf.norigins})")
+        if not isf.sample_n:
+            raise ValueError("no isf_sample yet: the current buffer holds nothing")
+        _lib.check(self._lib.pse_isf_store(isf._handle(self), slot))
+        isf.slot_n[slot] = isf.sample_n
+
+    def isf_correlate(self, isf, slots, rows, self_sums=None, coll=None):
+        """The current buffer of `isf` against stored origins (pse_isf_correlate): for every pair (slots[q], rows[q]), types a, b and
+        mode m, self_sums[rows[q], a, m] += (re, im) of the sum over the group members of type a of exp(-2 pi i m.(s(now) - s(slot)))
+        and coll[rows[q], a, b, m] += Re(rho_a(m; now) conj rho_b(m; slot)).  `self_sums`: a contiguous (nrows, ntypes, nk, 2)
+        float64 CUDA tensor, `coll`: (nrows, ntypes, ntypes, nk), both ADDED to, either may be None, not both; at most 64 pairs,
+        every slot stored before with the N of the current sample, no row twice.  Queue-only: nothing is read back, no atomics, equal
+        inputs give equal bits.  Returns (self_sums, coll)."""
+        import torch
+        if self_sums is None and coll is None:
+            raise ValueError("self_sums and coll are both None: nothing to compute")
+        first = self_sums if self_sums is not None else coll
+        nrows = int(first.shape[0]) if _is_cuda(first, torch.float64) and first.dim() >= 1 else 0
+        for t, name, tail in ((self_sums, "self_sums", (isf.ntypes, isf.nk, 2)), (coll, "coll", (isf.ntypes, isf.ntypes, isf.nk))):
+            if t is not None and not (_is_cuda(t, torch.float64) and nrows >= 1 and tuple(t.shape) == (nrows,) + tail):
+                raise ValueError(f"{name} must be a contiguous {('nrows',) + tail} float64 CUDA tensor, nrows the same for both")
+        if not isf.sample_n:
+            raise ValueError("no isf_sample yet: the current buffer holds nothing")
+        slots, rows = _msd_pairs(slots, rows, isf.norigins, nrows)
+        for q, sl in enumerate(slots.tolist()):
+            if isf.slot_n[sl] != isf.sample_n:
+                raise ValueError(f"pair {q} names the slot {sl}, " + ("which was never stored" if not isf.slot_n[sl] else
+                                 f"stored with N = {isf.slot_n[sl]}: the current sample has N = {isf.sample_n}"))
+        _lib.check(self._lib.pse_isf_correlate(isf._handle(self), int(slots.shape[0]), _vp(slots), _vp(rows), nrows, _ptr(self_sums),
+                                               _ptr(coll)))
+        return self_sums, coll
 
     def clusters(self, types, ntypes, rlink, n=None):
         """The link criterion of a cluster analysis on the device (pse_clusters_create; see include/pse_amd.h): `types` (n,) the type
