@@ -510,8 +510,9 @@ int pse_isf_correlate(pse_isf *f, int npairs, const int *slots_host, const int *
  * and size = 0 everywhere.  pse_clusters_status waits for the stream and returns the word (0: every call so far was complete); once it
  * has returned a non-zero word, pse_clusters_label refuses.  Until the host has read the word, later calls are still queued and,
  * the word being sticky on the device, write ~0u labels too: a caller that meets a ~0u label asks pse_clusters_status.
- * Not computed: whether a cluster is connected to its own periodic image (percolation); per-cluster geometry (centre of mass,
- * gyration tensor); links longer than the real-space cutoff.  A slab rank (n_slabs >= 2) orders only its own cells: pse_clusters_label refuses
+ * Whether a cluster is connected to its own periodic image (percolation), the clusters made whole across the boundaries and their
+ * radii of gyration: pse_clusters_span below.  Not computed: the centre of mass and the gyration tensor per cluster (the unfolded
+ * positions give the host what it needs); links longer than the real-space cutoff.  A slab rank (n_slabs >= 2) orders only its own cells: pse_clusters_label refuses
  * it; teams and owned-particle steps have no cluster entry point.
  * The object belongs to its handle as a pse_pair_hist does (pse_destroy frees it; pse_clusters_destroy waits for the stream).
  * PSE_ERR_INVALID, with a message naming the value, nothing launched, nothing written: pse_clusters_create, in this order: a null out
@@ -528,6 +529,52 @@ int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *
                        unsigned long long *hist /* DEVICE, nhist, ADDED to, may be NULL */, unsigned nhist,
                        const pse_exclusions *ex /* may be NULL */);
 int pse_clusters_status(pse_clusters *g, unsigned *status /* HOST */);
+
+/* ---- cluster analysis with percolation: spanning flags, images and radii of gyration (no reference counterpart) ----
+ * Definitions.  The lattice is a1 = (Lx, 0, 0), a2 = (xy Ly, Ly, 0), a3 = (0, 0, Lz).  For a linked pair (i, j) the minimum image turns
+ * d = r_i - r_j into d - (n1 a1 + n2 a2 + n3 a3), n2 = rint(d_y / Ly), n1 = rint((d_x - n2 xy Ly) / Lx), n3 = rint(d_z / Lz), the
+ * integers the device's own; a link is never near a tie of rint (a tie means |d| ~ L/2 > rcut >= rlink).  n_ij = (n1, n2, n3) is
+ * the SHIFT of the link.  An UNFOLDING of a cluster gives every member an integer vector c with c_j = c_i + n_ij on every link: then
+ * U_i = r_i + c_i (a1, a2, a3) has U_i - U_j equal to the minimum-image vector on every link.  The WINDING of a closed walk over
+ * links is the sum of its shifts; a cluster SPANS lattice axis k when some closed walk in it has a winding whose k-th component is
+ * not zero.  An unfolding exists exactly when the cluster spans no axis, and is then unique up to one constant vector.
+ * pse_clusters_span runs on a pse_clusters object, with the links of pse_clusters_label, and writes DEVICE arrays, each may be NULL
+ * but not all:
+ *   label, size, stats, hist   the outputs of pse_clusters_label, bit for bit
+ *   span[t]    (unsigned, by caller index) bits 0, 1, 2 are set when t's cluster spans a1, a2, a3
+ *   image[3 t .. 3 t + 2]  (int) c_t - c_label for a member of a cluster that spans nothing, label the cluster's label member: that
+ *              member has (0, 0, 0) and the value does not depend on the sort; stated for the positions as the caller passes them,
+ *              wrapped or not: pos[t] + image (a1, a2, a3) is the cluster made whole around its label member.  A member of a spanning
+ *              cluster gets (0, 0, 0): an unfolding of it would depend on the order of the hooks
+ *   rg2[t]     (double) the squared radius of gyration of t's cluster, 0 for a singleton, -1 for a spanning cluster: with 0 the
+ *              label member, D_i = (r_i - r_0) + image_i (a1, a2, a3) in fp64 in this order,
+ *                Dx = ((x_i - x_0) + i1 Lx) + i2 (xy Ly),  Dy = (y_i - y_0) + i2 Ly,  Dz = (z_i - z_0) + i3 Lz,
+ *              q_i = llrint(D_i 2^20) per component, the integer sums sum q (three signed 64-bit words) and sum q^2 (two unsigned
+ *              64-bit words: the low 32 bits of every q_k^2 into one, q_k^2 >> 32 into the other), and
+ *                Rg^2 = 2^-40 (S2 / s - ((sx sx + sy sy) + sz sz) / (s s)),  S2 = (double)hi 2^32 + (double)lo,
+ *              evaluated in fp64 in this order without contraction (the resolution of a coordinate is 2^-20, under 1e-6)
+ *   pstats     eight unsigned 64-bit words, 8-byte aligned, OVERWRITTEN: spanning clusters; their members; clusters spanning a1; a2;
+ *              a3; all three; the largest size among the clusters that span nothing; the sum of s^2 over those
+ * Queue-only as pse_clusters_label, in a fixed sequence of launches of its own (the union-find with a 64-bit word per row: the
+ * parent in 28 bits and the image offset to it in three 12-bit fields; the geometry launch only with rg2); no floating-point
+ * atomics, only integers are summed: equal inputs give equal bits, rg2 included.  The first call on an object places its scratch
+ * (68 bytes per particle of n_max), so a capture needs one call before it.
+ * Three caps set further bits of the object's sticky status word and behave as the trip caps do (label = ~0u, size = 0, span = 0,
+ * image = 0, rg2 = -1, stats and pstats zero; pse_clusters_status reports the word): 4, an image offset beyond +-2047 box lengths; 8,
+ * a |q| >= 2^31, a member further than 2048 length units from its label member; 16, N > 2^28.  None is reachable at any size that is
+ * tested or run.
+ * PSE_ERR_INVALID as for pse_clusters_label and in its order -- the all-outputs-null refusal covering all eight outputs -- then rg2
+ * or pstats not 8-byte aligned.  A slab rank is refused.
+ * pse_host_cluster_word packs (parent < 2^28, c[3] each in [-2047, 2047]) into the word of the union-find as the device does,
+ * pse_host_cluster_word_parts unpacks one; a value out of range or a null pointer is refused. */
+int pse_clusters_span(pse_clusters *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *label /* DEVICE, may be NULL */,
+                      unsigned *size /* DEVICE, may be NULL */, unsigned long long *stats /* DEVICE, 4, may be NULL */,
+                      unsigned long long *hist /* DEVICE, nhist, ADDED to, may be NULL */, unsigned nhist,
+                      unsigned *span /* DEVICE, may be NULL */, int *image /* DEVICE, 3 per particle, may be NULL */,
+                      double *rg2 /* DEVICE, may be NULL */, unsigned long long *pstats /* DEVICE, 8, may be NULL */,
+                      const pse_exclusions *ex /* may be NULL */);
+int pse_host_cluster_word(unsigned parent, const int *c /* 3 */, unsigned long long *word);
+int pse_host_cluster_word_parts(unsigned long long word, unsigned *parent, int *c /* 3 */);
 
 /* ---- bond-orientational order: the Steinhardt q_l per particle, the neighbour-averaged q-bar_l and solid-like bonds (no reference counterpart) ----
  * A pse_bond_order object fixes the types of the particles, the neighbour distances and the degrees: types_host, ntypes <= 8 and the

@@ -12,5 +12,5 @@ try:   # torch first: its bundled HIP/rocFFT/RCCL (same SONAMEs) must be the cop
     import torch as _torch  # noqa: F401
 except ImportError:  # pragma: no cover - the C-ABI itself does not need torch
     _torch = None
-from .engine import Engine, host_lanczos_sqrt_e1, host_select_params, host_realspace_table, host_lz_decide, host_rouse_weights, debug_lz_decide, debug_lz_decide_supported  # noqa: F401
+from .engine import Engine, host_lanczos_sqrt_e1, host_select_params, host_realspace_table, host_lz_decide, host_rouse_weights, host_cluster_word, host_cluster_word_parts, debug_lz_decide, debug_lz_decide_supported  # noqa: F401
 from ._lib import PSEError  # noqa: F401

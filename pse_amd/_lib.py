@@ -161,6 +161,9 @@ SYMBOLS = {
     "pse_clusters_destroy": (_i, [_vp]),
     "pse_clusters_label": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _vp, _u, _vp]),
     "pse_clusters_status": (_i, [_vp, _vp]),
+    "pse_clusters_span": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp]),
+    "pse_host_cluster_word": (_i, [_u, _vp, _vp]),
+    "pse_host_cluster_word_parts": (_i, [ctypes.c_ulonglong, _vp, _vp]),
     "pse_bond_order_create": (_i, [_vp, _u, _vp, _i, _vp, _i, _vp, _vp]),
     "pse_bond_order_destroy": (_i, [_vp]),
     "pse_bond_order_compute": (_i, [_vp, _vp, _vp, _u, _vp, _vp, _vp, _i, _d, _u, _vp, _vp, _vp]),

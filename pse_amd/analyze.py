@@ -658,6 +658,54 @@ def averages_of(rows):
     return (float(rows[:, 3].sum() / rows[:, 0].sum()), float(rows[:, 2].sum() / rows[:, 3].sum()), float((rows[:, 1] / rows[:, 3]).mean()))
 
 
+def unfold_clusters(pos, images, box):
+    """pos + images (a1, a2, a3) for the box (Lx, Ly, Lz[, xy]): every cluster that spans nothing made whole around its label member
+    (the `image` of Engine.cluster_span, Clusters.images()).  pos (n, 3) or (n, 4); returns (n, 3).  NumPy only."""
+    import numpy as np
+    pos, images = np.asarray(pos, dtype=np.float64), np.asarray(images)
+    if pos.ndim != 2 or pos.shape[1] not in (3, 4) or images.shape != (pos.shape[0], 3):
+        raise ValueError("pos must be (n, 3) or (n, 4) and images (n, 3)")
+    Lx, Ly, Lz = (float(b) for b in box[:3])
+    xy = float(box[3]) if len(box) > 3 else 0.0
+    im = images.astype(np.float64)
+    out = pos[:, :3].copy()
+    out[:, 0] += im[:, 0] * Lx + im[:, 1] * (xy * Ly)
+    out[:, 1] += im[:, 1] * Ly
+    out[:, 2] += im[:, 2] * Lz
+    return out
+
+
+def fractal_dimension_of(sizes, rg2, smin=5):
+    """d_f from s ~ Rg^d_f: the least-squares slope of log s on log Rg over the clusters with s >= smin and Rg^2 > 0 (one entry per
+    cluster; spanning clusters, rg2 = -1, and singletons drop out).  At least two distinct radii are needed.  NumPy only."""
+    import numpy as np
+    sizes, rg2 = np.asarray(sizes, dtype=np.float64).ravel(), np.asarray(rg2, dtype=np.float64).ravel()
+    if sizes.shape != rg2.shape:
+        raise ValueError("sizes and rg2 must have one entry per cluster each")
+    keep = (sizes >= smin) & (rg2 > 0.0)
+    x, y = 0.5 * np.log(rg2[keep]), np.log(sizes[keep])
+    if len(x) < 2 or np.ptp(x) == 0.0:
+        raise ValueError(f"fewer than two clusters of {smin} or more members with distinct radii: no slope")
+    x0, y0 = x - x.mean(), y - y.mean()
+    return float((x0 * y0).sum() / (x0 * x0).sum())
+
+
+def percolation_averages_of(rows, axis=None):
+    """From the per-sample rows of eight words (Engine.cluster_span's pstats) and the rows of four (stats), one per sample:
+    (the share of samples with a cluster spanning `axis` -- 0, 1, 2; None: any --, the weight-average size of the clusters that span
+    nothing, sum s^2 / sum s over them; nan where every particle is in a spanning cluster).  NumPy only."""
+    import numpy as np
+    p, st = rows
+    p, st = np.asarray(p, dtype=np.float64).reshape(-1, 8), np.asarray(st, dtype=np.float64).reshape(-1, 4)
+    if p.shape[0] < 1 or p.shape[0] != st.shape[0]:
+        raise ValueError("no samples yet")
+    if axis is not None and int(axis) not in (0, 1, 2):
+        raise ValueError("axis must be None, 0, 1 or 2")
+    col = p[:, 0] if axis is None else p[:, 2 + int(axis)]
+    free = (st[:, 3] - p[:, 1]).sum()
+    return float((col > 0).mean()), float(p[:, 7].sum() / free) if free > 0 else float("nan")
+
+
 def _cluster_analyzer_arguments(rlink, types, type_names, period, nhist, capacity):
     """What Clusters checks before it touches the device.  A dict `rlink` may name its types by `type_names`.  Returns (types uint32
     or None, ntypes, rlink (npt,), names or None, period, nhist or None, capacity)."""
@@ -678,16 +726,28 @@ class Clusters(_TypedAnalyzer, _SampleRing):
     Each sample writes its row (clusters, largest, sum of s^2, N) into a device ring of `capacity` rows -- once full, the oldest rows
     are replaced -- and adds its clusters to the size counts, `nhist` words (default: the number of particles; the last holds every
     larger cluster).  Sampling only queues work; the readers are the only places that wait for the device.
-    Not measured: percolation (a cluster connected to its own periodic image) and per-cluster geometry.
+    `percolation=True`: every sample also finds which clusters are connected to their own periodic image and along which lattice
+    axes, makes every other cluster whole across the boundaries and takes its radius of gyration (pse_clusters_span; the definitions
+    are in include/pse_amd.h), and keeps a second device ring of eight words per sample.  The default leaves every call, row and
+    column as without it.  Not measured: the centre of mass and the gyration tensor per cluster (unfolded() gives the host what it needs).
 
     labels(), sizes() -- the last sample, by particle index (-1 / 0 outside the group);  table() -- (samples kept, 5): step, clusters,
     largest, sum s^2, N;  size_distribution() -- mean n(s) per sample;  number_average(), weight_average(), largest_fraction() -- over
-    the samples kept;  members(label);  samples;  reset()."""
+    the samples kept;  members(label);  samples;  reset().
+    With percolation: spanning() -- (n,) bits 0, 1, 2 per particle;  images() -- (n, 3);  unfolded() -- the sampled positions plus
+    images (a1, a2, a3);  rg2() -- (n,), -1 in a spanning cluster;  cluster_table() -- one row per cluster
+    of the last sample: label, size, span, Rg^2;  percolation_table() -- (samples kept, 9): step and PERCOLATION_COLUMNS;
+    percolation_probability(axis=None) -- the share of kept samples with a spanning cluster;  finite_weight_average() -- sum s^2 /
+    sum s over the clusters that span nothing."""
 
     COLUMNS = ("timestep", "clusters", "largest", "sum_s2", "N")
+    PERCOLATION_COLUMNS = ("timestep", "spanning", "spanning_members", "span_a1", "span_a2", "span_a3", "span_all", "largest_finite",
+                           "sum_s2_finite")
 
-    def __init__(self, integrator, rlink, types=None, type_names=None, exclusions=None, period=1, nhist=None, capacity=1024):
+    def __init__(self, integrator, rlink, types=None, type_names=None, exclusions=None, period=1, nhist=None, capacity=1024,
+                 percolation=False):
         import torch
+        self.percolation = bool(percolation)
         types, self.ntypes, self.rlink, self.type_names, self.period, nhist, self.capacity = _cluster_analyzer_arguments(
             rlink, types, type_names, period, nhist, capacity)   # (raises before the device is touched)
         with self._attach(integrator, types) as system:
@@ -699,20 +759,91 @@ class Clusters(_TypedAnalyzer, _SampleRing):
             self._size = torch.zeros(system.n, dtype=torch.int32, device=dev)
             self._rows = torch.zeros((self.capacity, 4), dtype=torch.int64, device=dev)
             self._hist = torch.zeros(self.nhist, dtype=torch.int64, device=dev)
+            if self.percolation:
+                self._span = torch.zeros(system.n, dtype=torch.int32, device=dev)
+                self._image = torch.zeros((system.n, 3), dtype=torch.int32, device=dev)
+                self._rg2 = torch.zeros(system.n, dtype=torch.float64, device=dev)
+                self._prows = torch.zeros((self.capacity, 8), dtype=torch.int64, device=dev)
+                self._pos_at = torch.zeros_like(system.pos)
             self._ring_reset()
 
     def analyze(self, timestep):
         if not self._due(timestep):
             return
         q = self._slot()
-        self.integrator.engine.cluster_label(self.system.pos, self._links, label=self._label, size=self._size, stats=self._rows[q],
-                                             hist=self._hist, group=self.integrator.group.members, exclusions=self._excl)
+        if self.percolation:
+            self.integrator.engine.cluster_span(self.system.pos, self._links, label=self._label, size=self._size, stats=self._rows[q],
+                                                hist=self._hist, span=self._span, image=self._image, rg2=self._rg2, pstats=self._prows[q],
+                                                group=self.integrator.group.members, exclusions=self._excl)
+            self._pos_at.copy_(self.system.pos)   # (queued behind the pass: the step that follows moves the particles)
+        else:
+            self.integrator.engine.cluster_label(self.system.pos, self._links, label=self._label, size=self._size, stats=self._rows[q],
+                                                 hist=self._hist, group=self.integrator.group.members, exclusions=self._excl)
         self._record(q, timestep)
 
     def reset(self):
         self._rows.zero_(); self._hist.zero_()
         self._label.fill_(-1); self._size.zero_()
+        if self.percolation:
+            self._span.zero_(); self._image.zero_(); self._rg2.zero_(); self._prows.zero_()
         self._ring_reset()
+
+    def _percolating(self):
+        if not self.percolation:
+            raise ValueError("this analyzer was made without percolation=True")
+        self._sampled()
+
+    def spanning(self):
+        """(n,) int64: bits 0, 1, 2 are set when the particle's cluster in the last sample spans a1, a2, a3; 0 outside the group."""
+        self._percolating()
+        return self._span.cpu().numpy().astype("int64")
+
+    def images(self):
+        """(n, 3) int64: the lattice vector that makes the particle's cluster whole around its label member; zeros in a spanning cluster."""
+        self._percolating()
+        return self._image.cpu().numpy().astype("int64")
+
+    def unfolded(self):
+        """(n, 3): the positions of the last sample plus images() (a1, a2, a3) in the current box: every cluster that spans nothing
+        in one piece.  The analyzer keeps a device copy of the sampled positions, since the step that follows a sample moves the
+        particles; valid until the box changes."""
+        self._percolating()
+        return unfold_clusters(self._pos_at.cpu().numpy(), self.images(), self.system.box)
+
+    def rg2(self):
+        """(n,) float64: Rg^2 of the particle's cluster in the last sample; 0 for a singleton and outside the group, -1 in a spanning one."""
+        self._percolating()
+        return self._rg2.cpu().numpy()
+
+    def cluster_table(self):
+        """One row per cluster of the last sample, by ascending label: a structured array with the fields label, size, span, rg2."""
+        import numpy as np
+        label, size, span, rg2 = self.labels(), self.sizes(), self.spanning(), self.rg2()
+        roots = np.nonzero(label == np.arange(len(label)))[0]
+        out = np.zeros(len(roots), dtype=[("label", np.int64), ("size", np.int64), ("span", np.int64), ("rg2", np.float64)])
+        out["label"], out["size"], out["span"], out["rg2"] = roots, size[roots], span[roots], rg2[roots]
+        return out
+
+    def percolation_table(self):
+        """(samples kept, 9) int64, oldest first: PERCOLATION_COLUMNS."""
+        import numpy as np
+        if not self.percolation:
+            raise ValueError("this analyzer was made without percolation=True")
+        n = min(self.samples, self.capacity)
+        dev = self._prows.cpu().numpy()
+        out = np.zeros((n, 9), dtype=np.int64)
+        for r in range(n):
+            q = (self.samples - n + r) % self.capacity
+            out[r, 0], out[r, 1:] = self._steps[q], dev[q]
+        return out
+
+    def percolation_probability(self, axis=None):
+        """The share of the kept samples in which some cluster spans `axis` (0, 1, 2; None: any axis)."""
+        return percolation_averages_of((self.percolation_table()[:, 1:], self.table()[:, 1:]), axis)[0]
+
+    def finite_weight_average(self):
+        """sum s^2 / sum s over the clusters that span nothing, over the kept samples: the weight-average size short of the gel."""
+        return percolation_averages_of((self.percolation_table()[:, 1:], self.table()[:, 1:]))[1]
 
     def status(self):
         """The give-up word of the device object (0: every sample was labelled completely; see include/pse_amd.h)."""

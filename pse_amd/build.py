@@ -4,7 +4,7 @@ Run as `python -m pse_amd.build` or through __graft_entry__.build(). No cmake: o
 objects and their entry points) are host code that launches through the wrappers of the kernel units: pse_kernels.hip (cell sort, near
 field), pse_farfield.hip (spread, gather), pse_fft.hip and pse_zfft.hip (the transforms), pse_vectors.hip (Lanczos, integrator),
 pse_local.hip (owned-particle ranks), pse_forces.hip (the force providers), pse_analysis.hip (histogram, clusters, structure factor,
-displacement moments), pse_order.hip (bond order), pse_molecules.hip (chain conformations), pse_molpairs.hip (chain statistics), pse_molmodes.hip (chain normal modes) and pse_scatter.hip (intermediate scattering functions).
+displacement moments), pse_percolation.hip (clusters with image offsets: percolation), pse_order.hip (bond order), pse_molecules.hip (chain conformations), pse_molpairs.hip (chain statistics), pse_molmodes.hip (chain normal modes) and pse_scatter.hip (intermediate scattering functions).
 """
 import os
 import subprocess
@@ -53,7 +53,7 @@ def _all_sources():
 
 LIB_UNITS = (("pse_kernels.hip", HIPFLAGS), ("pse_farfield.hip", HIPFLAGS + FARFLAGS), ("pse_capi.hip", HIPFLAGS), ("pse_engine.hip", HIPFLAGS), ("pse_local.hip", HIPFLAGS), ("pse_zfft.hip", HIPFLAGS),
              ("pse_fft.hip", HIPFLAGS), ("pse_vectors.hip", HIPFLAGS),
-             ("pse_forces.hip", HIPFLAGS), ("pse_analysis.hip", HIPFLAGS), ("pse_order.hip", HIPFLAGS), ("pse_molecules.hip", HIPFLAGS), ("pse_molpairs.hip", HIPFLAGS), ("pse_molmodes.hip", HIPFLAGS), ("pse_scatter.hip", HIPFLAGS), ("pse_objects.hip", HIPFLAGS),
+             ("pse_forces.hip", HIPFLAGS), ("pse_analysis.hip", HIPFLAGS), ("pse_percolation.hip", HIPFLAGS), ("pse_order.hip", HIPFLAGS), ("pse_molecules.hip", HIPFLAGS), ("pse_molpairs.hip", HIPFLAGS), ("pse_molmodes.hip", HIPFLAGS), ("pse_scatter.hip", HIPFLAGS), ("pse_objects.hip", HIPFLAGS),
              ("pse_params.cpp", ["-x", "c++"]), ("pse_host_api.cpp", ["-x", "c++"]))
 _report = []   # what build_all did, one entry per artefact: (name, "compiled" | "reused")
 

@@ -261,6 +261,13 @@ int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const unsigned *
     return clusters_label_validate(g, h, h ? h->par.n_max : 0u, h ? h->par.n_slabs : 1, 0u, N, pos, label, size, stats, hist, nhist, ex,
                                    ex ? ex->h : nullptr);
 }
+int pse_clusters_span(pse_clusters *g, const pse_double4 *pos, const unsigned *, unsigned N, unsigned *label, unsigned *size,
+                      unsigned long long *stats, unsigned long long *hist, unsigned nhist, unsigned *span, int *image, double *rg2,
+                      unsigned long long *pstats, const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;   // (as pse_clusters_label: nothing is read or written)
+    return clusters_span_validate(g, h, h ? h->par.n_max : 0u, h ? h->par.n_slabs : 1, 0u, N, pos, label, size, stats, hist, nhist, span, image,
+                                  rg2, pstats, ex, ex ? ex->h : nullptr);
+}
 int pse_clusters_status(pse_clusters *g, unsigned *status) {
     if (!g) return fail(PSE_ERR_INVALID, "pse_clusters_status: null cluster object");
     if (!status) return fail(PSE_ERR_INVALID, "pse_clusters_status: null status");

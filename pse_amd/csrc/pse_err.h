@@ -109,6 +109,11 @@ int clusters_create_validate(double rcut, unsigned n_max, unsigned n, const unsi
 int clusters_label_validate(const void *g, const void *g_handle, unsigned n_max, int n_slabs, unsigned known_status, unsigned N, const void *pos,
                             const void *label, const void *size, const void *stats, const void *hist, unsigned nhist, const void *ex,
                             const void *ex_handle);
+// the same for pse_clusters_span: those checks in that order, the all-null refusal over all eight outputs, then the alignment of
+// rg2 and pstats
+int clusters_span_validate(const void *g, const void *g_handle, unsigned n_max, int n_slabs, unsigned known_status, unsigned N, const void *pos,
+                           const void *label, const void *size, const void *stats, const void *hist, unsigned nhist, const void *span,
+                           const void *image, const void *rg2, const void *pstats, const void *ex, const void *ex_handle);
 // the argument checks of pse_bond_order_create behind its null-out and null-handle checks, in the order include/pse_amd.h lists them
 // (types may be null: one type), with the handle's rcut and n_max
 int bond_order_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rnb, int nl,

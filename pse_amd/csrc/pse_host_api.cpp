@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "pse_err.h"
+#include "pse_cluster_word.h"
 
 namespace pse {
 
@@ -511,6 +512,30 @@ int clusters_label_validate(const void *g, const void *g_handle, unsigned n_max,
     return 0;
 }
 
+int clusters_span_validate(const void *g, const void *g_handle, unsigned n_max, int n_slabs, unsigned known_status, unsigned N, const void *pos,
+                           const void *label, const void *size, const void *stats, const void *hist, unsigned nhist, const void *span,
+                           const void *image, const void *rg2, const void *pstats, const void *ex, const void *ex_handle) {
+    const char *who = "pse_clusters_span";
+    if (!g) return fail(PSE_ERR_INVALID, "%s: null cluster object", who);
+    if (N == 0 || N > n_max) return fail(PSE_ERR_INVALID, "%s: N = %u outside (0, n_max = %u]", who, N, n_max);
+    if (!pos) return fail(PSE_ERR_INVALID, "%s: null pos", who);
+    if (!label && !size && !stats && !hist && !span && !image && !rg2 && !pstats)
+        return fail(PSE_ERR_INVALID, "%s: label, size, stats, hist, span, image, rg2 and pstats are all null: nothing to write", who);
+    if (((uintptr_t)stats & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: stats is not 8-byte aligned (64-bit words)", who);
+    if (((uintptr_t)hist & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: hist is not 8-byte aligned (64-bit words)", who);
+    if (hist && nhist == 0) return fail(PSE_ERR_INVALID, "%s: hist given with nhist = 0, need at least one word", who);
+    if (ex) if (int rc = pair_excl_validate(who, ex, ex_handle, g_handle)) return rc;
+    if (n_slabs > 1)
+        return fail(PSE_ERR_INVALID, "%s: this handle is a slab rank (n_slabs = %d): it orders only its own cells, the clusters would be partial", who,
+                    n_slabs);
+    if (known_status)
+        return fail(PSE_ERR_INVALID, "%s: an earlier call gave up (status word 0x%x, pse_clusters_status): its labels were not complete", who,
+                    known_status);
+    if (((uintptr_t)rg2 & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: rg2 is not 8-byte aligned (doubles)", who);
+    if (((uintptr_t)pstats & 7u) != 0) return fail(PSE_ERR_INVALID, "%s: pstats is not 8-byte aligned (64-bit words)", who);
+    return 0;
+}
+
 int bond_order_create_validate(double rcut, unsigned n_max, unsigned n, const unsigned *types, int ntypes, const double *rnb, int nl,
                                const int *degrees) {
     const char *who = "pse_bond_order_create";
@@ -985,6 +1010,23 @@ extern "C" int pse_host_lz_decide(const double *scal_host, int n_dec, const pse_
 }
 
 // Counting sort of the 2 nbonds bond ends by particle, then each row sorted by (partner, type): O(nbonds) plus the row sorts.
+extern "C" int pse_host_cluster_word(unsigned parent, const int *c, unsigned long long *word) {
+    const char *who = "pse_host_cluster_word";
+    if (!c || !word) return fail(PSE_ERR_INVALID, "%s: null %s", who, !c ? "c" : "word");
+    if (parent >= CLUSTER_WORD_MAX_ROWS) return fail(PSE_ERR_INVALID, "%s: parent = %u outside [0, 2^28)", who, parent);
+    if (!cluster_offset_fits(c[0], c[1], c[2]))
+        return fail(PSE_ERR_INVALID, "%s: offset (%d, %d, %d) has a component outside [-%d, %d]", who, c[0], c[1], c[2], CLUSTER_WORD_MAX_OFFSET,
+                    CLUSTER_WORD_MAX_OFFSET);
+    *word = cluster_word_pack(parent, c[0], c[1], c[2]);
+    return 0;
+}
+extern "C" int pse_host_cluster_word_parts(unsigned long long word, unsigned *parent, int *c) {
+    const char *who = "pse_host_cluster_word_parts";
+    if (!parent || !c) return fail(PSE_ERR_INVALID, "%s: null %s", who, !parent ? "parent" : "c");
+    cluster_word_unpack(word, *parent, c[0], c[1], c[2]);
+    return 0;
+}
+
 extern "C" int pse_host_bond_rows(unsigned n, unsigned nbonds, const unsigned *pairs, const unsigned *types, int *row_off, unsigned *entries) {
     if (!pairs || !row_off || !entries) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: null array");
     if (n == 0) return fail(PSE_ERR_INVALID, "pse_host_bond_rows: n = 0");

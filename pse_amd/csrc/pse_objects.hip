@@ -1,6 +1,6 @@
 // The device objects of the C-ABI (include/pse_amd.h) and the passes that take them: the pair passes on the cell list (repulsion, table,
 // typed table, histogram, clusters, bond order), the bonded passes (bonds, angles, dihedrals), pair exclusions, structure factors, displacement
-// moments, chain conformations, chain statistics, chain normal modes and intermediate scattering functions.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_order.h, pse_molecules.h, pse_molpairs.h, pse_molmodes.h or pse_scatter.h, the objects own their arrays through DeviceObject
+// moments, chain conformations, chain statistics, chain normal modes and intermediate scattering functions.  Host code only: every kernel is behind a launch wrapper of pse_forces.h, pse_analysis.h, pse_percolation.h, pse_order.h, pse_molecules.h, pse_molpairs.h, pse_molmodes.h or pse_scatter.h, the objects own their arrays through DeviceObject
 // (pse_handle.h), and every argument check is a validator of pse_host_api.cpp (pse_err.h), shared with the sanitizer build's stand-in.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "pse_handle.h"
 #include "pse_forces.h"
 #include "pse_analysis.h"
+#include "pse_percolation.h"
 #include "pse_order.h"
 #include "pse_molecules.h"
 #include "pse_molpairs.h"
@@ -39,6 +40,7 @@ struct pse_typed_table : DeviceObject { PairTypedTables tt{}; };
 struct pse_pair_hist : DeviceObject { PairHist ph{}; };
 struct pse_clusters : DeviceObject {
     ClusterLinks cl{};
+    ClusterSpan sp{};                       // the scratch of pse_clusters_span, placed by its first call (word == null: not yet)
     unsigned known_status = 0u;             // the last word pse_clusters_status read
 };
 struct pse_bond_order : DeviceObject { BondOrder bo{}; };
@@ -561,6 +563,31 @@ extern "C" int pse_clusters_label(pse_clusters *g, const pse_double4 *pos, const
     CellPass cp;
     TRY(cp.begin(h, pos, group, N, ex));
     launch_clusters(h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, g->cl, label, size, stats, hist, nhist, h->stream, cp.rows);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// The same pass with the image offsets (pse_percolation.h).  The first call on an object places the scratch: 68 bytes per particle of
+// n_max, written by k_span_init before anything reads it.  Queue-only from then on (a capture needs one call before it, as it needs
+// the sort's buffers).
+extern "C" int pse_clusters_span(pse_clusters *g, const pse_double4 *pos, const unsigned *group, unsigned N, unsigned *label, unsigned *size,
+                                 unsigned long long *stats, unsigned long long *hist, unsigned nhist, unsigned *span, int *image, double *rg2,
+                                 unsigned long long *pstats, const pse_exclusions *ex) {
+    pse_handle *h = g ? g->h : nullptr;
+    TRY(clusters_span_validate(g, h, h ? (unsigned)h->n_max : 0u, h ? h->n_slabs : 1, g ? g->known_status : 0u, N, pos, label, size, stats, hist,
+                               nhist, span, image, rg2, pstats, ex, ex ? ex->h : nullptr));
+    CellPass cp;
+    TRY(cp.begin(h, pos, group, N, ex));
+    if (!g->sp.word) {
+        const size_t nm = (size_t)h->n_max;
+        unsigned long long *words = nullptr;
+        hipError_t e = g->put(&words, nullptr, 7 * nm);   // one array: word, minkey (n_max each), sums (5 n_max)
+        e = g->put(&g->sp.flag, nullptr, nm);
+        if (e != hipSuccess) return fail(PSE_ERR_HIP, "pse_clusters_span: placing the scratch of %zu particles on the device failed: %s", nm,
+                                         hipGetErrorString(e));
+        g->sp.word = words; g->sp.minkey = words + nm; g->sp.sums = words + 2 * nm;
+    }
+    launch_clusters_span((const double4 *)pos, h->pos_s, h->tag_s, (int)N, h->cell_off, h->dbox, h->nc, g->cl, g->sp, label, size, stats, hist,
+                         nhist, span, image, rg2, pstats, h->stream, cp.rows);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -665,6 +665,29 @@ CHAIN_MODES_STATIC = 6    # PSE_CHAIN_MODES_STATIC: xx, yy, zz, xy, xz, yz
 CHAIN_MODES_CORR = 9      # PSE_CHAIN_MODES_CORR: 3 alpha + beta, alpha of now, beta of the origin
 
 
+def host_cluster_word(parent, c):
+    """The 64-bit word of the union-find with image offsets (pse_host_cluster_word; host only): the parent row, below 2^28, and the
+    offset c (three integers in [-2047, 2047]) packed as the device packs them."""
+    import numpy as np
+    parent, c = int(parent), [int(v) for v in c]
+    if not 0 <= parent < 2 ** 32 or len(c) != 3 or any(not -2 ** 31 <= v < 2 ** 31 for v in c):
+        raise ValueError("parent no C unsigned, or c not three C ints")
+    word = ctypes.c_ulonglong(0)
+    _lib.check(_lib.load().pse_host_cluster_word(parent, _vp(np.array(c, dtype=np.int32)), ctypes.byref(word)))
+    return int(word.value)
+
+
+def host_cluster_word_parts(word):
+    """(parent, (c1, c2, c3)) of a word of host_cluster_word (pse_host_cluster_word_parts; host only)."""
+    import numpy as np
+    word = int(word)
+    if not 0 <= word < 2 ** 64:
+        raise ValueError("word no unsigned 64-bit integer")
+    parent, c = ctypes.c_uint(0), np.zeros(3, dtype=np.int32)
+    _lib.check(_lib.load().pse_host_cluster_word_parts(word, ctypes.byref(parent), _vp(c)))
+    return int(parent.value), tuple(int(v) for v in c)
+
+
 def host_rouse_weights(m, nmodes):
     """The (nmodes, m) weights of pse_host_rouse_weights for a chain of m members (host only): row 0 the end-to-end functional
     (-1, 0, ..., 0, +1), rows p >= 1 the Rouse modes cos(pi p (2 q + 1) / (2 m)) / m with the argument reduced in integers."""
@@ -1106,6 +1129,52 @@ class _ForcePasses:
             if w is not None:
                 t.copy_(w)
         return label, size, stats, hist
+
+    def cluster_span(self, pos, links, label=None, size=None, stats=None, hist=None, span=None, image=None, rg2=None, pstats=None,
+                     group=None, exclusions=None):
+        """cluster_label with percolation (pse_clusters_span; the definitions are in include/pse_amd.h): `label`, `size`, `stats`,
+        `hist` as there, bit for bit, and
+        `span`: contiguous 1-D int32 of at least pos.shape[0] entries, by caller index -- bits 0, 1, 2 set when the particle's cluster
+        is connected to its own periodic image along the lattice axis a1, a2, a3;
+        `image`: contiguous (>= pos.shape[0], 3) int32 -- the lattice vector that, added to the particle, makes its cluster whole
+        around the cluster's label member; zeros in a spanning cluster;
+        `rg2`: contiguous 1-D float64 of at least pos.shape[0] entries -- the squared radius of gyration of the particle's cluster, 0
+        for a singleton, -1 for a spanning cluster;
+        `pstats`: contiguous (8,) int64, OVERWRITTEN: spanning clusters, their members, clusters spanning a1, a2, a3, all three, the
+        largest size and the sum of s^2 among the clusters that span nothing.
+        All may be None, not all.  Queue-only, integers only behind the fixed-point conversion: equal inputs give equal bits.
+        Returns (label, size, stats, hist, span, image, rg2, pstats)."""
+        import torch
+        n = pos.shape[0] if group is None else group.shape[0]
+        rows = pos.shape[0]
+        _chk4(pos, "pos"); _chk_group(group)
+        for t, name in ((label, "label"), (size, "size")):
+            if t is not None and not (_is_cuda(t, torch.int32, torch.int64) and t.dim() == 1 and t.shape[0] >= rows):
+                raise ValueError(f"{name} must be a contiguous 1-D int32 or int64 CUDA tensor of at least {rows} entries")
+        if stats is not None and not (_is_cuda(stats, torch.int64) and tuple(stats.shape) == (4,)):
+            raise ValueError("stats must be a contiguous (4,) int64 CUDA tensor")
+        if hist is not None and not (_is_cuda(hist, torch.int64) and hist.dim() == 1 and hist.shape[0] >= 1):
+            raise ValueError("hist must be a contiguous 1-D int64 CUDA tensor of at least one entry")
+        if span is not None and not (_is_cuda(span, torch.int32) and span.dim() == 1 and span.shape[0] >= rows):
+            raise ValueError(f"span must be a contiguous 1-D int32 CUDA tensor of at least {rows} entries")
+        if image is not None and not (_is_cuda(image, torch.int32) and image.dim() == 2 and image.shape[1] == 3 and image.shape[0] >= rows):
+            raise ValueError(f"image must be a contiguous (>= {rows}, 3) int32 CUDA tensor")
+        if rg2 is not None and not (_is_cuda(rg2, torch.float64) and rg2.dim() == 1 and rg2.shape[0] >= rows):
+            raise ValueError(f"rg2 must be a contiguous 1-D float64 CUDA tensor of at least {rows} entries")
+        if pstats is not None and not (_is_cuda(pstats, torch.int64) and tuple(pstats.shape) == (8,)):
+            raise ValueError("pstats must be a contiguous (8,) int64 CUDA tensor")
+        if all(t is None for t in (label, size, stats, hist, span, image, rg2, pstats)):
+            raise ValueError("label, size, stats, hist, span, image, rg2 and pstats are all None: nothing to compute")
+        obj = links._handle(self)
+        ex = None if exclusions is None else exclusions._handle(self)
+        narrow = [None if t is None or t.dtype == torch.int32 else t.to(torch.int32) for t in (label, size)]   # (keeps the entries outside the group)
+        l32, s32 = [t if w is None else w for t, w in zip((label, size), narrow)]
+        _lib.check(self._lib.pse_clusters_span(obj, _ptr(pos), _ptr(group), n, _ptr(l32), _ptr(s32), _ptr(stats), _ptr(hist),
+                                               0 if hist is None else int(hist.shape[0]), _ptr(span), _ptr(image), _ptr(rg2), _ptr(pstats), ex))
+        for t, w in zip((label, size), narrow):
+            if w is not None:
+                t.copy_(w)
+        return label, size, stats, hist, span, image, rg2, pstats
 
     def bond_order_shells(self, types, ntypes, rnb, degrees=(4, 6), n=None):
         """The neighbour criterion and the degrees of a bond-order analysis on the device (pse_bond_order_create; see

@@ -3,14 +3,17 @@ pse_clusters_label (label, size, stats and hist all written) and of pse_pair_his
 cell walk over the same pairs, without the union-find -- on N particles at volume fraction phi, uniform random positions, one type.
   clusters    pse_clusters_label: sort, type mirror, init, link, flatten, write
   hist1       pse_pair_hist_accumulate, one bin, rmax = rlink
+  span        (with --span) pse_clusters_span on the same object, all eight outputs written: the union-find with image offsets
 Each figure is the time between one pair of events around `--calls` back-to-back calls (sort + cell walk, as a sampling loop pays
 them) after three warm-up calls; `--windows` windows per variant, taken alternately in one process.  `--rlink 0` means rcut.  The
 stats row of the last labelling is printed with a host-side check of its labels and sizes (label[label] == label, size ==
 bincount(label)[label]) and the histogram's count, which is the number of links.  `--host` adds a host baseline once, for the sense of
 scale: the positions on the host, the pair list below rlink in the periodic cube (scipy's cKDTree), scipy's connected_components.
+`--span` adds the third variant to the alternation, checks that its label, size and stats equal those of pse_clusters_label, and
+prints its eight percolation words and the ratio span / clusters.
 Prints one JSON line.
 
-  python tools/perf_clusters.py [--n 1000000] [--phi 0.1] [--rlink 2.2] [--calls 20] [--windows 5] [--only clusters] [--host]"""
+  python tools/perf_clusters.py [--n 1000000] [--phi 0.1] [--rlink 2.2] [--calls 20] [--windows 5] [--only clusters] [--host] [--span]"""
 import argparse
 import json
 import math
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--only", default="", help="comma-separated variants to run (a kernel trace then shows one variant per kernel name)")
     ap.add_argument("--host", action="store_true", help="also time the host baseline once")
+    ap.add_argument("--span", action="store_true", help="also time pse_clusters_span (percolation), alternated with the others")
     a = ap.parse_args()
     import torch
     import pse_amd
@@ -66,6 +70,15 @@ def main():
     counts = torch.zeros((1, 1), dtype=torch.int64, device="cuda")
     variants = {"clusters": lambda: eng.cluster_label(pos, links, label=label, size=size, stats=stats, hist=hist),
                 "hist1": lambda: eng.pair_hist_accumulate(pos, h1, counts)}
+    if a.span:
+        label2, size2, stats2 = torch.zeros_like(label), torch.zeros_like(size), torch.zeros_like(stats)
+        hist2 = torch.zeros_like(hist)
+        span = torch.zeros(n, dtype=torch.int32, device="cuda")
+        image = torch.zeros((n, 3), dtype=torch.int32, device="cuda")
+        rg2 = torch.zeros(n, dtype=torch.float64, device="cuda")
+        pstats = torch.zeros(8, dtype=torch.int64, device="cuda")
+        variants["span"] = lambda: eng.cluster_span(pos, links, label=label2, size=size2, stats=stats2, hist=hist2, span=span, image=image,
+                                                    rg2=rg2, pstats=pstats)
     if a.only:
         variants = {name: call for name, call in variants.items() if name in a.only.split(",")}
     for call in variants.values():
@@ -96,7 +109,17 @@ def main():
         counts.zero_()
         variants["hist1"]()
         res["links"] = int(counts.sum())
-    if len(variants) == 2:
+    if "span" in variants:
+        res["pstats"] = dict(zip(("spanning", "spanning_members", "span_a1", "span_a2", "span_a3", "span_all", "largest_finite", "sum_s2_finite"),
+                                 pstats.cpu().tolist()))
+        res["status"] = links.status()
+        if "clusters" in variants:
+            res["span_equals_label"] = bool(torch.equal(label, label2) and torch.equal(size, size2) and torch.equal(stats, stats2))
+            res["span_over_clusters"] = round(med["span"] / med["clusters"], 3)
+        r = rg2.cpu().numpy()
+        res["rg2_max"] = float(r.max())
+        res["spanning_rows_marked"] = bool(((r == -1.0) == (span.cpu().numpy() != 0)).all())
+    if "clusters" in variants and "hist1" in variants:
         res["clusters_over_hist1"] = round(med["clusters"] / med["hist1"], 3)
     if a.host:
         res["host"] = host_baseline(p4[:, :3], L, rlink)
